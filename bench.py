@@ -10,9 +10,15 @@ N>1: one process per GPU, records sharded in contiguous ranges (pairs never spli
 data-path collective; the only collective is the RCCL all-reduce of the hit-count / summary
 vector at the end of the job (mk_comm_reduce_counters of the C ABI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--scaling weak|strong] [--total-records R] [--paired]
                     [--records R] [--read-len L] [--patterns P] [--k K] [--mode any|hits] ...
+
+  --full            also run what the headline does not need: the CPU baseline (N = 1) and the short
+                    runs of the other BASELINE configurations (other_configs, default workload only).
+                    Without it a run sets up, warms up, times the K steps and prints the line.
+  --dump-outputs DIR  after the timed steps, write what the last step computed as DIR/<name>.npy
+                    (float32 / float64, at most 64 MB; fixed seeded samples of the long arrays)
 
   --scaling weak    (default) every rank scans --records reads: the job grows with N
   --scaling strong  the job is --total-records reads (or pairs with --paired) divided over the
@@ -26,8 +32,8 @@ it runs as one rank.  With fewer GPUs than ranks (a 1-GPU box) it runs in REHEAR
 ranks share devices round-robin, process group on gloo, counter reduction through
 torch.distributed -- functional check only, marked "rehearsal": true in the output.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (HBM) and,
-at N=1, `cpu_baseline` objects.
+Prints ONE JSON line on rank 0, with a `roofline` (HBM) object and, with --full at N=1, a
+`cpu_baseline` object.
 """
 import argparse
 import hashlib
@@ -119,9 +125,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-rec-index", action="store_true", help="diagnostic with --ragged: do not tell the library that lengths vary")
     ap.add_argument("--no-counters", action="store_true", help="diagnostic: scan without the device counter vector")
     ap.add_argument("--no-order", action="store_true", help="diagnostic with --mode hits: leave the tuples unordered")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, default workload only: skip the short runs of the other BASELINE configurations that are "
+                    help="with --full, default workload only: skip the short runs of the other BASELINE configurations that are "
                          "appended to the JSON line as other_configs")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     # filter-geometry tuning hooks (mk_matcher_options; results never depend on them)
@@ -153,6 +163,8 @@ def spawn_ranks(args):
 
 def main():
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps: at least one timed step")
     if args.ragged and (args.paired or args.ragged >= args.read_len):
         raise SystemExit("--ragged SPREAD: single-end only, SPREAD < --read-len")
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
@@ -358,6 +370,9 @@ def main():
     kernel_ms = m.kernel_times_ms()
     cnt = d_cnt.cpu().numpy()
     summ = cnt[len(patterns):]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mk, torch, mates, d_keep, d_hits, d_nh, not args.no_order, cnt,
+                     len(patterns), n_rec, args.steps, rank, world)
     # what every rank saw of its own shard (N > 1: gathered on rank 0 -- the first real multi-GPU run should say which rank
     # sat on which device, what its kernel took and how many ranks RCCL counted in its communicator)
     comm_ranks = None
@@ -440,16 +455,16 @@ def main():
             out["rehearsal"] = True
             out["rehearsal_note"] = f"{world} ranks share {n_dev} GPU(s): functional check, not a scaling measurement"
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic(m.kernel_name, n_rec, L, len(patterns), args.plant_every)
-        if world == 1 and not args.no_cpu_baseline and not args.paired and not args.ragged:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.paired and not args.ragged:
             out["cpu_baseline"] = cpu_baseline(mk, m, patterns, seed, n_rec, L, args.plant_every, mates[0][2],
                                                args.cpu_seconds)
         default_workload = default_workload_flag(args, options)
-        if world == 1 and default_workload and not (args.no_other_configs or args.paired or args.ragged or args.with_offsets):
+        if args.full and world == 1 and default_workload and not (args.no_other_configs or args.paired or args.ragged or args.with_offsets):
             try:  # (whatever happens in the side runs, the headline line must reach the driver -- with the failure named in it)
                 out["other_configs"] = other_configs(mk, lib, torch, dev, dev_index, m, mates[0], n_rec, L, seed, st)
             except Exception as e:
                 out["other_configs"] = f"FAILED: {e!r}"
-    if world > 1 and default_workload_flag(args, options) and not (args.no_other_configs or args.paired or args.ragged or args.with_offsets):
+    if args.full and world > 1 and default_workload_flag(args, options) and not (args.no_other_configs or args.paired or args.ragged or args.with_offsets):
         # BASELINE's multi-GPU configurations next to the headline (every rank takes part; rank 0 reports): config 3
         # (paired, pairs unsplit) and config 5 (500 k 21-mers, level-1 filter in global memory), one shard per rank
         del mates, d_keep
@@ -487,6 +502,60 @@ def main():
 def default_workload_flag(args, options):
     return (args.records, args.read_len, args.patterns, args.k, args.mode, args.plant_every, args.rc, args.scaling) == \
         (100_000_000, 150, 10_000, 31, "any", 100, False, "weak") and options is None
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, mk, torch, mates, d_keep, d_hits, d_nh, hits_ordered, cnt, n_pat, n_rec, steps, rank, world):
+    """--dump-outputs: what the timed path hands its caller after its last step, as .npy files of float32 / float64.
+    flags.npy (paired: flags_mate1 / flags_mate2 / keep.npy): the per-record flags; above 2^20 records a fixed seeded
+    sample, the records' indices in records_index.npy.  Hits mode: hits_record / hits_pattern / hits_position.npy, the
+    last scan's tuples (sorted by record, pattern, position when --no-order left them unordered); above 2^19 tuples a
+    fixed seeded sample, indices in hits_index.npy.  summary.npy: [hits, records hit, records, bases] of one step and,
+    in hits mode, pattern_counts.npy: occurrences per pattern of one step (the counter vector adds up over the timed
+    steps, which all scan the same batch: its sum / steps).  N > 1: every rank writes its shard's flags and tuples as
+    rank<r>_<name>.npy with 1/N of the samples, rank 0 the job's counters."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    arrays = {}
+
+    def sample(n, cap, seed):  # sorted indices of a fixed sample of range(n), or None when all n fit
+        return None if n <= cap else np.unique(np.random.default_rng(seed).integers(0, n, size=cap))
+
+    idx = sample(n_rec, (1 << 20) // world, 0x666C6167 + rank)
+    sel = slice(0, n_rec) if idx is None else torch.from_numpy(idx).to(mates[0][2].device)
+    named = [("flags", mates[0][2])] if len(mates) == 1 else [("flags_mate1", mates[0][2]), ("flags_mate2", mates[1][2]), ("keep", d_keep)]
+    for name, d in named:
+        arrays[prefix + name] = d[:n_rec][sel].cpu().numpy().astype(np.float32)
+    if idx is not None:
+        arrays[prefix + "records_index"] = idx.astype(np.float64)
+    if d_hits is not None:
+        nh = min(int(d_nh.item()), d_hits.numel() // 2)
+        t = d_hits[:2 * nh].cpu().numpy().view(mk.HIT_DTYPE)
+        if not hits_ordered:
+            t = t[np.lexsort((t["pos"], t["pat"], t["rec"]))]
+        hidx = sample(nh, (1 << 19) // world, 0x68697473 + rank)
+        if hidx is not None:
+            t = t[hidx]
+            arrays[prefix + "hits_index"] = hidx.astype(np.float64)
+        for name, field in (("hits_record", "rec"), ("hits_pattern", "pat"), ("hits_position", "pos")):
+            arrays[prefix + name] = t[field].astype(np.float64)
+    if rank == 0:
+        summ = cnt[n_pat:].astype(np.float64) / steps
+        arrays["summary"] = summ[[mk.MK_SUM_HITS, mk.MK_SUM_RECORDS_HIT, mk.MK_SUM_RECORDS, mk.MK_SUM_BASES]]
+        if d_hits is not None:
+            pidx = sample(n_pat, 1 << 20, 0x70617473)
+            counts = cnt[:n_pat].astype(np.float64) / steps
+            arrays["pattern_counts"] = counts if pidx is None else counts[pidx]
+            if pidx is not None:
+                arrays["pattern_counts_index"] = pidx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def other_configs_multi(mk, lib, torch, dist, rehearsal, dev, dev_index, m0, rank, world, seed, st, barrier, steps=5, warmup=2):

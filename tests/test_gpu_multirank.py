@@ -212,10 +212,10 @@ def test_bench_starts_its_own_ranks_and_strong_scaling_is_the_same_job():
 
 
 def test_bench_default_job_at_two_ranks_reports_every_rank_and_the_multi_gpu_configs():
-    """The driver's own command line at N = 2 (rehearsal: both ranks on the one GPU): the JSON line names every rank's
+    """The driver's own command line at N = 2 with --full (rehearsal: both ranks on the one GPU): the JSON line names every rank's
     device, kernel time and communicator size, and carries BASELINE's multi-GPU configurations -- config 3 (paired, pairs
     unsplit) and config 5 (500 k 21-mers) -- sharded over the same ranks."""
-    out = _bench("--gpus", "2", "--steps", "2", "--warmup", "1")
+    out = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--full")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["records_total"] == 200_000_000
     assert [r["rank"] for r in out["ranks"]] == [0, 1] and all(r["records"] == 100_000_000 and r["kernel_ms_avg"] > 0 for r in out["ranks"])
     assert all("device" in r and "ncclCommCount" in r and "device_name" in r for r in out["ranks"])
@@ -227,6 +227,28 @@ def test_bench_default_job_at_two_ranks_reports_every_rank_and_the_multi_gpu_con
     assert c5["workload"].startswith("config 5") and c5["filter"]["in_lds"] == 0 and len(c5["ranks"]) == 2
     assert all(e["value_gbases_per_s"] > 0 and 0 < e["frac"] < 1 for e in oc)
 
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` line carries the headline without the --full extras; --dump-outputs writes what the last timed
+    step computed: the same arrays whatever --steps is, flags and tuples that agree with the step's own counters."""
+    plain = _bench("--steps", "2", "--warmup", "1")
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and "cpu_baseline" not in plain and "other_configs" not in plain
+    small = ["--records", "1000000", "--patterns", "2000", "--warmup", "1"]  # (fewer than 2^20 records: every flag is written)
+    for mode in ("any", "hits"):
+        dumps = []
+        for steps in (2, 3):
+            d = tmp_path / f"{mode}{steps}"
+            _bench(*small, "--mode", mode, "--steps", str(steps), "--dump-outputs", str(d))
+            dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+        a, b = dumps
+        assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+        hits, records_hit, records, _ = a["summary.npy"]
+        assert records == 1000000 and a["flags.npy"].shape == (1000000,) and a["flags.npy"].dtype == np.float32
+        assert np.count_nonzero(a["flags.npy"]) == records_hit > 0
+        if mode == "hits":
+            assert a["hits_record.npy"].shape == (hits,) and a["pattern_counts.npy"].sum() == hits
+            assert set(a["hits_record.npy"].astype(np.int64).tolist()) == set(np.flatnonzero(a["flags.npy"]).tolist())
 
 def _agree_worker(rank, world, port, out_dir):
     import torch
