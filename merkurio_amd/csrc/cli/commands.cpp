@@ -29,7 +29,6 @@ static const char *kVersion = "1.0.0";  // crate version of the reference tree (
 // The handles of a finished command.  The program that is about to end (main.cpp: every output is flushed and closed when
 // run_extract / run_tag return, then the process leaves through _exit) does not free device memory, streams and
 // communicators one by one first: with the HIP runtime's own exit handlers that teardown was 0.15 s of a 0.6 s run.
-bool g_process_is_ending = false;
 static void release_matchers(const std::vector<mk_matcher *> &ms) {
     if (g_process_is_ending) return;
     for (mk_matcher *x : ms) mk_matcher_destroy(x);
@@ -123,6 +122,18 @@ static std::pair<size_t, size_t> shard_range(size_t n, size_t parts, size_t d) {
     const size_t base = n / parts, rem = n % parts;
     const size_t lo = d * base + std::min(d, rem);
     return {lo, lo + base + (d < rem ? 1 : 0)};
+}
+
+// A window of n records (pairs) over the devices: fn(d, lo, hi, out[d]) scans shard_range(n, N, d) on device d's own host thread and
+// keeps its results in out[d]; they come back in device order = record order, to be emitted in that order.
+template <class Result, class F>
+static std::vector<Result> run_shards(size_t n, size_t n_dev, F fn) {
+    std::vector<Result> out(n_dev);
+    run_threads(n_dev, [&](size_t d) {
+        const auto [lo, hi] = shard_range(n, n_dev, d);
+        fn(d, lo, hi, out[d]);
+    });
+    return out;
 }
 
 // the scalars of src/cmd_extract.rs:285-290 / src/cmd_tag.rs:360-364 and pattern_hit_counts of every
@@ -247,10 +258,42 @@ static void write_summary(TextLogger &t, const Patterns &p, const std::vector<ui
     t.flush();
 }
 
-static Json command_line_json(const std::vector<std::string> &argv) {
-    Json a = Json::array();
-    for (auto &s : argv) a.push(Json::string(s));
-    return a;
+// The end of a job's logs: the text log's summary and the JSON log's meta information, pattern hit counts and summary statistics
+// (src/cmd_extract.rs:673-714, src/cmd_tag.rs:650-686).  The subcommands differ in input_files' record files, tag's `tag` and
+// extract's paired-end object.
+static void finish_logs(Loggers &lg, const CommonArgs &a, const char *subcommand, const std::vector<std::string> &argv, bool use_ac,
+                        const Patterns &pats, const std::vector<uint32_t> &counts, const mk_counters &c, bool paired, Json input_files,
+                        const std::string *tag, const Json *paired_end) {
+    if (lg.active) {
+        lg.text.flush();
+        write_summary(lg.text, pats, counts, c, paired);
+    }
+    if (!lg.has_json) return;
+    Json command_line = Json::array();
+    for (auto &s : argv) command_line.push(Json::string(s));
+    input_files.set("kmer_file", a.kmer_file ? Json::string(*a.kmer_file) : Json::null());
+    Json meta = Json::object();
+    meta.set("program", Json::string(kProgram)).set("version", Json::string(kVersion));
+    meta.set("timestamp", Json::string(timestamp_now())).set("subcommand", Json::string(subcommand));
+    meta.set("command_line", command_line);
+    meta.set("search_algorithm", Json::string(use_ac ? "Aho-Corasick" : "BNDMq"));
+    meta.set("inverted_matching", Json::boolean(a.invert_match)).set("case_insensitive", Json::boolean(a.case_insensitive));
+    meta.set("input_files", input_files);
+    if (tag) meta.set("tag", Json::string(*tag));
+    Json cj = Json::object();
+    size_t found = 0;
+    for (size_t k = 0; k < counts.size(); ++k) {
+        cj.set(pats.list[k], Json::integer(counts[k]));
+        found += counts[k] > 0;
+    }
+    Json sum = Json::object();
+    sum.set("number_of_patterns_searched", Json::integer((long long)pats.list.size()));
+    sum.set("number_of_patterns_found", Json::integer((long long)found));
+    sum.set("number_of_records_searched", Json::integer((long long)c.nb_records_tot));
+    sum.set("number_of_characters_searched", Json::integer((long long)c.nb_bases));
+    sum.set("number_of_matches", Json::integer((long long)(c.nb_hits_tot[0] + c.nb_hits_tot[1])));
+    sum.set("number_of_distinct_records_with_a_hit", Json::integer((long long)(c.nb_records_hit[0] + c.nb_records_hit[1])));
+    lg.json.finalize(meta, cj, sum, paired_end);
 }
 static std::string join(const std::vector<std::string> &v) {
     std::string s;
@@ -426,11 +469,8 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
                         if (mk_matcher_batch_times(mm, ms4) == MK_OK)
                             for (int k = 0; k < 4; ++k) call_ms[k] += ms4[k];
                     }
-                    cc.nb_records_tot += cb.nb_records_tot; cc.nb_bases += cb.nb_bases;
-                    cc.nb_hits_tot[0] += cb.nb_hits_tot[0]; cc.nb_hits_tot[1] += cb.nb_hits_tot[1];
-                    cc.nb_records_hit[0] += cb.nb_records_hit[0]; cc.nb_records_hit[1] += cb.nb_records_hit[1];
-                    cc.nb_records_extracted += cb.nb_records_extracted;
-                    for (size_t k = 0; k < cnts.size(); ++k) cnts[k] += cnt_b[k];
+                    add_counters(cc, cb);
+                    add_counts(cnts, cnt_b);
                     break;
                 }
                 on_batch(b0, nb, keep.data(), rows.data(), lg.active ? n_rows : 0);
@@ -476,28 +516,21 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
                 tm.mark("batch: rows + records out");
             });
         } else {
-            // --gpus N: device d scans the contiguous record (pair) range shard_range(n, N, d) of the window on
-            // its own host thread; results are buffered per device and emitted in device order = record order
+            // --gpus N: device d scans a contiguous record (pair) range of the window
             struct Shard {
                 size_t r0 = 0, r1 = 0;
                 std::vector<uint8_t> keep;
                 std::vector<mk_row> rows;  // rec = index inside the shard
             };
-            std::vector<Shard> shards(ms.size());
-            for (size_t d = 0; d < ms.size(); ++d) {
-                auto [lo, hi] = shard_range(n, ms.size(), d);
-                shards[d].r0 = lo;
-                shards[d].r1 = hi;
-                shards[d].keep.assign(hi - lo, 0);
-            }
-            run_threads(ms.size(), [&](size_t d) {
-                Shard &S = shards[d];
-                scan_range(ms[d], dev_bufs[d], S.r0, S.r1, dev_c[d], dev_counts[d],
+            std::vector<Shard> shards = run_shards<Shard>(n, ms.size(), [&](size_t d, size_t lo, size_t hi, Shard &S) {
+                S.r0 = lo, S.r1 = hi;
+                S.keep.assign(hi - lo, 0);
+                scan_range(ms[d], dev_bufs[d], lo, hi, dev_c[d], dev_counts[d],
                            [&](size_t b0, uint64_t nb, const uint8_t *keep, const mk_row *rows, uint64_t n_rows) {
-                               memcpy(S.keep.data() + (b0 - S.r0), keep, nb);
+                               memcpy(S.keep.data() + (b0 - lo), keep, nb);
                                for (uint64_t k = 0; k < n_rows; ++k) {
                                    mk_row r = rows[k];
-                                   r.rec += b0 - S.r0;
+                                   r.rec += b0 - lo;
                                    S.rows.push_back(r);
                                }
                            });
@@ -530,44 +563,15 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
         fprintf(stderr, "[timing] inside the batch calls: upload %.3f s, device %.3f s, download %.3f s, host loop %.3f s\n", call_ms[0] * 1e-3,
                 call_ms[1] * 1e-3, call_ms[2] * 1e-3, call_ms[3] * 1e-3);
     report_order_paths(ms);
-    if (lg.active) {
-        lg.text.flush();
-        write_summary(lg.text, pats, counts, c, paired);
-    }
-    if (lg.has_json) {  // src/cmd_extract.rs:673-714
-        Json files = Json::object();
-        files.set("kmer_file", a.kmer_file ? Json::string(*a.kmer_file) : Json::null());
-        files.set("record_file_1", Json::string(name1));
-        files.set("record_file_2", paired ? Json::string(name2) : Json::null());
-        Json meta = Json::object();
-        meta.set("program", Json::string(kProgram)).set("version", Json::string(kVersion));
-        meta.set("timestamp", Json::string(timestamp_now())).set("subcommand", Json::string("extract"));
-        meta.set("command_line", command_line_json(argv));
-        meta.set("search_algorithm", Json::string(use_ac ? "Aho-Corasick" : "BNDMq"));
-        meta.set("inverted_matching", Json::boolean(a.invert_match)).set("case_insensitive", Json::boolean(a.case_insensitive));
-        meta.set("input_files", files);
-        Json cj = Json::object();
-        size_t found = 0;
-        for (size_t k = 0; k < counts.size(); ++k) {
-            cj.set(pats.list[k], Json::integer(counts[k]));
-            found += counts[k] > 0;
-        }
-        Json sum = Json::object();
-        sum.set("number_of_patterns_searched", Json::integer((long long)pats.list.size()));
-        sum.set("number_of_patterns_found", Json::integer((long long)found));
-        sum.set("number_of_records_searched", Json::integer((long long)c.nb_records_tot));
-        sum.set("number_of_characters_searched", Json::integer((long long)c.nb_bases));
-        sum.set("number_of_matches", Json::integer((long long)(c.nb_hits_tot[0] + c.nb_hits_tot[1])));
-        sum.set("number_of_distinct_records_with_a_hit", Json::integer((long long)(c.nb_records_hit[0] + c.nb_records_hit[1])));
-        Json pe = Json::object();
-        pe.set("searching_paired_end_reads", Json::boolean(paired));
-        pe.set("number_of_hits_in_file_1", Json::integer((long long)c.nb_hits_tot[0]));
-        pe.set("number_of_hits_in_file_2", paired ? Json::integer((long long)c.nb_hits_tot[1]) : Json::null());
-        pe.set("number_of_distinct_records_with_a_hit_in_file_1", Json::integer((long long)c.nb_records_hit[0]));
-        pe.set("number_of_distinct_records_with_a_hit_in_file_2", paired ? Json::integer((long long)c.nb_records_hit[1]) : Json::null());
-        pe.set("number_of_extracted_records", Json::integer((long long)c.nb_records_extracted));
-        lg.json.finalize(meta, cj, sum, &pe);
-    }
+    Json files = Json::object(), pe = Json::object();
+    files.set("record_file_1", Json::string(name1)).set("record_file_2", paired ? Json::string(name2) : Json::null());
+    pe.set("searching_paired_end_reads", Json::boolean(paired));
+    pe.set("number_of_hits_in_file_1", Json::integer((long long)c.nb_hits_tot[0]));
+    pe.set("number_of_hits_in_file_2", paired ? Json::integer((long long)c.nb_hits_tot[1]) : Json::null());
+    pe.set("number_of_distinct_records_with_a_hit_in_file_1", Json::integer((long long)c.nb_records_hit[0]));
+    pe.set("number_of_distinct_records_with_a_hit_in_file_2", paired ? Json::integer((long long)c.nb_records_hit[1]) : Json::null());
+    pe.set("number_of_extracted_records", Json::integer((long long)c.nb_records_extracted));
+    finish_logs(lg, a, "extract", argv, use_ac, pats, counts, c, paired, files, nullptr, &pe);
     release_matchers(ms);
     return 0;
 }
@@ -710,10 +714,8 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
                     continue;
                 }
                 mk_check(rc, "Error during matching");
-                cc.nb_records_tot += cb.nb_records_tot; cc.nb_bases += cb.nb_bases;
-                cc.nb_hits_tot[0] += cb.nb_hits_tot[0]; cc.nb_records_hit[0] += cb.nb_records_hit[0];
-                cc.nb_records_extracted += cb.nb_records_extracted;
-                for (size_t k = 0; k < cnts.size(); ++k) cnts[k] += cnt_b[k];
+                add_counters(cc, cb);
+                add_counts(cnts, cnt_b);
                 break;
             }
             if (ms.size() == 1) tm.mark("  batch: mk_tag_records");
@@ -841,13 +843,10 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
                 tm.mark("  batch: rows + write");
             });
         } else {
-            // --gpus N: contiguous record ranges of the window per device, one host thread each; batch results
-            // are kept per device and emitted in device order = record order
-            std::vector<std::vector<BatchOut>> outs(ms.size());
-            run_threads(ms.size(), [&](size_t d) {
-                auto [lo, hi] = shard_range(n, ms.size(), d);
+            // --gpus N: device d scans and tags a contiguous record range of the window
+            auto outs = run_shards<std::vector<BatchOut>>(n, ms.size(), [&](size_t d, size_t lo, size_t hi, std::vector<BatchOut> &out) {
                 scan_range(ms[d], dev_bufs[d], lo, hi, dev_c[d], dev_counts[d], std::max<size_t>(1, io_threads() / ms.size()),
-                           [&](BatchOut &&o) { outs[d].push_back(std::move(o)); });
+                           [&](BatchOut &&o) { out.push_back(std::move(o)); });
             });
             tm.mark("window: scan + tag on all devices");
             for (auto &v : outs)
@@ -874,36 +873,9 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
     if (getenv("MERKURIO_TIMING") && bgzf_device_seconds() > 0)
         fprintf(stderr, "[timing] BGZF inflate calls of the device codec (inside the window reads): %.3f s\n", bgzf_device_seconds());
     report_order_paths(ms);
-    if (lg.active) {
-        lg.text.flush();
-        write_summary(lg.text, pats, counts, c, false);
-    }
-    if (lg.has_json) {  // src/cmd_tag.rs:650-686
-        Json files = Json::object();
-        files.set("kmer_file", a.kmer_file ? Json::string(*a.kmer_file) : Json::null());
-        files.set("record_file_1", Json::string(in_name));
-        Json meta = Json::object();
-        meta.set("program", Json::string(kProgram)).set("version", Json::string(kVersion));
-        meta.set("timestamp", Json::string(timestamp_now())).set("subcommand", Json::string("tag"));
-        meta.set("command_line", command_line_json(argv));
-        meta.set("search_algorithm", Json::string(use_ac ? "Aho-Corasick" : "BNDMq"));
-        meta.set("inverted_matching", Json::boolean(a.invert_match)).set("case_insensitive", Json::boolean(a.case_insensitive));
-        meta.set("input_files", files).set("tag", Json::string(a.tag));
-        Json cj = Json::object();
-        size_t found = 0;
-        for (size_t k = 0; k < counts.size(); ++k) {
-            cj.set(pats.list[k], Json::integer(counts[k]));
-            found += counts[k] > 0;
-        }
-        Json sum = Json::object();
-        sum.set("number_of_patterns_searched", Json::integer((long long)pats.list.size()));
-        sum.set("number_of_patterns_found", Json::integer((long long)found));
-        sum.set("number_of_records_searched", Json::integer((long long)c.nb_records_tot));
-        sum.set("number_of_characters_searched", Json::integer((long long)c.nb_bases));
-        sum.set("number_of_matches", Json::integer((long long)c.nb_hits_tot[0]));
-        sum.set("number_of_distinct_records_with_a_hit", Json::integer((long long)c.nb_records_hit[0]));
-        lg.json.finalize(meta, cj, sum, nullptr);
-    }
+    Json files = Json::object();
+    files.set("record_file_1", Json::string(in_name));
+    finish_logs(lg, a, "tag", argv, use_ac, pats, counts, c, false, files, &a.tag, nullptr);
     release_matchers(ms);
     release_matchers(seconds);
     return 0;

@@ -36,9 +36,6 @@ struct CommonArgs {
                                // (BAM records indexed and tagged on the host threads) where BAM -> BAM would keep them on the device
 };
 
-// set by main(): the process ends right after the command (handles are not destroyed one by one, commands.cpp)
-extern bool g_process_is_ending;
-
 struct ExtractArgs : CommonArgs {
     std::string in_fastx;                   // -i / -1
     std::optional<std::string> in_fastq_2;  // -2

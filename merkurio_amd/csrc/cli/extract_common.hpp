@@ -36,6 +36,18 @@ inline void mk_check(int rc, const char *what) {
     if (rc != MK_OK) bail(std::string(what) + ": " + mk_last_error());
 }
 
+// the counters and per-pattern counts of a batch / window added to a device's or the job's (the tag calls leave the file-2 halves
+// nb_hits_tot[1] / nb_records_hit[1] at zero)
+inline void add_counters(mk_counters &into, const mk_counters &from) {
+    into.nb_records_tot += from.nb_records_tot, into.nb_bases += from.nb_bases;
+    into.nb_hits_tot[0] += from.nb_hits_tot[0], into.nb_hits_tot[1] += from.nb_hits_tot[1];
+    into.nb_records_hit[0] += from.nb_records_hit[0], into.nb_records_hit[1] += from.nb_records_hit[1];
+    into.nb_records_extracted += from.nb_records_extracted;
+}
+inline void add_counts(std::vector<uint32_t> &into, const std::vector<uint32_t> &from) {
+    for (size_t k = 0; k < from.size(); ++k) into[k] += from[k];
+}
+
 struct Patterns {
     std::vector<std::string> list;
     std::vector<uint8_t> bytes;

@@ -41,18 +41,9 @@ namespace {
 
 constexpr uint64_t kFirstWindow = 8ull << 20;  // (page-locked staging needs the HIP runtime, which is still starting: a small first window)
 
-struct Pinned {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    void need(uint64_t n) {
-        if (n <= cap) return;
-        mk_host_free(p);
-        p = nullptr;
-        cap = 0;
-        mk_check(mk_host_alloc((size_t)(n + n / 8 + 4096), &p), "Error allocating page-locked memory");
-        cap = n + n / 8 + 4096;
-    }
-};
+void grow_pin(HostBuffer &b, uint64_t n) {
+    if (!b.grow(n, 4096)) bail(std::string("Error allocating page-locked memory: ") + mk_last_error());
+}
 
 // one input file as a producer of window bodies
 struct Input {
@@ -72,7 +63,7 @@ struct Input {
     const char *first_text = nullptr;  // the first raw window (prepare())
     uint64_t first_n = 0, first_resume = 0;
     bool have_first = false;
-    std::vector<Pinned> pins;
+    std::vector<HostBuffer> pins;  // page-locked staging buffers
     std::deque<int> free_pins;
 };
 
@@ -152,8 +143,8 @@ struct WindowExtract::Impl {
     // ---- reader side ---------------------------------------------------------------------------------------------------------
     // the window's bytes into pinned memory, on all host threads (page-cache pages cannot be DMA sources).  A plain file is read with
     // pread() -- the kernel copies from the page cache without a page fault per 4 KiB of a mapping --, inflated text is copied.
-    void stage(Input &I, Pinned &dst, const char *src, uint64_t n, uint64_t file_off) {
-        dst.need(n);
+    void stage(Input &I, HostBuffer &dst, const char *src, uint64_t n, uint64_t file_off) {
+        grow_pin(dst, n);
         const size_t T = std::max<size_t>(1, std::min<size_t>(io_threads(), (size_t)(n >> 22) + 1));
         const int fd = I.fd;
         run_threads(T, [&](size_t t) {
@@ -386,11 +377,8 @@ struct WindowExtract::Impl {
                     continue;
                 }
                 mk_check(rc, "Error during matching");
-                W.cb.nb_records_tot += cb.nb_records_tot, W.cb.nb_bases += cb.nb_bases;
-                W.cb.nb_hits_tot[0] += cb.nb_hits_tot[0], W.cb.nb_hits_tot[1] += cb.nb_hits_tot[1];
-                W.cb.nb_records_hit[0] += cb.nb_records_hit[0], W.cb.nb_records_hit[1] += cb.nb_records_hit[1];
-                W.cb.nb_records_extracted += cb.nb_records_extracted;
-                for (size_t q = 0; q < W.cnt.size(); ++q) W.cnt[q] += cnt_b[q];
+                add_counters(W.cb, cb);
+                add_counts(W.cnt, cnt_b);
                 break;
             }
             if (lg->active)
@@ -717,13 +705,11 @@ WindowExtract::~WindowExtract() {
     if (!impl) return;
     for (int i = 0; i < 2; ++i)
         if (impl->in[i].fd >= 0) close(impl->in[i].fd);
-    // (page-locked buffers and codec handles are not released at the end of the run: unpinning costs more than the process has left to live)
+    // (codec handles, like the page-locked buffers, are not released at the end of the run: that costs more than the process has left to live)
     if (!g_process_is_ending) {
         for (mk_codec *c : impl->codecs) mk_codec_destroy(c);
         for (int i = 0; i < 2; ++i)
             if (impl->in[i].gz_codec) mk_codec_destroy(impl->in[i].gz_codec);
-        for (int i = 0; i < 2; ++i)
-            for (Pinned &p : impl->in[i].pins) mk_host_free(p.p);
     }
     delete impl;
 }
@@ -858,7 +844,7 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             Input &I = J.in[i];
             for (size_t q = 0; q < I.pins.size(); ++q) {
                 try {
-                    I.pins[q].need(J.plain_target + (1u << 20));
+                    grow_pin(I.pins[q], J.plain_target + (1u << 20));
                 } catch (const Error &e) {
                     J.fail_all(e.what());
                     return;
@@ -897,12 +883,8 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             }
             if (!W->error.empty()) bail(W->error);
             tm.mark(W->by_host ? "window: host parser + scan" : "window: H2D + index + scan + D2H");
-            mk_counters &c = dev_c[W->dev];
-            c.nb_records_tot += W->cb.nb_records_tot, c.nb_bases += W->cb.nb_bases;
-            c.nb_hits_tot[0] += W->cb.nb_hits_tot[0], c.nb_hits_tot[1] += W->cb.nb_hits_tot[1];
-            c.nb_records_hit[0] += W->cb.nb_records_hit[0], c.nb_records_hit[1] += W->cb.nb_records_hit[1];
-            c.nb_records_extracted += W->cb.nb_records_extracted;
-            for (size_t q = 0; q < W->cnt.size(); ++q) dev_counts[W->dev][q] += W->cnt[q];
+            add_counters(dev_c[W->dev], W->cb);
+            add_counts(dev_counts[W->dev], W->cnt);
             J.write_window(*W, w1, w2, name1, name2, tm);
             {
                 std::lock_guard<std::mutex> lk(J.mu);

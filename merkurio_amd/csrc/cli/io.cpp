@@ -9,8 +9,9 @@
 
 #include "../../../include/merkurio_hip.h"
 
-// The device codec is reached through weak references: the reader / writer harnesses of the CPU tests compile this file
-// without libmerkurio_hip.so (they never select a device: set_bgzf_device / BamWriter::use_device), the CLI links it.
+// The device codec and page-locked memory are reached through weak references: the reader / writer harnesses of the CPU tests
+// compile this file without libmerkurio_hip.so (they never select a device: set_bgzf_device / BamWriter::use_device; HostBuffer
+// takes malloc's memory there), the CLI links it.
 extern "C" {
 __attribute__((weak)) int mk_codec_create(int device, mk_codec **out);
 __attribute__((weak)) void mk_codec_destroy(mk_codec *c);
@@ -33,6 +34,33 @@ __attribute__((weak)) void mk_host_free(void *p);
 
 namespace cli {
 
+
+HostBuffer &HostBuffer::operator=(HostBuffer &&o) noexcept {
+    if (this != &o) {
+        reset();
+        p = o.p, cap = o.cap, pinned = o.pinned;
+        o.p = nullptr, o.cap = 0, o.pinned = false;
+    }
+    return *this;
+}
+
+void HostBuffer::reset() {
+    if (pinned) mk_host_free(p);
+    else free(p);
+    p = nullptr, cap = 0, pinned = false;
+}
+
+bool HostBuffer::grow(size_t n, size_t headroom, bool or_malloc) {
+    if (n <= cap) return true;
+    reset();
+    const size_t want = n + n / 8 + headroom;
+    void *q = nullptr;
+    if (mk_host_alloc && mk_host_alloc(want, &q) == MK_OK) pinned = true;
+    else q = or_malloc ? malloc(want) : nullptr;
+    if (!q) return false;
+    p = (uint8_t *)q, cap = want;
+    return true;
+}
 
 static unsigned g_io_threads_cap = 0;  // 0 = no cap
 void set_io_threads_cap(unsigned n) { g_io_threads_cap = n; }
@@ -1403,49 +1431,29 @@ void BamWriter::put_encoded(std::vector<uint8_t> &&bytes) {
 
 constexpr size_t kMaxQueuedRuns = 6;
 
-void BamWriter::free_raw_buffer(RawBuffer &b) {
-    if (b.p) {
-        if (b.pinned) mk_host_free(b.p);
-        else free(b.p);
-    }
-    b = RawBuffer();
-}
-
-BamWriter::RawBuffer BamWriter::take_raw_buffer(size_t min_size) {
-    RawBuffer b;
+HostBuffer BamWriter::take_raw_buffer(size_t min_size) {
+    HostBuffer b;
     {
         std::lock_guard<std::mutex> lk(mu_);
         for (size_t k = 0; k < free_raw_.size(); ++k)
             if (free_raw_[k].cap >= min_size || k + 1 == free_raw_.size()) {
-                b = free_raw_[k];
+                b = std::move(free_raw_[k]);
                 free_raw_.erase(free_raw_.begin() + k);
                 break;
             }
     }
-    if (b.cap >= min_size) return b;
-    free_raw_buffer(b);
-    const size_t want = min_size + min_size / 8;
-    void *q = nullptr;
-    if (mk_host_alloc && mk_host_alloc(want, &q) == MK_OK) {  // (weak: the CPU harnesses link without the library)
-        b.p = (uint8_t *)q, b.cap = want, b.pinned = true;
-    } else {
-        b.p = (uint8_t *)malloc(want), b.cap = want, b.pinned = false;
-        if (!b.p) bail("Error writing BAM file: out of memory");
-    }
+    if (!b.grow(min_size, 0, true)) bail("Error writing BAM file: out of memory");
     return b;
 }
 
-void BamWriter::put_members(RawBuffer buffer, size_t used) {
-    flush(true);
+void BamWriter::put_members(HostBuffer &&buffer, size_t used) {
     Run run;
     run.raw = true;
-    run.raw_buf = buffer;
+    run.raw_buf = std::move(buffer);
     run.raw_used = used;
+    flush(true);
     std::unique_lock<std::mutex> lk(mu_);
-    if (failed_) {
-        free_raw_buffer(buffer);
-        std::rethrow_exception(failed_);
-    }
+    if (failed_) std::rethrow_exception(failed_);
     if (!writer_.joinable()) writer_ = std::thread([this] { writer_loop(); });
     cv_.wait(lk, [&] { return queue_.size() < kMaxQueuedRuns; });
     queue_.push_back(std::move(run));
@@ -1495,12 +1503,9 @@ void BamWriter::writer_loop() {
                 const bool ok = failed_ || fwrite(run.raw_buf.p, 1, run.raw_used, f) == run.raw_used;
                 {
                     std::lock_guard<std::mutex> lk(mu_);
-                    if (free_raw_.size() < 4) {
-                        free_raw_.push_back(run.raw_buf);
-                        run.raw_buf = RawBuffer();
-                    }
+                    if (free_raw_.size() < 4) free_raw_.push_back(std::move(run.raw_buf));
                 }
-                free_raw_buffer(run.raw_buf);
+                run.raw_buf.reset();  // (a fifth spare is freed now, not kept to the end of the process)
                 if (!ok) bail("Error writing BAM file");
             } else if (!failed_) {
                 compress_and_write(run);
@@ -1880,7 +1885,7 @@ void BamWriter::close() {
     fclose(f);
     f = nullptr;
     if (codec_) mk_codec_destroy((mk_codec *)codec_), codec_ = nullptr;
-    for (auto &b : free_raw_) free_raw_buffer(b);
+    for (HostBuffer &b : free_raw_) b.reset();  // (freed at close, not kept to the end of the process)
     free_raw_.clear();
     closing_ = false;
     failed_ = nullptr;

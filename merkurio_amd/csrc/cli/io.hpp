@@ -49,6 +49,28 @@ void run_threads(size_t T, F fn) {
         if (!e.empty()) bail(e);
 }
 
+// Host memory with one owner, page-locked where it can be (mk_host_alloc: the device copies from and into it directly).  Move-only;
+// the destructor frees it, except in a process that is about to end (g_process_is_ending: unpinning costs more than the process
+// has left to live).
+struct HostBuffer {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    bool pinned = false;  // mk_host_alloc's (else malloc's)
+    HostBuffer() = default;
+    HostBuffer(HostBuffer &&o) noexcept : p(o.p), cap(o.cap), pinned(o.pinned) { o.p = nullptr, o.cap = 0, o.pinned = false; }
+    HostBuffer &operator=(HostBuffer &&o) noexcept;
+    HostBuffer(const HostBuffer &) = delete;
+    HostBuffer &operator=(const HostBuffer &) = delete;
+    ~HostBuffer() {
+        if (!g_process_is_ending) reset();
+    }
+    // at least n bytes: a smaller buffer is freed and n + n / 8 + headroom bytes take its place (the contents are not kept), page-locked
+    // or, with or_malloc, from malloc where page-locked memory cannot be had.  false: no memory, the buffer is empty (mk_last_error()
+    // says why page-locking failed)
+    bool grow(size_t n, size_t headroom, bool or_malloc = false);
+    void reset();  // frees the memory now
+};
+
 // whole file into memory; transparently inflates gzip (magic 1f 8b; BGZF members in parallel) and,
 // like needletail's `compression` feature, bzip2 / xz / zstd (decompress.cpp)
 std::vector<char> read_file_maybe_gz(const std::string &path);
@@ -301,19 +323,14 @@ struct BamWriter {
     // slow part of SAM -> BAM and runs on every host thread), then put_encoded() in record order
     void encode_record(const std::string &sam_line, std::vector<uint8_t> &dst) const;
     void put_encoded(std::vector<uint8_t> &&bytes);
-    // complete BGZF members made elsewhere (mk_tag_bam_window: the tagged records deflated on the device): what has been put so
-    // far is closed with a member of its own, then these bytes follow it in the file as they are
+    // complete BGZF members made elsewhere (mk_tag_bam_window: the tagged records deflated on the device), in buffer[0, used): what
+    // has been put so far is closed with a member of its own, then these bytes follow it in the file as they are.  The buffer is the
+    // writer's from the call on, whether it returns or throws: the caller's is empty afterwards.
     // (the buffer: page-locked memory the device writes into directly -- a fresh pageable buffer costs a page fault per 4 KiB inside
     // the copy, more than the copy itself --, handed back and forth between the caller and the writer thread)
-    struct RawBuffer {
-        uint8_t *p = nullptr;
-        size_t cap = 0;
-        bool pinned = false;
-    };
-    void put_members(RawBuffer buffer, size_t used);
+    void put_members(HostBuffer &&buffer, size_t used);
     // a buffer of at least min_size bytes for such members: one the writer thread has written out, or a new one
-    RawBuffer take_raw_buffer(size_t min_size);
-    static void free_raw_buffer(RawBuffer &b);
+    HostBuffer take_raw_buffer(size_t min_size);
     // an empty buffer for the next slice of encoded records: one the writer thread is done with (its pages are mapped
     // already: a fresh 16 MB vector costs 4 000 page faults), or a new one
     std::vector<uint8_t> take_buffer();
@@ -324,7 +341,7 @@ struct BamWriter {
    private:
     struct Run : std::vector<std::vector<uint8_t>> {  // a run of whole members, as the pieces it arrived in
         bool raw = false;                               // the run IS members already (put_members) ...
-        RawBuffer raw_buf;                              // ... in the first raw_used bytes of this buffer
+        HostBuffer raw_buf;                             // ... in the first raw_used bytes of this buffer
         size_t raw_used = 0;
     };
     void put(const void *p, size_t n);
@@ -343,7 +360,7 @@ struct BamWriter {
     bool closing_ = false, busy_ = false;
     std::exception_ptr failed_;
     std::vector<std::vector<uint8_t>> free_;  // buffers of written runs (guarded by mu_)
-    std::vector<RawBuffer> free_raw_;  // buffers of written raw runs (guarded by mu_)
+    std::vector<HostBuffer> free_raw_;  // buffers of written raw runs (guarded by mu_)
 };
 
 }  // namespace cli

@@ -32,25 +32,6 @@ namespace cli {
 
 namespace {
 
-struct PinnedBuffer {
-    uint8_t *p = nullptr;
-    uint64_t cap = 0;
-    ~PinnedBuffer() {
-        if (p && !g_process_is_ending) mk_host_free(p);
-    }
-    void need(uint64_t n) {
-        if (n <= cap) return;
-        if (p) mk_host_free(p);
-        p = nullptr;
-        cap = 0;
-        void *q = nullptr;
-        const uint64_t want = n + n / 8 + (1u << 20);
-        if (mk_host_alloc(want, &q) != MK_OK) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
-        p = (uint8_t *)q;
-        cap = want;
-    }
-};
-
 // members [m0, m1) of the file: their table re-based to the first one's DEFLATE stream, and that byte range of the file
 struct WindowMembers {
     size_t m0 = 0, m1 = 0;
@@ -149,13 +130,8 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
                 if (!g_process_is_ending) mk_codec_destroy(c);
             }
         } guard{codec};
-        PinnedBuffer stage;
+        HostBuffer stage, out;  // the window's members (page-locked); the members it turns into (moved to the writer)
         std::vector<uint8_t> tail(1u << 20), names(1u << 16);
-        BamWriter::RawBuffer out;
-        struct OutGuard {
-            BamWriter::RawBuffer &b;
-            ~OutGuard() { BamWriter::free_raw_buffer(b); }
-        } out_guard{out};
         std::vector<mk_row> rows(4096);
         std::vector<uint64_t> row_name(4096);
         for (size_t k = id; k < n_win; k += n_workers) {
@@ -165,11 +141,11 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
                 if (pipe.stop) return;
             }
             if (!X.mem.empty()) {
-                stage.need(X.file_hi - X.file_lo);
+                if (!stage.grow(X.file_hi - X.file_lo, 1u << 20)) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
                 copy_in(file, X.file_lo, X.file_hi, stage.p);
             }
             if (bw && out.cap < out_guess(X.text + (1u << 20))) {
-                BamWriter::free_raw_buffer(out);
+                out.reset();
                 out = bw->take_raw_buffer(out_guess(X.text + (1u << 20)));
             }
             std::vector<uint8_t> head;
@@ -203,7 +179,7 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
                 bool grew = false;
                 if (w.n_tail > tail.size()) tail.resize(w.n_tail + (1u << 20)), grew = true;
                 if (bw && w.out_len > out.cap) {
-                    BamWriter::free_raw_buffer(out);
+                    out.reset();
                     out = bw->take_raw_buffer(w.out_len);
                     grew = true;
                 }
@@ -239,9 +215,8 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
             }
             lk.unlock();
             // (only the worker whose turn it is gets here: the counters of its device, the loggers and the writer are its alone)
-            c.nb_records_tot += wc.nb_records_tot, c.nb_bases += wc.nb_bases, c.nb_hits_tot[0] += wc.nb_hits_tot[0];
-            c.nb_records_hit[0] += wc.nb_records_hit[0], c.nb_records_extracted += wc.nb_records_extracted;
-            for (size_t i = 0; i < wcounts.size(); ++i) counts[i] += wcounts[i];
+            add_counters(c, wc);
+            add_counts(counts, wcounts);
             for (int i = 0; i < 8; ++i) t_dev[i] += w.ms[i];
             std::string emit_err;
             try {
@@ -253,10 +228,7 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
                             return std::pair<const char *, size_t>(nm, strlen(nm));
                         },
                         [&](const mk_row &) -> const std::string & { return in_name; });
-                if (bw && w.out_len) {
-                    bw->put_members(out, w.out_len);
-                    out = BamWriter::RawBuffer();
-                }
+                if (bw && w.out_len) bw->put_members(std::move(out), w.out_len);
             } catch (const Error &e) {
                 emit_err = e.what()[0] ? e.what() : "error";
             }

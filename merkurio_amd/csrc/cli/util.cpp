@@ -8,6 +8,8 @@
 
 namespace cli {
 
+bool g_process_is_ending = false;
+
 std::string file_name(const std::string &path) {
     size_t e = path.size();
     while (e > 0 && path[e - 1] == '/') --e;

@@ -17,6 +17,9 @@ struct Error : std::runtime_error {
 };
 [[noreturn]] inline void bail(const std::string &msg) { throw Error(msg); }
 
+// set by main(): the process ends right after the command (handles and page-locked buffers are not freed one by one, commands.cpp)
+extern bool g_process_is_ending;
+
 // ---- paths (std::path semantics used by the reference) -------------------------------------
 std::string file_name(const std::string &path);                   // Path::file_name
 std::string extension(const std::string &path);                   // Path::extension ("" if none)

@@ -5,12 +5,28 @@
 // usage: harness <in.sam> <out.bam> <records per piece> [members per run of the writer queue, default 1536]
 //        harness --members <header.sam> <out.bam> <file of finished BGZF members>...: the header through the writer, then members made
 //        elsewhere passed through as they are (BamWriter::put_members: what `tag` does with the members the device hands back)
+//        harness --failing-sink <header.sam> <out> <file of finished BGZF members>: the same into a sink whose writes fail (/dev/full),
+//        until put_members throws the writer thread's error (at most 64 puts); then close()
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
 #include "io.hpp"
 using namespace cli;
+
+// a file's bytes into a buffer of the writer's (larger than its content by `spare`: recycled ones)
+static size_t read_members(BamWriter &bw, const char *path, size_t spare, HostBuffer &b) {
+    FILE *g = fopen(path, "rb");
+    if (!g) bail(std::string("cannot open ") + path);
+    fseek(g, 0, SEEK_END);
+    const size_t n = (size_t)ftell(g);
+    fseek(g, 0, SEEK_SET);
+    b = bw.take_raw_buffer(n + spare);
+    if (fread(b.p, 1, n, g) != n) bail("short read");
+    fclose(g);
+    return n;
+}
+
 int main(int argc, char **argv) {
     try {
         if (argc > 3 && std::string(argv[1]) == "--members") {
@@ -19,18 +35,37 @@ int main(int argc, char **argv) {
             BamWriter bw;
             bw.open(argv[3], h.header);
             for (int k = 4; k < argc; ++k) {
-                FILE *g = fopen(argv[k], "rb");
-                if (!g) bail(std::string("cannot open ") + argv[k]);
-                fseek(g, 0, SEEK_END);
-                const size_t n = (size_t)ftell(g);
-                fseek(g, 0, SEEK_SET);
-                BamWriter::RawBuffer b = bw.take_raw_buffer(n + (k % 2 ? 100000 : 0));  // (buffers larger than their content; recycled ones)
-                if (fread(b.p, 1, n, g) != n) bail("short read");
-                fclose(g);
-                bw.put_members(b, n);
+                HostBuffer b;
+                const size_t n = read_members(bw, argv[k], k % 2 ? 100000 : 0, b);
+                bw.put_members(std::move(b), n);
             }
             bw.close();
             printf("#members files %d\n", argc - 4);
+            return 0;
+        }
+        if (argc == 5 && std::string(argv[1]) == "--failing-sink") {
+            SamFile h;
+            h.open(argv[2]);
+            BamWriter bw;
+            bw.open(argv[3], h.header);
+            int puts = 0;
+            for (; puts < 64; ++puts) {
+                HostBuffer b;
+                const size_t n = read_members(bw, argv[4], 0, b);
+                try {
+                    bw.put_members(std::move(b), n);
+                } catch (const Error &e) {
+                    printf("#put_members error: %s; caller's buffer %s\n", e.what(), b.p || b.cap ? "kept" : "empty");
+                    break;
+                }
+            }
+            if (puts == 64) printf("#put_members never failed\n");
+            try {
+                bw.close();
+                printf("#close ok\n");
+            } catch (const Error &e) {
+                printf("#close error: %s\n", e.what());
+            }
             return 0;
         }
         SamFile f;

@@ -320,12 +320,15 @@ def test_windowed_sam_bam_reader(tmp_path, golden):
     assert run_h("bigbroken.bam", 1 << 30).rsplit("#windows", 1)[0] == run_h("bigbroken.bam", 1 << 22).rsplit("#windows", 1)[0]
 
 
-def test_bam_writer_pieces_queue_and_encoder(tmp_path):
+def test_bam_writer_pieces_queue_encoder_and_members(tmp_path):
     """BamWriter without a device (the --host-codec path; the device path differs in the deflate call only): records
     encoded by the allocation-free encoder, handed over in pieces of 1 / 7 / 5 000 records or one by one, cut into 65 280-byte
     members by the writer's queue and thread -- the BAM gunzips to the same stream whatever the pieces, its members are
     whole BGZF members with an end-of-file marker, and the records read back (SamFile) are the SAM lines that went in,
-    optional fields of every type included."""
+    optional fields of every type included.  Finished members put into the writer (put_members) follow the header as they are;
+    put into a file whose writes fail (/dev/full), put_members raises the writer thread's error, the caller's buffer is the
+    writer's from the call on (empty afterwards), close() raises the same error, and nothing is freed twice or leaked
+    (MERKURIO_TEST_SANITIZE=1: ASan + UBSan)."""
     import gzip
     import random
     import struct
@@ -398,6 +401,12 @@ def test_bam_writer_pieces_queue_and_encoder(tmp_path):
     hdr_stream = streams[0][:streams[0].index(b"read0/x") - 36]  # the BAM header as the first runs wrote it (records start 36 bytes in front of the first name)
     assert gzip.decompress(raw) == hdr_stream + b"".join(payloads)
     assert raw.endswith(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+    # the write-error path: members of random bytes (each put is more than stdio buffers, so it reaches the file at once)
+    (tmp_path / "rand.bin").write_bytes(bgzf(random.Random(5).randbytes(4 * 0xff00)))
+    r = subprocess.run([wexe, "--failing-sink", str(tmp_path / "h.sam"), "/dev/full", str(tmp_path / "rand.bin")], capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    assert r.stdout.split("\n")[:2] == ["#put_members error: Error writing BAM file; caller's buffer empty", "#close error: Error writing BAM file"], \
+        (r.stdout, r.stderr)
 
 
 def test_log_rows_are_formatted_like_serde_json(tmp_path):
