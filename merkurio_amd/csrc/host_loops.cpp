@@ -103,19 +103,25 @@ struct DeviceLoop {
         if ((rc = batch_upload(m, seq, off, n_rec, n_bytes, &batch_len))) return rc;
         if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload failed");
         mark(1);
-        // all tuples stay on the device: no caller-side limit.  The scan starts with the room the handle already has
-        // (hit-dense batches -- tag / extract -l on already extracted reads -- overflowed n_rec / 8 on EVERY batch and
-        // ran their scan twice; after the first such batch one scan suffices)
-        const uint64_t cap0 = std::max<uint64_t>(std::max<uint64_t>(4096, n_rec / 8), m->d_hits_cap / sizeof(mk_hit));
-        if ((rc = batch_scan(m, n_bytes, n_rec, mode, batch_len, cap0, ~0ull, &found))) return rc;
-        mark(2);
-        if ((rc = batch_flags(m, n_rec, flags, flagged))) return rc;
-        mark(1);
-        return MK_OK;
+        return scan_flags(n_rec, mode, batch_len, flags, flagged);
     }
-    // the batch is already in m->d_seq / m->d_off (ingest.hip put it there): scan + flags
+    // the batch is already in m->d_seq / m->d_off (ingest.hip put it there; batch_len > 0: every record has that length): scan + flags
     int scan_resident(uint64_t n_seq_bytes, uint64_t n_rec, uint32_t mode, uint32_t batch_len, uint8_t *flags, uint64_t *flagged) {
         n_bytes = n_seq_bytes;
+        m->ragged = !batch_len;
+        *flagged = 0;
+        if (n_bytes == 0) {  // every sequence is empty: nothing can match
+            std::fill(flags, flags + n_rec, 0);
+            found = 0;
+            if (n_rec && hipMemsetAsync(m->d_flags, 0, n_rec, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
+            return MK_OK;
+        }
+        return scan_flags(n_rec, mode, batch_len, flags, flagged);
+    }
+    // the scan of the batch on the device and its flags -> host.  All tuples stay on the device: no caller-side limit.  The scan starts
+    // with the room the handle already has (hit-dense batches -- tag / extract -l on already extracted reads -- overflowed n_rec / 8 on
+    // EVERY batch and ran their scan twice; after the first such batch one scan suffices)
+    int scan_flags(uint64_t n_rec, uint32_t mode, uint32_t batch_len, uint8_t *flags, uint64_t *flagged) {
         const uint64_t cap0 = std::max<uint64_t>(std::max<uint64_t>(4096, n_rec / 8), m->d_hits_cap / sizeof(mk_hit));
         int rc = batch_scan(m, n_bytes, n_rec, mode, batch_len, cap0, ~0ull, &found);
         if (rc) return rc;
@@ -124,15 +130,17 @@ struct DeviceLoop {
         mark(1);
         return MK_OK;
     }
-    int order(bool ac_order) { return order_hits_on_device(m, m->d_hits, found, ac_order, st); }
+    // rec_bound: the records the tuples come from (the bins of the ordering)
+    int order(bool ac_order, uint64_t rec_bound) { return order_hits_on_device(m, m->d_hits, found, ac_order, rec_bound, st); }
 
-    // mk_row per tuple (in their current order) -> rows[0, min(found, cap))
-    int rows_to_host(uint32_t file, mk_row *rows, uint64_t cap) {
+    // mk_row per tuple (in their current order) -> rows[0, min(found, cap)); pair: the marked pair list (sets.hip), rows with their mate
+    int rows_to_host(mk_row *rows, uint64_t cap, bool pair = false) {
         const uint64_t n = std::min<uint64_t>(found, rows ? cap : 0);
         if (!n) return MK_OK;
         int rc = ensure_device(&m->d_aux, &m->d_aux_cap, n * sizeof(mk_row));
         if (rc) return rc;
-        launch_rows(m->d_hits, n, file, (mk_row *)m->d_aux, st);
+        if (pair) launch_rows_pair(m->d_hits, n, m->algo == MK_ALGO_AC, (mk_row *)m->d_aux, st);
+        else launch_rows(m->d_hits, n, 0, (mk_row *)m->d_aux, st);
         if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "row kernel failed");
         mark(2);
         if (hipMemcpy(rows, m->d_aux, n * sizeof(mk_row), hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the log rows failed");
@@ -140,41 +148,79 @@ struct DeviceLoop {
         return MK_OK;
     }
 
-    // paired extract: the marked pair list (sets.hip) -> rows with their mate
-    int pair_rows_to_host(bool ac, mk_row *rows, uint64_t cap) {
-        const uint64_t n = std::min<uint64_t>(found, rows ? cap : 0);
-        if (!n) return MK_OK;
-        int rc = ensure_device(&m->d_aux, &m->d_aux_cap, n * sizeof(mk_row));
-        if (rc) return rc;
-        launch_rows_pair(m->d_hits, n, ac, (mk_row *)m->d_aux, st);
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "row kernel failed");
-        mark(2);
-        if (hipMemcpy(rows, m->d_aux, n * sizeof(mk_row), hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the log rows failed");
+    // counts[i] += the n_pat counts at d_counts (u32; wide: u64, of which the low words count); the copy is charged to the download,
+    // the sums to the host.  d_counts == nullptr: nothing to add.
+    int add_counts(const void *d_counts, bool wide, uint32_t *counts) {
+        const uint32_t n_pat = m->n_pat, stride = wide ? 2 : 1;
+        std::vector<uint32_t> v(d_counts ? (size_t)n_pat * stride : 0);
+        if (!v.empty() && hipMemcpy(v.data(), d_counts, v.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
+        mark(3);
+        for (size_t i = 0; i < v.size(); i += stride) counts[i / stride] += v[i];
         mark(1);
         return MK_OK;
     }
-    // pattern_hit_counts of the ordered pair list: AC one per hit of either mate (:492,:520); BNDMq one per pair,
-    // pattern and mate with a hit (:575-584)
-    int pair_counts(bool ac, uint32_t *counts) {
-        const uint32_t n_pat = m->n_pat;
+
+    // counters of one file's scan of n_rec records (single :326-387, tag :443-451), its tuples in emission order (AC / BNDMq)
+    // and their log rows
+    int log_single(mk_counters *c, uint64_t n_rec, uint64_t n_bases, uint64_t flagged, mk_row *rows, uint64_t rows_cap) {
+        c->nb_records_tot += n_rec;
+        c->nb_bases += n_bases;
+        c->nb_hits_tot[0] += found;
+        c->nb_records_hit[0] += flagged;
+        int rc = order(m->algo == MK_ALGO_AC, n_rec);
+        if (rc) return rc;
+        return rows_to_host(rows, rows_cap);
+    }
+
+    // paired extract, after mate 1's scan: its tuples wait in their own buffer while mate 2 is scanned
+    int stash_mate1() {
+        if (!found) return MK_OK;
+        int rc = ensure_device(&m->d_pair, &m->d_pair_cap, found * sizeof(mk_hit));
+        if (rc) return rc;
+        if (hipMemcpyAsync(m->d_pair, m->d_hits, found * sizeof(mk_hit), hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "copy of the first mate's tuples failed");
+        return MK_OK;
+    }
+
+    // paired extract, after mate 2's scan of n_rec records (stash_mate1 kept mate 1's n1 tuples): one list -- mate 2's tuples (already
+    // in the scan buffer), then mate 1's, the mate marked inside a key field -- in pair order, its log rows and pattern_hit_counts:
+    // AC one per hit of either mate (:492,:520); BNDMq one per pair, pattern and mate with a hit (:575-584)
+    int join_mates(unsigned long long n1, uint64_t n_rec, mk_row *rows, uint64_t rows_cap, uint32_t *counts) {
+        const bool ac = m->algo == MK_ALGO_AC;
+        const unsigned long long n2 = found;
+        if (n1 + n2 == 0) return MK_OK;
+        int rc;
+        if ((n1 + n2) * sizeof(mk_hit) > m->d_hits_cap) {  // grow the scan buffer, keeping mate 2's tuples
+            void *bigger = nullptr;
+            size_t cap = 0;
+            if ((rc = ensure_device(&bigger, &cap, (n1 + n2) * sizeof(mk_hit)))) return rc;
+            if (n2 && hipMemcpy(bigger, m->d_hits, n2 * sizeof(mk_hit), hipMemcpyDeviceToDevice) != hipSuccess) {
+                (void)hipFree(bigger);
+                return fail(MK_E_HIP, "copy of the second mate's tuples failed");
+            }
+            if (m->d_hits) (void)hipFree(m->d_hits);
+            m->d_hits = (mk_hit *)bigger;
+            m->d_hits_cap = cap;
+        }
+        if (n1 && hipMemcpyAsync(m->d_hits + n2, m->d_pair, n1 * sizeof(mk_hit), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(MK_E_HIP, "copy of the first mate's tuples failed");
+        launch_pair_mark(m->d_hits, n2, 1, ac, st);
+        launch_pair_mark(m->d_hits + n2, n1, 0, ac, st);
+        found = n1 + n2;
+        if ((rc = order(ac, ac ? 2 * n_rec : n_rec))) return rc;  // (AC: record' = 2 * record + mate)
+        if ((rc = rows_to_host(rows, rows_cap, true))) return rc;
         if (ac) {
             unsigned long long n = found;  // the histogram kernel reads the tuple count from the device
             if (hipMemcpyAsync(m->d_nhits, &n, sizeof(n), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
                 return fail(MK_E_HIP, "copy failed");
             return pattern_counts(true, 0, counts);
         }
-        int rc = ensure_device(&m->d_aux, &m->d_aux_cap, (size_t)n_pat * 4);
-        if (rc) return rc;
-        if (hipMemsetAsync(m->d_aux, 0, (size_t)n_pat * 4, st) != hipSuccess) return fail(MK_E_HIP, "memset failed");
-        launch_count_pair_heads(m->d_hits, found, (uint32_t *)m->d_aux, n_pat, st);
-        std::vector<uint32_t> v(n_pat);
+        if ((rc = ensure_device(&m->d_aux, &m->d_aux_cap, (size_t)m->n_pat * 4))) return rc;
+        if (hipMemsetAsync(m->d_aux, 0, (size_t)m->n_pat * 4, st) != hipSuccess) return fail(MK_E_HIP, "memset failed");
+        launch_count_pair_heads(m->d_hits, found, (uint32_t *)m->d_aux, m->n_pat, st);
         if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "count kernel failed");
         mark(2);
-        if (hipMemcpy(v.data(), m->d_aux, (size_t)n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
-        mark(3);
-        for (uint32_t i = 0; i < n_pat; ++i) counts[i] += v[i];
-        mark(1);
-        return MK_OK;
+        return add_counts(m->d_aux, false, counts);
     }
 
     // pattern_hit_counts += this batch's: per hit (AC, src/cmd_extract.rs:353) or per (record, pattern) with a hit
@@ -194,14 +240,9 @@ struct DeviceLoop {
             p.counters = (unsigned long long *)m->d_aux;
             p.n_pat = n_pat;
             launch_hist_hits(p, m->num_cus, st);
-            std::vector<unsigned long long> v(n_pat);
             if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "histogram kernel failed");
             mark(2);
-            if (hipMemcpy(v.data(), m->d_aux, (size_t)n_pat * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
-            mark(3);
-            for (uint32_t i = 0; i < n_pat; ++i) counts[i] += (uint32_t)v[i];
-            mark(1);
-            return MK_OK;
+            return add_counts(m->d_aux, true, counts);
         }
         // BNDMq: the heads of the (record, pattern) runs = the entries of the pattern sets
         uint64_t n_found = 0;
@@ -243,26 +284,34 @@ struct DeviceLoop {
 
     // the same, copied to the host.  found_off == nullptr: only the counts.
     int pattern_sets(uint64_t n_rec, uint64_t *found_off, uint32_t *found_pat, uint64_t found_cap, uint64_t *n_found, uint32_t *counts) {
-        const uint32_t n_pat = m->n_pat;
         const size_t off_bytes = (n_rec + 1) * 8;
         unsigned long long *d_off = nullptr;
         uint32_t *d_pat = nullptr, *d_cnt = nullptr;
         int rc = pattern_sets_device(n_rec, counts != nullptr, &d_off, &d_pat, &d_cnt, n_found);
         if (rc) return rc;
         const uint64_t total = *n_found;
-        std::vector<uint32_t> v;
-        if (counts && total) v.resize(n_pat);
         mark(2);
         if (found_off && hipMemcpy(found_off, d_off, off_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the set offsets failed");
         const uint64_t n_copy = std::min<uint64_t>(total, found_pat ? found_cap : 0);
         if (n_copy && hipMemcpy(found_pat, d_pat, n_copy * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the sets failed");
-        if (!v.empty() && hipMemcpy(v.data(), d_cnt, (size_t)n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
-        mark(3);
-        for (size_t i = 0; i < v.size(); ++i) counts[i] += v[i];
-        mark(1);
-        return MK_OK;
+        return add_counts(counts && total ? d_cnt : nullptr, false, counts);
     }
 };
+
+// keep flags of the extract loop (single :400-405, paired :600-606; f2 == nullptr: single): a record -- a pair -- is kept when it has
+// a hit, or under -v when it has none, and counts once per record, twice per pair
+void extract_keep(const uint8_t *f1, const uint8_t *f2, uint64_t n, int invert, uint8_t *keep, mk_counters *c) {
+    for (uint64_t r = 0; r < n; ++r) {
+        const bool hit = f1[r] || (f2 && f2[r]);
+        keep[r] = (uint8_t)(hit != (invert != 0));
+        c->nb_records_extracted += (f2 ? 2u : 1u) * keep[r];
+    }
+}
+
+int check_rows_cap(int logging, const mk_row *rows, uint64_t rows_cap, uint64_t need) {
+    if (logging && rows && need > rows_cap) return fail(MK_E_CAPACITY, "rows buffer too small: need %llu", (unsigned long long)need);
+    return MK_OK;
+}
 
 }  // namespace
 
@@ -281,26 +330,16 @@ int mk_extract_single(mk_matcher *m, const uint8_t *seq, const uint64_t *off, ui
     int rc = dl.scan(seq, off, n_rec, logging ? MK_MODE_HITS : MK_MODE_ANY, flags.data(), &flagged);
     if (rc) return rc;
     if (logging) {
-        c->nb_records_tot += n_rec;              // :326
-        c->nb_bases += off[n_rec] - off[0];      // :327
-        c->nb_hits_tot[0] += dl.found;           // :354 / :378
-        c->nb_records_hit[0] += flagged;         // :358-360 / :385-387
         // rows in emission order (:338-351 / :369-377) and pattern_hit_counts: AC one per hit (:353), BNDMq one per
         // record and pattern (:380-383) -- BNDMq's emission order is the set order, so its heads are counted in place
-        if ((rc = dl.order(m->algo == MK_ALGO_AC))) return rc;
-        if ((rc = dl.rows_to_host(0, rows, rows_cap))) return rc;
+        if ((rc = dl.log_single(c, n_rec, off[n_rec] - off[0], flagged, rows, rows_cap))) return rc;
         if ((rc = dl.pattern_counts(m->algo == MK_ALGO_AC, n_rec, counts))) return rc;
     }
     dl.host_begin();
-    for (uint64_t r = 0; r < n_rec; ++r) {  // :400-405
-        keep[r] = (uint8_t)((flags[r] != 0) != (invert != 0));
-        c->nb_records_extracted += keep[r];
-    }
+    extract_keep(flags.data(), nullptr, n_rec, invert, keep, c);
     dl.finish();
     if (n_rows) *n_rows = dl.found;
-    if (logging && rows && dl.found > rows_cap)
-        return fail(MK_E_CAPACITY, "rows buffer too small: need %llu", (unsigned long long)dl.found);
-    return MK_OK;
+    return check_rows_cap(logging, rows, rows_cap, dl.found);
     MK_ABI_END
 }
 
@@ -308,25 +347,6 @@ int mk_extract_single(mk_matcher *m, const uint8_t *seq, const uint64_t *off, ui
 // input file go to the device as they are (plain text is uploaded, BGZF members are inflated there), are indexed and gathered on
 // the device (ingest.hip), then the extract loop runs as in mk_extract_single / mk_extract_paired
 }  // extern "C"
-
-namespace mk {
-void launch_ingest_count(const uint8_t *d_text, uint64_t n, uint32_t *d_block_cnt, uint32_t *d_total, hipStream_t st);
-void launch_ingest_records(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start,
-                           uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start, uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st);
-void launch_ingest_lines(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start, hipStream_t st);
-void launch_ingest_offsets(const uint32_t *d_seq_len, uint64_t n_rec, unsigned long long *d_tile, unsigned long long *d_off, hipStream_t st);
-void launch_ingest_gather(const uint8_t *d_text, const uint32_t *d_seq_start, const uint32_t *d_seq_len, const unsigned long long *d_off,
-                          uint32_t fixed_len, uint64_t n_rec, uint8_t *d_seq, hipStream_t st, uint32_t skip_from = 0xFFFFFFFFu);
-void launch_ingest_select(const uint8_t *d_flags, uint32_t invert, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
-                          hipStream_t st);
-void launch_ingest_fasta_count(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                               unsigned long long *d_block64, hipStream_t st);
-void launch_ingest_fasta_emit(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                              unsigned long long *d_block64, uint8_t *d_seq, uint32_t *d_rec_start, unsigned long long *d_off, hipStream_t st);
-void launch_ingest_or_flags(uint8_t *d_flags, const uint8_t *d_other, uint64_t n, hipStream_t st);
-uint32_t ingest_block_bytes();
-uint32_t ingest_scan_tile();
-}  // namespace mk
 
 namespace {
 
@@ -342,7 +362,7 @@ struct WindowSide {
     uint64_t seq_total = 0; // FASTA: sequence bytes of all records
     uint32_t *d_block = nullptr, *d_total = nullptr, *d_st = nullptr, *d_line = nullptr, *d_rec_start = nullptr, *d_seq_start = nullptr,
              *d_seq_len = nullptr;
-    unsigned long long *d_tile = nullptr, *d_block64 = nullptr, *d_fa_off = nullptr;
+    unsigned long long *d_tile = nullptr, *d_block64 = nullptr, *d_fa_off = nullptr;  // d_fa_off: FASTA's sequence offsets
 };
 
 constexpr uint32_t kBigRecord = 1u << 20;  // records from here on are copied one by one when the kept records are packed
@@ -528,51 +548,49 @@ int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide
     return MK_OK;
 }
 
-// the first n records of side W -> m->d_seq / m->d_off, scanned: flags (host + m->d_flags), tuples in m->d_hits (dl.found)
-int window_scan(mk_matcher *m, uint32_t format, WindowSide &W, uint64_t n, DeviceLoop &dl, uint32_t mode, uint8_t *flags, uint64_t *flagged, uint64_t *n_seq_out) {
+// exclusive scan of d_len[0, n) -> d_off[0, n], its total d_off[n] -> *total (enqueued work waited for; `what`: the message of a failure)
+int scan_offsets(const uint32_t *d_len, uint64_t n, unsigned long long *d_tile, unsigned long long *d_off, hipStream_t st, unsigned long long *total,
+                 const char *what) {
+    launch_ingest_offsets(d_len, n, d_tile, d_off, st);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "%s", what);
+    return MK_OK;
+}
+
+// the sequences of W's first n records -> the scan buffer, scanned: flags (host + m->d_flags), tuples in m->d_hits (dl.found), *n_seq
+// sequence bytes.  FASTQ / BAM (bam: 4-bit codes, unpacked) are gathered by W.d_seq_start / W.d_seq_len (W.fixed > 0: all of that
+// length); FASTA's were compacted by the index step.
+int scan_sequences(mk_matcher *m, const WindowSide &W, uint64_t n, bool bam, DeviceLoop &dl, uint32_t mode, uint8_t *flags, uint64_t *flagged,
+                   uint64_t *n_seq) {
     hipStream_t st = dl.st;
+    const uint32_t fixed = W.fixed;
+    unsigned long long total = (unsigned long long)n * fixed;
     int rc;
-    unsigned long long n_seq = 0;
-    if ((rc = ensure_device((void **)&m->d_flags, &m->d_flags_cap, n + 8))) return rc;
-    uint32_t fixed = 0;
-    if (format == MK_TEXT_FASTA) {
-        // (the sequences were compacted into d_seq by the index step; their offsets become the batch's)
-        if ((rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = ensure_device((void **)&m->d_flags, &m->d_flags_cap, n + 8)) || (rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t))))
+        return rc;
+    if (W.d_fa_off) {  // FASTA: the offsets of the compacted sequences become the batch's
         if (hipMemcpyAsync(m->d_off, W.d_fa_off, (n + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(&n_seq, W.d_fa_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            hipMemcpyAsync(&total, W.d_fa_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return fail(MK_E_HIP, "copy of the sequence offsets failed");
-    } else {
-        fixed = W.fixed;
-        n_seq = (unsigned long long)n * fixed;
-        if ((rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t)))) return rc;
-        if (!fixed) {
-            launch_ingest_offsets(W.d_seq_len, n, W.d_tile, (unsigned long long *)m->d_off, st);
-            if (hipMemcpyAsync(&n_seq, m->d_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                return fail(MK_E_HIP, "offset scan failed");
-        }
-        launch_ingest_gather((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
-        if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "ingest kernels failed to launch");
+        *n_seq = total;
+        // (one record of 4 GiB or more cannot be addressed by mk_hit.pos, as mk_scan_batch refuses it.)  The sequences lie in the
+        // slot's own buffer: it stands in for the scan buffer for this scan.
+        mk_matcher::TextSlot &T = *W.T;
+        void *seq = m->d_seq;
+        size_t cap = m->d_seq_cap;
+        m->d_seq = (uint8_t *)T.d_fa_seq, m->d_seq_cap = T.d_fa_seq_cap;
+        rc = dl.scan_resident(total, n, mode, 0, flags, flagged);
+        T.d_fa_seq = m->d_seq, T.d_fa_seq_cap = m->d_seq_cap;
+        m->d_seq = (uint8_t *)seq, m->d_seq_cap = cap;
+        return rc;
     }
-    m->ragged = !fixed;
-    *n_seq_out = n_seq;
-    *flagged = 0;
-    // FASTA: one record of 4 GiB or more cannot be addressed by mk_hit.pos (as mk_scan_batch refuses it)
-    if (n_seq == 0) {  // every sequence is empty: nothing can match
-        std::fill(flags, flags + n, 0);
-        dl.found = 0;
-        if (n && hipMemsetAsync(m->d_flags, 0, n, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
-        return MK_OK;
-    }
-    if (format != MK_TEXT_FASTA) return dl.scan_resident(n_seq, n, mode, fixed, flags, flagged);
-    // FASTA: the compacted sequences lie in the slot's own buffer -- it stands in for the scan buffer for this scan
-    mk_matcher::TextSlot &T = *W.T;
-    void *seq = m->d_seq;
-    size_t cap = m->d_seq_cap;
-    m->d_seq = (uint8_t *)T.d_fa_seq, m->d_seq_cap = T.d_fa_seq_cap;
-    rc = dl.scan_resident(n_seq, n, mode, 0, flags, flagged);
-    T.d_fa_seq = m->d_seq, T.d_fa_seq_cap = m->d_seq_cap;
-    m->d_seq = (uint8_t *)seq, m->d_seq_cap = cap;
-    return rc;
+    if (!fixed && (rc = scan_offsets(W.d_seq_len, n, W.d_tile, (unsigned long long *)m->d_off, st, &total, "offset scan failed"))) return rc;
+    *n_seq = total;
+    if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
+    if (bam) launch_bam_unpack((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
+    else launch_ingest_gather((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
+    if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, bam ? "sequence unpacking failed to launch" : "ingest kernels failed to launch");
+    return dl.scan_resident(total, n, mode, fixed, flags, flagged);
 }
 
 // text of the kept records of side W (keep flags in d_keep, already final: invert applied by the caller as 0), packed -> host
@@ -595,10 +613,7 @@ int window_kept(mk_matcher *m, uint32_t format, WindowSide &W, uint64_t n, const
     unsigned long long total = 0;
     launch_ingest_select(d_keep, 0u, W.d_rec_start, n, (uint32_t)W.n_used, d_len, st);
     if ((rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t)))) return rc;
-    launch_ingest_offsets(d_len, n, d_tile, (unsigned long long *)m->d_off, st);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, m->d_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "selection of the kept records failed");
+    if ((rc = scan_offsets(d_len, n, d_tile, (unsigned long long *)m->d_off, st, &total, "selection of the kept records failed"))) return rc;
     S.n_kept_bytes = total;
     if (total > S.kept_cap) return fail(MK_E_CAPACITY, "the kept records take %llu bytes", total);
     if (!total) return MK_OK;
@@ -759,28 +774,13 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
     unsigned long long found[2] = {0, 0};
     for (uint32_t k = 0; k < n_sources; ++k) {
         f[k].resize(n);
-        if ((rc = window_scan(m, format, W[k], n, dl, mode, f[k].data(), &flagged[k], &n_seq[k]))) return rc;
+        if ((rc = scan_sequences(m, W[k], n, false, dl, mode, f[k].data(), &flagged[k], &n_seq[k]))) return rc;
         found[k] = dl.found;
-        if (paired && k == 0) {
-            // mate 1's flags (the kept text is selected on the device) and tuples wait while mate 2 is scanned
-            if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
-            if (hipMemcpyAsync(m->d_flags2, m->d_flags, n, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(MK_E_HIP, "copy of the flags failed");
-            if (logging && found[0]) {
-                if ((rc = ensure_device(&m->d_pair, &m->d_pair_cap, found[0] * sizeof(mk_hit)))) return rc;
-                if (hipMemcpyAsync(m->d_pair, m->d_hits, found[0] * sizeof(mk_hit), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    return fail(MK_E_HIP, "copy of the first mate's tuples failed");
-            }
-            if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "copy of the first mate's results failed");
-        }
+        if (paired && k == 0 && logging && (rc = dl.stash_mate1())) return rc;
     }
     uint64_t total_rows = 0;
     if (logging && !paired) {
-        c->nb_records_tot += n;
-        c->nb_bases += n_seq[0];
-        c->nb_hits_tot[0] += found[0];
-        c->nb_records_hit[0] += flagged[0];
-        if ((rc = dl.order(ac))) return rc;
-        if ((rc = dl.rows_to_host(0, rows, rows_cap))) return rc;
+        if ((rc = dl.log_single(c, n, n_seq[0], flagged[0], rows, rows_cap))) return rc;
         if ((rc = dl.pattern_counts(ac, n, counts))) return rc;
         total_rows = found[0];
     } else if (logging) {
@@ -791,44 +791,13 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
         c->nb_records_hit[0] += flagged[0];
         c->nb_records_hit[1] += flagged[1];
         total_rows = found[0] + found[1];
-        const unsigned long long n1 = found[0], n2 = found[1];
         if (!ac && std::max(n_seq[0], n_seq[1]) >= (1ull << 31))  // (BNDMq's pair order keeps the mate in bit 31 of the position)
             return fail(MK_E_UNSUPPORTED, "mk_extract_window: paired windows of 2 GiB of sequence or more under BNDMq");
-        if (total_rows) {
-            // one list: mate 2's tuples (already in the scan buffer), then mate 1's, the mate marked inside a key field
-            if ((n1 + n2) * sizeof(mk_hit) > m->d_hits_cap) {  // grow the scan buffer, keeping mate 2's tuples
-                void *bigger = nullptr;
-                size_t cap = 0;
-                if ((rc = ensure_device(&bigger, &cap, (n1 + n2) * sizeof(mk_hit)))) return rc;
-                if (n2 && hipMemcpy(bigger, m->d_hits, n2 * sizeof(mk_hit), hipMemcpyDeviceToDevice) != hipSuccess) {
-                    (void)hipFree(bigger);
-                    return fail(MK_E_HIP, "copy of the second mate's tuples failed");
-                }
-                if (m->d_hits) (void)hipFree(m->d_hits);
-                m->d_hits = (mk_hit *)bigger;
-                m->d_hits_cap = cap;
-            }
-            if (n1 && hipMemcpyAsync(m->d_hits + n2, m->d_pair, n1 * sizeof(mk_hit), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return fail(MK_E_HIP, "copy of the first mate's tuples failed");
-            launch_pair_mark(m->d_hits, n2, 1, ac, st);
-            launch_pair_mark(m->d_hits + n2, n1, 0, ac, st);
-            dl.found = total_rows;
-            const uint64_t bound = m->last_n_rec;
-            if (ac) m->last_n_rec = 2 * n;  // record' = 2 * record + mate: the bins of the ordering
-            rc = dl.order(ac);
-            m->last_n_rec = bound;
-            if (rc) return rc;
-            if ((rc = dl.pair_rows_to_host(ac, rows, rows_cap))) return rc;
-            if ((rc = dl.pair_counts(ac, counts))) return rc;
-        }
+        if ((rc = dl.join_mates(found[0], n, rows, rows_cap, counts))) return rc;
     }
     // ---- keep (single :400-405, paired :600-606), on the host for the caller and on the device for the kept records' text
     dl.host_begin();
-    for (uint64_t r = 0; r < n; ++r) {
-        const bool hit = f[0][r] || (paired && f[1][r]);
-        keep[r] = (uint8_t)(hit != (invert != 0));
-        c->nb_records_extracted += (paired ? 2u : 1u) * keep[r];
-    }
+    extract_keep(f[0].data(), paired ? f[1].data() : nullptr, n, invert, keep, c);
     dl.mark(1);
     bool want_kept = false;
     for (uint32_t k = 0; k < n_sources; ++k) want_kept = want_kept || src[k].kept != nullptr || src[k].kept_cap != 0;
@@ -846,8 +815,7 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
     }
     dl.finish();
     if (n_rows) *n_rows = total_rows;
-    if (logging && rows && total_rows > rows_cap) return fail(MK_E_CAPACITY, "rows buffer too small: need %llu", (unsigned long long)total_rows);
-    return MK_OK;
+    return check_rows_cap(logging, rows, rows_cap, total_rows);
     MK_ABI_END
 }
 
@@ -898,32 +866,13 @@ int mk_extract_fastq_bgzf(mk_matcher *m, mk_codec *codec, const uint8_t *head, u
 // ---- `tag` on a window of BAM text that stays on the device (r05, ABI v7; kernels: bam.hip) ---------------------------------------
 }  // extern "C"
 
-namespace mk {
-void launch_bam_find(const uint8_t *d_text, uint64_t n, uint32_t piece, uint32_t n_pieces, uint32_t *d_start, hipStream_t st);
-void launch_bam_walk_count(const uint8_t *d_text, uint64_t n, uint32_t piece, uint32_t n_pieces, const uint32_t *d_start, uint32_t *d_land,
-                           uint32_t *d_count, hipStream_t st);
-void launch_bam_walk_emit(const uint8_t *d_text, uint64_t n, uint32_t piece, uint32_t n_pieces, const uint32_t *d_start, const uint32_t *d_base,
-                          uint32_t *d_rec_off, uint32_t *d_rec_len, uint32_t *d_seq_start, uint32_t *d_seq_len, uint32_t *d_st, hipStream_t st);
-void launch_bam_unpack(const uint8_t *d_text, const uint32_t *d_seq_start, const uint32_t *d_seq_len, const unsigned long long *d_off, uint32_t fixed_len,
-                       uint64_t n_rec, uint8_t *d_seq, hipStream_t st);
-void launch_bam_taglen(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint32_t *d_seq_start, const uint32_t *d_seq_len,
-                       const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint32_t *d_pat_off, const uint8_t *d_pat_bytes, uint64_t n_rec,
-                       uint32_t filter_matching, uint32_t invert, uint32_t tag0, uint32_t tag1, uint8_t *d_keep, uint32_t *d_out_len, uint32_t *d_ex_off,
-                       uint32_t *d_st, hipStream_t st);
-void launch_bam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint32_t *d_out_len, const unsigned long long *d_out_off,
-                     const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off,
-                     const uint32_t *d_ex_off, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
-void launch_bam_names(const uint8_t *d_text, const uint32_t *d_rec_off, const uint8_t *d_flags, uint64_t n_rec, uint32_t *d_name_start, uint32_t *d_name_len,
-                      hipStream_t st);
-}  // namespace mk
-
 namespace {
 
 constexpr int kBamProofRounds = 8;  // walks of the record chain before a window is left to the host reader
 
 // the record chain of text[0, n) -> W's tables (d_rec_start = record offsets, d_seq_start, d_seq_len; rec_len behind them):
-// *n_rec records covering *n_used bytes; *fixed > 0: every sequence has this length.  *status |= 1: not for the device.
-int bam_index(mk_matcher *m, WindowSide &W, hipStream_t st, uint64_t *n_rec, uint64_t *n_used, uint32_t **d_rec_len, uint32_t *fixed, uint32_t *status) {
+// *n_rec records covering *n_used bytes; W.fixed > 0: every sequence has this length.  *status |= 1: not for the device.
+int bam_index(mk_matcher *m, WindowSide &W, hipStream_t st, uint64_t *n_rec, uint64_t *n_used, uint32_t **d_rec_len, uint32_t *status) {
     mk_matcher::TextSlot &T = *W.T;
     const uint64_t n = W.n_window;
     const uint8_t *d_text = (const uint8_t *)T.d_text;
@@ -1003,7 +952,7 @@ int bam_index(mk_matcher *m, WindowSide &W, hipStream_t st, uint64_t *n_rec, uin
         hipStreamSynchronize(st) != hipSuccess)
         return fail(MK_E_HIP, "BAM record indexing failed");
     if (st_host[0]) *status |= 1;  // a record the serial parser refuses ("truncated file"): the host reader words it
-    *fixed = (total && st_host[1] == st_host[2] && st_host[1] > 0) ? st_host[1] : 0;
+    W.fixed = (total && st_host[1] == st_host[2] && st_host[1] > 0) ? st_host[1] : 0;
     W.d_st = d_st;
     return MK_OK;
 }
@@ -1062,8 +1011,8 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     if (n_text == 0) return MK_OK;
     // ---- the record chain
     uint64_t n = 0, n_used = 0;
-    uint32_t *d_rec_len = nullptr, fixed = 0;
-    if ((rc = bam_index(m, W, st, &n, &n_used, &d_rec_len, &fixed, status))) return rc;
+    uint32_t *d_rec_len = nullptr;
+    if ((rc = bam_index(m, W, st, &n, &n_used, &d_rec_len, status))) return rc;
     if (*status) return MK_OK;
     if (w->last && n_used != n_text) {  // the file ends inside a record
         *status = 8;
@@ -1079,30 +1028,13 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     if (n == 0) return MK_OK;
     uint32_t *d_out_len = d_rec_len + n + 2, *d_ex_off = d_out_len + n + 2;
     unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_ex_off + n + 2) + 15) & ~(uintptr_t)15);
-    unsigned long long *d_tile = d_out_off + n + 2;
+    W.d_tile = d_out_off + n + 2;
     // ---- sequences -> the scan buffer, scan, emission order, pattern sets
-    unsigned long long n_seq = (unsigned long long)n * fixed;
-    if ((rc = ensure_device((void **)&m->d_flags, &m->d_flags_cap, n + 8)) || (rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t))))
-        return rc;
-    if (!fixed) {
-        launch_ingest_offsets(W.d_seq_len, n, d_tile, (unsigned long long *)m->d_off, st);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n_seq, m->d_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "offset scan failed");
-    }
-    if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, n_seq + 64))) return rc;
-    launch_bam_unpack((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
-    if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "sequence unpacking failed to launch");
-    m->ragged = !fixed;
     std::vector<uint8_t> flags(n);
     uint64_t flagged = 0;
+    uint64_t n_seq = 0;
+    if ((rc = scan_sequences(m, W, n, true, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
     const bool ac = m->algo == MK_ALGO_AC;
-    if (n_seq == 0) {
-        dl.found = 0;
-        if (hipMemsetAsync(m->d_flags, 0, n, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
-    } else if ((rc = dl.scan_resident(n_seq, n, MK_MODE_HITS, fixed, flags.data(), &flagged))) {
-        return rc;
-    }
     bool set_order = false;
     uint64_t n_rows = 0;
     // (counters of this window: added to the caller's only when the window is done -- a refused or repeated window counts nothing)
@@ -1110,13 +1042,8 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     memset(&lc, 0, sizeof(lc));
     std::vector<uint32_t> lcounts(logging ? m->n_pat : 0, 0);
     if (logging) {  // src/cmd_tag.rs:400-416, :443-451
-        lc.nb_hits_tot[0] = dl.found;
-        lc.nb_records_tot = n;
-        lc.nb_bases = n_seq;
-        lc.nb_records_hit[0] = flagged;
         n_rows = dl.found;
-        if ((rc = dl.order(ac))) return rc;
-        if ((rc = dl.rows_to_host(0, w->rows, w->rows_cap))) return rc;
+        if ((rc = dl.log_single(&lc, n, n_seq, flagged, w->rows, w->rows_cap))) return rc;
         set_order = !ac;
         if (ac && (rc = dl.pattern_counts(true, n, lcounts.data()))) return rc;
         // the names of the records with a hit, NUL-terminated, in record order; a row finds its record's by a walk along both
@@ -1125,10 +1052,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
             unsigned long long *d_name_off = (unsigned long long *)m->d_off;          // (the scan is done with the sequence offsets)
             unsigned long long total = 0;
             launch_bam_names((const uint8_t *)W.T->d_text, W.d_rec_start, m->d_flags, n, d_name_start, d_name_len, st);
-            launch_ingest_offsets(d_name_len, n, d_tile, d_name_off, st);
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, d_name_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                return fail(MK_E_HIP, "selection of the names failed");
+            if ((rc = scan_offsets(d_name_len, n, W.d_tile, d_name_off, st, &total, "selection of the names failed"))) return rc;
             w->n_names_bytes = total;
             if (total <= w->names_cap && n_rows <= w->rows_cap) {
                 // (the unpacked sequences have been scanned: their buffer holds the names now)
@@ -1153,7 +1077,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
         }
     }
     w->n_rows = n_rows;
-    if (!set_order && (rc = dl.order(false))) return rc;
+    if (!set_order && (rc = dl.order(false, n))) return rc;
     unsigned long long *d_found_off = nullptr;
     uint32_t *d_found_pat = nullptr, *d_cnt = nullptr;
     uint64_t n_found = 0;
@@ -1167,7 +1091,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     if (hipMemsetAsync(W.d_st, 0, 4, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
     launch_bam_taglen((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, d_found_off, d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
                       w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
-    launch_ingest_offsets(d_out_len, n, d_tile, d_out_off, st);
+    launch_ingest_offsets(d_out_len, n, W.d_tile, d_out_off, st);
     unsigned long long out_text = 0;
     uint32_t st_tag = 0;
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&out_text, d_out_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1321,15 +1245,9 @@ int mk_extract_paired(mk_matcher *m, const uint8_t *seq1, const uint64_t *off1, 
     int rc = dl.scan(seq1, off1, n_rec, mode, f1.data(), &flagged1);
     if (rc) return rc;
     const unsigned long long n1 = dl.found;
-    if (logging && n1) {  // mate 1's tuples wait in their own buffer while mate 2 is scanned
-        if ((rc = ensure_device(&m->d_pair, &m->d_pair_cap, n1 * sizeof(mk_hit)))) return rc;
-        if (hipMemcpyAsync(m->d_pair, m->d_hits, n1 * sizeof(mk_hit), hipMemcpyDeviceToDevice, dl.st) != hipSuccess ||
-            hipStreamSynchronize(dl.st) != hipSuccess)
-            return fail(MK_E_HIP, "copy of the first mate's tuples failed");
-    }
+    if (logging && (rc = dl.stash_mate1())) return rc;
     if ((rc = dl.scan(seq2, off2, n_rec, mode, f2.data(), &flagged2))) return rc;
     const unsigned long long n2 = dl.found;
-    uint64_t total_rows = 0;
     if (logging) {
         c->nb_records_tot += 2 * n_rec;  // :472
         c->nb_bases += (off1[n_rec] - off1[0]) + (off2[n_rec] - off2[0]);
@@ -1337,46 +1255,14 @@ int mk_extract_paired(mk_matcher *m, const uint8_t *seq1, const uint64_t *off1, 
         c->nb_hits_tot[1] += n2;
         c->nb_records_hit[0] += flagged1;
         c->nb_records_hit[1] += flagged2;
-        total_rows = n1 + n2;
-        if (total_rows) {
-            // one list: mate 2's tuples (already in the scan buffer), then mate 1's, the mate marked inside a key field
-            if ((n1 + n2) * sizeof(mk_hit) > m->d_hits_cap) {  // grow the scan buffer, keeping mate 2's tuples
-                void *bigger = nullptr;
-                size_t cap = 0;
-                if ((rc = ensure_device(&bigger, &cap, (n1 + n2) * sizeof(mk_hit)))) return rc;
-                if (n2 && hipMemcpy(bigger, m->d_hits, n2 * sizeof(mk_hit), hipMemcpyDeviceToDevice) != hipSuccess) {
-                    (void)hipFree(bigger);
-                    return fail(MK_E_HIP, "copy of the second mate's tuples failed");
-                }
-                if (m->d_hits) (void)hipFree(m->d_hits);
-                m->d_hits = (mk_hit *)bigger;
-                m->d_hits_cap = cap;
-            }
-            if (n1 && hipMemcpyAsync(m->d_hits + n2, m->d_pair, n1 * sizeof(mk_hit), hipMemcpyDeviceToDevice, dl.st) != hipSuccess)
-                return fail(MK_E_HIP, "copy of the first mate's tuples failed");
-            launch_pair_mark(m->d_hits, n2, 1, ac, dl.st);
-            launch_pair_mark(m->d_hits + n2, n1, 0, ac, dl.st);
-            dl.found = total_rows;
-            const uint64_t bound = m->last_n_rec;
-            if (ac) m->last_n_rec = 2 * n_rec;  // record' = 2 * record + mate: the bins of the ordering
-            rc = dl.order(ac);
-            m->last_n_rec = bound;
-            if (rc) return rc;
-            if ((rc = dl.pair_rows_to_host(ac, rows, rows_cap))) return rc;
-            if ((rc = dl.pair_counts(ac, counts))) return rc;
-        }
+        if ((rc = dl.join_mates(n1, n_rec, rows, rows_cap, counts))) return rc;
     }
     dl.host_begin();
-    for (uint64_t r = 0; r < n_rec; ++r) {  // :600-606
-        const bool found = f1[r] || f2[r];
-        keep[r] = (uint8_t)(found != (invert != 0));
-        c->nb_records_extracted += 2 * keep[r];
-    }
+    extract_keep(f1.data(), f2.data(), n_rec, invert, keep, c);
     dl.finish();
+    const uint64_t total_rows = logging ? n1 + n2 : 0;
     if (n_rows) *n_rows = total_rows;
-    if (logging && rows && total_rows > rows_cap)
-        return fail(MK_E_CAPACITY, "rows buffer too small: need %llu", (unsigned long long)total_rows);
-    return MK_OK;
+    return check_rows_cap(logging, rows, rows_cap, total_rows);
     MK_ABI_END
 }
 
@@ -1396,18 +1282,13 @@ int mk_tag_records(mk_matcher *m, const uint8_t *seq, const uint64_t *off, uint6
     if (rc) return rc;
     const bool ac = m->algo == MK_ALGO_AC;
     bool set_order = false;  // are the tuples in (record, pattern, position) order?
-    if (logging) {
-        c->nb_hits_tot[0] += dl.found;
-        c->nb_records_tot += n_rec;  // :446-450 (counted before filtering)
-        c->nb_bases += off[n_rec] - off[0];
-        c->nb_records_hit[0] += flagged;
-        if ((rc = dl.order(ac))) return rc;
-        if ((rc = dl.rows_to_host(0, rows, rows_cap))) return rc;
+    if (logging) {  // (records counted before filtering, :446-450)
+        if ((rc = dl.log_single(c, n_rec, off[n_rec] - off[0], flagged, rows, rows_cap))) return rc;
         set_order = !ac;
         if (ac && (rc = dl.pattern_counts(true, n_rec, counts))) return rc;  // one per hit (:412); BNDMq: below, from the sets
     }
     // distinct matched patterns per record, ascending: kmers_found after sort_unstable + dedup (:484-485)
-    if (!set_order && (rc = dl.order(false))) return rc;
+    if (!set_order && (rc = dl.order(false, n_rec))) return rc;
     uint64_t n_found = 0;
     if ((rc = dl.pattern_sets(n_rec, found_off, found_pat, found_cap, &n_found, (logging && !ac) ? counts : nullptr))) return rc;
     dl.host_begin();
@@ -1419,9 +1300,7 @@ int mk_tag_records(mk_matcher *m, const uint8_t *seq, const uint64_t *off, uint6
     dl.finish();
     if (n_rows) *n_rows = logging ? dl.found : 0;
     if (n_found > found_cap) return fail(MK_E_CAPACITY, "found_pat too small: need %llu", (unsigned long long)n_found);
-    if (logging && rows && dl.found > rows_cap)
-        return fail(MK_E_CAPACITY, "rows buffer too small: need %llu", (unsigned long long)dl.found);
-    return MK_OK;
+    return check_rows_cap(logging, rows, rows_cap, dl.found);
     MK_ABI_END
 }
 

@@ -437,15 +437,6 @@ void launch_ingest_lines(const uint8_t *d_text, uint64_t n, const uint32_t *d_bl
     hipLaunchKernelGGL(mk_ingest_lines_kernel, dim3(n_blocks), dim3(kIngestThreads), 0, st, d_text, n, d_block_off, d_total, d_line_start);
 }
 
-// flags |= other (paired windows: a pair is kept if either mate hits, src/cmd_extract.rs:600-606)
-__global__ __launch_bounds__(256) void mk_ingest_or_flags_kernel(uint8_t *__restrict__ flags, const uint8_t *__restrict__ other, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flags[i] |= other[i];
-}
-void launch_ingest_or_flags(uint8_t *d_flags, const uint8_t *d_other, uint64_t n, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(mk_ingest_or_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_flags, d_other, n);
-}
-
 void launch_ingest_select(const uint8_t *d_flags, uint32_t invert, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
                           hipStream_t st) {
     if (!n_rec) return;

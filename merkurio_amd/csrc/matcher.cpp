@@ -791,20 +791,20 @@ static int order_library(mk_matcher *m, mk_hit *d_hits, uint64_t n, bool ac, hip
 
 int mk_order_hits_device(mk_matcher *m, void *d_hits, uint64_t n_hits, void *stream) {
     if (!m) return fail(MK_E_INVALID_ARG, "null matcher");
-    return mk::order_hits_on_device(m, d_hits, n_hits, m->algo == MK_ALGO_AC, stream);
+    return mk::order_hits_on_device(m, d_hits, n_hits, m->algo == MK_ALGO_AC, m->last_n_rec, stream);
 }
 
 }  // extern "C"
 
 // ac: Aho-Corasick emission order; !ac: (record, pattern, position) -- BNDMq's emission order and, for any matcher,
 // the order in which a record's distinct patterns are adjacent and ascending (sets.hip)
-static int order_hits_on_device_impl(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, void *stream);
-int mk::order_hits_on_device(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, void *stream) {
-    const int rc = order_hits_on_device_impl(m, d_hits, n_hits, ac_order, stream);
+static int order_hits_on_device_impl(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, uint64_t rec_bound, void *stream);
+int mk::order_hits_on_device(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, uint64_t rec_bound, void *stream) {
+    const int rc = order_hits_on_device_impl(m, d_hits, n_hits, ac_order, rec_bound, stream);
     if (rc == MK_OK) ++m->order_path_calls[m->order_path & 3];  // (mk_matcher_order_stats: does the library sort ever fire on real data?)
     return rc;
 }
-static int order_hits_on_device_impl(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, void *stream) {
+static int order_hits_on_device_impl(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, uint64_t rec_bound, void *stream) {
     using namespace mk;
     m->order_path = 0;
     if (n_hits < 2) return MK_OK;
@@ -841,8 +841,8 @@ static int order_hits_on_device_impl(mk_matcher *m, void *d_hits, uint64_t n_hit
     L.rank = ac_order ? m->d_pat_rank : nullptr;
     L.unrank = ac_order ? m->d_pat_unrank : nullptr;
     L.ac = ac_order ? 1 : 0;
-    // first attempt: bins of 2^s consecutive records, s from the record count of the handle's last scan
-    uint64_t rec_bound = m->last_n_rec ? m->last_n_rec : (1ull << 32);
+    // first attempt: bins of 2^s consecutive records, s from the caller's record bound
+    if (!rec_bound) rec_bound = 1ull << 32;
     unsigned long long stats[6] = {0, 0, 0, 0, 0, 0};
     uint32_t s = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {

@@ -82,7 +82,7 @@ struct mk_matcher {
         size_t d_text_cap = 0, d_ing_a_cap = 0, d_ing_b_cap = 0, d_fa_seq_cap = 0;
     } txt[2];
     uint32_t bam_piece = 0;  // mk_tag_bam_window: bytes of text per piece of the record-chain index (0 = 64 KiB; mk_matcher_set_bam_piece)
-    uint8_t *d_flags2 = nullptr;  // paired windows: mate 1's flags while mate 2 is scanned; the keep flags the kept records are selected by
+    uint8_t *d_flags2 = nullptr;  // keep flags: what mk_extract_window selects the kept records by, what mk_tag_bam_window tags by
     size_t d_flags2_cap = 0;
     // mk_upload_text_ahead: text windows copied on a stream of their own while the current window is processed.  Four
     // slots (two windows of two inputs), so that an upload that arrives before the previous one was consumed cannot overwrite it; the slot
@@ -119,7 +119,8 @@ int batch_upload(mk_matcher *m, const uint8_t *seq_bytes, const uint64_t *seq_of
 int batch_scan(mk_matcher *m, uint64_t n_bytes, uint64_t n_rec, uint32_t mode, uint32_t batch_len, uint64_t cap, uint64_t limit,
                unsigned long long *found);
 int batch_flags(mk_matcher *m, uint64_t n_rec, uint8_t *rec_flags, uint64_t *flagged_out);
-// tuples on the device into emission order: ac_order ? Aho-Corasick's : (record, pattern, position)
-int order_hits_on_device(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, void *stream);
+// tuples on the device into emission order: ac_order ? Aho-Corasick's : (record, pattern, position).  rec_bound: the records
+// the tuples come from (the first binning; 0 = unknown)
+int order_hits_on_device(mk_matcher *m, void *d_hits, uint64_t n_hits, bool ac_order, uint64_t rec_bound, void *stream);
 int hip_fail(hipError_t e, const char *what);
 }  // namespace mk
