@@ -613,6 +613,56 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
 /* Tuning / test hook: bytes of text per piece of the record-chain index (0 = the default, 65536).  Results do not depend on it. */
 int mk_matcher_set_bam_piece(mk_matcher *m, uint32_t piece_bytes);
 
+/* -------------------------------------------------------------------------------------
+ * `tag` on a window of SAM TEXT with the lines resident on the device (an addition to v7; kernels: sam.hip) -- the reader loop,
+ * process_record and the text writer of src/cmd_tag.rs:559-612, :387-497 for SAM -> SAM or no output.  No codec: nothing is inflated
+ * or deflated.
+ *
+ * The window's text = head[0, n_head) (the unfinished line the previous window ended with; may be empty) ++ text[0, n_text), uploaded
+ * as it is (fastest from mk_host_alloc memory); together below 4 GiB (32-bit offsets; larger: MK_E_UNSUPPORTED).  On the device:
+ * lines are split at '\n', one trailing '\r' is not part of a line; empty lines and lines that start with '@' are not records and
+ * produce nothing.  A record line has at least 10 tab-separated fields; QNAME = the bytes before the first tab, SEQ = field 10 (a
+ * SEQ that is exactly "*" has length 0); the matcher sees SEQ with a-z upper-cased and every other byte as it is.  Scan, emission
+ * order, counters, pattern_hit_counts, rows, row_name and names (QNAME, NUL-terminated) as in mk_tag_bam_window; keep rule
+ * :457-467.  Of a KEPT record the optional fields (fields 12 ...) are searched for the first one that is at least 5 bytes long and
+ * starts with the tag's two bytes and ':': its type must be "Z:", its value is the rest of the field (an empty value counts as no
+ * tag).  A kept record leaves as  line (without "\r" / "\n") TAB tag ":Z:" value "\n",  value = mk_tag_value's string, packed back
+ * to back in record order in out[0, out_len); out_cap too small: MK_E_CAPACITY with out_len = the need and nothing counted (the
+ * counters are added when the window is done).  out == NULL && out_cap == 0: nothing is written (`tag -S`), the checks still run.
+ * n_used = bytes up to and including the last '\n' (last != 0: the whole window -- a final line without '\n' is a line); tail[0,
+ * n_tail) = the rest, the next window's head.  A caller that cuts its input at line starts has empty heads and tails: its windows
+ * are independent and may run on different handles at the same time.
+ * *status != 0: this window is not for the device and NOTHING was produced -- the caller's host reader takes it from the window's
+ * first byte (and words the reference's errors): 1 = a record line with fewer than 10 fields, 4 = a kept record whose field of the
+ * tag's name is not "Z:", or whose value is not plain ASCII or longer than 2 KiB.  Records that are dropped are not looked at.
+ * ms[]: milliseconds of [0] upload, [1] line index + fields, [2] gather + scan + sets, [3] tag + emit, [4] download; ms[7]: of
+ * these, growing device buffers.
+ * --------------------------------------------------------------------------------------- */
+typedef struct mk_sam_window {
+    /* in */
+    const uint8_t *head;
+    uint64_t n_head;
+    const uint8_t *text;
+    uint64_t n_text;
+    uint32_t last; /* no text follows this window */
+    uint32_t filter_matching, invert;
+    uint8_t tag[2];
+    uint8_t reserved[2];
+    uint8_t *tail;
+    uint64_t tail_cap;
+    uint8_t *out;
+    uint64_t out_cap;
+    mk_row *rows;
+    uint64_t rows_cap;
+    uint64_t *row_name; /* room for rows_cap entries */
+    uint8_t *names;
+    uint64_t names_cap;
+    /* out */
+    uint64_t n_window, n_used, n_tail, n_rec, n_kept, out_len, n_rows, n_names_bytes;
+    float ms[8];
+} mk_sam_window;
+int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status);
+
 /* walks the BSIZE chain of in[0, n): fills members[0, cap) (out_off = running sum of ISIZE), *n_members = how many there are,
  * *consumed = bytes of whole members, *text_bytes = sum of ISIZE.  MK_E_CORRUPT where a header is not BGZF; a trailing
  * partial member is not an error (*consumed < n).  Host code, no device. */

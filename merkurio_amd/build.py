@@ -54,6 +54,7 @@ def _units():
     units.append(("build_tables.o", "build_tables.hip", []))
     units.append(("ingest.o", "ingest.hip", []))
     units.append(("bam.o", "bam.hip", []))
+    units.append(("sam.o", "sam.hip", []))
     # the device BGZF codec (v5 of the ABI)
     units.append(("codec_bgzf_deflate.o", "codec/bgzf_deflate.hip", []))
     units.append(("codec_bgzf_inflate.o", "codec/bgzf_inflate.hip", []))

@@ -805,27 +805,37 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
     std::vector<std::vector<uint32_t>> dev_counts(ms.size(), std::vector<uint32_t>(counts.size(), 0));
     for (auto &x : dev_c) memset(&x, 0, sizeof(x));
     bool device_done = false;
-    // BAM -> BAM (or no output at all) on one device: the records stay on the device between inflate and deflate
-    // (tag_windows.cpp; two windows in flight, each on a handle of its own); false: a window was not for the device and the loop
-    // below takes the input from there
+    // BAM -> BAM (or no output at all): the records stay on the device between inflate and deflate
+    // (tag_windows.cpp; two windows per device in flight, each on a handle of its own); false: a window was not for the device and the
+    // loop below takes the input from there
     std::vector<mk_matcher *> seconds;
-    if (sam.bam_on_bgzf() && (to_bam || a.suppress_output) && !a.host_codec && !a.host_ingest) {
+    const bool bam_windows = sam.bam_on_bgzf() && (to_bam || a.suppress_output) && !a.host_codec && !a.host_ingest;
+    // SAM text -> SAM text / STDOUT (or no output at all) from a memory-mapped file: the lines stay on the device between the upload and
+    // the download of the kept ones (tag_windows.cpp: tag_sam_windows_on_device; windows cut at line starts, independent of each other)
+    const bool sam_windows = sam.sam_on_mapping() && !to_bam && !a.host_ingest;
+    if (bam_windows || sam_windows) {
         if (to_bam) bw.use_device(devs[0]);
-        // (240 MiB of text: the tagged records of a window then fill one round of the deflate kernel's 4 096 resident waves, not one and a bit)
+        // BAM: 240 MiB of text -- the tagged records of a window then fill one round of the deflate kernel's 4 096 resident waves, not one
+        // and a bit.  SAM: 64 MiB, the fastest of the 64 / 128 / 240 / 512 sweep (profiles/e2e_tag_sam_window.txt): the windows are
+        // independent, so small ones cost nothing but launches, and their page-locked staging buffers stay small.
         // (an explicit --window-mb is honoured up to 2 GiB: a window's text, head included, has to stay below 4 GiB on the device)
-        const uint64_t dev_window = a.window_mb_given ? std::min<uint64_t>(window_bytes, 2048ull << 20) : (240ull << 20);
+        const uint64_t dev_window = a.window_mb_given ? std::min<uint64_t>(window_bytes, 2048ull << 20) : ((bam_windows ? 240ull : 64ull) << 20);
+        // (a SAM text that is one window needs no second handle; BAM windows are not known before their members are walked)
+        const bool one_window = sam_windows && sam.source().text_size() - sam.text_cursor() <= dev_window;
         seconds.assign(ms.size(), nullptr);
-        run_threads(ms.size(), [&](size_t d) {
-            bool ac2 = false;
-            seconds[d] = make_matcher(a, pats, &ac2, devs[d]);
-        });
+        if (!one_window)
+            run_threads(ms.size(), [&](size_t d) {
+                bool ac2 = false;
+                seconds[d] = make_matcher(a, pats, &ac2, devs[d]);
+            });
         // window k runs on handle k mod 2N: devices in turn, and two windows per device in flight.  One device: the job's counters;
         // several: the per-device vectors that RCCL sums at the end
         std::vector<TagHandle> handles;
-        for (int rep = 0; rep < 2; ++rep)
+        for (int rep = 0; rep < (one_window ? 1 : 2); ++rep)
             for (size_t d = 0; d < ms.size(); ++d)
                 handles.push_back(TagHandle{rep ? seconds[d] : ms[d], devs[d], ms.size() == 1 ? &c : &dev_c[d], ms.size() == 1 ? &counts : &dev_counts[d]});
-        device_done = tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window);
+        device_done = bam_windows ? tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window)
+                                  : tag_sam_windows_on_device(a, sam, handles, lg, pats, in_name, a.suppress_output ? nullptr : &w, dev_window);
         tm.mark(device_done ? "windows on the device" : "windows on the device (the rest: host reader)");
     }
     // (the first window is small: nothing can run beside its read; the later, large ones are read beside their predecessors)

@@ -122,5 +122,9 @@ struct TagHandle {
 };
 bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
                                const std::string &in_name, BamWriter *bw, uint64_t window_bytes);
+// the same for plain (memory-mapped) SAM text -> SAM text (mk_tag_sam_window); out == nullptr: no output (-S).  The windows are cut at
+// line starts every ~window_bytes and are independent of each other.
+bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                               const std::string &in_name, Sink *out, uint64_t window_bytes);
 
 }  // namespace cli

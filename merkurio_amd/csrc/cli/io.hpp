@@ -281,6 +281,15 @@ struct SamFile {
         return buf.data() + cursor;
     }
     void seek_bam(size_t member, const char *head, uint64_t n_head);
+    // plain SAM text for a caller that keeps the lines on the device (run_tag: mk_tag_sam_window takes slices of the mapping): after
+    // open(), text_cursor() = the first byte behind the header lines; seek_text() hands the input back to fill(): the records
+    // continue at byte `offset` of the text (a line start).
+    bool sam_on_mapping() const { return !is_bam && src.mapped() && src.is_file_mapping(); }
+    uint64_t text_cursor() const { return cursor; }
+    void seek_text(uint64_t offset) {
+        cursor = offset;
+        recs.clear();
+    }
 
    private:
     WindowSource src;

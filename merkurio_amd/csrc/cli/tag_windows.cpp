@@ -17,6 +17,9 @@
 // field of the tag's name is not a plain string, a damaged member -- hands the input back to the host reader AT THAT WINDOW'S FIRST BYTE
 // (SamFile::seek_bam): the r04 path takes the rest of the file and words the reference's errors.  (The window behind it may have
 // been started already: its results are dropped.)
+//
+// Plain SAM text -> SAM text has a driver of the same shape further down (tag_sam_windows_on_device, mk_tag_sam_window), without the
+// head chain: text can be cut at line starts, so its windows are independent.
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -261,6 +264,164 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
         sam.seek_bam(wins[pipe.refused].m0, (const char *)pipe.refused_head.data(), pipe.refused_head.size());
         return false;
     }
+    return true;
+}
+
+// ---- SAM text -> SAM text (or -S) with the lines resident on the device (mk_tag_sam_window, sam.hip) -------------------------------
+// The host path parsed every line, upper-cased every SEQ into a batch buffer, sent that to the scan and appended the tags on the host
+// threads.  Here a window is a slice of the memory-mapped file, cut at a line start (a '\n' can be found without reading the
+// lines), so windows have no heads or tails and are INDEPENDENT: window k runs on handle k mod handles.size() -- devices in turn,
+// two windows per device in flight -- staged through a page-locked buffer (a mapping is not a DMA source), and comes back as the
+// kept lines with their tag field appended, written as they are.  Results leave in window order; a worker holds one finished
+// window at most while it waits for its turn, so at most handles.size() windows exist at any time.
+// A window the device refuses (a line with fewer than 10 fields, a kept record whose field of the tag's name is not a plain
+// string) hands the input back to the host loop at that window's first byte (SamFile::seek_text), which words the reference's error.
+bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                               const std::string &in_name, Sink *out_sink, uint64_t window_bytes) {
+    const WindowSource &src = sam.source();
+    const uint8_t *file = (const uint8_t *)src.text();
+    const uint64_t n_file = src.text_size();
+    const bool timing = getenv("MERKURIO_TIMING") != nullptr;
+    // the windows: [b, e), e = the first line start at or behind b + window_bytes
+    std::vector<std::pair<uint64_t, uint64_t>> wins;
+    for (uint64_t b = sam.text_cursor(); b < n_file;) {
+        uint64_t e = std::min(n_file, b + std::max<uint64_t>(window_bytes, 1));
+        if (e < n_file) {
+            const void *nl = memchr(file + e - 1, '\n', n_file - (e - 1));
+            e = nl ? (uint64_t)((const uint8_t *)nl - file) + 1 : n_file;
+        }
+        wins.emplace_back(b, e);
+        b = e;
+    }
+    if (wins.empty()) return true;
+    const size_t n_win = wins.size();
+    const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
+    struct {
+        std::mutex mu;
+        std::condition_variable cv;
+        size_t emit_turn = 0;         // windows before this one have been emitted
+        bool stop = false;            // a window was refused or failed: nothing further is emitted
+        size_t refused = ~(size_t)0;  // the window the host loop takes over at
+        uint32_t refused_status = 0;
+        std::string error;
+    } pipe;
+    double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    auto worker = [&](size_t id) {
+        mk_matcher *m = handles[id].m;
+        mk_counters &c = *handles[id].counters;
+        std::vector<uint32_t> &counts = *handles[id].pattern_counts;
+        HostBuffer stage, out;  // the window's text; the kept lines (both page-locked)
+        std::vector<uint8_t> names(1u << 16);
+        std::vector<mk_row> rows(4096);
+        std::vector<uint64_t> row_name(4096);
+        uint8_t no_tail[8];
+        for (size_t k = id; k < n_win; k += n_workers) {
+            const uint64_t b = wins[k].first, n = wins[k].second - wins[k].first;
+            {
+                std::lock_guard<std::mutex> lk(pipe.mu);
+                if (pipe.stop) return;
+            }
+            if (!stage.grow(n, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+            copy_in(file, b, b + n, stage.p);
+            // (a kept line grows by its tag field: a tenth of a 350-byte line per matched 31-mer; a window that does not fit is
+            // done again with the size it asked for)
+            if (out_sink && out.cap < n + n / 4 + (1u << 20) && !out.grow(n + n / 4 + (1u << 20), 1u << 20))
+                bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+            mk_sam_window w;
+            memset(&w, 0, sizeof(w));
+            w.text = stage.p, w.n_text = n;
+            w.last = 1;  // (the window ends at a line end or at the end of the file: all of it is lines)
+            w.filter_matching = a.filter_matching, w.invert = a.invert_match;
+            w.tag[0] = (uint8_t)a.tag[0], w.tag[1] = (uint8_t)a.tag[1];
+            mk_counters wc;
+            std::vector<uint32_t> wcounts(lg.active ? pats.list.size() : 0, 0);
+            uint32_t status = 0;
+            int rc;
+            for (;;) {
+                memset(&wc, 0, sizeof(wc));
+                std::fill(wcounts.begin(), wcounts.end(), 0);
+                w.tail = no_tail, w.tail_cap = sizeof(no_tail);
+                w.out = out_sink ? out.p : nullptr, w.out_cap = out_sink ? out.cap : 0;
+                w.rows = rows.data(), w.rows_cap = rows.size(), w.row_name = row_name.data(), w.names = names.data(), w.names_cap = names.size();
+                rc = mk_tag_sam_window(m, &w, lg.active, &wc, wcounts.data(), &status);
+                if (rc != MK_E_CAPACITY) break;
+                bool grew = false;
+                if (out_sink && w.out_len > out.cap) {
+                    if (!out.grow(w.out_len, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+                    grew = true;
+                }
+                if (w.n_rows > rows.size()) rows.resize(w.n_rows), row_name.resize(w.n_rows), grew = true;
+                if (w.n_names_bytes > names.size()) names.resize(w.n_names_bytes), grew = true;
+                if (!grew) break;
+            }
+            const bool refused = rc == MK_OK && status != 0;
+            std::string err;
+            if (rc != MK_OK) err = std::string("Error during matching: ") + mk_last_error();
+            // results leave in window order
+            std::unique_lock<std::mutex> lk(pipe.mu);
+            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.emit_turn == k; });
+            if (pipe.stop) return;  // (an earlier window ended the job: this one's results are dropped)
+            if (refused || !err.empty()) {
+                pipe.stop = true;
+                if (refused) pipe.refused = k, pipe.refused_status = status;
+                else pipe.error = err;
+                pipe.cv.notify_all();
+                return;
+            }
+            lk.unlock();
+            // (only the worker whose turn it is gets here: the counters of its device, the loggers and the sink are its alone)
+            add_counters(c, wc);
+            add_counts(counts, wcounts);
+            for (int i = 0; i < 8; ++i) t_dev[i] += w.ms[i];
+            std::string emit_err;
+            try {
+                if (lg.active)
+                    emit_log_rows(
+                        lg, pats, rows.data(), w.n_rows,
+                        [&](const mk_row &r) {
+                            const char *nm = (const char *)names.data() + row_name[&r - rows.data()];
+                            return std::pair<const char *, size_t>(nm, strlen(nm));
+                        },
+                        [&](const mk_row &) -> const std::string & { return in_name; });
+                if (out_sink && w.out_len) out_sink->write((const char *)out.p, w.out_len);
+            } catch (const Error &e) {
+                emit_err = e.what()[0] ? e.what() : "error";
+            }
+            lk.lock();
+            if (!emit_err.empty()) pipe.stop = true, pipe.error = emit_err;
+            pipe.emit_turn = k + 1;
+            pipe.cv.notify_all();
+            if (pipe.stop) return;
+        }
+    };
+    // (a worker that throws must not leave the others waiting)
+    run_threads(n_workers, [&](size_t id) {
+        try {
+            worker(id);
+        } catch (const Error &e) {
+            std::lock_guard<std::mutex> lk(pipe.mu);
+            if (pipe.error.empty()) pipe.error = e.what()[0] ? e.what() : "error";
+            pipe.stop = true;
+            pipe.cv.notify_all();
+        }
+    });
+    if (!pipe.error.empty()) bail(pipe.error);
+    if (timing) {
+        fprintf(stderr,
+                "[timing] %llu of %llu SAM text windows on the device (%llu in flight): upload %.3f, line index + fields %.3f, gather + scan + sets %.3f, "
+                "tag + emit %.3f, download %.3f s (of these, growing device buffers: %.3f s)\n",
+                (unsigned long long)pipe.emit_turn, (unsigned long long)n_win, (unsigned long long)n_workers, t_dev[0] / 1e3, t_dev[1] / 1e3, t_dev[2] / 1e3,
+                t_dev[3] / 1e3, t_dev[4] / 1e3, t_dev[7] / 1e3);
+        if (pipe.refused != ~(size_t)0)
+            fprintf(stderr, "[timing] window %llu left to the host reader (%s)\n", (unsigned long long)pipe.refused,
+                    pipe.refused_status & 1 ? "a line with too few fields" : "existing tag");
+    }
+    if (pipe.refused != ~(size_t)0) {
+        sam.seek_text(wins[pipe.refused].first);
+        return false;
+    }
+    sam.seek_text(n_file);
     return true;
 }
 

@@ -557,10 +557,13 @@ int scan_offsets(const uint32_t *d_len, uint64_t n, unsigned long long *d_tile, 
     return MK_OK;
 }
 
+// how a window's text holds its sequences: as they are (FASTQ), as BAM's 4-bit codes, as SAM's SEQ field (a-z upper-cased for the matcher)
+enum SeqForm { kSeqPlain, kSeqBam, kSeqSam };
+
 // the sequences of W's first n records -> the scan buffer, scanned: flags (host + m->d_flags), tuples in m->d_hits (dl.found), *n_seq
-// sequence bytes.  FASTQ / BAM (bam: 4-bit codes, unpacked) are gathered by W.d_seq_start / W.d_seq_len (W.fixed > 0: all of that
-// length); FASTA's were compacted by the index step.
-int scan_sequences(mk_matcher *m, const WindowSide &W, uint64_t n, bool bam, DeviceLoop &dl, uint32_t mode, uint8_t *flags, uint64_t *flagged,
+// sequence bytes.  FASTQ / BAM / SAM are gathered by W.d_seq_start / W.d_seq_len (W.fixed > 0: all of that length) in the way their
+// form asks for; FASTA's were compacted by the index step.
+int scan_sequences(mk_matcher *m, const WindowSide &W, uint64_t n, SeqForm form, DeviceLoop &dl, uint32_t mode, uint8_t *flags, uint64_t *flagged,
                    uint64_t *n_seq) {
     hipStream_t st = dl.st;
     const uint32_t fixed = W.fixed;
@@ -587,9 +590,10 @@ int scan_sequences(mk_matcher *m, const WindowSide &W, uint64_t n, bool bam, Dev
     if (!fixed && (rc = scan_offsets(W.d_seq_len, n, W.d_tile, (unsigned long long *)m->d_off, st, &total, "offset scan failed"))) return rc;
     *n_seq = total;
     if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
-    if (bam) launch_bam_unpack((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
+    if (form == kSeqBam) launch_bam_unpack((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
+    else if (form == kSeqSam) launch_sam_gather((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
     else launch_ingest_gather((const uint8_t *)W.T->d_text, W.d_seq_start, W.d_seq_len, (const unsigned long long *)m->d_off, fixed, n, m->d_seq, st);
-    if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, bam ? "sequence unpacking failed to launch" : "ingest kernels failed to launch");
+    if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, form == kSeqPlain ? "ingest kernels failed to launch" : "sequence unpacking failed to launch");
     return dl.scan_resident(total, n, mode, fixed, flags, flagged);
 }
 
@@ -774,7 +778,7 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
     unsigned long long found[2] = {0, 0};
     for (uint32_t k = 0; k < n_sources; ++k) {
         f[k].resize(n);
-        if ((rc = scan_sequences(m, W[k], n, false, dl, mode, f[k].data(), &flagged[k], &n_seq[k]))) return rc;
+        if ((rc = scan_sequences(m, W[k], n, kSeqPlain, dl, mode, f[k].data(), &flagged[k], &n_seq[k]))) return rc;
         found[k] = dl.found;
         if (paired && k == 0 && logging && (rc = dl.stash_mate1())) return rc;
     }
@@ -957,6 +961,22 @@ int bam_index(mk_matcher *m, WindowSide &W, hipStream_t st, uint64_t *n_rec, uin
     return MK_OK;
 }
 
+// names[0, total) = the NUL-terminated names of the flagged records among n, in record order; rows in emission order (record-major
+// in both orders) -> row_name[k] = where the name of row k's record starts: a walk along both
+void name_rows(const mk_row *rows, uint64_t n_rows, const uint8_t *flags, uint64_t n, const uint8_t *names, uint64_t total, uint64_t *row_name) {
+    uint64_t r = 0, at = 0;  // r = the flagged record whose name starts at `at`
+    while (r < n && !flags[r]) ++r;
+    for (uint64_t k = 0; k < n_rows; ++k) {
+        const uint64_t rec = rows[k].rec;
+        while (r < rec && at < total) {
+            at += strlen((const char *)names + at) + 1;
+            ++r;
+            while (r < n && !flags[r]) ++r;
+        }
+        row_name[k] = at;
+    }
+}
+
 double ms_since(std::chrono::steady_clock::time_point &t) {
     const auto now = std::chrono::steady_clock::now();
     const double ms = std::chrono::duration<double, std::milli>(now - t).count();
@@ -1033,7 +1053,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     std::vector<uint8_t> flags(n);
     uint64_t flagged = 0;
     uint64_t n_seq = 0;
-    if ((rc = scan_sequences(m, W, n, true, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
+    if ((rc = scan_sequences(m, W, n, kSeqBam, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
     const bool ac = m->algo == MK_ALGO_AC;
     bool set_order = false;
     uint64_t n_rows = 0;
@@ -1061,18 +1081,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
                 if (hipGetLastError() != hipSuccess || hipMemcpyAsync(w->names, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
                     hipStreamSynchronize(st) != hipSuccess)
                     return fail(MK_E_HIP, "download of the names failed");
-                // rows are in record order (both emission orders are record-major): r = the flagged record whose name starts at `at`
-                uint64_t r = 0, at = 0;
-                while (r < n && !flags[r]) ++r;
-                for (uint64_t k = 0; k < n_rows; ++k) {
-                    const uint64_t rec = w->rows[k].rec;
-                    while (r < rec && at < total) {
-                        at += strlen((const char *)w->names + at) + 1;
-                        ++r;
-                        while (r < n && !flags[r]) ++r;
-                    }
-                    w->row_name[k] = at;
-                }
+                name_rows(w->rows, n_rows, flags.data(), n, w->names, total, w->row_name);
             }
         }
     }
@@ -1161,6 +1170,194 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
         w->ms[6] = (float)ms_since(t);
     }
     commit();
+    return MK_OK;
+    MK_ABI_END
+}
+
+// ---- `tag` on a window of SAM text that stays on the device (an addition to ABI v7; kernels: sam.hip).  Lines can be cut by the host
+// without reading them, so a caller's windows need no tail chain: the tail exists for callers that cut anywhere.
+int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
+    if (!m || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
+    if ((w->n_head && !w->head) || (w->n_text && !w->text) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
+        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names))
+        return fail(MK_E_INVALID_ARG, "mk_tag_sam_window: a size without its buffer");
+    if (w->tag[0] == '\t' || w->tag[1] == '\t' || w->tag[0] == '\n' || w->tag[1] == '\n')
+        return fail(MK_E_INVALID_ARG, "mk_tag_sam_window: a tag name holds a tab or a line end");
+    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_len = w->n_rows = w->n_names_bytes = 0;
+    for (float &x : w->ms) x = 0;
+    *status = 0;
+    MK_ABI_BEGIN
+    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
+    DeviceLoop dl(m);
+    hipStream_t st = dl.st;
+    int rc;
+    auto t = std::chrono::steady_clock::now();
+    g_alloc_ms = 0, g_free_ms = 0;
+    struct AllocMs {  // (device buffers grown inside the call: part of the phases, reported on its own as ms[7])
+        float *out;
+        ~AllocMs() { *out = (float)g_alloc_ms; }
+    } alloc_ms{&w->ms[7]};
+    // ---- the text: head, then the body behind it
+    WindowSide W;
+    W.T = &m->txt[0];
+    mk_matcher::TextSlot &T = *W.T;
+    mk_window_source S;
+    memset(&S, 0, sizeof(S));
+    S.head = w->head, S.n_head = w->n_head, S.text = w->text, S.n_text = w->n_text;
+    if ((rc = window_assemble(m, nullptr, S, W, dl))) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
+    w->ms[0] = (float)ms_since(t);
+    w->n_window = W.n_window;
+    const uint64_t n_text = W.n_window;
+    if (n_text == 0) return MK_OK;
+    const uint8_t *d_text = (const uint8_t *)T.d_text;
+    // ---- line table (ingest.hip), then what every line is (sam.hip)
+    const uint32_t n_blocks = (uint32_t)((n_text + ingest_block_bytes() - 1) / ingest_block_bytes());
+    if ((rc = ensure_device(&T.d_ing_a, &T.d_ing_a_cap, ((size_t)n_blocks + 8) * 4))) return rc;  // newline count per block | total | status, min, max
+    W.d_block = (uint32_t *)T.d_ing_a;
+    W.d_total = W.d_block + n_blocks;
+    W.d_st = W.d_total + 1;
+    launch_ingest_count(d_text, n_text, W.d_block, W.d_total, st);
+    if (hipMemcpyAsync(&W.total_nl, W.d_total, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&W.last_byte, d_text + n_text - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "newline count failed");
+    // a last line without '\n' is a line when nothing follows the window, else the next window's head
+    const bool open_end = W.last_byte != '\n';
+    const uint64_t n_lines = (uint64_t)W.total_nl + (w->last && open_end ? 1 : 0);
+    const size_t per = n_lines + 2, n_tiles = n_lines / ingest_scan_tile() + 2;
+    // line starts | record-or-not | six entries per line | out lengths | existing-value offsets (u32) | offsets (u64) | tiles (u64)
+    if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, ((size_t)W.total_nl + 4 + 9 * per) * 4 + 16 + per * 8 + n_tiles * 8 + 64))) return rc;
+    W.d_line = (uint32_t *)T.d_ing_b;
+    uint32_t *d_is_rec = W.d_line + W.total_nl + 4;
+    SamTables L{d_is_rec + per, d_is_rec + 2 * per, d_is_rec + 3 * per, d_is_rec + 4 * per, d_is_rec + 5 * per, d_is_rec + 6 * per};
+    uint32_t *d_out_len = d_is_rec + 7 * per, *d_ex_off = d_is_rec + 8 * per;
+    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_is_rec + 9 * per) + 15) & ~(uintptr_t)15);
+    W.d_tile = d_out_off + per;
+    launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, W.d_line, st);
+    const uint32_t st_init[3] = {0u, 0xFFFFFFFFu, 0u};
+    if (hipMemcpyAsync(W.d_st, st_init, sizeof(st_init), hipMemcpyHostToDevice, st) != hipSuccess) return fail(MK_E_HIP, "copy failed");
+    launch_sam_fields(d_text, W.d_line, n_lines, d_is_rec, L, W.d_st, st);
+    unsigned long long n_rec_dev = 0;
+    if (n_lines && (rc = scan_offsets(d_is_rec, n_lines, W.d_tile, d_out_off, st, &n_rec_dev, "SAM line indexing failed"))) return rc;
+    uint32_t st_host[3] = {0, 0, 0};
+    if (hipMemcpyAsync(st_host, W.d_st, sizeof(st_host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "SAM line indexing failed");
+    if (st_host[0]) {  // a record line with fewer than 10 fields: the host reader words it
+        *status = 1;
+        return MK_OK;
+    }
+    const uint64_t n = n_rec_dev;
+    SamTables R = L;
+    if (n != n_lines) {  // header or empty lines among the records: the records' entries move to tables of their own
+        if ((rc = ensure_device(&T.d_fa_seq, &T.d_fa_seq_cap, 6 * (size_t)(n + 2) * 4))) return rc;
+        uint32_t *r0 = (uint32_t *)T.d_fa_seq;
+        R = SamTables{r0, r0 + (n + 2), r0 + 2 * (n + 2), r0 + 3 * (n + 2), r0 + 4 * (n + 2), r0 + 5 * (n + 2)};
+        launch_sam_compact(d_is_rec, d_out_off, n_lines, L, R, st);
+        if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "SAM line indexing failed");
+    }
+    W.d_rec_start = R.rec_start, W.d_seq_start = R.seq_start, W.d_seq_len = R.seq_len;
+    W.fixed = (n && st_host[1] == st_host[2] && st_host[1] > 0) ? st_host[1] : 0;
+    uint64_t used = n_text;
+    if (!w->last && open_end) {  // the bytes behind the last '\n' are the tail
+        uint32_t last_start = 0;
+        if (hipMemcpyAsync(&last_start, W.d_line + W.total_nl, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "SAM line indexing failed");
+        used = last_start;
+    }
+    w->n_rec = n, w->n_used = used, w->n_tail = n_text - used;
+    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "mk_tag_sam_window: the text behind the window's last line end takes %llu bytes", (unsigned long long)w->n_tail);
+    if (w->n_tail && (hipMemcpyAsync(w->tail, d_text + used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+        return fail(MK_E_HIP, "download of the tail failed");
+    w->ms[1] = (float)ms_since(t);
+    if (n == 0) return MK_OK;
+    // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets (as mk_tag_bam_window)
+    std::vector<uint8_t> flags(n);
+    uint64_t flagged = 0, n_seq = 0;
+    if ((rc = scan_sequences(m, W, n, kSeqSam, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
+    const bool ac = m->algo == MK_ALGO_AC;
+    bool set_order = false;
+    uint64_t n_rows = 0;
+    // (counters of this window: added to the caller's only when the window is done -- a refused or repeated window counts nothing)
+    mk_counters lc;
+    memset(&lc, 0, sizeof(lc));
+    std::vector<uint32_t> lcounts(logging ? m->n_pat : 0, 0);
+    if (logging) {  // src/cmd_tag.rs:400-416, :443-451
+        n_rows = dl.found;
+        if ((rc = dl.log_single(&lc, n, n_seq, flagged, w->rows, w->rows_cap))) return rc;
+        set_order = !ac;
+        if (ac && (rc = dl.pattern_counts(true, n, lcounts.data()))) return rc;
+        // the QNAMEs of the records with a hit, NUL-terminated, in record order: each is gathered with the tab behind it, which
+        // then becomes the NUL
+        if (flagged) {
+            uint32_t *d_name_len = d_out_len;                                 // (free until the tag step)
+            unsigned long long *d_name_off = (unsigned long long *)m->d_off;  // (the scan is done with the sequence offsets)
+            unsigned long long total = 0;
+            launch_sam_names(R.name_len, m->d_flags, n, d_name_len, st);
+            if ((rc = scan_offsets(d_name_len, n, W.d_tile, d_name_off, st, &total, "selection of the names failed"))) return rc;
+            w->n_names_bytes = total;
+            if (total <= w->names_cap && n_rows <= w->rows_cap) {
+                if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
+                launch_ingest_gather(d_text, R.rec_start, d_name_len, d_name_off, 0, n, m->d_seq, st);
+                launch_sam_name_ends(d_name_len, d_name_off, n, m->d_seq, st);
+                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(w->names, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipStreamSynchronize(st) != hipSuccess)
+                    return fail(MK_E_HIP, "download of the names failed");
+                name_rows(w->rows, n_rows, flags.data(), n, w->names, total, w->row_name);
+            }
+        }
+    }
+    w->n_rows = n_rows;
+    if (!set_order && (rc = dl.order(false, n))) return rc;
+    unsigned long long *d_found_off = nullptr;
+    uint32_t *d_found_pat = nullptr, *d_cnt = nullptr;
+    uint64_t n_found = 0;
+    if ((rc = dl.pattern_sets_device(n, logging && !ac, &d_found_off, &d_found_pat, &d_cnt, &n_found))) return rc;
+    if (logging && !ac && n_found) {  // BNDMq: one count per record and pattern (:431-433)
+        if (hipMemcpy(lcounts.data(), d_cnt, (size_t)m->n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
+    }
+    w->ms[2] = (float)ms_since(t);
+    // ---- keep, tag, pack
+    if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
+    if (hipMemsetAsync(W.d_st, 0, 4, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
+    launch_sam_taglen(d_text, R, d_found_off, d_found_pat, m->d_pat_off, m->d_pat_bytes, n, w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1],
+                      m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+    launch_ingest_offsets(d_out_len, n, W.d_tile, d_out_off, st);
+    unsigned long long out_text = 0;
+    uint32_t st_tag = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&out_text, d_out_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&st_tag, W.d_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(flags.data(), m->d_flags2, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "tag kernels failed");
+    if (st_tag) {  // an existing field the device does not decide about: this window is the host path's
+        *status = st_tag & 4u;
+        return MK_OK;
+    }
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < n; ++r) kept += flags[r];
+    w->n_kept = kept;
+    lc.nb_records_extracted = kept;
+    const bool write = w->out || w->out_cap;
+    if (write) w->out_len = out_text;
+    if (logging && (n_rows > w->rows_cap || w->n_names_bytes > w->names_cap))
+        return fail(MK_E_CAPACITY, "mk_tag_sam_window: %llu rows and %llu bytes of names", (unsigned long long)n_rows, (unsigned long long)w->n_names_bytes);
+    if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_sam_window: the kept lines take %llu bytes", out_text);
+    if (write && out_text) {
+        mk_matcher::TextSlot &O = m->txt[1];
+        if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
+        launch_sam_emit(d_text, R, d_out_len, d_out_off, d_found_off, d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n, w->tag[0], w->tag[1],
+                        (uint8_t *)O.d_text, st);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "line output kernel failed");
+        w->ms[3] = (float)ms_since(t);
+        if (hipMemcpyAsync(w->out, O.d_text, out_text, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "download of the kept lines failed");
+        w->ms[4] = (float)ms_since(t);
+    } else {
+        w->ms[3] = (float)ms_since(t);
+    }
+    c->nb_records_tot += lc.nb_records_tot, c->nb_bases += lc.nb_bases, c->nb_hits_tot[0] += lc.nb_hits_tot[0];
+    c->nb_records_hit[0] += lc.nb_records_hit[0], c->nb_records_extracted += lc.nb_records_extracted;
+    for (size_t i = 0; i < lcounts.size(); ++i) counts[i] += lcounts[i];
+    dl.finish();
     return MK_OK;
     MK_ABI_END
 }

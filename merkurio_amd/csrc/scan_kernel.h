@@ -175,6 +175,29 @@ void launch_bam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uin
                      const uint32_t *d_ex_off, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 void launch_bam_names(const uint8_t *d_text, const uint32_t *d_rec_off, const uint8_t *d_flags, uint64_t n_rec, uint32_t *d_name_start, uint32_t *d_name_len,
                       hipStream_t st);
+// ---- sam.hip: a window of SAM text whose line table exists (launch_ingest_count + launch_ingest_lines) -> record tables, the
+// sequences as the matcher sees them, the kept lines with their tag appended (host_loops.cpp: mk_tag_sam_window)
+struct SamTables {  // one entry per line (or, compacted, per record)
+    uint32_t *rec_start, *rec_len, *name_len, *seq_start, *seq_len, *aux_start;
+};
+// per line: is_rec[i] = 1 for a record line and its entries in L; st[0] |= 1: a record line with fewer than 10 fields, st[1] / st[2]
+// = smallest / largest SEQ length of the record lines
+void launch_sam_fields(const uint8_t *d_text, const uint32_t *d_line_start, uint64_t n_lines, uint32_t *d_is_rec, const SamTables &L, uint32_t *d_st,
+                       hipStream_t st);
+// R[d_rec_index[i]] = L[i] for the lines with is_rec[i] (d_rec_index: the exclusive scan of is_rec)
+void launch_sam_compact(const uint32_t *d_is_rec, const unsigned long long *d_rec_index, uint64_t n_lines, const SamTables &L, const SamTables &R,
+                        hipStream_t st);
+void launch_sam_gather(const uint8_t *d_text, const uint32_t *d_seq_start, const uint32_t *d_seq_len, const unsigned long long *d_off, uint32_t fixed_len,
+                       uint64_t n_rec, uint8_t *d_seq, hipStream_t st);
+// name_len_out[i] = flags[i] ? name_len[i] + 1 : 0 (the byte behind the name, its tab, becomes the NUL: launch_sam_name_ends)
+void launch_sam_names(const uint32_t *d_name_len, const uint8_t *d_flags, uint64_t n_rec, uint32_t *d_name_len_out, hipStream_t st);
+void launch_sam_name_ends(const uint32_t *d_name_len_out, const unsigned long long *d_name_off, uint64_t n_rec, uint8_t *d_names, hipStream_t st);
+void launch_sam_taglen(const uint8_t *d_text, const SamTables &R, const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint32_t *d_pat_off,
+                       const uint8_t *d_pat_bytes, uint64_t n_rec, uint32_t filter_matching, uint32_t invert, uint32_t tag0, uint32_t tag1, uint8_t *d_keep,
+                       uint32_t *d_out_len, uint32_t *d_ex_off, uint32_t *d_st, hipStream_t st);
+void launch_sam_emit(const uint8_t *d_text, const SamTables &R, const uint32_t *d_out_len, const unsigned long long *d_out_off,
+                     const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off,
+                     const uint32_t *d_ex_off, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 
 // ---- build_tables.hip: the pattern set compiled into filter images + exact table on the device -----------------
 struct BuildParams {
