@@ -423,6 +423,7 @@ int mk_comm_destroy(mk_matcher *m);
  * out + out_off.  Every member is checked: stream errors, ISIZE and CRC-32 (on the device).  A damaged member:
  * MK_E_CORRUPT, *bad_member = the first one, its status word in mk_last_error().  The call overwrites the span of out
  * its members cover (min out_off .. max out_off + isize: gaps between members included), nothing outside it.
+ * Bytes inside data_len behind the stream's final block are left unread, as zlib leaves them (unused_data): the text is given.
  * --------------------------------------------------------------------------------------- */
 typedef struct mk_codec mk_codec;
 typedef struct mk_bgzf_member {

@@ -11,7 +11,8 @@
 //                            lockstep): inflate_segment into 16-bit symbols; tables in LDS, 836 B per lane
 //   mk_gzip_maps_*_kernel    the 32 KiB context in front of every segment: "context j + 1 in terms of context j" composed over
 //                            doubling distances, log2(segments) rounds over all segments at once
-//   mk_gzip_translate_kernel a workgroup per segment: symbols -> bytes through the segment's context, coalesced
+//   mk_gzip_translate_kernel a workgroup per segment: symbols -> bytes through the segment's context, coalesced; a symbol that stands
+//                            for a byte in front of the stream's first one raises `bad` (the file is handed back)
 // Bound: latency of the serial decode per segment, hidden by the number of segments in flight (thousands) -- not HBM, not MFMA.
 #include <hip/hip_runtime.h>
 
@@ -187,7 +188,9 @@ __global__ __launch_bounds__(256) void mk_gzip_maps_step_kernel(const uint16_t *
     }
     *reinterpret_cast<uint4 *>(dst + (uint64_t)j * kSegPrefix + k) = make_uint4(w[0], w[1], w[2], w[3]);
 }
-// ctx[j + 1] from map j, now in terms of ctx[0] = zeros (blockIdx.y = 0: ctx[0] itself).  8 elements per thread.
+// ctx[j + 1] from map j, now in terms of ctx[0] = zeros (blockIdx.y = 0: ctx[0] itself).  8 elements per thread.  What is still a
+// place-holder of ctx[0] lies in front of the stream: the 0 written for it is never text -- the translation refuses the symbols
+// that would read it (seg_before_stream).
 __global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t *__restrict__ maps, uint8_t *__restrict__ ctx) {
     const uint32_t k = (blockIdx.x * 256 + threadIdx.x) * 8;
     uint2 bytes = make_uint2(0, 0);
@@ -202,7 +205,8 @@ __global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t 
     *reinterpret_cast<uint2 *>(ctx + (uint64_t)blockIdx.y * kSegPrefix + k) = bytes;
 }
 
-// text[text_off[j] + i] = the byte symbol i of segment j stands for
+// text[text_off[j] + i] = the byte symbol i of segment j stands for.  bad: a symbol that is neither a byte nor a place-holder, or the
+// place-holder of a byte in front of the stream (a distance too far back, however many matches carried it here).
 __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t *__restrict__ sym, const unsigned long long *__restrict__ seg_off,
                                                                  const unsigned long long *__restrict__ n_out, const unsigned long long *__restrict__ text_off,
                                                                  const uint8_t *__restrict__ ctx, uint32_t n_seg, uint8_t *__restrict__ text, uint32_t *__restrict__ bad) {
@@ -215,10 +219,11 @@ __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t 
     const uint16_t *o = sym + seg_off[j] + kSegPrefix;
     uint8_t *dst = text + text_off[j];
     const uint64_t n = n_out[j];
+    const uint32_t before = seg_context_before_stream(text_off[j]);
     uint32_t wrong = 0;
     for (uint64_t i = threadIdx.x; i < n; i += 1024) {
         const uint16_t v = o[i];
-        wrong |= (v >= 256 && !(v & kSegUnknown));
+        wrong |= (v >= 256 && !(v & kSegUnknown)) || seg_before_stream(v, before);
         dst[i] = (v & kSegUnknown) ? c[v & 0x7fffu] : (uint8_t)v;
     }
     if (wrong) atomicOr(bad, 1u);

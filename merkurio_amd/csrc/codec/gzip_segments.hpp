@@ -21,6 +21,8 @@
 //      copy inside the segment's buffer, and place-holders travel through later matches like bytes do.
 //   3. resolution.  Segment by segment, the last 32 KiB of resolved text become the next segment's context (sequential, 32 KiB per
 //      step); then every symbol of every segment is translated in parallel and the text is checked against the member's CRC-32 / ISIZE.
+//      A place-holder that stands for a byte in FRONT of the stream's first one (seg_before_stream) is a match that reaches too far
+//      back, in its own piece or carried on by later matches: zlib refuses such a stream, and so does the translation.
 // Anything that does not add up -- no block start found where one is needed, a segment that does not end exactly on the next start,
 // a buffer that is too small for an unusually compressible stream, a wrong CRC -- makes the whole call report "not taken": the
 // caller inflates that file with zlib, as before.  RFC 1951 / RFC 1952.
@@ -35,6 +37,12 @@ constexpr uint32_t kSegSlack = 16;         // elements a segment buffer holds be
 
 // error codes (negative; >= 0 are fine)
 constexpr int kSegDesync = -20, kSegOverflow = -21, kSegNoStart = -22;
+
+// Element k of the context of a segment whose text starts at byte text_off of the whole text is byte text_off - 32 768 + k of it:
+// how many elements at the context's front lie in front of the stream's first byte.  A symbol that is the place-holder of one of
+// them is a distance "too far back" (RFC 1951 3.2.3: a distance never reaches beyond the beginning of the output stream).
+MKZ_HD uint32_t seg_context_before_stream(uint64_t text_off) { return text_off < kSegPrefix ? kSegPrefix - (uint32_t)text_off : 0u; }
+MKZ_HD bool seg_before_stream(uint16_t symbol, uint32_t before) { return (symbol & kSegUnknown) && (uint32_t)(symbol & 0x7fffu) < before; }
 
 // ---- bit reader: straight from global memory, one dword ahead --------------------------------------------------------------------
 struct SegReader {

@@ -3,6 +3,8 @@
 // place-holders for the unknown 32 KiB in front, contexts resolved segment by segment, symbols translated -- and the text written to
 // stdout; tests/test_codec_cpu.py compares it with zlib's.
 // usage: gzip_harness <file.gz> <nominal chunk bytes>     (stderr: "segments N")
+// exit: 0 text written; 3 no gzip header / levels disagree; 4 a segment does not decode; 5 a symbol that is none; 6 a match that
+// reaches in front of the stream's first byte; 7 reserved FLG bits
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +25,7 @@ int main(int argc, char **argv) {
     if (gz.size() < 18 || gz[0] != 0x1f || gz[1] != 0x8b || gz[2] != 8) return 3;
     size_t p = 10;
     const uint8_t flg = gz[3];
+    if (flg & 0xE0) return 7;
     if (flg & 4) p += 2 + (gz[p] | gz[p + 1] << 8);
     if (flg & 8) p += strlen((const char *)&gz[p]) + 1;
     if (flg & 16) p += strlen((const char *)&gz[p]) + 1;
@@ -85,6 +88,7 @@ int main(int argc, char **argv) {
         for (uint64_t i = 0; i < n_out[j]; ++i) {
             const uint16_t v = o[i];
             if (v >= 256 && !(v & mkz::kSegUnknown)) return 5;
+            if (mkz::seg_before_stream(v, mkz::seg_context_before_stream(at))) return 6;
             text[at + i] = v & mkz::kSegUnknown ? ctx[v & 0x7fff] : (uint8_t)v;
         }
         // the next context: the last 32 KiB of everything so far

@@ -172,3 +172,61 @@ def test_parallel_gunzip_pieces_match_zlib(tmp_path):
         check(co.compress(fastq) + co.flush(), fastq, 30000, 1)  # (fixed / stored blocks have no findable starts: fewer pieces, same text)
     for data in (b"", b"A", b"ACGT" * 10, bytes(70000)):
         check(gzip.compress(data), data, 20000, 1)
+
+
+# ---- hand-made streams (tests/deflate_craft.py): the corners of RFC 1951 that no compressor here writes ---------------------------------
+def test_inflate_hand_made_streams_match_zlib(harness, tmp_path):
+    """the whole catalogue through the lane decoder: status 0 exactly for the streams zlib inflates to their end (`ok-`), their bytes
+    zlib's; every stream zlib refuses (`bad-`) is refused -- asked for the length zlib had written when it stopped, for the length
+    of the lenient reading where there is one, and for a generous one -- and no guard byte is touched"""
+    import deflate_craft as craft
+    recs, expect = [], []
+    for name, raw, lenient in craft.CATALOGUE:
+        text, _ = craft.verdict(raw)
+        if name.startswith("ok-"):
+            recs.append((raw, len(text)))
+            expect.append((name, text))
+        else:
+            for n_out in {len(craft.WRITTEN[name]), len(lenient) if lenient is not None else 1 << 16, 1 << 16}:
+                recs.append((raw, n_out))
+                expect.append((name, None))
+    status, got = run_inflate(harness, tmp_path, recs)
+    assert len(status) == len(recs)
+    at = 0
+    for (name, text), (raw, n_out), s in zip(expect, recs, status):
+        assert s != -99, (name, "guard byte")
+        assert (s == 0) == (text is not None), (name, n_out, s)
+        if text is not None:
+            assert got[at:at + n_out] == text, name
+        at += n_out
+
+
+@pytest.fixture(scope="module")
+def gzip_harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("gzip") / "gzip_harness")
+    subprocess.run(["g++", "-std=c++17", *_FLAGS, "-O2", "-Wall", "-I", os.path.join(ROOT, "merkurio_amd/csrc/codec"), "-I", os.path.join(ROOT, "merkurio_amd/csrc"),
+                    "-o", exe, os.path.join(ROOT, "tests/helpers/gzip_harness.cpp")], check=True)
+    return exe
+
+
+def test_parallel_gunzip_hand_made_streams(gzip_harness, tmp_path):
+    """the gunzip streams of deflate_craft.gunzip_streams() -- dynamic blocks of a little over 4 KiB each, cut every 4 KiB -- through the
+    serial form of the parallel gunzip: every `ok-` stream gives zlib's text in at least the pieces it was built to have (the block-start
+    search believes the hand-made blocks); a match that reaches in front of the stream's first byte -- in piece 0, or through
+    place-holders and copies of them in later pieces -- is refused as zlib refuses it (exit 6), reserved FLG bits likewise (7)"""
+    import deflate_craft as craft
+    for name, gz, text, pieces in craft.gunzip_streams():
+        (tmp_path / "t.gz").write_bytes(gz)
+        p = subprocess.run([gzip_harness, str(tmp_path / "t.gz"), str(craft.GUNZIP_CHUNK)], capture_output=True)
+        if text is None:
+            assert p.returncode == 6, (name, p.returncode, p.stderr[-300:])
+            assert int(p.stderr.split()[-1]) >= pieces, (name, p.stderr, pieces)  # (cut as built: the refusal is the resolution's)
+            with pytest.raises(zlib.error, match="too far back"):
+                zlib.decompress(gz, 31)
+            continue
+        assert p.returncode == 0, (name, p.returncode, p.stderr[-300:])
+        assert p.stdout == text == zlib.decompress(gz, 31), name
+        assert int(p.stderr.split()[-1]) >= pieces, (name, p.stderr, pieces)
+    name, gz, text, _ = craft.gunzip_streams()[1]
+    (tmp_path / "t.gz").write_bytes(gz[:3] + bytes([gz[3] | 0x20]) + gz[4:])
+    assert subprocess.run([gzip_harness, str(tmp_path / "t.gz"), str(craft.GUNZIP_CHUNK)], capture_output=True).returncode == 7
