@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void mk_bam_unpack_kernel(const uint8_t *__res
     }
 }
 
-// ---- the value of a record that already carries the tag (src/cmd_tag.rs:470-485): tag_merge.hpp (shared with sam.hip)
+// ---- the keep rule and the value of the tag (plain or merged with an existing one): tag_merge.hpp (shared with sam.hip)
 
 // Per record: keep or drop (src/cmd_tag.rs:457-467), and for a kept one the size of the record it leaves as --
 // 4 + block_size + tag (2) + 'Z' + value + NUL, the value being its distinct matched patterns joined by ',' (:484-490; ascending
@@ -211,8 +211,7 @@ __global__ __launch_bounds__(256) void mk_bam_taglen_kernel(const uint8_t *__res
     uint32_t bad = 0;
     if (i < n_rec) {
         const unsigned long long f0 = found_off[i], f1 = found_off[i + 1];
-        const bool has = f1 > f0;
-        const bool kept = filter_matching ? has : (invert ? !has : true);
+        const bool kept = tag_keeps(filter_matching, invert, f1 > f0);
         uint32_t len = 0, ex_at = 0, ex_n = 0;
         if (kept) {
             const uint32_t l = seq_len[i];
@@ -262,21 +261,8 @@ __global__ __launch_bounds__(256) void mk_bam_taglen_kernel(const uint8_t *__res
                 }
             }
             if (p > e) bad |= 2;
-            uint32_t vlen = 0;
-            if (ex_n == 0) {  // no tag of that name, or an empty value ("do nothing if tag is empty", :472-473)
-                ex_at = 0;
-                for (unsigned long long k = f0; k < f1; ++k) {
-                    const uint32_t pt = found_pat[k];
-                    vlen += pat_off[pt + 1] - pat_off[pt];
-                }
-                if (has) vlen += (uint32_t)(f1 - f0) - 1;
-            } else if (!bad) {
-                const uint8_t *prev = nullptr, *it;
-                uint32_t nprev = 0, nit, items = 0;
-                while (bam_merge_next(text + ex_at, ex_n, f0, f1, found_pat, pat_bytes, pat_off, items != 0, prev, nprev, &it, &nit))
-                    vlen += nit, prev = it, nprev = nit, ++items;
-                vlen += items - 1;
-            }
+            if (ex_n == 0) ex_at = 0;  // no tag of that name, or an empty value ("do nothing if tag is empty", :472-473)
+            const uint32_t vlen = (ex_n && bad) ? 0u : tag_value_len(text + ex_at, ex_n, f0, f1, found_pat, pat_off, pat_bytes);
             len = rec_len[i] + 3 + vlen + 1;
         }
         keep[i] = kept ? 1 : 0;
@@ -317,26 +303,11 @@ __global__ __launch_bounds__(256) void mk_bam_emit_kernel(const uint8_t *__restr
         t[0] = (uint8_t)tag0, t[1] = (uint8_t)tag1, t[2] = 'Z';
         t += 3;
         const unsigned long long f0 = found_off[i], f1 = found_off[i + 1];
-        const uint32_t ex_at = ex_off[i];
-        if (ex_at == 0) {
-            for (unsigned long long f = f0; f < f1; ++f) {
-                if (f > f0) *t++ = ',';
-                const uint32_t pt = found_pat[f];
-                const uint32_t a = pat_off[pt], b = pat_off[pt + 1];
-                for (uint32_t j = a; j < b; ++j) *t++ = pat_bytes[j];
-            }
-        } else {  // merged with the record's existing value (the old field stays where it is: push_string appends, :488-490)
-            uint32_t ex_n = 0;
+        const uint32_t ex_at = ex_off[i];  // (0: no existing value; else it ends at its NUL)
+        uint32_t ex_n = 0;
+        if (ex_at)
             while (text[ex_at + ex_n]) ++ex_n;
-            const uint8_t *prev = nullptr, *it;
-            uint32_t nprev = 0, nit, items = 0;
-            while (bam_merge_next(text + ex_at, ex_n, f0, f1, found_pat, pat_bytes, pat_off, items != 0, prev, nprev, &it, &nit)) {
-                if (items) *t++ = ',';
-                for (uint32_t j = 0; j < nit; ++j) *t++ = it[j];
-                prev = it, nprev = nit, ++items;
-            }
-        }
-        *t = 0;
+        *tag_value_put(t, text + ex_at, ex_n, f0, f1, found_pat, pat_off, pat_bytes) = 0;
     }
 }
 

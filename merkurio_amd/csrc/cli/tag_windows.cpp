@@ -18,8 +18,14 @@
 // (SamFile::seek_bam): the r04 path takes the rest of the file and words the reference's errors.  (The window behind it may have
 // been started already: its results are dropped.)
 //
-// Plain SAM text -> SAM text has a driver of the same shape further down (tag_sam_windows_on_device, mk_tag_sam_window), without the
-// head chain: text can be cut at line starts, so its windows are independent.
+// Plain SAM text -> SAM text (or -S) goes the same way (tag_sam_windows_on_device, mk_tag_sam_window, sam.hip) without the codec and
+// without the head chain: a window is a slice of the memory-mapped file cut at a line start (a '\n' can be found without reading the
+// lines), so windows are INDEPENDENT; it is staged through a page-locked buffer and comes back as the kept lines with their tag field
+// appended, written as they are.  A refused window (a line with fewer than 10 fields, a kept record whose field of the tag's name is
+// not a plain string) hands the input back to the host loop at its first byte (SamFile::seek_text).
+//
+// Both formats share one driver (run_windows): the round-robin over the workers, the repeat of a call that asked for more room, the
+// emit turn, refusal and error bookkeeping, counters and log rows.  BamWorker / SamWorker say how a window is staged, run and written.
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -49,19 +55,114 @@ void copy_in(const uint8_t *file, uint64_t lo, uint64_t hi, uint8_t *dst) {
     run_threads(T, [&](size_t t) { memcpy(dst + n * t / T, file + lo + n * t / T, (size_t)(n * (t + 1) / T - n * t / T)); });
 }
 
-// what the two workers share: whose head is known, whose turn it is to emit, and how the job ends early
+// what the workers share: whose turn it is to emit, and how the job ends early
 struct Pipe {
     std::mutex mu;
     std::condition_variable cv;
+    size_t emit_turn = 0;         // windows before this one have been emitted
+    bool stop = false;            // a window was refused or failed: nothing further is emitted
+    size_t refused = ~(size_t)0;  // the window the host reader takes over at
+    std::string error;
+    // BAM's head chain: window k + 1 starts with window k's tail, reported by the library as soon as it is known (on_tail)
     size_t heads_ready = 0;  // the head of window `heads_ready` is in `head` (windows before it have theirs already)
     std::vector<uint8_t> head;
-    size_t emit_turn = 0;               // windows before this one have been emitted
-    bool stop = false;                  // a window was refused or failed: nothing further is emitted
-    size_t refused = ~(size_t)0;        // the window the host reader takes over at ...
-    std::vector<uint8_t> refused_head;  // ... and the head it was given
-    std::string error;
+    std::vector<uint8_t> refused_head;  // the head the refused window was given
 };
 
+// One worker per handle: window k runs on worker k mod n_workers (with the handles of several devices in a row, consecutive windows
+// go to different devices).  `make(id)` gives worker id its format's state W: W.w is the library's window struct (tag and keep rule
+// filled in here), W.load(k) puts window k's input where the device reads it (false: the job has been stopped), W.call(...) runs the
+// window, W.grow() makes the room for tail and output that a call asked for, W.write() hands the output on, W.refused(k, rc, status)
+// notes a window left to the host reader (pipe.mu held).  Results leave in window order, and after `stop` none do; a worker holds
+// one finished window at most while it waits for its turn.  Ends with bail() on the first error.
+template <class Make>
+void run_windows(const TagArgs &a, Pipe &pipe, size_t n_win, size_t n_workers, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                 const std::string &in_name, double (&t_dev)[8], Make make) {
+    auto worker = [&](size_t id) {
+        auto W = make(id);
+        std::vector<uint8_t> names(1u << 16);
+        std::vector<mk_row> rows(4096);
+        std::vector<uint64_t> row_name(4096);
+        mk_counters wc;
+        std::vector<uint32_t> wcounts(lg.active ? pats.list.size() : 0, 0);
+        for (size_t k = id; k < n_win; k += n_workers) {
+            {
+                std::lock_guard<std::mutex> lk(pipe.mu);
+                if (pipe.stop) return;
+            }
+            auto &w = W.w;
+            memset(&w, 0, sizeof(w));
+            w.filter_matching = a.filter_matching, w.invert = a.invert_match;
+            w.tag[0] = (uint8_t)a.tag[0], w.tag[1] = (uint8_t)a.tag[1];
+            if (!W.load(k)) return;
+            uint32_t status = 0;
+            int rc;
+            for (;;) {  // (a window that does not fit is done again with the sizes it asked for)
+                memset(&wc, 0, sizeof(wc));
+                std::fill(wcounts.begin(), wcounts.end(), 0);
+                w.rows = rows.data(), w.rows_cap = rows.size(), w.row_name = row_name.data(), w.names = names.data(), w.names_cap = names.size();
+                rc = W.call(lg.active, &wc, wcounts.data(), &status);
+                if (rc != MK_E_CAPACITY) break;
+                bool grew = W.grow();
+                if (w.n_rows > rows.size()) rows.resize(w.n_rows), row_name.resize(w.n_rows), grew = true;
+                if (w.n_names_bytes > names.size()) names.resize(w.n_names_bytes), grew = true;
+                if (!grew) break;
+            }
+            const bool refused = (W.corrupt_is_refused && rc == MK_E_CORRUPT) || (rc == MK_OK && status != 0);
+            std::string err;
+            if (!refused && rc != MK_OK) err = std::string("Error during matching: ") + mk_last_error();
+            // results leave in window order
+            std::unique_lock<std::mutex> lk(pipe.mu);
+            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.emit_turn == k; });
+            if (pipe.stop) return;  // (an earlier window ended the job: this one's results are dropped)
+            if (refused || !err.empty()) {
+                pipe.stop = true;
+                if (refused) pipe.refused = k, W.refused(k, rc, status);
+                else pipe.error = err;
+                pipe.cv.notify_all();
+                return;
+            }
+            lk.unlock();
+            // (only the worker whose turn it is gets here: the counters of its device, the loggers and the output are its alone)
+            add_counters(*handles[id].counters, wc);
+            add_counts(*handles[id].pattern_counts, wcounts);
+            for (int i = 0; i < 8; ++i) t_dev[i] += w.ms[i];
+            std::string emit_err;
+            try {
+                if (lg.active)
+                    emit_log_rows(
+                        lg, pats, rows.data(), w.n_rows,
+                        [&](const mk_row &r) {
+                            const char *nm = (const char *)names.data() + row_name[&r - rows.data()];
+                            return std::pair<const char *, size_t>(nm, strlen(nm));
+                        },
+                        [&](const mk_row &) -> const std::string & { return in_name; });
+                W.write();
+            } catch (const Error &e) {
+                emit_err = e.what()[0] ? e.what() : "error";
+            }
+            lk.lock();
+            if (!emit_err.empty()) pipe.stop = true, pipe.error = emit_err;
+            pipe.emit_turn = k + 1;
+            pipe.cv.notify_all();
+            if (pipe.stop) return;
+        }
+    };
+    // (a worker that throws must not leave the others waiting)
+    run_threads(n_workers, [&](size_t id) {
+        try {
+            worker(id);
+        } catch (const Error &e) {
+            std::lock_guard<std::mutex> lk(pipe.mu);
+            if (pipe.error.empty()) pipe.error = e.what()[0] ? e.what() : "error";
+            pipe.stop = true;
+            pipe.cv.notify_all();
+        }
+    });
+    if (!pipe.error.empty()) bail(pipe.error);
+}
+
+// ---- BAM
 struct TailCtx {
     Pipe *pipe;
     size_t k;
@@ -75,6 +176,120 @@ void on_tail(void *ctx, const uint8_t *tail, uint64_t n_tail) {
     t->pipe->heads_ready = t->k + 1;
     t->pipe->cv.notify_all();
 }
+
+// (BAM-shaped text deflates to a third; a window that does not fit is done again with the size it asked for)
+uint64_t out_guess(uint64_t text) { return text / 3 + (4u << 20); }
+
+struct BamWorker {
+    const std::vector<WindowMembers> &wins;
+    const uint8_t *file;
+    BamWriter *bw;
+    Pipe &pipe;
+    bool timing;
+    mk_matcher *m;
+    mk_codec *codec;
+    HostBuffer stage, out;  // the window's members (page-locked); the members it turns into (moved to the writer)
+    std::vector<uint8_t> tail = std::vector<uint8_t>(1u << 20), head;
+    TailCtx tctx{};
+    mk_bam_window w{};
+    static constexpr bool corrupt_is_refused = true;  // (a damaged member)
+    ~BamWorker() {
+        if (!g_process_is_ending) mk_codec_destroy(codec);
+    }
+    bool load(size_t k) {
+        const WindowMembers &X = wins[k];
+        if (!X.mem.empty()) {
+            if (!stage.grow(X.file_hi - X.file_lo, 1u << 20)) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
+            copy_in(file, X.file_lo, X.file_hi, stage.p);
+        }
+        if (bw && out.cap < out_guess(X.text + (1u << 20))) {
+            out.reset();
+            out = bw->take_raw_buffer(out_guess(X.text + (1u << 20)));
+        }
+        {
+            std::unique_lock<std::mutex> lk(pipe.mu);
+            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.heads_ready >= k; });
+            if (pipe.stop) return false;
+            head = pipe.head;
+        }
+        tctx = TailCtx{&pipe, k};
+        w.head = head.data(), w.n_head = head.size();
+        w.bgzf = stage.p, w.n_bgzf = X.file_hi - X.file_lo;
+        w.members = X.mem.data(), w.n_members = X.mem.size();
+        w.last = k + 1 == wins.size();
+        w.on_tail = on_tail, w.on_tail_ctx = &tctx;
+        return true;
+    }
+    int call(int logging, mk_counters *wc, uint32_t *wcounts, uint32_t *status) {
+        w.tail = tail.data(), w.tail_cap = tail.size();
+        w.out = bw ? out.p : nullptr, w.out_cap = bw ? out.cap : 0;
+        const int rc = mk_tag_bam_window(m, codec, &w, logging, wc, wcounts, status);
+        if (rc == MK_OK && !*status) on_tail(&tctx, tail.data(), w.n_tail);  // (an empty window returns before the library reports it)
+        return rc;
+    }
+    bool grow() {
+        bool grew = false;
+        if (w.n_tail > tail.size()) tail.resize(w.n_tail + (1u << 20)), grew = true;
+        if (bw && w.out_len > out.cap) {
+            out.reset();
+            out = bw->take_raw_buffer(w.out_len);
+            grew = true;
+        }
+        return grew;
+    }
+    void refused(size_t k, int rc, uint32_t status) {  // (the head the window was given, not the current one)
+        pipe.refused_head = head;
+        if (timing)
+            fprintf(stderr, "[timing] window %llu left to the host reader (%s)\n", (unsigned long long)k,
+                    rc == MK_E_CORRUPT ? "a damaged member"
+                    : status & 1       ? "record chain"
+                    : status & 2       ? "optional fields"
+                    : status & 4       ? "existing tag"
+                                       : "unfinished record");
+    }
+    void write() {
+        if (bw && w.out_len) bw->put_members(std::move(out), w.out_len);
+    }
+};
+
+// ---- SAM text: windows cut at line starts have no heads or tails and are independent
+struct SamWorker {
+    const std::vector<std::pair<uint64_t, uint64_t>> &wins;
+    const uint8_t *file;
+    Sink *out_sink;
+    uint32_t &refused_status;
+    mk_matcher *m;
+    HostBuffer stage, out;  // the window's text; the kept lines (both page-locked)
+    uint8_t no_tail[8];
+    mk_sam_window w{};
+    static constexpr bool corrupt_is_refused = false;
+    bool load(size_t k) {
+        const uint64_t b = wins[k].first, n = wins[k].second - wins[k].first;
+        if (!stage.grow(n, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+        copy_in(file, b, b + n, stage.p);
+        // (a kept line grows by its tag field: a tenth of a 350-byte line per matched 31-mer; a window that does not fit is
+        // done again with the size it asked for)
+        if (out_sink && out.cap < n + n / 4 + (1u << 20) && !out.grow(n + n / 4 + (1u << 20), 1u << 20))
+            bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+        w.text = stage.p, w.n_text = n;
+        w.last = 1;  // (the window ends at a line end or at the end of the file: all of it is lines)
+        return true;
+    }
+    int call(int logging, mk_counters *wc, uint32_t *wcounts, uint32_t *status) {
+        w.tail = no_tail, w.tail_cap = sizeof(no_tail);
+        w.out = out_sink ? out.p : nullptr, w.out_cap = out_sink ? out.cap : 0;
+        return mk_tag_sam_window(m, &w, logging, wc, wcounts, status);
+    }
+    bool grow() {
+        if (!out_sink || w.out_len <= out.cap) return false;
+        if (!out.grow(w.out_len, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+        return true;
+    }
+    void refused(size_t, int, uint32_t status) { refused_status = status; }
+    void write() {
+        if (out_sink && w.out_len) out_sink->write((const char *)out.p, w.out_len);
+    }
+};
 
 }  // namespace
 
@@ -118,142 +333,11 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
     // (window k runs on handle k mod n_workers: with the handles of several devices in a row, consecutive windows go to different devices)
     const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
     double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // (BAM-shaped text deflates to a third; a window that does not fit is done again with the size it asked for)
-    auto out_guess = [](uint64_t text) { return text / 3 + (4u << 20); };
-
-    auto worker = [&](size_t id) {
-        mk_matcher *m = handles[id].m;
-        mk_counters &c = *handles[id].counters;
-        std::vector<uint32_t> &counts = *handles[id].pattern_counts;
+    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev, [&](size_t id) {
         mk_codec *codec = nullptr;
         if (mk_codec_create(handles[id].device, &codec) != MK_OK) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
-        struct CodecGuard {
-            mk_codec *c;
-            ~CodecGuard() {
-                if (!g_process_is_ending) mk_codec_destroy(c);
-            }
-        } guard{codec};
-        HostBuffer stage, out;  // the window's members (page-locked); the members it turns into (moved to the writer)
-        std::vector<uint8_t> tail(1u << 20), names(1u << 16);
-        std::vector<mk_row> rows(4096);
-        std::vector<uint64_t> row_name(4096);
-        for (size_t k = id; k < n_win; k += n_workers) {
-            const WindowMembers &X = wins[k];
-            {
-                std::lock_guard<std::mutex> lk(pipe.mu);
-                if (pipe.stop) return;
-            }
-            if (!X.mem.empty()) {
-                if (!stage.grow(X.file_hi - X.file_lo, 1u << 20)) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
-                copy_in(file, X.file_lo, X.file_hi, stage.p);
-            }
-            if (bw && out.cap < out_guess(X.text + (1u << 20))) {
-                out.reset();
-                out = bw->take_raw_buffer(out_guess(X.text + (1u << 20)));
-            }
-            std::vector<uint8_t> head;
-            {
-                std::unique_lock<std::mutex> lk(pipe.mu);
-                pipe.cv.wait(lk, [&] { return pipe.stop || pipe.heads_ready >= k; });
-                if (pipe.stop) return;
-                head = pipe.head;
-            }
-            TailCtx tctx{&pipe, k};
-            mk_bam_window w;
-            memset(&w, 0, sizeof(w));
-            w.head = head.data(), w.n_head = head.size();
-            w.bgzf = stage.p, w.n_bgzf = X.file_hi - X.file_lo;
-            w.members = X.mem.data(), w.n_members = X.mem.size();
-            w.last = k + 1 == n_win, w.filter_matching = a.filter_matching, w.invert = a.invert_match;
-            w.tag[0] = (uint8_t)a.tag[0], w.tag[1] = (uint8_t)a.tag[1];
-            w.on_tail = on_tail, w.on_tail_ctx = &tctx;
-            mk_counters wc;
-            std::vector<uint32_t> wcounts(lg.active ? pats.list.size() : 0, 0);
-            uint32_t status = 0;
-            int rc;
-            for (;;) {
-                memset(&wc, 0, sizeof(wc));
-                std::fill(wcounts.begin(), wcounts.end(), 0);
-                w.tail = tail.data(), w.tail_cap = tail.size();
-                w.out = bw ? out.p : nullptr, w.out_cap = bw ? out.cap : 0;
-                w.rows = rows.data(), w.rows_cap = rows.size(), w.row_name = row_name.data(), w.names = names.data(), w.names_cap = names.size();
-                rc = mk_tag_bam_window(m, codec, &w, lg.active, &wc, wcounts.data(), &status);
-                if (rc != MK_E_CAPACITY) break;
-                bool grew = false;
-                if (w.n_tail > tail.size()) tail.resize(w.n_tail + (1u << 20)), grew = true;
-                if (bw && w.out_len > out.cap) {
-                    out.reset();
-                    out = bw->take_raw_buffer(w.out_len);
-                    grew = true;
-                }
-                if (w.n_rows > rows.size()) rows.resize(w.n_rows), row_name.resize(w.n_rows), grew = true;
-                if (w.n_names_bytes > names.size()) names.resize(w.n_names_bytes), grew = true;
-                if (!grew) break;
-            }
-            const bool refused = rc == MK_E_CORRUPT || (rc == MK_OK && status != 0);
-            if (rc == MK_OK && !status) on_tail(&tctx, tail.data(), w.n_tail);  // (an empty window returns before the library reports it)
-            std::string err;
-            if (!refused && rc != MK_OK) err = std::string("Error during matching: ") + mk_last_error();
-            // results leave in window order
-            std::unique_lock<std::mutex> lk(pipe.mu);
-            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.emit_turn == k; });
-            if (pipe.stop) return;  // (an earlier window ended the job: this one's results are dropped)
-            if (refused || !err.empty()) {
-                pipe.stop = true;
-                if (refused) {
-                    pipe.refused = k;
-                    pipe.refused_head = head;
-                    if (timing)
-                        fprintf(stderr, "[timing] window %llu left to the host reader (%s)\n", (unsigned long long)k,
-                                rc == MK_E_CORRUPT ? "a damaged member"
-                                : status & 1       ? "record chain"
-                                : status & 2       ? "optional fields"
-                                : status & 4       ? "existing tag"
-                                                   : "unfinished record");
-                } else {
-                    pipe.error = err;
-                }
-                pipe.cv.notify_all();
-                return;
-            }
-            lk.unlock();
-            // (only the worker whose turn it is gets here: the counters of its device, the loggers and the writer are its alone)
-            add_counters(c, wc);
-            add_counts(counts, wcounts);
-            for (int i = 0; i < 8; ++i) t_dev[i] += w.ms[i];
-            std::string emit_err;
-            try {
-                if (lg.active)
-                    emit_log_rows(
-                        lg, pats, rows.data(), w.n_rows,
-                        [&](const mk_row &r) {
-                            const char *nm = (const char *)names.data() + row_name[&r - rows.data()];
-                            return std::pair<const char *, size_t>(nm, strlen(nm));
-                        },
-                        [&](const mk_row &) -> const std::string & { return in_name; });
-                if (bw && w.out_len) bw->put_members(std::move(out), w.out_len);
-            } catch (const Error &e) {
-                emit_err = e.what()[0] ? e.what() : "error";
-            }
-            lk.lock();
-            if (!emit_err.empty()) pipe.stop = true, pipe.error = emit_err;
-            pipe.emit_turn = k + 1;
-            pipe.cv.notify_all();
-            if (pipe.stop) return;
-        }
-    };
-    // (a worker that throws must not leave the other one waiting)
-    run_threads(n_workers, [&](size_t id) {
-        try {
-            worker(id);
-        } catch (const Error &e) {
-            std::lock_guard<std::mutex> lk(pipe.mu);
-            if (pipe.error.empty()) pipe.error = e.what()[0] ? e.what() : "error";
-            pipe.stop = true;
-            pipe.cv.notify_all();
-        }
+        return BamWorker{wins, file, bw, pipe, timing, handles[id].m, codec};
     });
-    if (!pipe.error.empty()) bail(pipe.error);
     if (timing)
         fprintf(stderr,
                 "[timing] %llu of %llu windows on the device (%llu in flight): upload %.3f, inflate %.3f, record index %.3f, unpack + scan + sets %.3f, "
@@ -267,15 +351,6 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
     return true;
 }
 
-// ---- SAM text -> SAM text (or -S) with the lines resident on the device (mk_tag_sam_window, sam.hip) -------------------------------
-// The host path parsed every line, upper-cased every SEQ into a batch buffer, sent that to the scan and appended the tags on the host
-// threads.  Here a window is a slice of the memory-mapped file, cut at a line start (a '\n' can be found without reading the
-// lines), so windows have no heads or tails and are INDEPENDENT: window k runs on handle k mod handles.size() -- devices in turn,
-// two windows per device in flight -- staged through a page-locked buffer (a mapping is not a DMA source), and comes back as the
-// kept lines with their tag field appended, written as they are.  Results leave in window order; a worker holds one finished
-// window at most while it waits for its turn, so at most handles.size() windows exist at any time.
-// A window the device refuses (a line with fewer than 10 fields, a kept record whose field of the tag's name is not a plain
-// string) hands the input back to the host loop at that window's first byte (SamFile::seek_text), which words the reference's error.
 bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
                                const std::string &in_name, Sink *out_sink, uint64_t window_bytes) {
     const WindowSource &src = sam.source();
@@ -296,117 +371,11 @@ bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
     if (wins.empty()) return true;
     const size_t n_win = wins.size();
     const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
-    struct {
-        std::mutex mu;
-        std::condition_variable cv;
-        size_t emit_turn = 0;         // windows before this one have been emitted
-        bool stop = false;            // a window was refused or failed: nothing further is emitted
-        size_t refused = ~(size_t)0;  // the window the host loop takes over at
-        uint32_t refused_status = 0;
-        std::string error;
-    } pipe;
+    Pipe pipe;
+    uint32_t refused_status = 0;
     double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    auto worker = [&](size_t id) {
-        mk_matcher *m = handles[id].m;
-        mk_counters &c = *handles[id].counters;
-        std::vector<uint32_t> &counts = *handles[id].pattern_counts;
-        HostBuffer stage, out;  // the window's text; the kept lines (both page-locked)
-        std::vector<uint8_t> names(1u << 16);
-        std::vector<mk_row> rows(4096);
-        std::vector<uint64_t> row_name(4096);
-        uint8_t no_tail[8];
-        for (size_t k = id; k < n_win; k += n_workers) {
-            const uint64_t b = wins[k].first, n = wins[k].second - wins[k].first;
-            {
-                std::lock_guard<std::mutex> lk(pipe.mu);
-                if (pipe.stop) return;
-            }
-            if (!stage.grow(n, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
-            copy_in(file, b, b + n, stage.p);
-            // (a kept line grows by its tag field: a tenth of a 350-byte line per matched 31-mer; a window that does not fit is
-            // done again with the size it asked for)
-            if (out_sink && out.cap < n + n / 4 + (1u << 20) && !out.grow(n + n / 4 + (1u << 20), 1u << 20))
-                bail(std::string("Error during SAM record parsing: ") + mk_last_error());
-            mk_sam_window w;
-            memset(&w, 0, sizeof(w));
-            w.text = stage.p, w.n_text = n;
-            w.last = 1;  // (the window ends at a line end or at the end of the file: all of it is lines)
-            w.filter_matching = a.filter_matching, w.invert = a.invert_match;
-            w.tag[0] = (uint8_t)a.tag[0], w.tag[1] = (uint8_t)a.tag[1];
-            mk_counters wc;
-            std::vector<uint32_t> wcounts(lg.active ? pats.list.size() : 0, 0);
-            uint32_t status = 0;
-            int rc;
-            for (;;) {
-                memset(&wc, 0, sizeof(wc));
-                std::fill(wcounts.begin(), wcounts.end(), 0);
-                w.tail = no_tail, w.tail_cap = sizeof(no_tail);
-                w.out = out_sink ? out.p : nullptr, w.out_cap = out_sink ? out.cap : 0;
-                w.rows = rows.data(), w.rows_cap = rows.size(), w.row_name = row_name.data(), w.names = names.data(), w.names_cap = names.size();
-                rc = mk_tag_sam_window(m, &w, lg.active, &wc, wcounts.data(), &status);
-                if (rc != MK_E_CAPACITY) break;
-                bool grew = false;
-                if (out_sink && w.out_len > out.cap) {
-                    if (!out.grow(w.out_len, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
-                    grew = true;
-                }
-                if (w.n_rows > rows.size()) rows.resize(w.n_rows), row_name.resize(w.n_rows), grew = true;
-                if (w.n_names_bytes > names.size()) names.resize(w.n_names_bytes), grew = true;
-                if (!grew) break;
-            }
-            const bool refused = rc == MK_OK && status != 0;
-            std::string err;
-            if (rc != MK_OK) err = std::string("Error during matching: ") + mk_last_error();
-            // results leave in window order
-            std::unique_lock<std::mutex> lk(pipe.mu);
-            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.emit_turn == k; });
-            if (pipe.stop) return;  // (an earlier window ended the job: this one's results are dropped)
-            if (refused || !err.empty()) {
-                pipe.stop = true;
-                if (refused) pipe.refused = k, pipe.refused_status = status;
-                else pipe.error = err;
-                pipe.cv.notify_all();
-                return;
-            }
-            lk.unlock();
-            // (only the worker whose turn it is gets here: the counters of its device, the loggers and the sink are its alone)
-            add_counters(c, wc);
-            add_counts(counts, wcounts);
-            for (int i = 0; i < 8; ++i) t_dev[i] += w.ms[i];
-            std::string emit_err;
-            try {
-                if (lg.active)
-                    emit_log_rows(
-                        lg, pats, rows.data(), w.n_rows,
-                        [&](const mk_row &r) {
-                            const char *nm = (const char *)names.data() + row_name[&r - rows.data()];
-                            return std::pair<const char *, size_t>(nm, strlen(nm));
-                        },
-                        [&](const mk_row &) -> const std::string & { return in_name; });
-                if (out_sink && w.out_len) out_sink->write((const char *)out.p, w.out_len);
-            } catch (const Error &e) {
-                emit_err = e.what()[0] ? e.what() : "error";
-            }
-            lk.lock();
-            if (!emit_err.empty()) pipe.stop = true, pipe.error = emit_err;
-            pipe.emit_turn = k + 1;
-            pipe.cv.notify_all();
-            if (pipe.stop) return;
-        }
-    };
-    // (a worker that throws must not leave the others waiting)
-    run_threads(n_workers, [&](size_t id) {
-        try {
-            worker(id);
-        } catch (const Error &e) {
-            std::lock_guard<std::mutex> lk(pipe.mu);
-            if (pipe.error.empty()) pipe.error = e.what()[0] ? e.what() : "error";
-            pipe.stop = true;
-            pipe.cv.notify_all();
-        }
-    });
-    if (!pipe.error.empty()) bail(pipe.error);
+    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev,
+                [&](size_t id) { return SamWorker{wins, file, out_sink, refused_status, handles[id].m}; });
     if (timing) {
         fprintf(stderr,
                 "[timing] %llu of %llu SAM text windows on the device (%llu in flight): upload %.3f, line index + fields %.3f, gather + scan + sets %.3f, "
@@ -415,7 +384,7 @@ bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
                 t_dev[3] / 1e3, t_dev[4] / 1e3, t_dev[7] / 1e3);
         if (pipe.refused != ~(size_t)0)
             fprintf(stderr, "[timing] window %llu left to the host reader (%s)\n", (unsigned long long)pipe.refused,
-                    pipe.refused_status & 1 ? "a line with too few fields" : "existing tag");
+                    refused_status & 1 ? "a line with too few fields" : "existing tag");
     }
     if (pipe.refused != ~(size_t)0) {
         sam.seek_text(wins[pipe.refused].first);

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -984,6 +985,135 @@ double ms_since(std::chrono::steady_clock::time_point &t) {
     return ms;
 }
 
+// ---- `tag` on a window that stays on the device: what mk_tag_bam_window and mk_tag_sam_window share.  Each entry point makes its
+// record table (window_assemble, then bam_index / the line table and mk_sam_fields_kernel) and sends the kept records off in its own way
+// (BGZF members / text); in between, both go through tag_scan, tag_keep and tag_commit.
+// ms[7] of such a call: the time spent growing device buffers inside it (part of the phases, reported on its own)
+struct AllocMs {
+    float *out;
+    explicit AllocMs(float *out_) : out(out_) { g_alloc_ms = 0, g_free_ms = 0; }
+    ~AllocMs() { *out = (float)g_alloc_ms; }
+};
+
+// One such window between the steps: the fields of mk_bam_window / mk_sam_window that the steps use, the record table's per-record
+// arrays, and what a step leaves for the next one
+struct TagWindow {
+    const char *who;  // the entry point, for its messages
+    mk_row *rows;
+    uint64_t rows_cap, *row_name;
+    uint8_t *names;
+    uint64_t names_cap, *n_kept, *n_rows, *n_names_bytes;
+    uint64_t n;  // records
+    uint32_t *d_out_len, *d_ex_off;
+    unsigned long long *d_out_off;
+    const uint32_t *d_qname_len;  // SAM: the QNAMEs' lengths (BAM's names are found from the records)
+    // tag_scan ->
+    std::vector<uint8_t> flags;  // records with a hit; after tag_keep: the kept records
+    mk_counters lc{};            // counters of this window: added to the caller's only when the window is done (tag_commit) -- a refused
+    std::vector<uint32_t> lcounts;  // or repeated window counts nothing
+    unsigned long long *d_found_off = nullptr;
+    uint32_t *d_found_pat = nullptr;
+    unsigned long long out_text = 0;  // tag_keep -> bytes of the kept records with their tags
+};
+template <class Win>
+TagWindow tag_window(Win *w, const char *who, uint64_t n, uint32_t *d_out_len, uint32_t *d_ex_off, unsigned long long *d_out_off, const uint32_t *d_qname_len) {
+    return TagWindow{who, w->rows, w->rows_cap, w->row_name, w->names, w->names_cap, &w->n_kept, &w->n_rows, &w->n_names_bytes, n, d_out_len, d_ex_off, d_out_off,
+                     d_qname_len};
+}
+
+// sequences -> the scan buffer, scan, log rows with the names of their records, emission order, pattern sets
+int tag_scan(mk_matcher *m, DeviceLoop &dl, const WindowSide &W, TagWindow &X, SeqForm form, int logging) {
+    hipStream_t st = dl.st;
+    const uint64_t n = X.n;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    int rc;
+    uint64_t flagged = 0, n_seq = 0;
+    X.flags.resize(n);
+    if ((rc = scan_sequences(m, W, n, form, dl, MK_MODE_HITS, X.flags.data(), &flagged, &n_seq))) return rc;
+    const bool ac = m->algo == MK_ALGO_AC;
+    bool set_order = false;
+    uint64_t n_rows = 0;
+    X.lcounts.assign(logging ? m->n_pat : 0, 0);
+    if (logging) {  // src/cmd_tag.rs:400-416, :443-451
+        n_rows = dl.found;
+        if ((rc = dl.log_single(&X.lc, n, n_seq, flagged, X.rows, X.rows_cap))) return rc;
+        set_order = !ac;
+        if (ac && (rc = dl.pattern_counts(true, n, X.lcounts.data()))) return rc;
+        // the names of the records with a hit, NUL-terminated, in record order; a row finds its record's by a walk along both.
+        // BAM: read_name with its NUL.  SAM: QNAME gathered with the tab behind it, which then becomes the NUL.
+        if (flagged) {
+            const bool sam = form == kSeqSam;
+            uint32_t *d_name_len = sam ? X.d_out_len : (uint32_t *)X.d_out_off;       // (both free until the tag step)
+            const uint32_t *d_name_start = sam ? W.d_rec_start : X.d_out_len;
+            unsigned long long *d_name_off = (unsigned long long *)m->d_off;          // (the scan is done with the sequence offsets)
+            unsigned long long total = 0;
+            if (sam) launch_sam_names(X.d_qname_len, m->d_flags, n, d_name_len, st);
+            else launch_bam_names(d_text, W.d_rec_start, m->d_flags, n, X.d_out_len, d_name_len, st);
+            if ((rc = scan_offsets(d_name_len, n, W.d_tile, d_name_off, st, &total, "selection of the names failed"))) return rc;
+            *X.n_names_bytes = total;
+            if (total <= X.names_cap && n_rows <= X.rows_cap) {
+                // (the sequences have been scanned: their buffer holds the names now)
+                if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
+                launch_ingest_gather(d_text, d_name_start, d_name_len, d_name_off, 0, n, m->d_seq, st);
+                if (sam) launch_sam_name_ends(d_name_len, d_name_off, n, m->d_seq, st);
+                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(X.names, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipStreamSynchronize(st) != hipSuccess)
+                    return fail(MK_E_HIP, "download of the names failed");
+                name_rows(X.rows, n_rows, X.flags.data(), n, X.names, total, X.row_name);
+            }
+        }
+    }
+    *X.n_rows = n_rows;
+    if (!set_order && (rc = dl.order(false, n))) return rc;
+    uint32_t *d_cnt = nullptr;
+    uint64_t n_found = 0;
+    if ((rc = dl.pattern_sets_device(n, logging && !ac, &X.d_found_off, &X.d_found_pat, &d_cnt, &n_found))) return rc;
+    if (logging && !ac && n_found) {  // BNDMq: one count per record and pattern (:431-433)
+        if (hipMemcpy(X.lcounts.data(), d_cnt, (size_t)m->n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
+    }
+    return MK_OK;
+}
+
+// keep or drop and the size every kept record leaves with (`taglen`: the format's kernel, which fills m->d_flags2, d_out_len,
+// d_ex_off and W.d_st), where each goes (d_out_off), and whether the rows and names fit.  *status != 0: optional fields the device does
+// not decide about (the kernel's bits & status_mask) -- this window is the host path's, nothing further is set.
+int tag_keep(mk_matcher *m, DeviceLoop &dl, const WindowSide &W, TagWindow &X, int logging, uint32_t status_mask, const std::function<void()> &taglen,
+             uint32_t *status) {
+    hipStream_t st = dl.st;
+    const uint64_t n = X.n;
+    int rc;
+    if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
+    if (hipMemsetAsync(W.d_st, 0, 4, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
+    taglen();
+    launch_ingest_offsets(X.d_out_len, n, W.d_tile, X.d_out_off, st);
+    unsigned long long out_text = 0;
+    uint32_t st_tag = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&out_text, X.d_out_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&st_tag, W.d_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(X.flags.data(), m->d_flags2, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "tag kernels failed");
+    if (st_tag) {
+        *status = st_tag & status_mask;
+        return MK_OK;
+    }
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < n; ++r) kept += X.flags[r];
+    *X.n_kept = kept;
+    X.lc.nb_records_extracted = kept;
+    X.out_text = out_text;
+    if (logging && (*X.n_rows > X.rows_cap || *X.n_names_bytes > X.names_cap))
+        return fail(MK_E_CAPACITY, "%s: %llu rows and %llu bytes of names", X.who, (unsigned long long)*X.n_rows, (unsigned long long)*X.n_names_bytes);
+    return MK_OK;
+}
+
+// the window is done: its counters join the caller's
+void tag_commit(DeviceLoop &dl, const TagWindow &X, mk_counters *c, uint32_t *counts) {
+    c->nb_records_tot += X.lc.nb_records_tot, c->nb_bases += X.lc.nb_bases, c->nb_hits_tot[0] += X.lc.nb_hits_tot[0];
+    c->nb_records_hit[0] += X.lc.nb_records_hit[0], c->nb_records_extracted += X.lc.nb_records_extracted;
+    for (size_t i = 0; i < X.lcounts.size(); ++i) counts[i] += X.lcounts[i];
+    dl.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1010,11 +1140,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     hipStream_t st = dl.st;
     int rc;
     auto t = std::chrono::steady_clock::now();
-    g_alloc_ms = 0, g_free_ms = 0;
-    struct AllocMs {  // (device buffers grown inside the call: part of the phases above, reported on its own as ms[7])
-        float *out;
-        ~AllocMs() { *out = (float)g_alloc_ms; }
-    } alloc_ms{&w->ms[7]};
+    AllocMs alloc_ms(&w->ms[7]);
     // ---- the text: head, then the members inflated behind it (window_assemble: upload, inflate, CRC-32 / ISIZE of every member)
     WindowSide W;
     W.T = &m->txt[0];
@@ -1049,88 +1175,25 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     uint32_t *d_out_len = d_rec_len + n + 2, *d_ex_off = d_out_len + n + 2;
     unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_ex_off + n + 2) + 15) & ~(uintptr_t)15);
     W.d_tile = d_out_off + n + 2;
+    TagWindow X = tag_window(w, "mk_tag_bam_window", n, d_out_len, d_ex_off, d_out_off, nullptr);
     // ---- sequences -> the scan buffer, scan, emission order, pattern sets
-    std::vector<uint8_t> flags(n);
-    uint64_t flagged = 0;
-    uint64_t n_seq = 0;
-    if ((rc = scan_sequences(m, W, n, kSeqBam, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
-    const bool ac = m->algo == MK_ALGO_AC;
-    bool set_order = false;
-    uint64_t n_rows = 0;
-    // (counters of this window: added to the caller's only when the window is done -- a refused or repeated window counts nothing)
-    mk_counters lc;
-    memset(&lc, 0, sizeof(lc));
-    std::vector<uint32_t> lcounts(logging ? m->n_pat : 0, 0);
-    if (logging) {  // src/cmd_tag.rs:400-416, :443-451
-        n_rows = dl.found;
-        if ((rc = dl.log_single(&lc, n, n_seq, flagged, w->rows, w->rows_cap))) return rc;
-        set_order = !ac;
-        if (ac && (rc = dl.pattern_counts(true, n, lcounts.data()))) return rc;
-        // the names of the records with a hit, NUL-terminated, in record order; a row finds its record's by a walk along both
-        if (flagged) {
-            uint32_t *d_name_start = d_out_len, *d_name_len = (uint32_t *)d_out_off;  // (free until the tag step)
-            unsigned long long *d_name_off = (unsigned long long *)m->d_off;          // (the scan is done with the sequence offsets)
-            unsigned long long total = 0;
-            launch_bam_names((const uint8_t *)W.T->d_text, W.d_rec_start, m->d_flags, n, d_name_start, d_name_len, st);
-            if ((rc = scan_offsets(d_name_len, n, W.d_tile, d_name_off, st, &total, "selection of the names failed"))) return rc;
-            w->n_names_bytes = total;
-            if (total <= w->names_cap && n_rows <= w->rows_cap) {
-                // (the unpacked sequences have been scanned: their buffer holds the names now)
-                if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
-                launch_ingest_gather((const uint8_t *)W.T->d_text, d_name_start, d_name_len, d_name_off, 0, n, m->d_seq, st);
-                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(w->names, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess)
-                    return fail(MK_E_HIP, "download of the names failed");
-                name_rows(w->rows, n_rows, flags.data(), n, w->names, total, w->row_name);
-            }
-        }
-    }
-    w->n_rows = n_rows;
-    if (!set_order && (rc = dl.order(false, n))) return rc;
-    unsigned long long *d_found_off = nullptr;
-    uint32_t *d_found_pat = nullptr, *d_cnt = nullptr;
-    uint64_t n_found = 0;
-    if ((rc = dl.pattern_sets_device(n, logging && !ac, &d_found_off, &d_found_pat, &d_cnt, &n_found))) return rc;
-    if (logging && !ac && n_found) {  // BNDMq: one count per record and pattern (:431-433)
-        if (hipMemcpy(lcounts.data(), d_cnt, (size_t)m->n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
-    }
+    if ((rc = tag_scan(m, dl, W, X, kSeqBam, logging))) return rc;
     w->ms[3] = (float)ms_since(t);
     // ---- keep, tag, pack
-    if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
-    if (hipMemsetAsync(W.d_st, 0, 4, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
-    launch_bam_taglen((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, d_found_off, d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
-                      w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
-    launch_ingest_offsets(d_out_len, n, W.d_tile, d_out_off, st);
-    unsigned long long out_text = 0;
-    uint32_t st_tag = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&out_text, d_out_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&st_tag, W.d_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(flags.data(), m->d_flags2, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "tag kernels failed");
-    if (st_tag) {  // optional fields the device does not decide about: this window is the host path's
-        *status = st_tag & 6u;
-        return MK_OK;
-    }
-    uint64_t kept = 0;
-    for (uint64_t r = 0; r < n; ++r) kept += flags[r];
-    w->n_kept = kept;
-    lc.nb_records_extracted = kept;
+    rc = tag_keep(m, dl, W, X, logging, 6u, [&] {
+        launch_bam_taglen((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
+                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+    }, status);
+    const unsigned long long out_text = X.out_text;
     w->out_text_bytes = out_text;
-    if (logging && (n_rows > w->rows_cap || w->n_names_bytes > w->names_cap))
-        return fail(MK_E_CAPACITY, "mk_tag_bam_window: %llu rows and %llu bytes of names", (unsigned long long)n_rows, (unsigned long long)w->n_names_bytes);
-    auto commit = [&] {
-        c->nb_records_tot += lc.nb_records_tot, c->nb_bases += lc.nb_bases, c->nb_hits_tot[0] += lc.nb_hits_tot[0];
-        c->nb_records_hit[0] += lc.nb_records_hit[0], c->nb_records_extracted += lc.nb_records_extracted;
-        for (size_t i = 0; i < lcounts.size(); ++i) counts[i] += lcounts[i];
-        dl.finish();
-    };
+    if (rc || *status) return rc;
     if ((!w->out && !w->out_cap) || out_text == 0) {  // tag -s (the checks have run, nothing is written) / nothing is kept
-        commit();
+        tag_commit(dl, X, c, counts);
         return MK_OK;
     }
     mk_matcher::TextSlot &O = m->txt[1];
     if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64))) return rc;
-    launch_bam_emit((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, d_out_len, d_out_off, d_found_off, d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n,
+    launch_bam_emit((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, d_out_len, d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n,
                     w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
     if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return fail(MK_E_HIP, "record output kernel failed");
@@ -1169,7 +1232,7 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
             return fail(MK_E_HIP, "download of the members failed");
         w->ms[6] = (float)ms_since(t);
     }
-    commit();
+    tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
 }
@@ -1192,11 +1255,7 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
     hipStream_t st = dl.st;
     int rc;
     auto t = std::chrono::steady_clock::now();
-    g_alloc_ms = 0, g_free_ms = 0;
-    struct AllocMs {  // (device buffers grown inside the call: part of the phases, reported on its own as ms[7])
-        float *out;
-        ~AllocMs() { *out = (float)g_alloc_ms; }
-    } alloc_ms{&w->ms[7]};
+    AllocMs alloc_ms(&w->ms[7]);
     // ---- the text: head, then the body behind it
     WindowSide W;
     W.T = &m->txt[0];
@@ -1270,81 +1329,24 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
         return fail(MK_E_HIP, "download of the tail failed");
     w->ms[1] = (float)ms_since(t);
     if (n == 0) return MK_OK;
-    // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets (as mk_tag_bam_window)
-    std::vector<uint8_t> flags(n);
-    uint64_t flagged = 0, n_seq = 0;
-    if ((rc = scan_sequences(m, W, n, kSeqSam, dl, MK_MODE_HITS, flags.data(), &flagged, &n_seq))) return rc;
-    const bool ac = m->algo == MK_ALGO_AC;
-    bool set_order = false;
-    uint64_t n_rows = 0;
-    // (counters of this window: added to the caller's only when the window is done -- a refused or repeated window counts nothing)
-    mk_counters lc;
-    memset(&lc, 0, sizeof(lc));
-    std::vector<uint32_t> lcounts(logging ? m->n_pat : 0, 0);
-    if (logging) {  // src/cmd_tag.rs:400-416, :443-451
-        n_rows = dl.found;
-        if ((rc = dl.log_single(&lc, n, n_seq, flagged, w->rows, w->rows_cap))) return rc;
-        set_order = !ac;
-        if (ac && (rc = dl.pattern_counts(true, n, lcounts.data()))) return rc;
-        // the QNAMEs of the records with a hit, NUL-terminated, in record order: each is gathered with the tab behind it, which
-        // then becomes the NUL
-        if (flagged) {
-            uint32_t *d_name_len = d_out_len;                                 // (free until the tag step)
-            unsigned long long *d_name_off = (unsigned long long *)m->d_off;  // (the scan is done with the sequence offsets)
-            unsigned long long total = 0;
-            launch_sam_names(R.name_len, m->d_flags, n, d_name_len, st);
-            if ((rc = scan_offsets(d_name_len, n, W.d_tile, d_name_off, st, &total, "selection of the names failed"))) return rc;
-            w->n_names_bytes = total;
-            if (total <= w->names_cap && n_rows <= w->rows_cap) {
-                if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
-                launch_ingest_gather(d_text, R.rec_start, d_name_len, d_name_off, 0, n, m->d_seq, st);
-                launch_sam_name_ends(d_name_len, d_name_off, n, m->d_seq, st);
-                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(w->names, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess)
-                    return fail(MK_E_HIP, "download of the names failed");
-                name_rows(w->rows, n_rows, flags.data(), n, w->names, total, w->row_name);
-            }
-        }
-    }
-    w->n_rows = n_rows;
-    if (!set_order && (rc = dl.order(false, n))) return rc;
-    unsigned long long *d_found_off = nullptr;
-    uint32_t *d_found_pat = nullptr, *d_cnt = nullptr;
-    uint64_t n_found = 0;
-    if ((rc = dl.pattern_sets_device(n, logging && !ac, &d_found_off, &d_found_pat, &d_cnt, &n_found))) return rc;
-    if (logging && !ac && n_found) {  // BNDMq: one count per record and pattern (:431-433)
-        if (hipMemcpy(lcounts.data(), d_cnt, (size_t)m->n_pat * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MK_E_HIP, "copy of the counts failed");
-    }
+    TagWindow X = tag_window(w, "mk_tag_sam_window", n, d_out_len, d_ex_off, d_out_off, R.name_len);
+    // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets
+    if ((rc = tag_scan(m, dl, W, X, kSeqSam, logging))) return rc;
     w->ms[2] = (float)ms_since(t);
-    // ---- keep, tag, pack
-    if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
-    if (hipMemsetAsync(W.d_st, 0, 4, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
-    launch_sam_taglen(d_text, R, d_found_off, d_found_pat, m->d_pat_off, m->d_pat_bytes, n, w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1],
-                      m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
-    launch_ingest_offsets(d_out_len, n, W.d_tile, d_out_off, st);
-    unsigned long long out_text = 0;
-    uint32_t st_tag = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&out_text, d_out_off + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&st_tag, W.d_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(flags.data(), m->d_flags2, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "tag kernels failed");
-    if (st_tag) {  // an existing field the device does not decide about: this window is the host path's
-        *status = st_tag & 4u;
-        return MK_OK;
-    }
-    uint64_t kept = 0;
-    for (uint64_t r = 0; r < n; ++r) kept += flags[r];
-    w->n_kept = kept;
-    lc.nb_records_extracted = kept;
+    // ---- keep, tag, emit
+    rc = tag_keep(m, dl, W, X, logging, 4u, [&] {
+        launch_sam_taglen(d_text, R, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n, w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1],
+                          m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+    }, status);
+    const unsigned long long out_text = X.out_text;
     const bool write = w->out || w->out_cap;
     if (write) w->out_len = out_text;
-    if (logging && (n_rows > w->rows_cap || w->n_names_bytes > w->names_cap))
-        return fail(MK_E_CAPACITY, "mk_tag_sam_window: %llu rows and %llu bytes of names", (unsigned long long)n_rows, (unsigned long long)w->n_names_bytes);
+    if (rc || *status) return rc;
     if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_sam_window: the kept lines take %llu bytes", out_text);
     if (write && out_text) {
         mk_matcher::TextSlot &O = m->txt[1];
         if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
-        launch_sam_emit(d_text, R, d_out_len, d_out_off, d_found_off, d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n, w->tag[0], w->tag[1],
+        launch_sam_emit(d_text, R, d_out_len, d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n, w->tag[0], w->tag[1],
                         (uint8_t *)O.d_text, st);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "line output kernel failed");
         w->ms[3] = (float)ms_since(t);
@@ -1354,10 +1356,7 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
     } else {
         w->ms[3] = (float)ms_since(t);
     }
-    c->nb_records_tot += lc.nb_records_tot, c->nb_bases += lc.nb_bases, c->nb_hits_tot[0] += lc.nb_hits_tot[0];
-    c->nb_records_hit[0] += lc.nb_records_hit[0], c->nb_records_extracted += lc.nb_records_extracted;
-    for (size_t i = 0; i < lcounts.size(); ++i) counts[i] += lcounts[i];
-    dl.finish();
+    tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
 }

@@ -13,6 +13,7 @@
 //   mk_sam_gather_kernel   SEQ -> scan buffer, a-z upper-cased (eight bytes at a time)
 //   mk_sam_taglen_kernel   keep / drop; of a kept record the first optional field of the tag's name, its value, the output length
 //   mk_sam_emit_kernel     line TAB tag ":Z:" value '\n' at its place in the output
+// (the keep rule and the value itself are tag_merge.hpp's, shared with bam.hip; the host side of both is host_loops.cpp: tag_scan / tag_keep)
 // Every access is bounded by the line it belongs to: a load of 16 bytes starts inside the line and may run up to 15 bytes past its
 // end, which the text buffer's padding (64 bytes behind the window, host_loops.cpp: window_assemble) covers.
 #include "scan_kernel.h"
@@ -188,8 +189,7 @@ __global__ __launch_bounds__(256) void mk_sam_taglen_kernel(const uint8_t *__res
     uint32_t bad = 0;
     if (i < n_rec) {
         const unsigned long long f0 = found_off[i], f1 = found_off[i + 1];
-        const bool has = f1 > f0;
-        const bool kept = filter_matching ? has : (invert ? !has : true);
+        const bool kept = tag_keeps(filter_matching, invert, f1 > f0);
         uint32_t len = 0, ex_at = 0, ex_n = 0;
         if (kept) {
             const uint32_t a = R.aux_start[i], e = R.rec_start[i] + R.rec_len[i];
@@ -221,22 +221,8 @@ __global__ __launch_bounds__(256) void mk_sam_taglen_kernel(const uint8_t *__res
                         else ex_at = first + 5, ex_n = p - (first + 5);
                     }
                 }
-                uint32_t vlen = 0;
-                if (ex_n == 0) {  // no field of that name, or an empty value ("do nothing if tag is empty", :472-473)
-                    ex_at = 0;
-                    for (unsigned long long k = f0; k < f1; ++k) {
-                        const uint32_t pt = found_pat[k];
-                        vlen += pat_off[pt + 1] - pat_off[pt];
-                    }
-                    if (has) vlen += (uint32_t)(f1 - f0) - 1;
-                } else if (!bad) {
-                    const uint8_t *prev = nullptr, *it;
-                    uint32_t nprev = 0, nit, items = 0;
-                    while (bam_merge_next(text + ex_at, ex_n, f0, f1, found_pat, pat_bytes, pat_off, items != 0, prev, nprev, &it, &nit))
-                        vlen += nit, prev = it, nprev = nit, ++items;
-                    vlen += items - 1;
-                }
-                len = R.rec_len[i] + 6 + vlen + 1;
+                if (ex_n == 0) ex_at = 0;  // no field of that name, or an empty value ("do nothing if tag is empty", :472-473)
+                len = R.rec_len[i] + 6 + tag_value_len(text + ex_at, ex_n, f0, f1, found_pat, pat_off, pat_bytes) + 1;
             }
         }
         if (sub == 0) {
@@ -273,26 +259,11 @@ __global__ __launch_bounds__(256) void mk_sam_emit_kernel(const uint8_t *__restr
         t[0] = '\t', t[1] = (uint8_t)tag0, t[2] = (uint8_t)tag1, t[3] = ':', t[4] = 'Z', t[5] = ':';
         t += 6;
         const unsigned long long f0 = found_off[i], f1 = found_off[i + 1];
-        const uint32_t ex_at = ex_off[i];
-        if (ex_at == 0) {
-            for (unsigned long long f = f0; f < f1; ++f) {
-                if (f > f0) *t++ = ',';
-                const uint32_t pt = found_pat[f];
-                const uint32_t a = pat_off[pt], b = pat_off[pt + 1];
-                for (uint32_t j = a; j < b; ++j) *t++ = pat_bytes[j];
-            }
-        } else {  // merged with the record's existing value (the old field stays where it is)
-            uint32_t ex_n = 0;
+        const uint32_t ex_at = ex_off[i];  // (0: no existing value; else it ends at the next tab or with the line)
+        uint32_t ex_n = 0;
+        if (ex_at)
             while (ex_at + ex_n < s + L && text[ex_at + ex_n] != '\t') ++ex_n;
-            const uint8_t *prev = nullptr, *it;
-            uint32_t nprev = 0, nit, items = 0;
-            while (bam_merge_next(text + ex_at, ex_n, f0, f1, found_pat, pat_bytes, pat_off, items != 0, prev, nprev, &it, &nit)) {
-                if (items) *t++ = ',';
-                for (uint32_t j = 0; j < nit; ++j) *t++ = it[j];
-                prev = it, nprev = nit, ++items;
-            }
-        }
-        *t = '\n';
+        *tag_value_put(t, text + ex_at, ex_n, f0, f1, found_pat, pat_off, pat_bytes) = '\n';
     }
 }
 
