@@ -8,6 +8,7 @@ import re
 import pytest
 
 import oracle_binding as ob
+import structured_sets as ss
 from merkurio_amd import native as mk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -179,6 +180,60 @@ def test_geometry_plan_and_length_classes():
         mk.plan_geometry([31, 8], dict(length_classes=3))
     with pytest.raises(mk.MerkurioError):
         mk.plan_geometry([31, 8], dict(force_q2=9))
+
+
+def test_keys_per_entry_on_a_hand_worked_set():
+    """structured_sets.keys_per_entry restates code2 / pack_qgram (filter.hpp, build_tables.hip).  The three overlapping 6-mers
+    of ACGTACGT at q = 4, S = 2: pattern i at offset 1 and pattern i + 1 at offset 0 are the same q-gram."""
+    assert [ss.code2(c) for c in b"ACTGactgNURY"] == [0, 1, 2, 3, 0, 1, 2, 3, 3, 2, 1, 0]
+    pats = [b"ACGTAC", b"CGTACG", b"GTACGT"]
+    # ACGT = 0 + (1 << 2) + (3 << 4) + (2 << 6), CGTA = 1 + (3 << 2) + (2 << 4) + 0, GTAC = 3 + (2 << 2) + 0 + (1 << 6), TACG = 2 + 0 + (1 << 4) + (3 << 6)
+    assert [ss.pattern_keys(p, 4, 2) for p in pats] == [[180, 45], [45, 75], [75, 210]]
+    assert ss.entries_per_key(pats, 4, 2) == {180: 1, 45: 2, 75: 2, 210: 1}
+    assert ss.keys_per_entry(pats, 4, 2) == {1: 2, 2: 2}
+    assert ss.max_entries_on_a_key(pats, 4, 2) == 2 and ss.overflowing_share(pats, 4, 2) == 0.0
+    # q = 2, S = 5: ACGTAC gives AC CG GT TA AC, CGTACG gives CG GT TA AC CG, GTACGT gives GT TA AC CG GT
+    assert ss.keys_per_entry(pats, 2, 5) == {4: 3, 3: 1}
+    assert ss.entries_per_key(pats, 2, 5) == {ss.pack_qgram(b"AC", 0, 2): 4, ss.pack_qgram(b"CG", 0, 2): 4, ss.pack_qgram(b"GT", 0, 2): 4,
+                                              ss.pack_qgram(b"TA", 0, 2): 3}
+    # letters that share a code are one key: N / G, U / T, R / C, Y / A, and either case
+    assert ss.pack_qgram(b"ACNU", 0, 4) == ss.pack_qgram(b"yrgt", 0, 4) == 180
+
+
+def test_structured_sets_stress_the_table_at_the_planned_geometry():
+    """the preconditions of tests/test_gpu_structured_sets.py, at the geometry mk_plan_geometry gives (no device needed): the
+    consecutive k-mers of a locus put `stride` entries on a key, a shared prefix puts a whole group there, a homopolymer puts
+    all its entries on one key, other spellings of a pattern share its keys"""
+    def geometry(pats, options=None):
+        g = mk.plan_geometry([len(p) for p in pats], options)
+        return g["q_gram"], g["stride"], [p for p in pats if len(p) >= g["split_len"]]
+
+    for k, options in ((31, None), (21, None), (31, dict(force_stride=8)), (19, None), (27, dict(force_stride=8))):
+        raw, recs = ss.tiled(10, 100, k, n_reads=5, long_bytes=130_000)
+        q, S, main = geometry(mk.parse_pattern_list(kmer_seq=raw), options)
+        assert S >= 8 and ss.max_entries_on_a_key(main, q, S) == S and ss.overflowing_share(main, q, S) >= 0.5, (k, q, S)
+        assert len(recs) == 16 and len(recs[-1]) >= 130_000 and recs[0] != recs[1] and len(recs[0]) == len(recs[1]) == 150
+    raw, recs = ss.shared_prefix(120)
+    pats = mk.parse_pattern_list(kmer_seq=raw)
+    assert len(pats) == 240 and sum(p.startswith(raw[0][:31]) or p.startswith(raw[120][:20]) for p in pats) == 240
+    for options in (None, dict(force_stride=16), dict(force_stride=1)):
+        q, S, main = geometry(pats, options)
+        assert ss.max_entries_on_a_key(main, q, S) >= 120, (options, q, S)  # the 31-base group: all on its offset-0 key
+    raw, recs = ss.repeats()
+    assert len(raw) == len(set(raw)) == 4 + 12 + 60 + 240 and len(recs[-1]) == 200_000
+    q, S, main = geometry(raw)
+    assert S == 16 and sum(len(set(ss.pattern_keys(p, q, S))) == 1 for p in main) == 4
+    for kind in ("dna", "protein"):
+        raw, recs = ss.code_collisions(kind)
+        pats = mk.parse_pattern_list(kmer_seq=raw)
+        q, S, main = geometry(pats)
+        keys = {}
+        for p in main:
+            keys.setdefault(tuple(ss.pattern_keys(p, q, S)), set()).add(p)
+        assert sum(len(v) > 1 for v in keys.values()) >= 20, kind  # patterns that differ, all of whose keys are equal
+    raw, recs = ss.with_short(*ss.tiled(10, 100, 31, n_reads=5, long_bytes=0))
+    shorts = [p for p in raw if len(p) < 31]
+    assert 1 <= len(shorts) <= 5 and all(5 <= len(s) <= 12 and any(s in p for p in raw[:1000]) for s in shorts)
 
 
 def test_bgzf_member_walk_and_codec_without_gpu():
