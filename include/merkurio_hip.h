@@ -20,7 +20,12 @@
  *    the next scan of a handle on the same stream, or after the previous one has completed;
  *    distinct handles (one per GPU / per process / per stream) are independent;
  *  - nothing here reads environment variables: tuning goes through mk_matcher_options;
- *  - the caller owns every buffer it passes; the library copies patterns at create time.
+ *  - the caller owns every buffer it passes; the library copies patterns at create time;
+ *  - every output that comes with a capacity: a call that needs more returns MK_E_CAPACITY, states the size it needs where the
+ *    entry point says so, and writes nothing at or behind the capacity it was given (a capacity of 0 with a pointer is a
+ *    capacity).  Such a call leaves the handle as a call that fits does: the next call's answer does not depend on it.  What
+ *    a refused call leaves in its other outputs is said per call family below; where nothing is said it is unspecified, and
+ *    counters / pattern_hit_counts, which are += updated, must be fresh for every attempt.
  */
 #ifndef MERKURIO_HIP_H
 #define MERKURIO_HIP_H
@@ -196,7 +201,7 @@ int mk_matcher_filter_mode(const mk_matcher *m, uint32_t *in_lds, uint64_t *filt
  * the matcher's algorithm: AC: record, end ascending, start ascending, pattern ascending;
  * BNDMq: record, pattern ascending, start ascending.
  * If more than hits_cap occurrences exist: returns MK_E_CAPACITY, *n_hits = required
- * count, rec_flags valid, hits content unspecified.  Never truncates silently.
+ * count, rec_flags valid, hits content unspecified (nothing at or behind hits_cap is written).  Never truncates silently.
  * ---------------------------------------------------------------------------------- */
 int mk_scan_batch(mk_matcher *m, const uint8_t *seq_bytes, const uint64_t *seq_off, uint64_t n_rec, uint32_t mode,
                   uint8_t *rec_flags, mk_hit *hits, uint64_t hits_cap, uint64_t *n_hits);
@@ -217,7 +222,11 @@ int mk_scan_batch(mk_matcher *m, const uint8_t *seq_bytes, const uint64_t *seq_o
  *                         src/cmd_extract.rs:353).  MK_MODE_HITS only, counted from the stored tuples
  *                         (all of them unless *d_n_hits exceeds hits_cap); MK_MODE_ANY leaves these
  *                         entries untouched -- the reference's no-logging path counts nothing either
- *   [n_pat + MK_SUM_*]    see below
+ *   [n_pat + MK_SUM_*]    see below; they do not depend on hits_cap: MK_SUM_HITS counts every occurrence, as *d_n_hits does
+ *                         (nb_hits_tot counts hits, not log rows), also beyond hits_cap
+ * More than hits_cap occurrences is not an error of this call (it only enqueues): d_hits[0, hits_cap) then holds hits_cap
+ * distinct occurrences, nothing at or behind d_hits[hits_cap] is written, the flags are valid, and the caller sees it from
+ * *d_n_hits > hits_cap.
  * It is the vector a multi-GPU host sums across ranks (RCCL allReduce) at the end of a job.
  * ---------------------------------------------------------------------------------- */
 #define MK_NUM_SUMMARY 8
@@ -303,7 +312,10 @@ int mk_matcher_kernel_times(mk_matcher *m, float *ms, uint32_t cap, uint32_t *n_
 /* extract, single file: loop body src/cmd_extract.rs:321-406.
  * logging == 0: only keep[] and nb_records_extracted are produced (like the reference).
  * rows (may be NULL when logging == 0) receives the log rows in emission order; on overflow
- * returns MK_E_CAPACITY with *n_rows = required.  pattern_hit_counts[n_pat] is += updated. */
+ * returns MK_E_CAPACITY with *n_rows = required.  pattern_hit_counts[n_pat] is += updated.
+ * A call of this family (mk_extract_single / _paired, mk_tag_records, mk_extract_fastq_text / _bgzf, mk_extract_window) that
+ * returns MK_E_CAPACITY for its rows, found_pat or kept text has done all its work: keep is valid, counters and
+ * pattern_hit_counts have been added to (pass fresh ones with the next attempt), rows[0, rows_cap) are the first rows. */
 int mk_extract_single(mk_matcher *m, const uint8_t *seq, const uint64_t *off, uint64_t n_rec, int logging,
                       int invert, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows,
                       mk_counters *counters, uint32_t *pattern_hit_counts);
@@ -316,7 +328,7 @@ int mk_extract_paired(mk_matcher *m, const uint8_t *seq1, const uint64_t *off1, 
  * found_off[n_rec+1] / found_pat: CSR of the distinct matched pattern indices per record,
  * ascending (= kmers_found after sort_unstable + dedup, src/cmd_tag.rs:484-485, before the
  * merge with a pre-existing tag value).  On found_cap overflow: MK_E_CAPACITY, found_off[n_rec]
- * = required. */
+ * = required.  One call states both needs, *n_rows and found_off[n_rec], whichever was too small. */
 int mk_tag_records(mk_matcher *m, const uint8_t *seq, const uint64_t *off, uint64_t n_rec, int logging,
                    int filter_matching, int invert, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows,
                    mk_counters *counters, uint32_t *pattern_hit_counts, uint64_t *found_off, uint32_t *found_pat,
@@ -499,6 +511,9 @@ int mk_extract_fastq_bgzf(mk_matcher *m, mk_codec *codec, const uint8_t *head, u
  *                     callers that do not hold the text themselves (BGZF bodies)          (MK_E_CAPACITY: n_kept_bytes = the need)
  *   all  (all_cap):   the whole window text (logging with invert: rows name records that are not kept)
  * A damaged BGZF member: MK_E_CORRUPT.  More than rec_cap records: MK_E_CAPACITY with *n_rec = the need.
+ * A call reports the first thing that does not fit, in this order: rec_cap (nothing is scanned, nothing else stated); per source
+ * tail, then all; kept (of every source at once); rows (*n_rows is stated only by a call whose texts all fit).  A caller that grows what
+ * the call names and calls again with fresh counters is done after at most one call per output.
  * --------------------------------------------------------------------------------------- */
 #define MK_TEXT_FASTQ 0
 #define MK_TEXT_FASTA 1
@@ -569,6 +584,8 @@ int mk_gzip_info(const mk_codec *c, uint32_t *segments, float ms[5]);
  * Outputs: n_window (bytes of text), n_rec whole records covering n_used bytes, tail[0, n_tail) = the text behind them (the next
  * window's head; tail_cap too small: MK_E_CAPACITY, n_tail = the need), n_kept, out_text_bytes (bytes of the kept records as
  * written), out_len (out_cap too small: MK_E_CAPACITY, out_len = the need).  out == NULL: nothing is written (`tag -s`).
+ * A call that returns MK_E_CAPACITY (tail, then rows and names together, then out) has counted nothing: counters and
+ * pattern_hit_counts are added to when the window is done.
  * logging != 0 (the reference's -l / -j): counters and pattern_hit_counts as mk_tag_records, rows[0, n_rows) in emission order
  * (row.rec = index in the window) and, per row, row_name[r] = offset of the record's NUL-terminated name in names[0, n_names_bytes)
  * (logger.log_fields' record.name(), :412); too small a rows / names buffer: MK_E_CAPACITY with n_rows / n_names_bytes = the need.
