@@ -681,6 +681,68 @@ typedef struct mk_sam_window {
 } mk_sam_window;
 int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status);
 
+/* -------------------------------------------------------------------------------------
+ * `tag` on a window of SAM TEXT whose kept records leave as BAM (an addition to v7; kernels: sam.hip) -- SAM -> BAM: the window,
+ * its lines, the scan, the keep rule, the tag's value, rows, names, counters, tail and n_used are mk_tag_sam_window's; what leaves is
+ * mk_tag_bam_window's: every kept record as  block_size | BAM record,  back to back in record order (out_text_bytes of them),
+ * deflated into BGZF members of block_bytes of text (0 = 65280) in out[0, out_len).  The members inflate to exactly the bytes the
+ * CLI's host path writes for these records: it appends TAB tag ":Z:" value to the line and encodes the line (cli/io.cpp:
+ * BamWriter::encode_record), which is the definition.  Restated:
+ *   refID / next_refID: the index of RNAME / RNEXT among the n_refs reference names ref_names[ref_off[i], ref_off[i + 1]) (the @SQ
+ *     lines' SN, in the order of the BAM header; of equal names the first), -1 for "*" or a name not among them; RNEXT "=" = refID.
+ *   pos, next_pos = POS - 1, PNEXT - 1; mapq, flag, tlen = the low 8 / 16 / 32 bits of MAPQ, FLAG, TLEN;
+ *   bin = reg2bin(pos, pos + (the reference bases of the CIGAR, or 1 without any)) on signed 64-bit values (POS 0: 4680);
+ *   l_read_name = QNAME + NUL; CIGAR "*" = no ops, else len << 4 | op of "MIDNSHP=X"; SEQ "*" = l_seq 0, else two bases per byte from
+ *   "=ACMGRSVTWYHKDBN" in either case (any other byte: 15; an odd length pads with 0); QUAL "*" = l_seq bytes 0xFF, else each byte - 33;
+ *   optional fields TAG:TYPE:VALUE in line order, then the tag:  A = one byte (none: 0);  i = the smallest of C S I (>= 0) or c s i
+ *   (< 0) that holds the value;  f = a float;  Z / H = the bytes and NUL;  B = subtype, count, items ("B:c,1,2").
+ * The device converts plain numbers only (sam_numbers.hpp): an integer is [+-] and 1-18 digits, a CIGAR length 1-9 digits, a float
+ * [+-]digits[.digits][e[+-]digits] whose digits without the point are an integer below 2^24 and whose net power of ten is within
+ * +-10 (one exactly rounded double operation, then one rounding to float: strtof's value).
+ * *status != 0: this window is not for the device and NOTHING was produced or counted -- the caller's host path takes it from the
+ * window's first byte (and words the errors).  Bits: 1 = a record line with fewer than 10 fields, or a KEPT line with fewer than 11;
+ * 2 = a kept record that does not encode as above: QNAME longer than 254 bytes; a CIGAR with a byte that is no op, a length that is
+ * not 1-9 digits, or more than 65 535 ops; QUAL of another length than SEQ; FLAG, POS, MAPQ, PNEXT, TLEN, an `i` value or an integer
+ * item that is not a plain integer; an `f` value or item outside the float rule (inf, nan, hex, long digit strings, large exponents);
+ * an optional field shorter than 5 bytes or without its two colons (an empty field behind a final tab included); an unknown type; a B
+ * field without a subtype, with an unknown one, or whose items do not each follow a ','; 4 = as in mk_tag_sam_window.  Records that
+ * are dropped are not looked at.
+ * MK_E_CAPACITY (tail, then rows and names together, then out; the need in n_tail / n_rows + n_names_bytes / out_len) has counted
+ * nothing.  out == NULL && out_cap == 0: nothing is encoded or written, the checks still run (out_text_bytes is set, out_len 0).
+ * ms[]: milliseconds of [0] upload, [1] line index + fields, [2] gather + scan + sets, [3] tag + encode, [4] deflate, [5] download;
+ * ms[7]: of these, growing device buffers.
+ * --------------------------------------------------------------------------------------- */
+typedef struct mk_sam_bam_window {
+    /* in */
+    const uint8_t *head;
+    uint64_t n_head;
+    const uint8_t *text;
+    uint64_t n_text;
+    uint32_t last; /* no text follows this window */
+    uint32_t filter_matching, invert;
+    uint8_t tag[2];
+    uint8_t reserved[2];
+    const uint8_t *ref_names; /* the reference names, back to back */
+    const uint64_t *ref_off;  /* n_refs + 1 ascending offsets into ref_names */
+    uint64_t n_refs;
+    uint32_t block_bytes;
+    uint32_t reserved2;
+    uint8_t *tail;
+    uint64_t tail_cap;
+    uint8_t *out;
+    uint64_t out_cap;
+    mk_row *rows;
+    uint64_t rows_cap;
+    uint64_t *row_name; /* room for rows_cap entries */
+    uint8_t *names;
+    uint64_t names_cap;
+    /* out */
+    uint64_t n_window, n_used, n_tail, n_rec, n_kept, out_text_bytes, out_len, n_rows, n_names_bytes;
+    float ms[8];
+} mk_sam_bam_window;
+int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, int logging, mk_counters *counters, uint32_t *pattern_hit_counts,
+                          uint32_t *status);
+
 /* walks the BSIZE chain of in[0, n): fills members[0, cap) (out_off = running sum of ISIZE), *n_members = how many there are,
  * *consumed = bytes of whole members, *text_bytes = sum of ISIZE.  MK_E_CORRUPT where a header is not BGZF; a trailing
  * partial member is not an error (*consumed < n).  Host code, no device. */

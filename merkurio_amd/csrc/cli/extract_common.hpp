@@ -126,5 +126,9 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
 // line starts every ~window_bytes and are independent of each other.
 bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
                                const std::string &in_name, Sink *out, uint64_t window_bytes);
+// the same for plain SAM text -> BAM (mk_tag_sam_bam_window): the kept lines come back as BGZF members of BAM records, encoded on the
+// device against bw's reference names (bw is open), and go to bw.put_members
+bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes);
 
 }  // namespace cli

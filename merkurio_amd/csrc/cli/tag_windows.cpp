@@ -24,8 +24,13 @@
 // appended, written as they are.  A refused window (a line with fewer than 10 fields, a kept record whose field of the tag's name is
 // not a plain string) hands the input back to the host loop at its first byte (SamFile::seek_text).
 //
+// Plain SAM text -> BAM (tag_sam_bam_windows_on_device, mk_tag_sam_bam_window) is the SAM driver's input side and the BAM driver's
+// output side: the same independent windows, whose kept lines come back as BGZF members of BAM records (encoded on the device from
+// the @SQ names the BamWriter's header was written from) and go to BamWriter::put_members.  On top of SAM -> SAM's refusals, a window
+// with a kept line that BamWriter::encode_record would refuse, or whose numbers are not plain ones, is the host loop's.
+//
 // Both formats share one driver (run_windows): the round-robin over the workers, the repeat of a call that asked for more room, the
-// emit turn, refusal and error bookkeeping, counters and log rows.  BamWorker / SamWorker say how a window is staged, run and written.
+// emit turn, refusal and error bookkeeping, counters and log rows.  BamWorker / SamWorker / SamBamWorker say how a window is staged, run and written.
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -291,6 +296,69 @@ struct SamWorker {
     }
 };
 
+// ---- SAM text -> BAM: SamWorker's windows, BamWorker's output
+struct SamBamWorker {
+    const std::vector<std::pair<uint64_t, uint64_t>> &wins;
+    const uint8_t *file;
+    BamWriter *bw;
+    const std::vector<uint8_t> &ref_bytes;
+    const std::vector<uint64_t> &ref_off;
+    uint32_t &refused_status;
+    mk_matcher *m;
+    mk_codec *codec;
+    HostBuffer stage, out;  // the window's text (page-locked); the members it turns into (moved to the writer)
+    uint8_t no_tail[8];
+    mk_sam_bam_window w{};
+    static constexpr bool corrupt_is_refused = false;
+    ~SamBamWorker() {
+        if (!g_process_is_ending) mk_codec_destroy(codec);
+    }
+    bool load(size_t k) {
+        const uint64_t b = wins[k].first, n = wins[k].second - wins[k].first;
+        if (!stage.grow(n, 1u << 20)) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+        copy_in(file, b, b + n, stage.p);
+        // (a BAM record is shorter than its line, and BAM-shaped text deflates to a third)
+        if (out.cap < out_guess(n)) {
+            out.reset();
+            out = bw->take_raw_buffer(out_guess(n));
+        }
+        w.text = stage.p, w.n_text = n;
+        w.last = 1;  // (the window ends at a line end or at the end of the file: all of it is lines)
+        w.ref_names = ref_bytes.data(), w.ref_off = ref_off.data(), w.n_refs = ref_off.size() - 1;
+        return true;
+    }
+    int call(int logging, mk_counters *wc, uint32_t *wcounts, uint32_t *status) {
+        w.tail = no_tail, w.tail_cap = sizeof(no_tail);
+        w.out = out.p, w.out_cap = out.cap;
+        return mk_tag_sam_bam_window(m, codec, &w, logging, wc, wcounts, status);
+    }
+    bool grow() {
+        if (w.out_len <= out.cap) return false;
+        out.reset();
+        out = bw->take_raw_buffer(w.out_len);
+        return true;
+    }
+    void refused(size_t, int, uint32_t status) { refused_status = status; }
+    void write() {
+        if (w.out_len) bw->put_members(std::move(out), w.out_len);
+    }
+};
+
+// [b, e) per window, e = the first line start at or behind b + window_bytes
+std::vector<std::pair<uint64_t, uint64_t>> cut_at_lines(const uint8_t *file, uint64_t from, uint64_t n_file, uint64_t window_bytes) {
+    std::vector<std::pair<uint64_t, uint64_t>> wins;
+    for (uint64_t b = from; b < n_file;) {
+        uint64_t e = std::min(n_file, b + std::max<uint64_t>(window_bytes, 1));
+        if (e < n_file) {
+            const void *nl = memchr(file + e - 1, '\n', n_file - (e - 1));
+            e = nl ? (uint64_t)((const uint8_t *)nl - file) + 1 : n_file;
+        }
+        wins.emplace_back(b, e);
+        b = e;
+    }
+    return wins;
+}
+
 }  // namespace
 
 bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
@@ -357,17 +425,7 @@ bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
     const uint8_t *file = (const uint8_t *)src.text();
     const uint64_t n_file = src.text_size();
     const bool timing = getenv("MERKURIO_TIMING") != nullptr;
-    // the windows: [b, e), e = the first line start at or behind b + window_bytes
-    std::vector<std::pair<uint64_t, uint64_t>> wins;
-    for (uint64_t b = sam.text_cursor(); b < n_file;) {
-        uint64_t e = std::min(n_file, b + std::max<uint64_t>(window_bytes, 1));
-        if (e < n_file) {
-            const void *nl = memchr(file + e - 1, '\n', n_file - (e - 1));
-            e = nl ? (uint64_t)((const uint8_t *)nl - file) + 1 : n_file;
-        }
-        wins.emplace_back(b, e);
-        b = e;
-    }
+    const std::vector<std::pair<uint64_t, uint64_t>> wins = cut_at_lines(file, sam.text_cursor(), n_file, window_bytes);
     if (wins.empty()) return true;
     const size_t n_win = wins.size();
     const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
@@ -385,6 +443,52 @@ bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
         if (pipe.refused != ~(size_t)0)
             fprintf(stderr, "[timing] window %llu left to the host reader (%s)\n", (unsigned long long)pipe.refused,
                     refused_status & 1 ? "a line with too few fields" : "existing tag");
+    }
+    if (pipe.refused != ~(size_t)0) {
+        sam.seek_text(wins[pipe.refused].first);
+        return false;
+    }
+    sam.seek_text(n_file);
+    return true;
+}
+
+bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes) {
+    const WindowSource &src = sam.source();
+    const uint8_t *file = (const uint8_t *)src.text();
+    const uint64_t n_file = src.text_size();
+    const bool timing = getenv("MERKURIO_TIMING") != nullptr;
+    const std::vector<std::pair<uint64_t, uint64_t>> wins = cut_at_lines(file, sam.text_cursor(), n_file, window_bytes);
+    if (wins.empty()) return true;
+    // the reference names the writer's header holds, in its order: what encode_record looks RNAME and RNEXT up in
+    std::vector<uint8_t> ref_bytes;
+    std::vector<uint64_t> ref_off(1, 0);
+    for (const std::string &nm : bw.ref_names) {
+        ref_bytes.insert(ref_bytes.end(), nm.begin(), nm.end());
+        ref_off.push_back(ref_bytes.size());
+    }
+    ref_bytes.push_back(0);  // (never empty: a pointer to hand over)
+    const size_t n_win = wins.size();
+    const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
+    Pipe pipe;
+    uint32_t refused_status = 0;
+    double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev, [&](size_t id) {
+        mk_codec *codec = nullptr;
+        if (mk_codec_create(handles[id].device, &codec) != MK_OK) bail(std::string("Error during SAM record parsing: ") + mk_last_error());
+        return SamBamWorker{wins, file, &bw, ref_bytes, ref_off, refused_status, handles[id].m, codec};
+    });
+    if (timing) {
+        fprintf(stderr,
+                "[timing] %llu of %llu SAM text -> BAM windows on the device (%llu in flight): upload %.3f, line index + fields %.3f, gather + scan + sets "
+                "%.3f, tag + encode %.3f, deflate %.3f, download %.3f s (of these, growing device buffers: %.3f s)\n",
+                (unsigned long long)pipe.emit_turn, (unsigned long long)n_win, (unsigned long long)n_workers, t_dev[0] / 1e3, t_dev[1] / 1e3, t_dev[2] / 1e3,
+                t_dev[3] / 1e3, t_dev[4] / 1e3, t_dev[5] / 1e3, t_dev[7] / 1e3);
+        if (pipe.refused != ~(size_t)0)
+            fprintf(stderr, "[timing] window %llu left to the host loop (%s)\n", (unsigned long long)pipe.refused,
+                    refused_status & 1   ? "a line with too few fields"
+                    : refused_status & 2 ? "a record the device does not encode"
+                                         : "existing tag");
     }
     if (pipe.refused != ~(size_t)0) {
         sam.seek_text(wins[pipe.refused].first);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "matcher_internal.h"
+#include "sam_numbers.hpp"
 #include "codec/codec_internal.h"
 #include "codec/codec_kernels.h"
 
@@ -1114,6 +1115,189 @@ void tag_commit(DeviceLoop &dl, const TagWindow &X, mk_counters *c, uint32_t *co
     dl.finish();
 }
 
+
+// the window's tagged records, back to back in text slot 1 (out_text bytes, kPad zero bytes behind them), deflated into BGZF members of
+// bb bytes of text and downloaded: the last step of mk_tag_bam_window and mk_tag_sam_bam_window (the codec's buffers; its kernels on
+// this stream).  *out_len = the members' bytes (more than out_cap: MK_E_CAPACITY); ms_deflate / ms_download: the two phases.
+int window_deflate(mk_matcher *m, mk_codec *codec, const WindowSide &W, DeviceLoop &dl, const char *who, unsigned long long out_text, uint32_t bb, uint8_t *out,
+                   uint64_t out_cap, uint64_t *out_len, float *ms_deflate, float *ms_download, std::chrono::steady_clock::time_point &t) {
+    hipStream_t st = dl.st;
+    int rc;
+    mk_matcher::TextSlot &O = m->txt[1];
+    std::lock_guard<std::mutex> lock(codec->mu);
+    const uint64_t blocks64 = (out_text + bb - 1) / bb;
+    if (blocks64 >= 0xFFFFFFFFull) return fail(MK_E_UNSUPPORTED, "%s: %llu output members", who, (unsigned long long)blocks64);
+    const uint32_t blocks = (uint32_t)blocks64;
+    const uint32_t grid = mkz::deflate_grid(blocks, codec->num_cus);
+    if ((rc = ensure_device(&codec->d_crc, &codec->crc_cap, blocks * 4ull)) ||
+        (rc = ensure_device(&codec->d_tokens, &codec->tokens_cap, (uint64_t)grid * mkz::kTokensPerWave * 4)) ||
+        (rc = ensure_device(&codec->d_slots, &codec->slots_cap, (uint64_t)blocks * mkz::kSlotBytes)) ||
+        (rc = ensure_device(&codec->d_len, &codec->len_cap, (blocks + 1) * 4ull)) || (rc = ensure_device(&codec->d_off, &codec->off_cap, (blocks + 2) * 8ull)))
+        return rc;
+    // the packed members go where the window's text was: it has been read for the last time by the record output kernel (a buffer
+    // of the output's size less to grow -- growing device buffers is what a job's first windows spend most of their time on)
+    void *d_packed = W.T->d_text;
+    if (W.T->d_text_cap < mk_bgzf_deflate_bound(out_text, bb)) {
+        if ((rc = ensure_device(&codec->d_out, &codec->out_cap, mk_bgzf_deflate_bound(out_text, bb)))) return rc;
+        d_packed = codec->d_out;
+    }
+    uint64_t *d_total = (uint64_t *)codec->d_off + blocks;
+    mkz::launch_crc((const uint8_t *)O.d_text, out_text, bb, blocks, (uint32_t *)codec->d_crc, st);
+    mkz::launch_deflate((const uint8_t *)O.d_text, out_text, bb, blocks, (const uint32_t *)codec->d_crc, (uint32_t *)codec->d_tokens, (uint8_t *)codec->d_slots,
+                        (uint32_t *)codec->d_len, (uint32_t *)(d_total + 1), grid, st);
+    mkz::launch_pack((const uint8_t *)codec->d_slots, (const uint32_t *)codec->d_len, (uint64_t *)codec->d_off, d_total, blocks, (uint8_t *)d_packed, st);
+    uint64_t total = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "BGZF deflate of the tagged records failed");
+    *ms_deflate = (float)ms_since(t);
+    *out_len = total;
+    if (total > out_cap) return fail(MK_E_CAPACITY, "%s: the members take %llu bytes", who, (unsigned long long)total);
+    if (hipMemcpyAsync(out, d_packed, total, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "download of the members failed");
+    *ms_download = (float)ms_since(t);
+    return MK_OK;
+}
+
+// ---- a window of SAM text -> its record tables: what mk_tag_sam_window and mk_tag_sam_bam_window start with
+struct SamIndex {
+    uint64_t n = 0;  // records
+    SamTables R{};
+    uint32_t *d_out_len = nullptr, *d_ex_off = nullptr, *d_extra = nullptr;  // one entry per line each (d_extra: `extra` of them)
+    unsigned long long *d_out_off = nullptr;
+};
+// upload (ms[0]), line table and fields (ms[1]), n_window / n_rec / n_used / the tail; *status = 1: a record line with fewer than 10 fields
+template <class Win>
+int sam_index(mk_matcher *m, Win *w, const char *who, uint32_t extra, DeviceLoop &dl, WindowSide &W, SamIndex &I, uint32_t *status,
+              std::chrono::steady_clock::time_point &t) {
+    hipStream_t st = dl.st;
+    int rc;
+    // ---- the text: head, then the body behind it
+    W.T = &m->txt[0];
+    mk_matcher::TextSlot &T = *W.T;
+    mk_window_source S;
+    memset(&S, 0, sizeof(S));
+    S.head = w->head, S.n_head = w->n_head, S.text = w->text, S.n_text = w->n_text;
+    if ((rc = window_assemble(m, nullptr, S, W, dl))) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
+    w->ms[0] = (float)ms_since(t);
+    w->n_window = W.n_window;
+    const uint64_t n_text = W.n_window;
+    if (n_text == 0) return MK_OK;  // (I.n == 0)
+    const uint8_t *d_text = (const uint8_t *)T.d_text;
+    // ---- line table (ingest.hip), then what every line is (sam.hip)
+    const uint32_t n_blocks = (uint32_t)((n_text + ingest_block_bytes() - 1) / ingest_block_bytes());
+    if ((rc = ensure_device(&T.d_ing_a, &T.d_ing_a_cap, ((size_t)n_blocks + 8) * 4))) return rc;  // newline count per block | total | status, min, max
+    W.d_block = (uint32_t *)T.d_ing_a;
+    W.d_total = W.d_block + n_blocks;
+    W.d_st = W.d_total + 1;
+    launch_ingest_count(d_text, n_text, W.d_block, W.d_total, st);
+    if (hipMemcpyAsync(&W.total_nl, W.d_total, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&W.last_byte, d_text + n_text - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "newline count failed");
+    // a last line without '\n' is a line when nothing follows the window, else the next window's head
+    const bool open_end = W.last_byte != '\n';
+    const uint64_t n_lines = (uint64_t)W.total_nl + (w->last && open_end ? 1 : 0);
+    const size_t per = n_lines + 2, n_tiles = n_lines / ingest_scan_tile() + 2;
+    // line starts | record-or-not | six entries per line | out lengths | existing-value offsets | `extra` more arrays (u32) | offsets (u64) | tiles (u64)
+    if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, ((size_t)W.total_nl + 4 + (9 + extra) * per) * 4 + 16 + per * 8 + n_tiles * 8 + 64))) return rc;
+    W.d_line = (uint32_t *)T.d_ing_b;
+    uint32_t *d_is_rec = W.d_line + W.total_nl + 4;
+    SamTables L{d_is_rec + per, d_is_rec + 2 * per, d_is_rec + 3 * per, d_is_rec + 4 * per, d_is_rec + 5 * per, d_is_rec + 6 * per};
+    uint32_t *d_out_len = d_is_rec + 7 * per, *d_ex_off = d_is_rec + 8 * per;
+    I.d_extra = d_is_rec + 9 * per;
+    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_is_rec + (9 + extra) * per) + 15) & ~(uintptr_t)15);
+    W.d_tile = d_out_off + per;
+    launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, W.d_line, st);
+    const uint32_t st_init[3] = {0u, 0xFFFFFFFFu, 0u};
+    if (hipMemcpyAsync(W.d_st, st_init, sizeof(st_init), hipMemcpyHostToDevice, st) != hipSuccess) return fail(MK_E_HIP, "copy failed");
+    launch_sam_fields(d_text, W.d_line, n_lines, d_is_rec, L, W.d_st, st);
+    unsigned long long n_rec_dev = 0;
+    if (n_lines && (rc = scan_offsets(d_is_rec, n_lines, W.d_tile, d_out_off, st, &n_rec_dev, "SAM line indexing failed"))) return rc;
+    uint32_t st_host[3] = {0, 0, 0};
+    if (hipMemcpyAsync(st_host, W.d_st, sizeof(st_host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "SAM line indexing failed");
+    if (st_host[0]) {  // a record line with fewer than 10 fields: the host reader words it
+        *status = 1;
+        return MK_OK;
+    }
+    const uint64_t n = n_rec_dev;
+    SamTables R = L;
+    if (n != n_lines) {  // header or empty lines among the records: the records' entries move to tables of their own
+        if ((rc = ensure_device(&T.d_fa_seq, &T.d_fa_seq_cap, 6 * (size_t)(n + 2) * 4))) return rc;
+        uint32_t *r0 = (uint32_t *)T.d_fa_seq;
+        R = SamTables{r0, r0 + (n + 2), r0 + 2 * (n + 2), r0 + 3 * (n + 2), r0 + 4 * (n + 2), r0 + 5 * (n + 2)};
+        launch_sam_compact(d_is_rec, d_out_off, n_lines, L, R, st);
+        if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "SAM line indexing failed");
+    }
+    W.d_rec_start = R.rec_start, W.d_seq_start = R.seq_start, W.d_seq_len = R.seq_len;
+    W.fixed = (n && st_host[1] == st_host[2] && st_host[1] > 0) ? st_host[1] : 0;
+    uint64_t used = n_text;
+    if (!w->last && open_end) {  // the bytes behind the last '\n' are the tail
+        uint32_t last_start = 0;
+        if (hipMemcpyAsync(&last_start, W.d_line + W.total_nl, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "SAM line indexing failed");
+        used = last_start;
+    }
+    w->n_rec = n, w->n_used = used, w->n_tail = n_text - used;
+    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "%s: the text behind the window's last line end takes %llu bytes", who, (unsigned long long)w->n_tail);
+    if (w->n_tail && (hipMemcpyAsync(w->tail, d_text + used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+        return fail(MK_E_HIP, "download of the tail failed");
+    w->ms[1] = (float)ms_since(t);
+    I.n = n, I.R = R, I.d_out_len = d_out_len, I.d_ex_off = d_ex_off, I.d_out_off = d_out_off;
+    return MK_OK;
+}
+
+// The reference names of a SAM -> BAM window on the device: offsets (u32) | table | bytes.  The host builds an open-addressing table of
+// them -- a few thousand names in most files, 10^5 in some assemblies -- with the first of equal names in it (BamWriter::encode_record's
+// ref_id takes the first), so the kernel never walks the list.  A job's windows all bring the same names: the handle keeps a copy of
+// what it made the device's from, and a window whose names equal it (one memcmp) uploads nothing.
+struct SamRefsDevice {
+    const uint8_t *bytes = nullptr;
+    const uint32_t *off = nullptr, *table = nullptr;
+    uint32_t mask = 0;
+};
+int upload_refs(mk_matcher *m, const uint8_t *names, const uint64_t *off, uint64_t n_refs, hipStream_t st, SamRefsDevice &D) {
+    if (!n_refs) return MK_OK;
+    for (uint64_t i = 1; i <= n_refs; ++i)
+        if (off[i] < off[i - 1]) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: reference name offsets must ascend");
+    const uint64_t n_bytes = off[n_refs] - off[0];
+    if (n_refs >= (1u << 30) || n_bytes >= 0xFFFFFFF0ull) return fail(MK_E_UNSUPPORTED, "mk_tag_sam_bam_window: %llu reference names", (unsigned long long)n_refs);
+    const uint8_t *base = names + off[0];
+    bool same = m->refs_slots && m->refs_off.size() == n_refs + 1 && m->refs_names.size() == n_bytes && memcmp(m->refs_names.data(), base, n_bytes) == 0;
+    for (uint64_t i = 0; same && i <= n_refs; ++i) same = m->refs_off[i] == off[i] - off[0];
+    if (!same) {
+        m->refs_slots = 0;  // (until the new ones are up)
+        uint32_t slots = 16;
+        while (slots < 2 * n_refs) slots <<= 1;
+        std::vector<uint32_t> h(n_refs + 1 + slots, 0);
+        uint32_t *table = h.data() + n_refs + 1;
+        for (uint64_t i = 0; i <= n_refs; ++i) h[i] = (uint32_t)(off[i] - off[0]);
+        for (uint64_t i = 0; i < n_refs; ++i) {
+            const uint32_t a = h[i], n = h[i + 1] - h[i];
+            for (uint32_t slot = sam_name_hash(base + a, n) & (slots - 1);; slot = (slot + 1) & (slots - 1)) {
+                if (!table[slot]) {
+                    table[slot] = (uint32_t)i + 1;
+                    break;
+                }
+                const uint32_t j = table[slot] - 1;
+                if (h[j + 1] - h[j] == n && memcmp(base + h[j], base + a, n) == 0) break;  // (an earlier reference of that name)
+            }
+        }
+        int rc;
+        if ((rc = ensure_device(&m->d_refs, &m->d_refs_cap, h.size() * 4 + n_bytes + 64))) return rc;
+        uint8_t *d = (uint8_t *)m->d_refs;
+        if (hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+            (n_bytes && hipMemcpyAsync(d + h.size() * 4, base, n_bytes, hipMemcpyHostToDevice, st) != hipSuccess) || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "upload of the reference names failed");
+        m->refs_names.assign(base, base + n_bytes);
+        m->refs_off.resize(n_refs + 1);
+        for (uint64_t i = 0; i <= n_refs; ++i) m->refs_off[i] = off[i] - off[0];
+        m->refs_slots = slots;
+    }
+    const uint8_t *d = (const uint8_t *)m->d_refs;
+    D.off = (const uint32_t *)d, D.table = D.off + n_refs + 1, D.bytes = d + ((size_t)n_refs + 1 + m->refs_slots) * 4, D.mask = m->refs_slots - 1;
+    return MK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1198,40 +1382,8 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
     if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return fail(MK_E_HIP, "record output kernel failed");
     w->ms[4] = (float)ms_since(t);
-    // ---- BGZF members of the output text (the codec's buffers; its kernels on this stream)
-    {
-        std::lock_guard<std::mutex> lock(codec->mu);
-        const uint64_t blocks64 = (out_text + bb - 1) / bb;
-        if (blocks64 >= 0xFFFFFFFFull) return fail(MK_E_UNSUPPORTED, "mk_tag_bam_window: %llu output members", (unsigned long long)blocks64);
-        const uint32_t blocks = (uint32_t)blocks64;
-        const uint32_t grid = mkz::deflate_grid(blocks, codec->num_cus);
-        if ((rc = ensure_device(&codec->d_crc, &codec->crc_cap, blocks * 4ull)) ||
-            (rc = ensure_device(&codec->d_tokens, &codec->tokens_cap, (uint64_t)grid * mkz::kTokensPerWave * 4)) ||
-            (rc = ensure_device(&codec->d_slots, &codec->slots_cap, (uint64_t)blocks * mkz::kSlotBytes)) ||
-            (rc = ensure_device(&codec->d_len, &codec->len_cap, (blocks + 1) * 4ull)) || (rc = ensure_device(&codec->d_off, &codec->off_cap, (blocks + 2) * 8ull)))
-            return rc;
-        // the packed members go where the window's text was: it has been read for the last time by the record output kernel (a buffer
-        // of the output's size less to grow -- growing device buffers is what a job's first windows spend most of their time on)
-        void *d_packed = W.T->d_text;
-        if (W.T->d_text_cap < mk_bgzf_deflate_bound(out_text, bb)) {
-            if ((rc = ensure_device(&codec->d_out, &codec->out_cap, mk_bgzf_deflate_bound(out_text, bb)))) return rc;
-            d_packed = codec->d_out;
-        }
-        uint64_t *d_total = (uint64_t *)codec->d_off + blocks;
-        mkz::launch_crc((const uint8_t *)O.d_text, out_text, bb, blocks, (uint32_t *)codec->d_crc, st);
-        mkz::launch_deflate((const uint8_t *)O.d_text, out_text, bb, blocks, (const uint32_t *)codec->d_crc, (uint32_t *)codec->d_tokens, (uint8_t *)codec->d_slots,
-                            (uint32_t *)codec->d_len, (uint32_t *)(d_total + 1), grid, st);
-        mkz::launch_pack((const uint8_t *)codec->d_slots, (const uint32_t *)codec->d_len, (uint64_t *)codec->d_off, d_total, blocks, (uint8_t *)d_packed, st);
-        uint64_t total = 0;
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "BGZF deflate of the tagged records failed");
-        w->ms[5] = (float)ms_since(t);
-        w->out_len = total;
-        if (total > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_window: the members take %llu bytes", (unsigned long long)total);
-        if (hipMemcpyAsync(w->out, d_packed, total, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "download of the members failed");
-        w->ms[6] = (float)ms_since(t);
-    }
+    // ---- BGZF members of the output text
+    if ((rc = window_deflate(m, codec, W, dl, "mk_tag_bam_window", out_text, bb, w->out, w->out_cap, &w->out_len, &w->ms[5], &w->ms[6], t))) return rc;
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
@@ -1256,79 +1408,14 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
     int rc;
     auto t = std::chrono::steady_clock::now();
     AllocMs alloc_ms(&w->ms[7]);
-    // ---- the text: head, then the body behind it
     WindowSide W;
-    W.T = &m->txt[0];
-    mk_matcher::TextSlot &T = *W.T;
-    mk_window_source S;
-    memset(&S, 0, sizeof(S));
-    S.head = w->head, S.n_head = w->n_head, S.text = w->text, S.n_text = w->n_text;
-    if ((rc = window_assemble(m, nullptr, S, W, dl))) return rc;
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
-    w->ms[0] = (float)ms_since(t);
-    w->n_window = W.n_window;
-    const uint64_t n_text = W.n_window;
-    if (n_text == 0) return MK_OK;
-    const uint8_t *d_text = (const uint8_t *)T.d_text;
-    // ---- line table (ingest.hip), then what every line is (sam.hip)
-    const uint32_t n_blocks = (uint32_t)((n_text + ingest_block_bytes() - 1) / ingest_block_bytes());
-    if ((rc = ensure_device(&T.d_ing_a, &T.d_ing_a_cap, ((size_t)n_blocks + 8) * 4))) return rc;  // newline count per block | total | status, min, max
-    W.d_block = (uint32_t *)T.d_ing_a;
-    W.d_total = W.d_block + n_blocks;
-    W.d_st = W.d_total + 1;
-    launch_ingest_count(d_text, n_text, W.d_block, W.d_total, st);
-    if (hipMemcpyAsync(&W.total_nl, W.d_total, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&W.last_byte, d_text + n_text - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "newline count failed");
-    // a last line without '\n' is a line when nothing follows the window, else the next window's head
-    const bool open_end = W.last_byte != '\n';
-    const uint64_t n_lines = (uint64_t)W.total_nl + (w->last && open_end ? 1 : 0);
-    const size_t per = n_lines + 2, n_tiles = n_lines / ingest_scan_tile() + 2;
-    // line starts | record-or-not | six entries per line | out lengths | existing-value offsets (u32) | offsets (u64) | tiles (u64)
-    if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, ((size_t)W.total_nl + 4 + 9 * per) * 4 + 16 + per * 8 + n_tiles * 8 + 64))) return rc;
-    W.d_line = (uint32_t *)T.d_ing_b;
-    uint32_t *d_is_rec = W.d_line + W.total_nl + 4;
-    SamTables L{d_is_rec + per, d_is_rec + 2 * per, d_is_rec + 3 * per, d_is_rec + 4 * per, d_is_rec + 5 * per, d_is_rec + 6 * per};
-    uint32_t *d_out_len = d_is_rec + 7 * per, *d_ex_off = d_is_rec + 8 * per;
-    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_is_rec + 9 * per) + 15) & ~(uintptr_t)15);
-    W.d_tile = d_out_off + per;
-    launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, W.d_line, st);
-    const uint32_t st_init[3] = {0u, 0xFFFFFFFFu, 0u};
-    if (hipMemcpyAsync(W.d_st, st_init, sizeof(st_init), hipMemcpyHostToDevice, st) != hipSuccess) return fail(MK_E_HIP, "copy failed");
-    launch_sam_fields(d_text, W.d_line, n_lines, d_is_rec, L, W.d_st, st);
-    unsigned long long n_rec_dev = 0;
-    if (n_lines && (rc = scan_offsets(d_is_rec, n_lines, W.d_tile, d_out_off, st, &n_rec_dev, "SAM line indexing failed"))) return rc;
-    uint32_t st_host[3] = {0, 0, 0};
-    if (hipMemcpyAsync(st_host, W.d_st, sizeof(st_host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "SAM line indexing failed");
-    if (st_host[0]) {  // a record line with fewer than 10 fields: the host reader words it
-        *status = 1;
-        return MK_OK;
-    }
-    const uint64_t n = n_rec_dev;
-    SamTables R = L;
-    if (n != n_lines) {  // header or empty lines among the records: the records' entries move to tables of their own
-        if ((rc = ensure_device(&T.d_fa_seq, &T.d_fa_seq_cap, 6 * (size_t)(n + 2) * 4))) return rc;
-        uint32_t *r0 = (uint32_t *)T.d_fa_seq;
-        R = SamTables{r0, r0 + (n + 2), r0 + 2 * (n + 2), r0 + 3 * (n + 2), r0 + 4 * (n + 2), r0 + 5 * (n + 2)};
-        launch_sam_compact(d_is_rec, d_out_off, n_lines, L, R, st);
-        if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "SAM line indexing failed");
-    }
-    W.d_rec_start = R.rec_start, W.d_seq_start = R.seq_start, W.d_seq_len = R.seq_len;
-    W.fixed = (n && st_host[1] == st_host[2] && st_host[1] > 0) ? st_host[1] : 0;
-    uint64_t used = n_text;
-    if (!w->last && open_end) {  // the bytes behind the last '\n' are the tail
-        uint32_t last_start = 0;
-        if (hipMemcpyAsync(&last_start, W.d_line + W.total_nl, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "SAM line indexing failed");
-        used = last_start;
-    }
-    w->n_rec = n, w->n_used = used, w->n_tail = n_text - used;
-    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "mk_tag_sam_window: the text behind the window's last line end takes %llu bytes", (unsigned long long)w->n_tail);
-    if (w->n_tail && (hipMemcpyAsync(w->tail, d_text + used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-        return fail(MK_E_HIP, "download of the tail failed");
-    w->ms[1] = (float)ms_since(t);
-    if (n == 0) return MK_OK;
+    SamIndex I;
+    if ((rc = sam_index(m, w, "mk_tag_sam_window", 0, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    const uint64_t n = I.n;
+    const SamTables &R = I.R;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    uint32_t *d_out_len = I.d_out_len, *d_ex_off = I.d_ex_off;
+    unsigned long long *d_out_off = I.d_out_off;
     TagWindow X = tag_window(w, "mk_tag_sam_window", n, d_out_len, d_ex_off, d_out_off, R.name_len);
     // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets
     if ((rc = tag_scan(m, dl, W, X, kSeqSam, logging))) return rc;
@@ -1356,6 +1443,70 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
     } else {
         w->ms[3] = (float)ms_since(t);
     }
+    tag_commit(dl, X, c, counts);
+    return MK_OK;
+    MK_ABI_END
+}
+
+// ---- `tag` SAM text -> BAM with the records encoded on the device (an addition to ABI v7; kernels: the second half of sam.hip): the
+// front half is mk_tag_sam_window's, the back half mk_tag_bam_window's; between them a kept line becomes a BAM record.
+int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
+    if (!m || !codec || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
+    if ((w->n_head && !w->head) || (w->n_text && !w->text) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
+        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names) || (w->n_refs && (!w->ref_names || !w->ref_off)))
+        return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: a size without its buffer");
+    if (w->tag[0] == '\t' || w->tag[1] == '\t' || w->tag[0] == '\n' || w->tag[1] == '\n')
+        return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: a tag name holds a tab or a line end");
+    const uint32_t bb = w->block_bytes ? w->block_bytes : mkz::kMaxBlockBytes;
+    if (bb > mkz::kMaxBlockBytes) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: block_bytes %u > %u", bb, mkz::kMaxBlockBytes);
+    if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: the codec and the matcher are on different devices");
+    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_text_bytes = w->out_len = w->n_rows = w->n_names_bytes = 0;
+    for (float &x : w->ms) x = 0;
+    *status = 0;
+    MK_ABI_BEGIN
+    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
+    DeviceLoop dl(m);
+    hipStream_t st = dl.st;
+    int rc;
+    auto t = std::chrono::steady_clock::now();
+    AllocMs alloc_ms(&w->ms[7]);
+    WindowSide W;
+    SamIndex I;
+    if ((rc = sam_index(m, w, "mk_tag_sam_bam_window", 1, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    const uint64_t n = I.n;
+    const SamTables &R = I.R;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    uint32_t *d_n_cig = I.d_extra;
+    TagWindow X = tag_window(w, "mk_tag_sam_bam_window", n, I.d_out_len, I.d_ex_off, I.d_out_off, R.name_len);
+    // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets
+    if ((rc = tag_scan(m, dl, W, X, kSeqSam, logging))) return rc;
+    w->ms[2] = (float)ms_since(t);
+    // ---- keep, the tag's value, the size of every kept line as a BAM record
+    rc = tag_keep(m, dl, W, X, logging, 7u, [&] {
+        launch_sam_taglen(d_text, R, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n, w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1],
+                          m->d_flags2, I.d_out_len, I.d_ex_off, W.d_st, st);
+        launch_sam_bam_len(d_text, R, m->d_flags2, n, I.d_out_len, d_n_cig, W.d_st, st);
+    }, status);
+    const unsigned long long out_text = X.out_text;
+    w->out_text_bytes = out_text;
+    if (rc || *status) return rc;
+    if ((!w->out && !w->out_cap) || out_text == 0) {  // nothing is written (the checks have run) / nothing is kept
+        w->ms[3] = (float)ms_since(t);
+        tag_commit(dl, X, c, counts);
+        return MK_OK;
+    }
+    // ---- the records, back to back in text slot 1
+    SamRefsDevice F;
+    if ((rc = upload_refs(m, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
+    mk_matcher::TextSlot &O = m->txt[1];
+    if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64))) return rc;
+    launch_sam_bam_encode(d_text, R, m->d_flags2, I.d_out_len, I.d_out_off, d_n_cig, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, F.bytes,
+                          F.off, F.table, F.mask, n, w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
+    if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "record output kernels failed");
+    w->ms[3] = (float)ms_since(t);
+    // ---- BGZF members of the records
+    if ((rc = window_deflate(m, codec, W, dl, "mk_tag_sam_bam_window", out_text, bb, w->out, w->out_cap, &w->out_len, &w->ms[4], &w->ms[5], t))) return rc;
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END

@@ -198,6 +198,16 @@ void launch_sam_taglen(const uint8_t *d_text, const SamTables &R, const unsigned
 void launch_sam_emit(const uint8_t *d_text, const SamTables &R, const uint32_t *d_out_len, const unsigned long long *d_out_off,
                      const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off,
                      const uint32_t *d_ex_off, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
+// SAM -> BAM (mk_tag_sam_bam_window), after launch_sam_taglen: the kept lines' sizes as BAM records (d_out_len: text length in, record
+// size out; d_n_cig: CIGAR ops; d_st[0] |= 1: a kept line with fewer than 11 fields, |= 2: a field that does not encode), then the records
+// at d_out + d_out_off[i].  The reference names: bytes, n + 1 offsets, an open-addressing table (sam_name_hash & mask, linear probing)
+// of index + 1 with 0 = free; d_ref_table == nullptr: no names.
+void launch_sam_bam_len(const uint8_t *d_text, const SamTables &R, const uint8_t *d_keep, uint64_t n_rec, uint32_t *d_out_len, uint32_t *d_n_cig, uint32_t *d_st,
+                        hipStream_t st);
+void launch_sam_bam_encode(const uint8_t *d_text, const SamTables &R, const uint8_t *d_keep, const uint32_t *d_out_len, const unsigned long long *d_out_off,
+                           const uint32_t *d_n_cig, const unsigned long long *d_found_off, const uint32_t *d_found_pat, const uint8_t *d_pat_bytes,
+                           const uint32_t *d_pat_off, const uint32_t *d_ex_off, const uint8_t *d_ref_bytes, const uint32_t *d_ref_off, const uint32_t *d_ref_table,
+                           uint32_t ref_table_mask, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 
 // ---- build_tables.hip: the pattern set compiled into filter images + exact table on the device -----------------
 struct BuildParams {

@@ -2,7 +2,8 @@
 """End-to-end wall time of `merkurio tag` SAM -> SAM on the synthetic records of tools/e2e_tag.py written as plain SAM: the window
 path (mk_tag_sam_window, the default) against --host-ingest (the host loop) in the same job, and the window path at several
 --window-mb.  Shapes: -m with one record in `every` carrying a k-mer, everything kept, -S -j.
-usage: tools/e2e_tag_sam.py [n_records] [n_patterns] [every, default 5] [runs, default 5] [--sweep]"""
+--bam: SAM -> BAM instead (mk_tag_sam_bam_window against the host loop; shapes: everything kept, -m, -m -j; sweep 64 / 128 / 240).
+usage: tools/e2e_tag_sam.py [n_records] [n_patterns] [every, default 5] [runs, default 5] [--sweep] [--bam] [--keep]"""
 import os, statistics, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,20 +57,24 @@ def row(label, ts):
 
 
 shapes = (("-m", ["-o", out + ".sam", "-m"]), ("everything kept", ["-o", out + ".sam"]), ("-S -j", ["-S", "-j", out + ".json"]))
+kind, sizes = "SAM -> SAM", (64, 128, 240, 512)
+if "--bam" in sys.argv:
+    shapes = (("everything kept", ["-o", out + ".bam"]), ("-m", ["-o", out + ".bam", "-m"]), ("-m -j", ["-o", out + ".bam", "-m", "-j", out + ".json"]))
+    kind, sizes = "SAM -> BAM", (64, 128, 240)
 timed(shapes[0][1], 1)  # (page cache, output file)
 for name, args in shapes:
-    row(f"SAM -> SAM, {name}, --host-ingest", timed(args + ["--host-ingest"], runs))
-    row(f"SAM -> SAM, {name}, window path (default window)", timed(args, runs))
+    row(f"{kind}, {name}, --host-ingest", timed(args + ["--host-ingest"], runs))
+    row(f"{kind}, {name}, window path (default window)", timed(args, runs))
 if "--sweep" in sys.argv:
     for name, args in shapes[:2]:
-        for mb in (64, 128, 240, 512):
-            row(f"SAM -> SAM, {name}, window path --window-mb {mb}", timed(args + ["--window-mb", str(mb)], 3))
+        for mb in sizes:
+            row(f"{kind}, {name}, window path --window-mb {mb}", timed(args + ["--window-mb", str(mb)], 3))
 # where a window's time goes: the phases summed over the windows of one run
 for name, args in shapes[:2]:
     p = subprocess.run([binp, "tag", "-f", km, "-i", sam, *args], check=True, env=dict(env, MERKURIO_TIMING="1"), capture_output=True)
     for ln in p.stderr.decode().split("\n"):
         if "windows on the device" in ln:
             print(f"{name}: {ln}", flush=True)
-for f in (sam, km, out + ".sam", out + ".json"):
-    if os.path.exists(f):
+for f in (sam, km, out + ".sam", out + ".bam", out + ".json"):
+    if os.path.exists(f) and not (f in (sam, km) and "--keep" in sys.argv):  # (--keep: the input stays, for a kernel trace of one run)
         os.remove(f)
