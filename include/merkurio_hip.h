@@ -743,6 +743,66 @@ typedef struct mk_sam_bam_window {
 int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, int logging, mk_counters *counters, uint32_t *pattern_hit_counts,
                           uint32_t *status);
 
+/* -------------------------------------------------------------------------------------
+ * `tag` on a window of a BAM file whose kept records leave as SAM TEXT (an addition to v7; kernels: bam.hip) -- BAM -> SAM / STDOUT:
+ * the window, its members, head and tail, on_tail, the record index, the scan, the keep rule, the tag's value, rows, names and counters
+ * are mk_tag_bam_window's; what leaves is mk_tag_sam_window's: every kept record as  line TAB tag ":Z:" value "\n",  back to back in
+ * record order in out[0, out_len) -- only these lines are downloaded.  The line is what the CLI's host path writes for the record
+ * (cli/io.cpp: SamFile::append_line), which is the definition.  Restated, tab-separated:
+ *   QNAME: read_name without its NUL;  FLAG, MAPQ: decimal;
+ *   RNAME: reference name refID -- ref_names[ref_off[i], ref_off[i + 1]), the names of the BAM header in its order -- when
+ *     0 <= refID < n_refs, else "*";  RNEXT: "*" when next_refID < 0, "=" when it equals refID, its name when it is < n_refs, else "*";
+ *   POS, PNEXT: the field + 1;  TLEN: signed decimal;
+ *   CIGAR: "*" without ops, else per op its length and its letter of "MIDNSHP=X" (an op code of 9 or more prints '?');
+ *   SEQ: "*" when l_seq is 0, else "=ACMGRSVTWYHKDBN"[nibble], high nibble first;
+ *   QUAL: "*" when l_seq is 0 or the first byte is 0xFF, else each byte + 33 (modulo 256);
+ *   the optional fields in record order as TAG:TYPE:VALUE:  A = the byte;  c C s S i I = "i:" and the decimal value;  f = "f:" and
+ *     "%g" of the float;  Z / H = the bytes up to the NUL;  B = "B:", the subtype, then ",item" per item;
+ *   then the tag -- an existing field of that name stays where it is, the merged value is appended, as on every other path.
+ * Integers are plain decimal.  A float is formatted only where "%g" can be computed exactly in 64-bit integers (bam_numbers.hpp): +-0,
+ * and the finite values that, rounded to six significant digits, have a decimal exponent of -4 ... 5 ("%g"'s fixed notation).
+ * *status != 0: this window is not for the device and NOTHING was produced or counted -- the caller's host path takes it from the
+ * window's first byte (and words the errors).  Bits 1, 4 and 8 as in mk_tag_bam_window;  2 = a kept record whose optional fields do
+ * not parse (an unknown B subtype with items included), or with an `f` value / item outside the float rule (exponent notation, inf,
+ * nan, subnormals), or with POS or PNEXT = 2^31 - 1 (the host path adds 1 in 32 bits).  Records that are dropped are not looked at.
+ * MK_E_CAPACITY (tail, then rows and names together, then out; the need in n_tail / n_rows + n_names_bytes / out_len) has counted
+ * nothing.  out == NULL && out_cap == 0: nothing is formatted or written (out_len 0), the checks still run.
+ * ms[]: milliseconds of [0] upload, [1] inflate, [2] record index, [3] unpack + scan + sets, [4] tag + format, [5] download; ms[7]: of
+ * these, growing device buffers.
+ * --------------------------------------------------------------------------------------- */
+typedef struct mk_bam_sam_window {
+    /* in */
+    const uint8_t *head;
+    uint64_t n_head;
+    const uint8_t *bgzf;
+    uint64_t n_bgzf;
+    const mk_bgzf_member *members;
+    uint64_t n_members;
+    uint32_t last; /* no text follows this window */
+    uint32_t filter_matching, invert;
+    uint8_t tag[2];
+    uint8_t reserved[2];
+    const uint8_t *ref_names; /* the reference names, back to back */
+    const uint64_t *ref_off;  /* n_refs + 1 ascending offsets into ref_names */
+    uint64_t n_refs;
+    uint8_t *tail;
+    uint64_t tail_cap;
+    uint8_t *out;
+    uint64_t out_cap;
+    mk_row *rows;
+    uint64_t rows_cap;
+    uint64_t *row_name; /* room for rows_cap entries */
+    uint8_t *names;
+    uint64_t names_cap;
+    void (*on_tail)(void *ctx, const uint8_t *tail, uint64_t n_tail); /* as in mk_bam_window */
+    void *on_tail_ctx;
+    /* out */
+    uint64_t n_window, n_used, n_tail, n_rec, n_kept, out_len, n_rows, n_names_bytes;
+    float ms[8];
+} mk_bam_sam_window;
+int mk_tag_bam_sam_window(mk_matcher *m, mk_codec *codec, mk_bam_sam_window *w, int logging, mk_counters *counters, uint32_t *pattern_hit_counts,
+                          uint32_t *status);
+
 /* walks the BSIZE chain of in[0, n): fills members[0, cap) (out_off = running sum of ISIZE), *n_members = how many there are,
  * *consumed = bytes of whole members, *text_bytes = sum of ISIZE.  MK_E_CORRUPT where a header is not BGZF; a trailing
  * partial member is not an error (*consumed < n).  Host code, no device. */

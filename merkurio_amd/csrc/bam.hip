@@ -19,6 +19,7 @@
 // also words the error.
 #include <algorithm>
 
+#include "bam_numbers.hpp"
 #include "scan_kernel.h"
 #include "tag_merge.hpp"
 
@@ -311,6 +312,228 @@ __global__ __launch_bounds__(256) void mk_bam_emit_kernel(const uint8_t *__restr
     }
 }
 
+// ---- BAM record -> SAM line (mk_tag_bam_sam_window; the mirror of sam.hip's SAM -> BAM half): the bytes SamFile::append_line
+// (cli/io.cpp: bam_record_to_sam + aux_to_text) writes for the record, then TAB tag ":Z:" value "\n".  One walk, bam_sam_line<kWrite>,
+// sizes a line (mk_bam_sam_len_kernel) and writes everything of it that is not SEQ / QUAL (mk_bam_sam_fields_kernel): the same code
+// advances the same position in both, so the sizes of the first are the bytes of the second.  The walk is serial and short -- a few
+// dozen bytes per record -- so it is one lane per record; SEQ and QUAL, three quarters of a line, are 16 lanes per record
+// (mk_bam_sam_seq_kernel).  Numbers: bam_numbers.hpp.
+struct BamRefs {  // the reference names of the BAM header: name i = bytes[off[i], off[i + 1])
+    const uint8_t *bytes;
+    const uint32_t *off;
+    uint32_t n;
+};
+
+template <bool kWrite>
+__device__ __forceinline__ void bam_sam_ref(BamText<kWrite> &t, const BamRefs &F, int32_t id) {
+    if (id < 0 || (uint32_t)id >= F.n) {
+        t.put('*');
+        return;
+    }
+    const uint32_t a = F.off[id], b = F.off[id + 1];
+    if (kWrite)
+        for (uint32_t k = a; k < b; ++k) t.out[t.at + (k - a)] = F.bytes[k];
+    t.at += b - a;
+}
+
+// one item of an integer type at p (type one of c C s S i I); the caller has checked that its bytes are there
+template <bool kWrite>
+__device__ __forceinline__ void bam_sam_item(BamText<kWrite> &t, const uint8_t *p, uint32_t type) {
+    long long v;
+    if (type == 'c') v = (int8_t)p[0];
+    else if (type == 'C') v = p[0];
+    else if (type == 's') v = (int16_t)bam_ld16(p);
+    else if (type == 'S') v = bam_ld16(p);
+    else if (type == 'i') v = (int32_t)bam_ld32(p);
+    else v = bam_ld32(p);
+    bam_put_int(t, v);
+}
+
+// The record at text + r0 (its block_size field; rlen = 4 + block_size, sizes checked by the record index) as a SAM line without its
+// tag and line end, at t; SEQ and QUAL are left out -- *seq_at = where SEQ starts, QUAL one tab behind it -- except where they are "*".
+// Returns the refusal bits: 2 = optional fields that do not parse (the host path words that), an `f` outside bam_numbers.hpp's rule,
+// or POS / PNEXT = INT32_MAX (the host adds 1 in 32 bits, which is undefined: not imitated, the window is refused).
+template <bool kWrite>
+__device__ __forceinline__ uint32_t bam_sam_line(BamText<kWrite> &t, const uint8_t *__restrict__ text, uint64_t r0, uint32_t rlen, const BamRefs &F, uint32_t *seq_at) {
+    const uint8_t *r = text + r0 + 4;
+    const int32_t ref = (int32_t)bam_ld32(r), pos = (int32_t)bam_ld32(r + 4), l_seq = (int32_t)bam_ld32(r + 16), nref = (int32_t)bam_ld32(r + 20),
+                  npos = (int32_t)bam_ld32(r + 24), tlen = (int32_t)bam_ld32(r + 28);
+    const uint32_t l_name = r[8], mapq = r[9], n_cig = bam_ld16(r + 12), flag = bam_ld16(r + 14);
+    uint32_t bad = (pos == 0x7FFFFFFF || npos == 0x7FFFFFFF) ? 2u : 0u;
+    for (uint32_t k = 0; k + 1 < l_name; ++k) t.put(r[32 + k]);
+    t.put('\t');
+    bam_put_int(t, (long long)flag);
+    t.put('\t');
+    bam_sam_ref(t, F, ref);
+    t.put('\t');
+    bam_put_int(t, (long long)pos + 1);
+    t.put('\t');
+    bam_put_int(t, (long long)mapq);
+    t.put('\t');
+    const uint8_t *cg = r + 32 + l_name;
+    if (n_cig == 0) t.put('*');
+    for (uint32_t k = 0; k < n_cig; ++k) {
+        const uint32_t v = bam_ld32(cg + 4 * k), op = v & 15u;
+        bam_put_int(t, (long long)(v >> 4));
+        // "MIDNSHP=" as the bytes of one constant, indexed by a shift; 'X', and '?' for a code the specification does not have
+        t.put(op < 8 ? (uint32_t)(0x3D5048534E44494Dull >> (8 * op)) & 0xFFu : op == 8 ? 'X' : '?');
+    }
+    t.put('\t');
+    if (nref < 0) t.put('*');
+    else if (nref == ref) t.put('=');
+    else bam_sam_ref(t, F, nref);
+    t.put('\t');
+    bam_put_int(t, (long long)npos + 1);
+    t.put('\t');
+    bam_put_int(t, (long long)tlen);
+    t.put('\t');
+    const uint8_t *sq = cg + 4 * (uint64_t)n_cig, *ql = sq + ((uint32_t)l_seq + 1) / 2;
+    *seq_at = (uint32_t)t.at;
+    if (l_seq == 0) t.put('*');
+    else t.at += (uint32_t)l_seq;
+    t.put('\t');
+    if (l_seq == 0 || ql[0] == 0xFF) t.put('*');
+    else t.at += (uint32_t)l_seq;
+    // ---- the optional fields (aux_to_text)
+    const uint8_t *p = ql + (uint32_t)l_seq, *e = text + r0 + rlen;
+    while (p < e) {
+        if (e - p < 3) return bad | 2;
+        const uint32_t type = p[2];
+        t.put('\t'), t.put(p[0]), t.put(p[1]), t.put(':');
+        p += 3;
+        if (type == 'A') {
+            if (e - p < 1) return bad | 2;
+            t.put('A'), t.put(':'), t.put(p[0]);
+            p += 1;
+        } else if (type == 'c' || type == 'C' || type == 's' || type == 'S' || type == 'i' || type == 'I') {
+            const uint32_t w = (type == 'c' || type == 'C') ? 1 : (type == 's' || type == 'S') ? 2 : 4;
+            if (e - p < w) return bad | 2;
+            t.put('i'), t.put(':');
+            bam_sam_item(t, p, type);
+            p += w;
+        } else if (type == 'f') {
+            if (e - p < 4) return bad | 2;
+            t.put('f'), t.put(':');
+            if (!bam_put_float(t, bam_ld32(p))) bad |= 2;
+            p += 4;
+        } else if (type == 'Z' || type == 'H') {
+            t.put(type), t.put(':');
+            while (p < e && *p) t.put(*p++);
+            if (p == e) return bad | 2;  // (no NUL: today's rule of mk_bam_taglen_kernel)
+            ++p;
+        } else if (type == 'B') {
+            if (e - p < 5) return bad | 2;
+            const uint32_t sub = p[0];
+            const int32_t cnt = (int32_t)bam_ld32(p + 1);
+            p += 5;
+            const bool is_int = sub == 'c' || sub == 'C' || sub == 's' || sub == 'S' || sub == 'i' || sub == 'I';
+            const uint32_t w = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (cnt < 0 || (cnt > 0 && !is_int && sub != 'f') || (uint64_t)(e - p) < (uint64_t)w * (uint32_t)cnt) return bad | 2;
+            t.put('B'), t.put(':'), t.put(sub);
+            for (int32_t k = 0; k < cnt; ++k, p += w) {
+                t.put(',');
+                if (is_int) bam_sam_item(t, p, sub);
+                else if (!bam_put_float(t, bam_ld32(p))) bad |= 2;
+            }
+        } else {
+            return bad | 2;
+        }
+    }
+    return bad;
+}
+
+// Runs behind mk_bam_taglen_kernel (keep, ex_off, out_len = the record as BAM with its tag, refusal bits): a kept record's out_len
+// becomes the length of its line with the tag -- the value's length is taken from the BAM length -- and seq_at where its SEQ goes
+__global__ __launch_bounds__(256) void mk_bam_sam_len_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ rec_off,
+                                                            const uint32_t *__restrict__ rec_len, const uint8_t *__restrict__ keep, uint64_t n_rec, BamRefs F,
+                                                            uint32_t *__restrict__ out_len, uint32_t *__restrict__ seq_at, uint32_t *__restrict__ st) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    if (i < n_rec && keep[i]) {
+        BamText<false> t{nullptr, 0};
+        uint32_t sa = 0;
+        const uint32_t L = rec_len[i];
+        bad = bam_sam_line<false>(t, text, rec_off[i], L, F, &sa);
+        const uint64_t vlen = out_len[i] - L - 4;  // (out_len = L + tag (2) + 'Z' + value + NUL)
+        const uint64_t len = t.at + 6 + vlen + 1;  // TAB tag ":Z:" value "\n"
+        if (len > 0xFFFFFFFFull) bad |= 2;
+        out_len[i] = (uint32_t)len;
+        seq_at[i] = sa;
+    }
+    if (__ballot(bad != 0)) {
+        uint32_t all = bad;
+        for (int o = 32; o > 0; o >>= 1) all |= (uint32_t)__shfl_down(all, o);
+        if ((threadIdx.x & 63) == 0) atomicOr(&st[0], all);
+    }
+}
+
+// everything of a kept record's line that is not SEQ / QUAL, at out + out_off[i]; one lane per record
+__global__ __launch_bounds__(256) void mk_bam_sam_fields_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ rec_off,
+                                                               const uint32_t *__restrict__ rec_len, const uint32_t *__restrict__ out_len,
+                                                               const unsigned long long *__restrict__ out_off, const unsigned long long *__restrict__ found_off,
+                                                               const uint32_t *__restrict__ found_pat, const uint8_t *__restrict__ pat_bytes,
+                                                               const uint32_t *__restrict__ pat_off, const uint32_t *__restrict__ ex_off, BamRefs F, uint64_t n_rec,
+                                                               uint32_t tag0, uint32_t tag1, uint8_t *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec || !out_len[i]) return;
+    BamText<true> t{out + out_off[i], 0};
+    uint32_t sa;
+    bam_sam_line<true>(t, text, rec_off[i], rec_len[i], F, &sa);
+    t.put('\t'), t.put(tag0), t.put(tag1), t.put(':'), t.put('Z'), t.put(':');
+    const uint32_t ex_at = ex_off[i];  // (0: no existing value; else it ends at its NUL)
+    uint32_t ex_n = 0;
+    if (ex_at)
+        while (text[ex_at + ex_n]) ++ex_n;
+    *tag_value_put(t.out + t.at, text + ex_at, ex_n, found_off[i], found_off[i + 1], found_pat, pat_off, pat_bytes) = '\n';
+}
+
+// SEQ and QUAL of the kept records; 16 lanes per record, per lane and step eight packed bytes -> 16 letters and 16 quality bytes + 33
+// (per byte, as the host's (char)(q + 33): the low seven bits are added, the top bit is put back, so no carry crosses a byte)
+__global__ __launch_bounds__(256) void mk_bam_sam_seq_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ seq_start,
+                                                            const uint32_t *__restrict__ seq_len, const uint32_t *__restrict__ out_len,
+                                                            const unsigned long long *__restrict__ out_off, const uint32_t *__restrict__ seq_at, uint64_t n_rec,
+                                                            uint8_t *__restrict__ out) {
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t sub = threadIdx.x & 15u;
+    if (i >= n_rec || !out_len[i]) return;
+    const uint32_t len = seq_len[i];
+    if (!len) return;
+    const uint8_t *__restrict__ src = text + seq_start[i];
+    const uint8_t *__restrict__ ql = src + (len + 1) / 2;
+    uint8_t *__restrict__ dst = out + out_off[i] + seq_at[i];
+    uint8_t *__restrict__ qdst = dst + len + 1;
+    const bool has_q = ql[0] != 0xFF;
+    const unsigned long long tab_lo = 0x565352474D43413Dull;  // bytes 0..7  = '=' 'A' 'C' 'M' 'G' 'R' 'S' 'V'
+    const unsigned long long tab_hi = 0x4E42444B48595754ull;  // bytes 8..15 = 'T' 'W' 'Y' 'H' 'K' 'D' 'B' 'N'
+    for (uint32_t b0 = 16 * sub; b0 < len; b0 += 256) {  // bases [b0, b0 + 16) = packed bytes [b0 / 2, b0 / 2 + 8)
+        if (b0 + 16 <= len) {
+            unsigned long long w, v[2] = {0, 0};
+            __builtin_memcpy(&w, src + (b0 >> 1), 8);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t byte = (uint32_t)(w >> (8 * (k >> 1))) & 0xFFu;
+                const uint32_t nib = (k & 1) ? (byte & 15u) : (byte >> 4);
+                const unsigned long long c = ((nib < 8 ? tab_lo : tab_hi) >> (8 * (nib & 7))) & 0xFFull;
+                v[k >> 3] |= c << (8 * (k & 7));
+            }
+            __builtin_memcpy(dst + b0, v, 16);
+            if (has_q) {
+                unsigned long long q[2];
+                __builtin_memcpy(q, ql + b0, 16);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) q[k] = ((q[k] & 0x7F7F7F7F7F7F7F7Full) + 0x2121212121212121ull) ^ (q[k] & 0x8080808080808080ull);
+                __builtin_memcpy(qdst + b0, q, 16);
+            }
+        } else {  // (the last, shorter step of the record)
+            for (uint32_t b = b0; b < len; ++b) {
+                const uint32_t nib = (src[b >> 1] >> ((~b & 1u) << 2)) & 15u;
+                dst[b] = (uint8_t)(((nib < 8 ? tab_lo : tab_hi) >> (8 * (nib & 7))) & 0xFFull);
+                if (has_q) qdst[b] = (uint8_t)(ql[b] + 33u);
+            }
+        }
+    }
+}
+
 // names (NUL included) of the records with a hit, for the log rows: name_len[i] = flags[i] ? l_read_name : 0 and where the name starts
 __global__ __launch_bounds__(256) void mk_bam_names_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ rec_off,
                                                           const uint8_t *__restrict__ flags, uint64_t n_rec, uint32_t *__restrict__ name_start,
@@ -355,6 +578,22 @@ void launch_bam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uin
     if (!n_rec) return;
     hipLaunchKernelGGL(mk_bam_emit_kernel, dim3((unsigned)((n_rec * 16 + 255) / 256)), dim3(256), 0, st, d_text, d_rec_off, d_rec_len, d_out_len, d_out_off,
                        d_found_off, d_found_pat, d_pat_bytes, d_pat_off, d_ex_off, n_rec, tag0, tag1, d_out);
+}
+void launch_bam_sam_len(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint8_t *d_keep, uint64_t n_rec,
+                        const uint8_t *d_ref_bytes, const uint32_t *d_ref_off, uint32_t n_refs, uint32_t *d_out_len, uint32_t *d_seq_at, uint32_t *d_st, hipStream_t st) {
+    if (!n_rec) return;
+    hipLaunchKernelGGL(mk_bam_sam_len_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_text, d_rec_off, d_rec_len, d_keep, n_rec,
+                       BamRefs{d_ref_bytes, d_ref_off, n_refs}, d_out_len, d_seq_at, d_st);
+}
+void launch_bam_sam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint32_t *d_seq_start, const uint32_t *d_seq_len,
+                         const uint32_t *d_out_len, const unsigned long long *d_out_off, const uint32_t *d_seq_at, const unsigned long long *d_found_off,
+                         const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off, const uint32_t *d_ex_off, const uint8_t *d_ref_bytes,
+                         const uint32_t *d_ref_off, uint32_t n_refs, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st) {
+    if (!n_rec) return;
+    hipLaunchKernelGGL(mk_bam_sam_fields_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_text, d_rec_off, d_rec_len, d_out_len, d_out_off,
+                       d_found_off, d_found_pat, d_pat_bytes, d_pat_off, d_ex_off, BamRefs{d_ref_bytes, d_ref_off, n_refs}, n_rec, tag0, tag1, d_out);
+    hipLaunchKernelGGL(mk_bam_sam_seq_kernel, dim3((unsigned)((n_rec * 16 + 255) / 256)), dim3(256), 0, st, d_text, d_seq_start, d_seq_len, d_out_len, d_out_off,
+                       d_seq_at, n_rec, d_out);
 }
 void launch_bam_names(const uint8_t *d_text, const uint32_t *d_rec_off, const uint8_t *d_flags, uint64_t n_rec, uint32_t *d_name_start, uint32_t *d_name_len,
                       hipStream_t st) {

@@ -810,17 +810,20 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
     // loop below takes the input from there
     std::vector<mk_matcher *> seconds;
     const bool bam_windows = sam.bam_on_bgzf() && (to_bam || a.suppress_output) && !a.host_codec && !a.host_ingest;
+    // BAM -> SAM text / STDOUT: the same windows, whose kept records come back as SAM lines formatted on the device
+    // (tag_bam_sam_windows_on_device); --host-ingest keeps the host loop
+    const bool bam_sam_windows = sam.bam_on_bgzf() && !to_bam && !a.suppress_output && !a.host_codec && !a.host_ingest;
     // SAM text -> SAM text / STDOUT (or no output at all) from a memory-mapped file: the lines stay on the device between the upload and
     // the download of the kept ones (tag_windows.cpp: tag_sam_windows_on_device; windows cut at line starts, independent of each other)
     // SAM text -> BAM goes the same way with the kept lines encoded as BAM records and deflated on the device (tag_sam_bam_windows_on_device)
     const bool sam_windows = sam.sam_on_mapping() && !a.host_ingest && !(to_bam && a.host_codec);
-    if (bam_windows || sam_windows) {
+    if (bam_windows || bam_sam_windows || sam_windows) {
         if (to_bam) bw.use_device(devs[0]);
         // BAM: 240 MiB of text -- the tagged records of a window then fill one round of the deflate kernel's 4 096 resident waves, not one
         // and a bit.  SAM (to SAM and to BAM alike: the input side is the same): 64 MiB, the fastest of the 64 / 128 / 240 / 512 sweep (profiles/e2e_tag_sam_window.txt): the windows are
         // independent, so small ones cost nothing but launches, and their page-locked staging buffers stay small.
         // (an explicit --window-mb is honoured up to 2 GiB: a window's text, head included, has to stay below 4 GiB on the device)
-        const uint64_t dev_window = a.window_mb_given ? std::min<uint64_t>(window_bytes, 2048ull << 20) : ((bam_windows ? 240ull : 64ull) << 20);
+        const uint64_t dev_window = a.window_mb_given ? std::min<uint64_t>(window_bytes, 2048ull << 20) : ((bam_windows || bam_sam_windows ? 240ull : 64ull) << 20);
         // (a SAM text that is one window needs no second handle; BAM windows are not known before their members are walked)
         const bool one_window = sam_windows && sam.source().text_size() - sam.text_cursor() <= dev_window;
         seconds.assign(ms.size(), nullptr);
@@ -835,9 +838,10 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
         for (int rep = 0; rep < (one_window ? 1 : 2); ++rep)
             for (size_t d = 0; d < ms.size(); ++d)
                 handles.push_back(TagHandle{rep ? seconds[d] : ms[d], devs[d], ms.size() == 1 ? &c : &dev_c[d], ms.size() == 1 ? &counts : &dev_counts[d]});
-        device_done = bam_windows ? tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window)
-                      : to_bam    ? tag_sam_bam_windows_on_device(a, sam, handles, lg, pats, in_name, bw, dev_window)
-                                  : tag_sam_windows_on_device(a, sam, handles, lg, pats, in_name, a.suppress_output ? nullptr : &w, dev_window);
+        device_done = bam_windows       ? tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window)
+                      : bam_sam_windows ? tag_bam_sam_windows_on_device(a, sam, handles, lg, pats, in_name, w, dev_window)
+                      : to_bam          ? tag_sam_bam_windows_on_device(a, sam, handles, lg, pats, in_name, bw, dev_window)
+                                        : tag_sam_windows_on_device(a, sam, handles, lg, pats, in_name, a.suppress_output ? nullptr : &w, dev_window);
         tm.mark(device_done ? "windows on the device" : "windows on the device (the rest: host reader)");
     }
     // (the first window is small: nothing can run beside its read; the later, large ones are read beside their predecessors)

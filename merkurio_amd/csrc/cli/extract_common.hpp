@@ -130,5 +130,9 @@ bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
 // device against bw's reference names (bw is open), and go to bw.put_members
 bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
                                    const std::string &in_name, BamWriter &bw, uint64_t window_bytes);
+// BAM (BGZF members) -> SAM text / STDOUT (mk_tag_bam_sam_window): tag_bam_windows_on_device's windows, head chain and refusal (seek_bam);
+// the kept records come back as SAM lines formatted on the device and go to `out` in window order
+bool tag_bam_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                                   const std::string &in_name, Sink &out, uint64_t window_bytes);
 
 }  // namespace cli

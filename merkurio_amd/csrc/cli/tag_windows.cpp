@@ -29,8 +29,14 @@
 // the @SQ names the BamWriter's header was written from) and go to BamWriter::put_members.  On top of SAM -> SAM's refusals, a window
 // with a kept line that BamWriter::encode_record would refuse, or whose numbers are not plain ones, is the host loop's.
 //
+// BAM -> SAM text / STDOUT (tag_bam_sam_windows_on_device, mk_tag_bam_sam_window) is the BAM driver's input side -- member windows, the
+// head chain, two windows in flight per device -- and the SAM driver's output side: the kept records come back as finished SAM lines
+// (formatted on the device from the reference names of the BAM header) in a page-locked buffer and go to the text writer in window
+// order.  On top of BAM -> BAM's refusals, a window with a kept record that carries a float "%g" would write in exponent notation is
+// the host loop's.
+//
 // Both formats share one driver (run_windows): the round-robin over the workers, the repeat of a call that asked for more room, the
-// emit turn, refusal and error bookkeeping, counters and log rows.  BamWorker / SamWorker / SamBamWorker say how a window is staged, run and written.
+// emit turn, refusal and error bookkeeping, counters and log rows.  BamWorker / SamWorker / SamBamWorker / BamSamWorker say how a window is staged, run and written.
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -344,6 +350,86 @@ struct SamBamWorker {
     }
 };
 
+// ---- BAM -> SAM text: BamWorker's windows, SamWorker's output
+struct BamSamWorker {
+    const std::vector<WindowMembers> &wins;
+    const uint8_t *file;
+    Sink *out_sink;
+    const std::vector<uint8_t> &ref_bytes;
+    const std::vector<uint64_t> &ref_off;
+    Pipe &pipe;
+    uint32_t &refused_status;
+    int &refused_rc;
+    bool all_kept;  // neither -m nor -v
+    mk_matcher *m;
+    mk_codec *codec;
+    HostBuffer stage, out;  // the window's members; the kept lines (both page-locked)
+    std::vector<uint8_t> tail = std::vector<uint8_t>(1u << 20), head;
+    TailCtx tctx{};
+    double ratio = 0;  // line bytes per byte of window text of this worker's previous window (0: none yet)
+    mk_bam_sam_window w{};
+    static constexpr bool corrupt_is_refused = true;  // (a damaged member)
+    ~BamSamWorker() {
+        if (!g_process_is_ending) mk_codec_destroy(codec);
+    }
+    // The first guess comes from the flags: with everything kept the lines take more than the window's text (SEQ doubles, the numbers
+    // grow), with -m or -v what the k-mers select -- an eighth is a guess.  After that the previous window's ratio and a quarter: a
+    // window that does not fit is done again with the size it asked for, which this keeps the exception.
+    uint64_t out_room(uint64_t text) const {
+        const double r = ratio > 0 ? ratio * 1.25 : all_kept ? 2.25 : 0.125;
+        return (uint64_t)((double)text * r) + (1u << 20);
+    }
+    bool load(size_t k) {
+        const WindowMembers &X = wins[k];
+        if (!X.mem.empty()) {
+            if (!stage.grow(X.file_hi - X.file_lo, 1u << 20)) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
+            copy_in(file, X.file_lo, X.file_hi, stage.p);
+        }
+        if (out.cap < out_room(X.text + (1u << 20)) && !out.grow(out_room(X.text + (1u << 20)), 1u << 20))
+            bail(std::string("Error during BAM record parsing: ") + mk_last_error());
+        {
+            std::unique_lock<std::mutex> lk(pipe.mu);
+            pipe.cv.wait(lk, [&] { return pipe.stop || pipe.heads_ready >= k; });
+            if (pipe.stop) return false;
+            head = pipe.head;
+        }
+        tctx = TailCtx{&pipe, k};
+        w.head = head.data(), w.n_head = head.size();
+        w.bgzf = stage.p, w.n_bgzf = X.file_hi - X.file_lo;
+        w.members = X.mem.data(), w.n_members = X.mem.size();
+        w.last = k + 1 == wins.size();
+        w.ref_names = ref_bytes.data(), w.ref_off = ref_off.data(), w.n_refs = ref_off.size() - 1;
+        w.on_tail = on_tail, w.on_tail_ctx = &tctx;
+        return true;
+    }
+    int call(int logging, mk_counters *wc, uint32_t *wcounts, uint32_t *status) {
+        w.tail = tail.data(), w.tail_cap = tail.size();
+        w.out = out.p, w.out_cap = out.cap;
+        const int rc = mk_tag_bam_sam_window(m, codec, &w, logging, wc, wcounts, status);
+        if (rc == MK_OK && !*status) {
+            on_tail(&tctx, tail.data(), w.n_tail);  // (an empty window returns before the library reports it)
+            if (w.n_window) ratio = (double)w.out_len / (double)w.n_window;
+        }
+        return rc;
+    }
+    bool grow() {
+        bool grew = false;
+        if (w.n_tail > tail.size()) tail.resize(w.n_tail + (1u << 20)), grew = true;
+        if (w.out_len > out.cap) {
+            if (!out.grow(w.out_len, 1u << 20)) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
+            grew = true;
+        }
+        return grew;
+    }
+    void refused(size_t, int rc, uint32_t status) {  // (the head the window was given, not the current one)
+        pipe.refused_head = head;
+        refused_status = status, refused_rc = rc;
+    }
+    void write() {
+        if (w.out_len) out_sink->write((const char *)out.p, w.out_len);
+    }
+};
+
 // [b, e) per window, e = the first line start at or behind b + window_bytes
 std::vector<std::pair<uint64_t, uint64_t>> cut_at_lines(const uint8_t *file, uint64_t from, uint64_t n_file, uint64_t window_bytes) {
     std::vector<std::pair<uint64_t, uint64_t>> wins;
@@ -359,19 +445,10 @@ std::vector<std::pair<uint64_t, uint64_t>> cut_at_lines(const uint8_t *file, uin
     return wins;
 }
 
-}  // namespace
-
-bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes) {
-    const WindowSource &src = sam.source();
+// the BAM windows of the rest of the file: runs of members of ~window_bytes of text (the same whatever the heads turn out to be);
+// have_head: records behind the header that open() has inflated already -- a window of their own if no member follows
+std::vector<WindowMembers> cut_at_members(const WindowSource &src, uint64_t window_bytes, bool have_head) {
     const size_t n_mem = src.n_bgzf_members();
-    const uint8_t *file = src.file_bytes();
-    const bool timing = getenv("MERKURIO_TIMING") != nullptr;
-    uint64_t n_pending = 0;
-    const char *pend = sam.bam_pending(&n_pending);
-    Pipe pipe;
-    pipe.head.assign(pend, pend + n_pending);
-    // the windows: runs of members of ~window_bytes of text (the same whatever the heads turn out to be)
     std::vector<WindowMembers> wins;
     for (size_t m0 = src.next_member(); m0 < n_mem;) {
         WindowMembers W;
@@ -391,12 +468,27 @@ bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector
         m0 = m1;
         wins.push_back(std::move(W));
     }
-    if (wins.empty()) {
-        if (pipe.head.empty()) return true;
-        WindowMembers W;  // (records behind the header that open() has inflated already, and no member behind them)
+    if (wins.empty() && have_head) {
+        WindowMembers W;
         W.m0 = W.m1 = n_mem;
         wins.push_back(std::move(W));
     }
+    return wins;
+}
+
+}  // namespace
+
+bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes) {
+    const WindowSource &src = sam.source();
+    const uint8_t *file = src.file_bytes();
+    const bool timing = getenv("MERKURIO_TIMING") != nullptr;
+    uint64_t n_pending = 0;
+    const char *pend = sam.bam_pending(&n_pending);
+    Pipe pipe;
+    pipe.head.assign(pend, pend + n_pending);
+    const std::vector<WindowMembers> wins = cut_at_members(src, window_bytes, !pipe.head.empty());
+    if (wins.empty()) return true;
     const size_t n_win = wins.size();
     // (window k runs on handle k mod n_workers: with the handles of several devices in a row, consecutive windows go to different devices)
     const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
@@ -495,6 +587,57 @@ bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::ve
         return false;
     }
     sam.seek_text(n_file);
+    return true;
+}
+
+bool tag_bam_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
+                                   const std::string &in_name, Sink &out_sink, uint64_t window_bytes) {
+    const WindowSource &src = sam.source();
+    const uint8_t *file = src.file_bytes();
+    const bool timing = getenv("MERKURIO_TIMING") != nullptr;
+    uint64_t n_pending = 0;
+    const char *pend = sam.bam_pending(&n_pending);
+    Pipe pipe;
+    pipe.head.assign(pend, pend + n_pending);
+    const std::vector<WindowMembers> wins = cut_at_members(src, window_bytes, !pipe.head.empty());
+    if (wins.empty()) return true;
+    // the reference names of the input's binary header, in its order: what RNAME and RNEXT are printed from
+    std::vector<uint8_t> ref_bytes;
+    std::vector<uint64_t> ref_off(1, 0);
+    for (const std::string &nm : sam.ref_names) {
+        ref_bytes.insert(ref_bytes.end(), nm.begin(), nm.end());
+        ref_off.push_back(ref_bytes.size());
+    }
+    ref_bytes.push_back(0);  // (never empty: a pointer to hand over)
+    const size_t n_win = wins.size();
+    const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
+    uint32_t refused_status = 0;
+    int refused_rc = MK_OK;
+    double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev, [&](size_t id) {
+        mk_codec *codec = nullptr;
+        if (mk_codec_create(handles[id].device, &codec) != MK_OK) bail(std::string("Error during BAM record parsing: ") + mk_last_error());
+        return BamSamWorker{wins, file, &out_sink, ref_bytes, ref_off, pipe, refused_status, refused_rc, !a.filter_matching && !a.invert_match,
+                            handles[id].m, codec};
+    });
+    if (timing) {
+        fprintf(stderr,
+                "[timing] %llu of %llu BAM -> SAM text windows on the device (%llu in flight): upload %.3f, inflate %.3f, record index %.3f, unpack + scan + "
+                "sets %.3f, tag + format %.3f, download %.3f s (of these, growing device buffers: %.3f s)\n",
+                (unsigned long long)pipe.emit_turn, (unsigned long long)n_win, (unsigned long long)n_workers, t_dev[0] / 1e3, t_dev[1] / 1e3, t_dev[2] / 1e3,
+                t_dev[3] / 1e3, t_dev[4] / 1e3, t_dev[5] / 1e3, t_dev[7] / 1e3);
+        if (pipe.refused != ~(size_t)0)
+            fprintf(stderr, "[timing] window %llu left to the host loop (%s)\n", (unsigned long long)pipe.refused,
+                    refused_rc == MK_E_CORRUPT ? "a damaged member"
+                    : refused_status & 1       ? "record chain"
+                    : refused_status & 2       ? "a record the device does not format"
+                    : refused_status & 4       ? "existing tag"
+                                               : "unfinished record");
+    }
+    if (pipe.refused != ~(size_t)0) {
+        sam.seek_bam(wins[pipe.refused].m0, (const char *)pipe.refused_head.data(), pipe.refused_head.size());
+        return false;
+    }
     return true;
 }
 

@@ -941,9 +941,10 @@ int bam_index(mk_matcher *m, WindowSide &W, hipStream_t st, uint64_t *n_rec, uin
     *n_rec = total;
     *n_used = n_pieces ? land[n_pieces - 1] : 0;
     if (total >= 0xFFFFFFF0ull) return fail(MK_E_UNSUPPORTED, "%llu records in one BAM window", (unsigned long long)total);
-    // tables: record offsets | sequence starts | sequence lengths | record lengths | out lengths | existing-tag offsets (u32, n + 2 each) | out offsets (u64) | tiles (u64)
+    // tables: record offsets | sequence starts | sequence lengths | record lengths | out lengths | existing-tag offsets | (BAM -> SAM: where SEQ starts in
+    // the line) (u32, n + 2 each) | out offsets (u64) | tiles (u64)
     const size_t n_tiles = total / ingest_scan_tile() + 2;
-    if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, 6 * (total + 2) * 4 + 16 + (total + 2) * 8 + n_tiles * 8 + 64))) return rc;
+    if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, 7 * (total + 2) * 4 + 16 + (total + 2) * 8 + n_tiles * 8 + 64))) return rc;
     W.d_rec_start = (uint32_t *)T.d_ing_b;
     W.d_seq_start = W.d_rec_start + total + 2;
     W.d_seq_len = W.d_seq_start + total + 2;
@@ -1256,23 +1257,25 @@ struct SamRefsDevice {
     const uint32_t *off = nullptr, *table = nullptr;
     uint32_t mask = 0;
 };
-int upload_refs(mk_matcher *m, const uint8_t *names, const uint64_t *off, uint64_t n_refs, hipStream_t st, SamRefsDevice &D) {
+// (with_table = false: mk_tag_bam_sam_window, which finds a name by its index -- names a table was made for serve it as they are)
+int upload_refs(mk_matcher *m, const char *who, bool with_table, const uint8_t *names, const uint64_t *off, uint64_t n_refs, hipStream_t st, SamRefsDevice &D) {
     if (!n_refs) return MK_OK;
     for (uint64_t i = 1; i <= n_refs; ++i)
-        if (off[i] < off[i - 1]) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: reference name offsets must ascend");
+        if (off[i] < off[i - 1]) return fail(MK_E_INVALID_ARG, "%s: reference name offsets must ascend", who);
     const uint64_t n_bytes = off[n_refs] - off[0];
-    if (n_refs >= (1u << 30) || n_bytes >= 0xFFFFFFF0ull) return fail(MK_E_UNSUPPORTED, "mk_tag_sam_bam_window: %llu reference names", (unsigned long long)n_refs);
+    if (n_refs >= (1u << 30) || n_bytes >= 0xFFFFFFF0ull) return fail(MK_E_UNSUPPORTED, "%s: %llu reference names", who, (unsigned long long)n_refs);
     const uint8_t *base = names + off[0];
-    bool same = m->refs_slots && m->refs_off.size() == n_refs + 1 && m->refs_names.size() == n_bytes && memcmp(m->refs_names.data(), base, n_bytes) == 0;
+    bool same = m->refs_valid && (m->refs_slots || !with_table) && m->refs_off.size() == n_refs + 1 && m->refs_names.size() == n_bytes &&
+                memcmp(m->refs_names.data(), base, n_bytes) == 0;
     for (uint64_t i = 0; same && i <= n_refs; ++i) same = m->refs_off[i] == off[i] - off[0];
     if (!same) {
-        m->refs_slots = 0;  // (until the new ones are up)
-        uint32_t slots = 16;
-        while (slots < 2 * n_refs) slots <<= 1;
+        m->refs_valid = false, m->refs_slots = 0;  // (until the new ones are up)
+        uint32_t slots = with_table ? 16 : 0;
+        while (with_table && slots < 2 * n_refs) slots <<= 1;
         std::vector<uint32_t> h(n_refs + 1 + slots, 0);
         uint32_t *table = h.data() + n_refs + 1;
         for (uint64_t i = 0; i <= n_refs; ++i) h[i] = (uint32_t)(off[i] - off[0]);
-        for (uint64_t i = 0; i < n_refs; ++i) {
+        for (uint64_t i = 0; with_table && i < n_refs; ++i) {
             const uint32_t a = h[i], n = h[i + 1] - h[i];
             for (uint32_t slot = sam_name_hash(base + a, n) & (slots - 1);; slot = (slot + 1) & (slots - 1)) {
                 if (!table[slot]) {
@@ -1293,6 +1296,7 @@ int upload_refs(mk_matcher *m, const uint8_t *names, const uint64_t *off, uint64
         m->refs_off.resize(n_refs + 1);
         for (uint64_t i = 0; i <= n_refs; ++i) m->refs_off[i] = off[i] - off[0];
         m->refs_slots = slots;
+        m->refs_valid = true;
     }
     const uint8_t *d = (const uint8_t *)m->d_refs;
     D.off = (const uint32_t *)d, D.table = D.off + n_refs + 1, D.bytes = d + ((size_t)n_refs + 1 + m->refs_slots) * 4, D.mask = m->refs_slots - 1;
@@ -1497,7 +1501,7 @@ int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, 
     }
     // ---- the records, back to back in text slot 1
     SamRefsDevice F;
-    if ((rc = upload_refs(m, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
+    if ((rc = upload_refs(m, "mk_tag_sam_bam_window", true, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
     mk_matcher::TextSlot &O = m->txt[1];
     if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64))) return rc;
     launch_sam_bam_encode(d_text, R, m->d_flags2, I.d_out_len, I.d_out_off, d_n_cig, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, F.bytes,
@@ -1507,6 +1511,93 @@ int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, 
     w->ms[3] = (float)ms_since(t);
     // ---- BGZF members of the records
     if ((rc = window_deflate(m, codec, W, dl, "mk_tag_sam_bam_window", out_text, bb, w->out, w->out_cap, &w->out_len, &w->ms[4], &w->ms[5], t))) return rc;
+    tag_commit(dl, X, c, counts);
+    return MK_OK;
+    MK_ABI_END
+}
+
+// ---- `tag` BAM -> SAM text with the lines formatted on the device (an addition to ABI v7; kernels: the BAM -> SAM part of bam.hip): the
+// front half is mk_tag_bam_window's, the back half mk_tag_sam_window's; between them a kept record becomes its SAM line.
+int mk_tag_bam_sam_window(mk_matcher *m, mk_codec *codec, mk_bam_sam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
+    if (!m || !codec || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
+    if ((w->n_head && !w->head) || (w->n_members && (!w->bgzf || !w->members)) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
+        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names) || (w->n_refs && (!w->ref_names || !w->ref_off)))
+        return fail(MK_E_INVALID_ARG, "mk_tag_bam_sam_window: a size without its buffer");
+    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_len = w->n_rows = w->n_names_bytes = 0;
+    for (float &x : w->ms) x = 0;
+    *status = 0;
+    MK_ABI_BEGIN
+    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
+    DeviceLoop dl(m);
+    hipStream_t st = dl.st;
+    int rc;
+    auto t = std::chrono::steady_clock::now();
+    AllocMs alloc_ms(&w->ms[7]);
+    // ---- the text: head, then the members inflated behind it
+    WindowSide W;
+    W.T = &m->txt[0];
+    mk_window_source S;
+    memset(&S, 0, sizeof(S));
+    S.head = w->head, S.n_head = w->n_head, S.bgzf = w->bgzf, S.n_bgzf = w->n_bgzf, S.members = w->members, S.n_members = w->n_members;
+    if ((rc = window_assemble(m, codec, S, W, dl))) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
+    w->ms[1] = (float)ms_since(t);  // (upload + inflate: batch_ms splits them)
+    w->ms[0] = m->batch_ms[0];
+    w->ms[1] -= w->ms[0];
+    w->n_window = W.n_window;
+    const uint64_t n_text = W.n_window;
+    if (n_text == 0) return MK_OK;
+    // ---- the record chain
+    uint64_t n = 0, n_used = 0;
+    uint32_t *d_rec_len = nullptr;
+    if ((rc = bam_index(m, W, st, &n, &n_used, &d_rec_len, status))) return rc;
+    if (*status) return MK_OK;
+    if (w->last && n_used != n_text) {  // the file ends inside a record
+        *status = 8;
+        return MK_OK;
+    }
+    w->n_rec = n, w->n_used = n_used, w->n_tail = n_text - n_used;
+    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_sam_window: the text behind the window's records takes %llu bytes", (unsigned long long)w->n_tail);
+    if (w->n_tail && hipMemcpyAsync(w->tail, (const uint8_t *)W.T->d_text + n_used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(MK_E_HIP, "download of the tail failed");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "download of the tail failed");
+    if (w->on_tail) w->on_tail(w->on_tail_ctx, w->tail, w->n_tail);
+    w->ms[2] = (float)ms_since(t);
+    if (n == 0) return MK_OK;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    uint32_t *d_out_len = d_rec_len + n + 2, *d_ex_off = d_out_len + n + 2, *d_seq_at = d_ex_off + n + 2;
+    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_seq_at + n + 2) + 15) & ~(uintptr_t)15);
+    W.d_tile = d_out_off + n + 2;
+    TagWindow X = tag_window(w, "mk_tag_bam_sam_window", n, d_out_len, d_ex_off, d_out_off, nullptr);
+    // ---- sequences -> the scan buffer, scan, emission order, pattern sets
+    if ((rc = tag_scan(m, dl, W, X, kSeqBam, logging))) return rc;
+    w->ms[3] = (float)ms_since(t);
+    // ---- keep, the tag's value, the length of every kept record's line
+    SamRefsDevice F;
+    if ((rc = upload_refs(m, "mk_tag_bam_sam_window", false, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
+    rc = tag_keep(m, dl, W, X, logging, 6u, [&] {
+        launch_bam_taglen(d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
+                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+        launch_bam_sam_len(d_text, W.d_rec_start, d_rec_len, m->d_flags2, n, F.bytes, F.off, (uint32_t)w->n_refs, d_out_len, d_seq_at, W.d_st, st);
+    }, status);
+    const unsigned long long out_text = X.out_text;
+    const bool write = w->out || w->out_cap;
+    if (write) w->out_len = out_text;
+    if (rc || *status) return rc;
+    if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_sam_window: the kept lines take %llu bytes", out_text);
+    if (write && out_text) {
+        mk_matcher::TextSlot &O = m->txt[1];
+        if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
+        launch_bam_sam_emit(d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, d_out_len, d_out_off, d_seq_at, X.d_found_off, X.d_found_pat,
+                            m->d_pat_bytes, m->d_pat_off, d_ex_off, F.bytes, F.off, (uint32_t)w->n_refs, n, w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "line output kernels failed");
+        w->ms[4] = (float)ms_since(t);
+        if (hipMemcpyAsync(w->out, O.d_text, out_text, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "download of the kept lines failed");
+        w->ms[5] = (float)ms_since(t);
+    } else {
+        w->ms[4] = (float)ms_since(t);
+    }
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END

@@ -84,13 +84,15 @@ struct mk_matcher {
     uint32_t bam_piece = 0;  // mk_tag_bam_window: bytes of text per piece of the record-chain index (0 = 64 KiB; mk_matcher_set_bam_piece)
     uint8_t *d_flags2 = nullptr;  // keep flags: what mk_extract_window selects the kept records by, what mk_tag_bam_window tags by
     size_t d_flags2_cap = 0;
-    // mk_tag_sam_bam_window: the reference names on the device (offsets | hash table | bytes) and the host's copy of what they were
-    // made from -- a job's windows all bring the same names, which then go up once per handle
+    // mk_tag_sam_bam_window / mk_tag_bam_sam_window: the reference names on the device (offsets | hash table | bytes; BAM -> SAM looks
+    // names up by index and has no table: refs_slots = 0) and the host's copy of what they were made from (refs_valid) -- a job's
+    // windows all bring the same names, which then go up once per handle
     void *d_refs = nullptr;
     size_t d_refs_cap = 0;
     std::vector<uint8_t> refs_names;
     std::vector<uint64_t> refs_off;
     uint32_t refs_slots = 0;
+    bool refs_valid = false;
     // mk_upload_text_ahead: text windows copied on a stream of their own while the current window is processed.  Four
     // slots (two windows of two inputs), so that an upload that arrives before the previous one was consumed cannot overwrite it; the slot
     // states are guarded by ahead_mu (the uploader may be another host thread than the one inside the extract call).

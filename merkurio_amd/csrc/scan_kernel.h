@@ -175,6 +175,15 @@ void launch_bam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uin
                      const uint32_t *d_ex_off, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 void launch_bam_names(const uint8_t *d_text, const uint32_t *d_rec_off, const uint8_t *d_flags, uint64_t n_rec, uint32_t *d_name_start, uint32_t *d_name_len,
                       hipStream_t st);
+// BAM record -> SAM line (mk_tag_bam_sam_window): behind launch_bam_taglen, d_out_len of a kept record becomes the length of its line with
+// the tag and d_seq_at where SEQ starts in it (d_st |= 2: not formatted on the device); then the lines at d_out + d_out_off.  Reference
+// name i = d_ref_bytes[d_ref_off[i], d_ref_off[i + 1]) (n_refs = 0: neither is read)
+void launch_bam_sam_len(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint8_t *d_keep, uint64_t n_rec,
+                        const uint8_t *d_ref_bytes, const uint32_t *d_ref_off, uint32_t n_refs, uint32_t *d_out_len, uint32_t *d_seq_at, uint32_t *d_st, hipStream_t st);
+void launch_bam_sam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const uint32_t *d_rec_len, const uint32_t *d_seq_start, const uint32_t *d_seq_len,
+                         const uint32_t *d_out_len, const unsigned long long *d_out_off, const uint32_t *d_seq_at, const unsigned long long *d_found_off,
+                         const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off, const uint32_t *d_ex_off, const uint8_t *d_ref_bytes,
+                         const uint32_t *d_ref_off, uint32_t n_refs, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 // ---- sam.hip: a window of SAM text whose line table exists (launch_ingest_count + launch_ingest_lines) -> record tables, the
 // sequences as the matcher sees them, the kept lines with their tag appended (host_loops.cpp: mk_tag_sam_window)
 struct SamTables {  // one entry per line (or, compacted, per record)

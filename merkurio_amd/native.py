@@ -55,7 +55,7 @@ EXPORTS = [
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
     "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_extract_fastq_bgzf", "mk_extract_window",
-    "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window",
+    "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
 
@@ -137,6 +137,18 @@ class SamBamWindow(C.Structure):
                 ("rows", C.c_void_p), ("rows_cap", C.c_uint64), ("row_name", C.c_void_p), ("names", C.c_void_p), ("names_cap", C.c_uint64),
                 ("n_window", C.c_uint64), ("n_used", C.c_uint64), ("n_tail", C.c_uint64), ("n_rec", C.c_uint64), ("n_kept", C.c_uint64),
                 ("out_text_bytes", C.c_uint64), ("out_len", C.c_uint64), ("n_rows", C.c_uint64), ("n_names_bytes", C.c_uint64), ("ms", C.c_float * 8)]
+
+
+class BamSamWindow(C.Structure):
+    """mk_bam_sam_window (include/merkurio_hip.h, v7): a window of a BAM file handed to mk_tag_bam_sam_window"""
+    _fields_ = [("head", C.c_void_p), ("n_head", C.c_uint64), ("bgzf", C.c_void_p), ("n_bgzf", C.c_uint64), ("members", C.c_void_p), ("n_members", C.c_uint64),
+                ("last", C.c_uint32), ("filter_matching", C.c_uint32), ("invert", C.c_uint32), ("tag", C.c_uint8 * 2), ("reserved", C.c_uint8 * 2),
+                ("ref_names", C.c_void_p), ("ref_off", C.c_void_p), ("n_refs", C.c_uint64),
+                ("tail", C.c_void_p), ("tail_cap", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_uint64),
+                ("rows", C.c_void_p), ("rows_cap", C.c_uint64), ("row_name", C.c_void_p), ("names", C.c_void_p), ("names_cap", C.c_uint64),
+                ("on_tail", C.c_void_p), ("on_tail_ctx", C.c_void_p),
+                ("n_window", C.c_uint64), ("n_used", C.c_uint64), ("n_tail", C.c_uint64), ("n_rec", C.c_uint64), ("n_kept", C.c_uint64),
+                ("out_len", C.c_uint64), ("n_rows", C.c_uint64), ("n_names_bytes", C.c_uint64), ("ms", C.c_float * 8)]
 
 
 class Counters(C.Structure):
@@ -277,6 +289,7 @@ def load(build_if_missing=True):
     L.mk_matcher_set_bam_piece.argtypes = [C.c_void_p, C.c_uint32]
     L.mk_tag_sam_window.argtypes = [C.c_void_p, C.POINTER(SamWindow), C.c_int, C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_tag_sam_bam_window.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SamBamWindow), C.c_int, C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mk_tag_bam_sam_window.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BamSamWindow), C.c_int, C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_extract_paired.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(Counters), C.c_void_p]
@@ -891,6 +904,65 @@ class Matcher:
         return dict(status=status.value, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
                     out=out[:w.out_len].tobytes() if write else b"", out_text_bytes=w.out_text_bytes, rows=out_rows, counters=c2.as_dict(k2),
                     ms=list(w.ms))
+
+    def tag_bam_sam_window(self, codec, head: bytes, blob: bytes, members, last, refs=(), tag=b"km", logging=True, filter_matching=False, invert=False,
+                           write=True, piece_bytes=0, out_cap=None, guard=0):
+        """mk_tag_bam_sam_window: head + the text of `members` (entries of bgzf_members(blob), out_off re-based to 0) as BAM records, `refs`
+        = the reference names (bytes) in header order -> dict(status, rc, n_window, n_used, n_rec, n_kept, tail, out (the kept records as SAM
+        lines with their tag field appended), out_len, rows [(name, rec, pat, pos)], counters, ms).  out_cap: the output buffer is exactly
+        that large and a call that asks for more is NOT repeated (rc = MK_E_CAPACITY is returned); `guard` bytes of 0xA5 lie behind it and
+        come back as `guard`."""
+        mem = members.copy()
+        if len(mem):
+            mem["out_off"] -= mem["out_off"][0]
+        hb, bb = np.frombuffer(head, dtype=np.uint8), np.frombuffer(blob, dtype=np.uint8)
+        n_text = len(head) + (int(mem["isize"].sum()) if len(mem) else 0)
+        ref_bytes = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8)
+        ref_off = np.zeros(len(refs) + 1, dtype=np.uint64)
+        ref_off[1:] = np.cumsum([len(r) for r in refs], dtype=np.uint64)
+        _check(load().mk_matcher_set_bam_piece(self._h, piece_bytes))
+        w = BamSamWindow()
+        w.head, w.n_head, w.bgzf, w.n_bgzf = (hb.ctypes.data if len(hb) else None), len(hb), (bb.ctypes.data if len(bb) else None), len(bb)
+        w.members, w.n_members = (mem.ctypes.data if len(mem) else None), len(mem)
+        w.last, w.filter_matching, w.invert = int(bool(last)), int(bool(filter_matching)), int(bool(invert))
+        w.tag[0], w.tag[1] = tag[0], tag[1]
+        w.ref_names, w.ref_off, w.n_refs = ref_bytes.ctypes.data, ref_off.ctypes.data, len(refs)
+        tail = np.zeros(max(64, n_text), dtype=np.uint8)
+        w.tail, w.tail_cap = tail.ctypes.data, tail.size
+        fixed = out_cap is not None
+        cap = out_cap if fixed else 1 << 16
+        out = np.full(max(1, cap + guard), 0xA5, dtype=np.uint8)
+        rows = np.zeros(4096, dtype=ROW_DTYPE)
+        row_name = np.zeros(4096, dtype=np.uint64)
+        names = np.zeros(1 << 16, dtype=np.uint8)
+        status = C.c_uint32()
+        while True:
+            if write:
+                w.out, w.out_cap = out.ctypes.data, cap
+            w.rows, w.rows_cap, w.row_name, w.names, w.names_cap = rows.ctypes.data, len(rows), row_name.ctypes.data, names.ctypes.data, names.size
+            c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
+            rc = load().mk_tag_bam_sam_window(self._h, codec._h, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
+            if rc == MK_E_CAPACITY and (w.n_rows > len(rows) or w.n_names_bytes > names.size or (w.out_len > cap and not fixed)):
+                if w.n_rows > len(rows):
+                    rows, row_name = np.zeros(w.n_rows, dtype=ROW_DTYPE), np.zeros(w.n_rows, dtype=np.uint64)
+                if w.n_names_bytes > names.size:
+                    names = np.zeros(w.n_names_bytes, dtype=np.uint8)
+                if w.out_len > cap and not fixed:
+                    cap = w.out_len
+                    out = np.full(cap + guard, 0xA5, dtype=np.uint8)
+                continue
+            if not (fixed and rc == MK_E_CAPACITY):
+                _check(rc)
+            break
+        nb = names[:w.n_names_bytes].tobytes()
+        out_rows = []
+        if logging and status.value == 0 and rc == MK_OK:
+            for k in range(w.n_rows):
+                a = int(row_name[k])
+                out_rows.append((nb[a:nb.index(b"\0", a)], int(rows[k]["rec"]), int(rows[k]["pat"]), int(rows[k]["pos"])))
+        return dict(status=status.value, rc=rc, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
+                    out=out[:min(w.out_len, cap)].tobytes() if write and rc == MK_OK else b"", out_len=w.out_len, guard=out[cap:cap + guard].tobytes(),
+                    rows=out_rows, counters=c2.as_dict(k2), ms=list(w.ms))
 
     def tag_value(self, found, existing=None) -> bytes:
         arr = np.asarray(list(found) + [0], dtype=np.uint32)

@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """End-to-end wall time of `merkurio tag` on synthetic SAM / BAM (host codec + PCIe + scan + write).
-usage: tools/e2e_tag.py [n_records] [n_patterns] [one record in N carries a k-mer, default 100]"""
-import os, subprocess, sys, time
+usage: tools/e2e_tag.py [n_records] [n_patterns] [one record in N carries a k-mer, default 100] [--bam-sam REPS]
+--bam-sam REPS: only the BAM -> SAM shapes (everything kept, -m, -m -j), each REPS times on the window path and with --host-ingest in
+turn; medians with ranges, and the window path's own [timing] row of each shape's last run (profiles/e2e_tag_bam_sam_window.txt)"""
+import os, statistics, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+bam_sam_reps = 0
+if "--bam-sam" in sys.argv:
+    k = sys.argv.index("--bam-sam")
+    bam_sam_reps = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
 npat = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000
 every = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -36,6 +43,24 @@ binp = os.environ.get("MERKURIO_BIN") or os.path.join(ROOT, "merkurio_amd", "lib
 bam0, out = os.path.join(tmp, "e2e_in.bam"), os.path.join(tmp, "e2e_out")
 # (the input BAM of the BAM rows is written with another tag name: records that already carry `km` take the reference's merge rule,
 # which lives on the host path -- r05: BAM -> BAM keeps the records on the device, --host-ingest is the r04 path)
+if bam_sam_reps:
+    subprocess.run([binp, "tag", "-f", km, "-i", sam, "-o", bam0, "-t", "zz"], check=True)
+    os.remove(sam)
+    wmb = os.environ.get("E2E_WINDOW_MB")
+    for label, extra in (("BAM -> SAM, everything kept", []), ("BAM -> SAM, -m", ["-m"]), ("BAM -> SAM, -m -j", ["-m", "-j", out + ".json"])):
+        times, row = {"window": [], "--host-ingest": []}, b""
+        for rep in range(bam_sam_reps):
+            for path, flags in (("window", ["--window-mb", wmb] if wmb else []), ("--host-ingest", ["--host-ingest"])):
+                t0 = time.time()
+                p = subprocess.run([binp, "tag", "-f", km, "-i", bam0, "-o", out + "2.sam", *extra, *flags], check=True, stderr=subprocess.PIPE,
+                                   env=dict(os.environ, MERKURIO_TIMING="1"))
+                times[path].append(time.time() - t0)
+                if path == "window":
+                    row = b"\n".join(ln for ln in p.stderr.split(b"\n") if b"BAM -> SAM text windows" in ln or b"left to the host" in ln)
+        for path, ts in times.items():
+            print(f"{label}, {path}: median {statistics.median(ts):.2f} s [{min(ts):.2f}-{max(ts):.2f}] of {len(ts)}, output {os.path.getsize(out + '2.sam') / 1e6:.0f} MB", flush=True)
+        print("  " + row.decode(), flush=True)
+    sys.exit(0)
 for label, args in (("SAM -> SAM", ["-i", sam, "-o", out + ".sam"]), ("SAM -> BAM", ["-i", sam, "-o", bam0, "-t", "zz"]),
                     ("BAM -> BAM, -m", ["-i", bam0, "-o", out + ".bam", "-m"]), ("BAM -> BAM, -m, --host-ingest", ["-i", bam0, "-o", out + "h.bam", "-m", "--host-ingest"]),
                     ("BAM -> BAM", ["-i", bam0, "-o", out + "3.bam"]), ("BAM -> BAM, --host-ingest", ["-i", bam0, "-o", out + "3h.bam", "--host-ingest"]),
