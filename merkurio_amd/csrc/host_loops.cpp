@@ -987,9 +987,10 @@ double ms_since(std::chrono::steady_clock::time_point &t) {
     return ms;
 }
 
-// ---- `tag` on a window that stays on the device: what mk_tag_bam_window and mk_tag_sam_window share.  Each entry point makes its
-// record table (window_assemble, then bam_index / the line table and mk_sam_fields_kernel) and sends the kept records off in its own way
-// (BGZF members / text); in between, both go through tag_scan, tag_keep and tag_commit.
+// ---- `tag` on a window that stays on the device: what the four mk_tag_*_window share.  An entry point is one of two input sides, which
+// make the record table (bam_front: BGZF members behind a head, the record chain / sam_index: SAM text, the line table and
+// mk_sam_fields_kernel), then tag_scan and tag_keep, then one of two output sides, which send the kept records off (members_back: BGZF
+// members / text_back: text), then tag_commit.
 // ms[7] of such a call: the time spent growing device buffers inside it (part of the phases, reported on its own)
 struct AllocMs {
     float *out;
@@ -1116,7 +1117,29 @@ void tag_commit(DeviceLoop &dl, const TagWindow &X, mk_counters *c, uint32_t *co
     dl.finish();
 }
 
+// What every mk_tag_*_window starts with.  tag_args: the checks all four make (handles = the handles the entry point takes are there);
+// the entry point's own checks follow it.  TAG_WINDOW_BEGIN, behind those: nothing reported yet, the device, and the call's dl, st, rc,
+// t (the phase clock) and ms[7].
+template <class Win>
+int tag_args(const char *who, bool handles, const Win *w, const mk_counters *c, const uint32_t *counts, const uint32_t *status, int logging) {
+    if (!handles || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
+    if ((w->n_head && !w->head) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) || (logging && w->rows_cap && (!w->rows || !w->row_name)) ||
+        (w->names_cap && !w->names))
+        return fail(MK_E_INVALID_ARG, "%s: a size without its buffer", who);
+    return MK_OK;
+}
+#define TAG_WINDOW_BEGIN                                                                                        \
+    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_len = w->n_rows = w->n_names_bytes = 0; \
+    for (float &x : w->ms) x = 0;                                                                               \
+    *status = 0;                                                                                                \
+    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");                    \
+    DeviceLoop dl(m);                                                                                           \
+    hipStream_t st = dl.st;                                                                                     \
+    int rc;                                                                                                     \
+    auto t = std::chrono::steady_clock::now();                                                                  \
+    AllocMs alloc_ms(&w->ms[7]);
 
+// ---- the two output sides
 // the window's tagged records, back to back in text slot 1 (out_text bytes, kPad zero bytes behind them), deflated into BGZF members of
 // bb bytes of text and downloaded: the last step of mk_tag_bam_window and mk_tag_sam_bam_window (the codec's buffers; its kernels on
 // this stream).  *out_len = the members' bytes (more than out_cap: MK_E_CAPACITY); ms_deflate / ms_download: the two phases.
@@ -1159,7 +1182,56 @@ int window_deflate(mk_matcher *m, mk_codec *codec, const WindowSide &W, DeviceLo
     return MK_OK;
 }
 
-// ---- a window of SAM text -> its record tables: what mk_tag_sam_window and mk_tag_sam_bam_window start with
+// The members output: what mk_tag_bam_window and mk_tag_sam_bam_window end with.  rc = tag_keep's; `emit` writes the kept records back to
+// back to where it is told (the format's kernels, as `taglen`; `emit_failed` words their failure).  ms[0..2]: emit, deflate, download;
+// a window that writes nothing (no output buffer: the checks have run / nothing is kept) stamps ms[0] where stamp_idle says so.
+template <class Win>
+int members_back(mk_matcher *m, mk_codec *codec, Win *w, const WindowSide &W, const TagWindow &X, DeviceLoop &dl, int rc, const uint32_t *status, uint32_t bb,
+                 float *ms, bool stamp_idle, const char *emit_failed, const std::function<int(uint8_t *)> &emit, std::chrono::steady_clock::time_point &t) {
+    hipStream_t st = dl.st;
+    const unsigned long long out_text = X.out_text;
+    w->out_text_bytes = out_text;
+    if (rc || *status) return rc;
+    if ((!w->out && !w->out_cap) || out_text == 0) {
+        if (stamp_idle) ms[0] = (float)ms_since(t);
+        return MK_OK;
+    }
+    mk_matcher::TextSlot &O = m->txt[1];
+    if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64)) || (rc = emit((uint8_t *)O.d_text))) return rc;
+    if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "%s", emit_failed);
+    ms[0] = (float)ms_since(t);
+    return window_deflate(m, codec, W, dl, X.who, out_text, bb, w->out, w->out_cap, &w->out_len, &ms[1], &ms[2], t);
+}
+
+// The text output: what mk_tag_sam_window and mk_tag_bam_sam_window end with.  rc = tag_keep's; out_len is reported whatever became of the
+// window; `emit` writes the kept lines back to back to where it is told.  ms[0..1]: emit, download.
+template <class Win>
+int text_back(mk_matcher *m, Win *w, const TagWindow &X, DeviceLoop &dl, int rc, const uint32_t *status, float *ms, const char *emit_failed,
+              const std::function<void(uint8_t *)> &emit, std::chrono::steady_clock::time_point &t) {
+    hipStream_t st = dl.st;
+    const unsigned long long out_text = X.out_text;
+    const bool write = w->out || w->out_cap;
+    if (write) w->out_len = out_text;
+    if (rc || *status) return rc;
+    if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "%s: the kept lines take %llu bytes", X.who, out_text);
+    if (write && out_text) {
+        mk_matcher::TextSlot &O = m->txt[1];
+        if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
+        emit((uint8_t *)O.d_text);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "%s", emit_failed);
+        ms[0] = (float)ms_since(t);
+        if (hipMemcpyAsync(w->out, O.d_text, out_text, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "download of the kept lines failed");
+        ms[1] = (float)ms_since(t);
+    } else {
+        ms[0] = (float)ms_since(t);
+    }
+    return MK_OK;
+}
+
+// ---- the two input sides
+// a window of SAM text -> its record tables: what mk_tag_sam_window and mk_tag_sam_bam_window start with
 struct SamIndex {
     uint64_t n = 0;  // records
     SamTables R{};
@@ -1248,6 +1320,51 @@ int sam_index(mk_matcher *m, Win *w, const char *who, uint32_t extra, DeviceLoop
     return MK_OK;
 }
 
+// a window of BGZF members -> its record table: what mk_tag_bam_window and mk_tag_bam_sam_window start with
+struct BamIndex {
+    uint64_t n = 0;  // records
+    uint32_t *d_rec_len = nullptr, *d_out_len = nullptr, *d_ex_off = nullptr, *d_extra = nullptr;  // one entry per record each (d_extra: `extra` of them)
+    unsigned long long *d_out_off = nullptr;
+};
+// head, then the members inflated behind it (window_assemble: upload, inflate, CRC-32 / ISIZE of every member; ms[0], ms[1]), the record
+// chain, n_window / n_rec / n_used, the tail and on_tail (ms[2]); *status = 1: bam_index's, 8: the file ends inside a record
+template <class Win>
+int bam_front(mk_matcher *m, mk_codec *codec, Win *w, const char *who, uint32_t extra, DeviceLoop &dl, WindowSide &W, BamIndex &I, uint32_t *status,
+              std::chrono::steady_clock::time_point &t) {
+    hipStream_t st = dl.st;
+    int rc;
+    W.T = &m->txt[0];
+    mk_window_source S;
+    memset(&S, 0, sizeof(S));
+    S.head = w->head, S.n_head = w->n_head, S.bgzf = w->bgzf, S.n_bgzf = w->n_bgzf, S.members = w->members, S.n_members = w->n_members;
+    if ((rc = window_assemble(m, codec, S, W, dl))) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
+    w->ms[1] = (float)ms_since(t);  // (upload + inflate: batch_ms splits them)
+    w->ms[0] = m->batch_ms[0];
+    w->ms[1] -= w->ms[0];
+    w->n_window = W.n_window;
+    const uint64_t n_text = W.n_window;
+    if (n_text == 0) return MK_OK;  // (I.n == 0)
+    uint64_t n = 0, n_used = 0;
+    if ((rc = bam_index(m, W, st, &n, &n_used, &I.d_rec_len, status)) || *status) return rc;
+    if (w->last && n_used != n_text) {  // the file ends inside a record
+        *status = 8;
+        return MK_OK;
+    }
+    w->n_rec = n, w->n_used = n_used, w->n_tail = n_text - n_used;
+    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "%s: the text behind the window's records takes %llu bytes", who, (unsigned long long)w->n_tail);
+    if (w->n_tail && hipMemcpyAsync(w->tail, (const uint8_t *)W.T->d_text + n_used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(MK_E_HIP, "download of the tail failed");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "download of the tail failed");
+    if (w->on_tail) w->on_tail(w->on_tail_ctx, w->tail, w->n_tail);
+    w->ms[2] = (float)ms_since(t);
+    // behind the record lengths (bam_index has made the room): out lengths | existing-tag offsets | `extra` more arrays (u32) | offsets (u64) | tiles (u64)
+    I.n = n, I.d_out_len = I.d_rec_len + n + 2, I.d_ex_off = I.d_out_len + n + 2, I.d_extra = I.d_ex_off + n + 2;
+    I.d_out_off = (unsigned long long *)(((uintptr_t)(I.d_ex_off + (1 + extra) * (n + 2)) + 15) & ~(uintptr_t)15);
+    W.d_tile = I.d_out_off + n + 2;
+    return MK_OK;
+}
+
 // The reference names of a SAM -> BAM window on the device: offsets (u32) | table | bytes.  The host builds an open-addressing table of
 // them -- a few thousand names in most files, 10^5 in some assemblies -- with the first of equal names in it (BamWriter::encode_record's
 // ref_id takes the first), so the kernel never walks the list.  A job's windows all bring the same names: the handle keeps a copy of
@@ -1313,81 +1430,35 @@ int mk_matcher_set_bam_piece(mk_matcher *m, uint32_t piece_bytes) {
 }
 
 int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
-    if (!m || !codec || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
-    if ((w->n_head && !w->head) || (w->n_members && (!w->bgzf || !w->members)) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
-        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names))
-        return fail(MK_E_INVALID_ARG, "mk_tag_bam_window: a size without its buffer");
+    static const char who[] = "mk_tag_bam_window";
+    if (int bad = tag_args(who, m && codec, w, c, counts, status, logging)) return bad;
+    if (w->n_members && (!w->bgzf || !w->members)) return fail(MK_E_INVALID_ARG, "mk_tag_bam_window: a size without its buffer");
     const uint32_t bb = w->block_bytes ? w->block_bytes : mkz::kMaxBlockBytes;
     if (bb > mkz::kMaxBlockBytes) return fail(MK_E_INVALID_ARG, "mk_tag_bam_window: block_bytes %u > %u", bb, mkz::kMaxBlockBytes);
-    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_text_bytes = w->out_len = w->n_rows = w->n_names_bytes = 0;
-    for (float &x : w->ms) x = 0;
-    *status = 0;
+    w->out_text_bytes = 0;
     MK_ABI_BEGIN
-    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
-    DeviceLoop dl(m);
-    hipStream_t st = dl.st;
-    int rc;
-    auto t = std::chrono::steady_clock::now();
-    AllocMs alloc_ms(&w->ms[7]);
-    // ---- the text: head, then the members inflated behind it (window_assemble: upload, inflate, CRC-32 / ISIZE of every member)
+    TAG_WINDOW_BEGIN
     WindowSide W;
-    W.T = &m->txt[0];
-    mk_window_source S;
-    memset(&S, 0, sizeof(S));
-    S.head = w->head, S.n_head = w->n_head, S.bgzf = w->bgzf, S.n_bgzf = w->n_bgzf, S.members = w->members, S.n_members = w->n_members;
-    if ((rc = window_assemble(m, codec, S, W, dl))) return rc;
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
-    w->ms[1] = (float)ms_since(t);  // (upload + inflate: batch_ms splits them)
-    w->ms[0] = m->batch_ms[0];
-    w->ms[1] -= w->ms[0];
-    w->n_window = W.n_window;
-    const uint64_t n_text = W.n_window;
-    if (n_text == 0) return MK_OK;
-    // ---- the record chain
-    uint64_t n = 0, n_used = 0;
-    uint32_t *d_rec_len = nullptr;
-    if ((rc = bam_index(m, W, st, &n, &n_used, &d_rec_len, status))) return rc;
-    if (*status) return MK_OK;
-    if (w->last && n_used != n_text) {  // the file ends inside a record
-        *status = 8;
-        return MK_OK;
-    }
-    w->n_rec = n, w->n_used = n_used, w->n_tail = n_text - n_used;
-    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_window: the text behind the window's records takes %llu bytes", (unsigned long long)w->n_tail);
-    if (w->n_tail && hipMemcpyAsync(w->tail, (const uint8_t *)W.T->d_text + n_used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess)
-        return fail(MK_E_HIP, "download of the tail failed");
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "download of the tail failed");
-    if (w->on_tail) w->on_tail(w->on_tail_ctx, w->tail, w->n_tail);
-    w->ms[2] = (float)ms_since(t);
-    if (n == 0) return MK_OK;
-    uint32_t *d_out_len = d_rec_len + n + 2, *d_ex_off = d_out_len + n + 2;
-    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_ex_off + n + 2) + 15) & ~(uintptr_t)15);
-    W.d_tile = d_out_off + n + 2;
-    TagWindow X = tag_window(w, "mk_tag_bam_window", n, d_out_len, d_ex_off, d_out_off, nullptr);
+    BamIndex I;
+    if ((rc = bam_front(m, codec, w, who, 0, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    const uint64_t n = I.n;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    TagWindow X = tag_window(w, who, n, I.d_out_len, I.d_ex_off, I.d_out_off, nullptr);
     // ---- sequences -> the scan buffer, scan, emission order, pattern sets
     if ((rc = tag_scan(m, dl, W, X, kSeqBam, logging))) return rc;
     w->ms[3] = (float)ms_since(t);
     // ---- keep, tag, pack
     rc = tag_keep(m, dl, W, X, logging, 6u, [&] {
-        launch_bam_taglen((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
-                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+        launch_bam_taglen(d_text, W.d_rec_start, I.d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
+                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, I.d_out_len, I.d_ex_off, W.d_st, st);
     }, status);
-    const unsigned long long out_text = X.out_text;
-    w->out_text_bytes = out_text;
-    if (rc || *status) return rc;
-    if ((!w->out && !w->out_cap) || out_text == 0) {  // tag -s (the checks have run, nothing is written) / nothing is kept
-        tag_commit(dl, X, c, counts);
+    // ---- the records with their tags, then their BGZF members (tag -s, or nothing kept: neither)
+    rc = members_back(m, codec, w, W, X, dl, rc, status, bb, &w->ms[4], false, "record output kernel failed", [&](uint8_t *d_out) {
+        launch_bam_emit(d_text, W.d_rec_start, I.d_rec_len, I.d_out_len, I.d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, n,
+                        w->tag[0], w->tag[1], d_out, st);
         return MK_OK;
-    }
-    mk_matcher::TextSlot &O = m->txt[1];
-    if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64))) return rc;
-    launch_bam_emit((const uint8_t *)W.T->d_text, W.d_rec_start, d_rec_len, d_out_len, d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n,
-                    w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
-    if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "record output kernel failed");
-    w->ms[4] = (float)ms_since(t);
-    // ---- BGZF members of the output text
-    if ((rc = window_deflate(m, codec, W, dl, "mk_tag_bam_window", out_text, bb, w->out, w->out_cap, &w->out_len, &w->ms[5], &w->ms[6], t))) return rc;
+    }, t);
+    if (rc || *status) return rc;
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
@@ -1396,92 +1467,60 @@ int mk_tag_bam_window(mk_matcher *m, mk_codec *codec, mk_bam_window *w, int logg
 // ---- `tag` on a window of SAM text that stays on the device (an addition to ABI v7; kernels: sam.hip).  Lines can be cut by the host
 // without reading them, so a caller's windows need no tail chain: the tail exists for callers that cut anywhere.
 int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
-    if (!m || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
-    if ((w->n_head && !w->head) || (w->n_text && !w->text) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
-        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names))
-        return fail(MK_E_INVALID_ARG, "mk_tag_sam_window: a size without its buffer");
+    static const char who[] = "mk_tag_sam_window";
+    if (int bad = tag_args(who, m != nullptr, w, c, counts, status, logging)) return bad;
+    if (w->n_text && !w->text) return fail(MK_E_INVALID_ARG, "mk_tag_sam_window: a size without its buffer");
     if (w->tag[0] == '\t' || w->tag[1] == '\t' || w->tag[0] == '\n' || w->tag[1] == '\n')
         return fail(MK_E_INVALID_ARG, "mk_tag_sam_window: a tag name holds a tab or a line end");
-    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_len = w->n_rows = w->n_names_bytes = 0;
-    for (float &x : w->ms) x = 0;
-    *status = 0;
     MK_ABI_BEGIN
-    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
-    DeviceLoop dl(m);
-    hipStream_t st = dl.st;
-    int rc;
-    auto t = std::chrono::steady_clock::now();
-    AllocMs alloc_ms(&w->ms[7]);
+    TAG_WINDOW_BEGIN
     WindowSide W;
     SamIndex I;
-    if ((rc = sam_index(m, w, "mk_tag_sam_window", 0, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    if ((rc = sam_index(m, w, who, 0, dl, W, I, status, t)) || *status || I.n == 0) return rc;
     const uint64_t n = I.n;
     const SamTables &R = I.R;
     const uint8_t *d_text = (const uint8_t *)W.T->d_text;
-    uint32_t *d_out_len = I.d_out_len, *d_ex_off = I.d_ex_off;
-    unsigned long long *d_out_off = I.d_out_off;
-    TagWindow X = tag_window(w, "mk_tag_sam_window", n, d_out_len, d_ex_off, d_out_off, R.name_len);
+    TagWindow X = tag_window(w, who, n, I.d_out_len, I.d_ex_off, I.d_out_off, R.name_len);
     // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets
     if ((rc = tag_scan(m, dl, W, X, kSeqSam, logging))) return rc;
     w->ms[2] = (float)ms_since(t);
     // ---- keep, tag, emit
     rc = tag_keep(m, dl, W, X, logging, 4u, [&] {
         launch_sam_taglen(d_text, R, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n, w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1],
-                          m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
+                          m->d_flags2, I.d_out_len, I.d_ex_off, W.d_st, st);
     }, status);
-    const unsigned long long out_text = X.out_text;
-    const bool write = w->out || w->out_cap;
-    if (write) w->out_len = out_text;
+    rc = text_back(m, w, X, dl, rc, status, &w->ms[3], "line output kernel failed", [&](uint8_t *d_out) {
+        launch_sam_emit(d_text, R, I.d_out_len, I.d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, n, w->tag[0], w->tag[1], d_out, st);
+    }, t);
     if (rc || *status) return rc;
-    if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_sam_window: the kept lines take %llu bytes", out_text);
-    if (write && out_text) {
-        mk_matcher::TextSlot &O = m->txt[1];
-        if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
-        launch_sam_emit(d_text, R, d_out_len, d_out_off, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, d_ex_off, n, w->tag[0], w->tag[1],
-                        (uint8_t *)O.d_text, st);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "line output kernel failed");
-        w->ms[3] = (float)ms_since(t);
-        if (hipMemcpyAsync(w->out, O.d_text, out_text, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "download of the kept lines failed");
-        w->ms[4] = (float)ms_since(t);
-    } else {
-        w->ms[3] = (float)ms_since(t);
-    }
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
 }
 
 // ---- `tag` SAM text -> BAM with the records encoded on the device (an addition to ABI v7; kernels: the second half of sam.hip): the
-// front half is mk_tag_sam_window's, the back half mk_tag_bam_window's; between them a kept line becomes a BAM record.
+// line input and the members output; between them a kept line becomes a BAM record.
 int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
-    if (!m || !codec || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
-    if ((w->n_head && !w->head) || (w->n_text && !w->text) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
-        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names) || (w->n_refs && (!w->ref_names || !w->ref_off)))
+    static const char who[] = "mk_tag_sam_bam_window";
+    if (int bad = tag_args(who, m && codec, w, c, counts, status, logging)) return bad;
+    if ((w->n_text && !w->text) || (w->n_refs && (!w->ref_names || !w->ref_off)))
         return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: a size without its buffer");
     if (w->tag[0] == '\t' || w->tag[1] == '\t' || w->tag[0] == '\n' || w->tag[1] == '\n')
         return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: a tag name holds a tab or a line end");
     const uint32_t bb = w->block_bytes ? w->block_bytes : mkz::kMaxBlockBytes;
     if (bb > mkz::kMaxBlockBytes) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: block_bytes %u > %u", bb, mkz::kMaxBlockBytes);
     if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "mk_tag_sam_bam_window: the codec and the matcher are on different devices");
-    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_text_bytes = w->out_len = w->n_rows = w->n_names_bytes = 0;
-    for (float &x : w->ms) x = 0;
-    *status = 0;
+    w->out_text_bytes = 0;
     MK_ABI_BEGIN
-    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
-    DeviceLoop dl(m);
-    hipStream_t st = dl.st;
-    int rc;
-    auto t = std::chrono::steady_clock::now();
-    AllocMs alloc_ms(&w->ms[7]);
+    TAG_WINDOW_BEGIN
     WindowSide W;
     SamIndex I;
-    if ((rc = sam_index(m, w, "mk_tag_sam_bam_window", 1, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    if ((rc = sam_index(m, w, who, 1, dl, W, I, status, t)) || *status || I.n == 0) return rc;
     const uint64_t n = I.n;
     const SamTables &R = I.R;
     const uint8_t *d_text = (const uint8_t *)W.T->d_text;
     uint32_t *d_n_cig = I.d_extra;
-    TagWindow X = tag_window(w, "mk_tag_sam_bam_window", n, I.d_out_len, I.d_ex_off, I.d_out_off, R.name_len);
+    TagWindow X = tag_window(w, who, n, I.d_out_len, I.d_ex_off, I.d_out_off, R.name_len);
     // ---- SEQ fields -> the scan buffer, scan, emission order, pattern sets
     if ((rc = tag_scan(m, dl, W, X, kSeqSam, logging))) return rc;
     w->ms[2] = (float)ms_since(t);
@@ -1491,113 +1530,52 @@ int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, 
                           m->d_flags2, I.d_out_len, I.d_ex_off, W.d_st, st);
         launch_sam_bam_len(d_text, R, m->d_flags2, n, I.d_out_len, d_n_cig, W.d_st, st);
     }, status);
-    const unsigned long long out_text = X.out_text;
-    w->out_text_bytes = out_text;
-    if (rc || *status) return rc;
-    if ((!w->out && !w->out_cap) || out_text == 0) {  // nothing is written (the checks have run) / nothing is kept
-        w->ms[3] = (float)ms_since(t);
-        tag_commit(dl, X, c, counts);
+    // ---- the records (the reference names go up with the first window that writes any), then their BGZF members
+    rc = members_back(m, codec, w, W, X, dl, rc, status, bb, &w->ms[3], true, "record output kernels failed", [&](uint8_t *d_out) {
+        SamRefsDevice F;
+        if (int rc_refs = upload_refs(m, who, true, w->ref_names, w->ref_off, w->n_refs, st, F)) return rc_refs;
+        launch_sam_bam_encode(d_text, R, m->d_flags2, I.d_out_len, I.d_out_off, d_n_cig, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, F.bytes,
+                              F.off, F.table, F.mask, n, w->tag[0], w->tag[1], d_out, st);
         return MK_OK;
-    }
-    // ---- the records, back to back in text slot 1
-    SamRefsDevice F;
-    if ((rc = upload_refs(m, "mk_tag_sam_bam_window", true, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
-    mk_matcher::TextSlot &O = m->txt[1];
-    if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + mkz::kPad + 64))) return rc;
-    launch_sam_bam_encode(d_text, R, m->d_flags2, I.d_out_len, I.d_out_off, d_n_cig, X.d_found_off, X.d_found_pat, m->d_pat_bytes, m->d_pat_off, I.d_ex_off, F.bytes,
-                          F.off, F.table, F.mask, n, w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
-    if (hipGetLastError() != hipSuccess || hipMemsetAsync((uint8_t *)O.d_text + out_text, 0, mkz::kPad, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "record output kernels failed");
-    w->ms[3] = (float)ms_since(t);
-    // ---- BGZF members of the records
-    if ((rc = window_deflate(m, codec, W, dl, "mk_tag_sam_bam_window", out_text, bb, w->out, w->out_cap, &w->out_len, &w->ms[4], &w->ms[5], t))) return rc;
+    }, t);
+    if (rc || *status) return rc;
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END
 }
 
 // ---- `tag` BAM -> SAM text with the lines formatted on the device (an addition to ABI v7; kernels: the BAM -> SAM part of bam.hip): the
-// front half is mk_tag_bam_window's, the back half mk_tag_sam_window's; between them a kept record becomes its SAM line.
+// member input and the text output; between them a kept record becomes its SAM line.
 int mk_tag_bam_sam_window(mk_matcher *m, mk_codec *codec, mk_bam_sam_window *w, int logging, mk_counters *c, uint32_t *counts, uint32_t *status) {
-    if (!m || !codec || !w || !c || !status || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
-    if ((w->n_head && !w->head) || (w->n_members && (!w->bgzf || !w->members)) || (w->tail_cap && !w->tail) || (w->out_cap && !w->out) ||
-        (logging && w->rows_cap && (!w->rows || !w->row_name)) || (w->names_cap && !w->names) || (w->n_refs && (!w->ref_names || !w->ref_off)))
+    static const char who[] = "mk_tag_bam_sam_window";
+    if (int bad = tag_args(who, m && codec, w, c, counts, status, logging)) return bad;
+    if ((w->n_members && (!w->bgzf || !w->members)) || (w->n_refs && (!w->ref_names || !w->ref_off)))
         return fail(MK_E_INVALID_ARG, "mk_tag_bam_sam_window: a size without its buffer");
-    w->n_window = w->n_used = w->n_tail = w->n_rec = w->n_kept = w->out_len = w->n_rows = w->n_names_bytes = 0;
-    for (float &x : w->ms) x = 0;
-    *status = 0;
     MK_ABI_BEGIN
-    if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
-    DeviceLoop dl(m);
-    hipStream_t st = dl.st;
-    int rc;
-    auto t = std::chrono::steady_clock::now();
-    AllocMs alloc_ms(&w->ms[7]);
-    // ---- the text: head, then the members inflated behind it
+    TAG_WINDOW_BEGIN
     WindowSide W;
-    W.T = &m->txt[0];
-    mk_window_source S;
-    memset(&S, 0, sizeof(S));
-    S.head = w->head, S.n_head = w->n_head, S.bgzf = w->bgzf, S.n_bgzf = w->n_bgzf, S.members = w->members, S.n_members = w->n_members;
-    if ((rc = window_assemble(m, codec, S, W, dl))) return rc;
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "upload of the window failed");
-    w->ms[1] = (float)ms_since(t);  // (upload + inflate: batch_ms splits them)
-    w->ms[0] = m->batch_ms[0];
-    w->ms[1] -= w->ms[0];
-    w->n_window = W.n_window;
-    const uint64_t n_text = W.n_window;
-    if (n_text == 0) return MK_OK;
-    // ---- the record chain
-    uint64_t n = 0, n_used = 0;
-    uint32_t *d_rec_len = nullptr;
-    if ((rc = bam_index(m, W, st, &n, &n_used, &d_rec_len, status))) return rc;
-    if (*status) return MK_OK;
-    if (w->last && n_used != n_text) {  // the file ends inside a record
-        *status = 8;
-        return MK_OK;
-    }
-    w->n_rec = n, w->n_used = n_used, w->n_tail = n_text - n_used;
-    if (w->n_tail > w->tail_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_sam_window: the text behind the window's records takes %llu bytes", (unsigned long long)w->n_tail);
-    if (w->n_tail && hipMemcpyAsync(w->tail, (const uint8_t *)W.T->d_text + n_used, w->n_tail, hipMemcpyDeviceToHost, st) != hipSuccess)
-        return fail(MK_E_HIP, "download of the tail failed");
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "download of the tail failed");
-    if (w->on_tail) w->on_tail(w->on_tail_ctx, w->tail, w->n_tail);
-    w->ms[2] = (float)ms_since(t);
-    if (n == 0) return MK_OK;
+    BamIndex I;
+    if ((rc = bam_front(m, codec, w, who, 1, dl, W, I, status, t)) || *status || I.n == 0) return rc;
+    const uint64_t n = I.n;
     const uint8_t *d_text = (const uint8_t *)W.T->d_text;
-    uint32_t *d_out_len = d_rec_len + n + 2, *d_ex_off = d_out_len + n + 2, *d_seq_at = d_ex_off + n + 2;
-    unsigned long long *d_out_off = (unsigned long long *)(((uintptr_t)(d_seq_at + n + 2) + 15) & ~(uintptr_t)15);
-    W.d_tile = d_out_off + n + 2;
-    TagWindow X = tag_window(w, "mk_tag_bam_sam_window", n, d_out_len, d_ex_off, d_out_off, nullptr);
+    uint32_t *d_seq_at = I.d_extra;  // where SEQ starts in a kept record's line
+    TagWindow X = tag_window(w, who, n, I.d_out_len, I.d_ex_off, I.d_out_off, nullptr);
     // ---- sequences -> the scan buffer, scan, emission order, pattern sets
     if ((rc = tag_scan(m, dl, W, X, kSeqBam, logging))) return rc;
     w->ms[3] = (float)ms_since(t);
     // ---- keep, the tag's value, the length of every kept record's line
     SamRefsDevice F;
-    if ((rc = upload_refs(m, "mk_tag_bam_sam_window", false, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
+    if ((rc = upload_refs(m, who, false, w->ref_names, w->ref_off, w->n_refs, st, F))) return rc;
     rc = tag_keep(m, dl, W, X, logging, 6u, [&] {
-        launch_bam_taglen(d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
-                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, d_out_len, d_ex_off, W.d_st, st);
-        launch_bam_sam_len(d_text, W.d_rec_start, d_rec_len, m->d_flags2, n, F.bytes, F.off, (uint32_t)w->n_refs, d_out_len, d_seq_at, W.d_st, st);
+        launch_bam_taglen(d_text, W.d_rec_start, I.d_rec_len, W.d_seq_start, W.d_seq_len, X.d_found_off, X.d_found_pat, m->d_pat_off, m->d_pat_bytes, n,
+                          w->filter_matching != 0, w->invert != 0, w->tag[0], w->tag[1], m->d_flags2, I.d_out_len, I.d_ex_off, W.d_st, st);
+        launch_bam_sam_len(d_text, W.d_rec_start, I.d_rec_len, m->d_flags2, n, F.bytes, F.off, (uint32_t)w->n_refs, I.d_out_len, d_seq_at, W.d_st, st);
     }, status);
-    const unsigned long long out_text = X.out_text;
-    const bool write = w->out || w->out_cap;
-    if (write) w->out_len = out_text;
+    rc = text_back(m, w, X, dl, rc, status, &w->ms[4], "line output kernels failed", [&](uint8_t *d_out) {
+        launch_bam_sam_emit(d_text, W.d_rec_start, I.d_rec_len, W.d_seq_start, W.d_seq_len, I.d_out_len, I.d_out_off, d_seq_at, X.d_found_off, X.d_found_pat,
+                            m->d_pat_bytes, m->d_pat_off, I.d_ex_off, F.bytes, F.off, (uint32_t)w->n_refs, n, w->tag[0], w->tag[1], d_out, st);
+    }, t);
     if (rc || *status) return rc;
-    if (write && out_text > w->out_cap) return fail(MK_E_CAPACITY, "mk_tag_bam_sam_window: the kept lines take %llu bytes", out_text);
-    if (write && out_text) {
-        mk_matcher::TextSlot &O = m->txt[1];
-        if ((rc = ensure_device(&O.d_text, &O.d_text_cap, out_text + 64))) return rc;
-        launch_bam_sam_emit(d_text, W.d_rec_start, d_rec_len, W.d_seq_start, W.d_seq_len, d_out_len, d_out_off, d_seq_at, X.d_found_off, X.d_found_pat,
-                            m->d_pat_bytes, m->d_pat_off, d_ex_off, F.bytes, F.off, (uint32_t)w->n_refs, n, w->tag[0], w->tag[1], (uint8_t *)O.d_text, st);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "line output kernels failed");
-        w->ms[4] = (float)ms_since(t);
-        if (hipMemcpyAsync(w->out, O.d_text, out_text, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(MK_E_HIP, "download of the kept lines failed");
-        w->ms[5] = (float)ms_since(t);
-    } else {
-        w->ms[4] = (float)ms_since(t);
-    }
     tag_commit(dl, X, c, counts);
     return MK_OK;
     MK_ABI_END

@@ -770,163 +770,11 @@ class Matcher:
         found = [res["fpat"][int(foff[i]):int(foff[i + 1])].tolist() for i in range(n)]
         return keep[:n].astype(bool).tolist(), rows, res["c"].as_dict(res["counts"]), found
 
-    def tag_bam_window(self, codec, head: bytes, blob: bytes, members, last, tag=b"km", logging=True, filter_matching=False, invert=False,
-                       write=True, block_bytes=0, piece_bytes=0):
-        """mk_tag_bam_window: head + the text of `members` (entries of bgzf_members(blob), out_off re-based to 0) as BAM records ->
-        dict(status, n_window, n_used, n_rec, n_kept, tail, out (BGZF members of the tagged kept records), out_text_bytes, rows
-        [(name, rec, pat, pos)], counters, ms)"""
-        mem = members.copy()
-        if len(mem):
-            mem["out_off"] -= mem["out_off"][0]
-        hb, bb = np.frombuffer(head, dtype=np.uint8), np.frombuffer(blob, dtype=np.uint8)
-        n_text = len(head) + (int(mem["isize"].sum()) if len(mem) else 0)
-        _check(load().mk_matcher_set_bam_piece(self._h, piece_bytes))
-        w = BamWindow()
-        w.head, w.n_head, w.bgzf, w.n_bgzf = (hb.ctypes.data if len(hb) else None), len(hb), (bb.ctypes.data if len(bb) else None), len(bb)
-        w.members, w.n_members = (mem.ctypes.data if len(mem) else None), len(mem)
-        w.last, w.filter_matching, w.invert, w.block_bytes = int(bool(last)), int(bool(filter_matching)), int(bool(invert)), block_bytes
-        w.tag[0], w.tag[1] = tag[0], tag[1]
-        tail = np.zeros(max(64, n_text), dtype=np.uint8)
-        w.tail, w.tail_cap = tail.ctypes.data, tail.size
-        out = np.zeros(1 << 16, dtype=np.uint8)
-        rows = np.zeros(4096, dtype=ROW_DTYPE)
-        row_name = np.zeros(4096, dtype=np.uint64)
-        names = np.zeros(1 << 16, dtype=np.uint8)
-        status = C.c_uint32()
-        while True:
-            if write:
-                w.out, w.out_cap = out.ctypes.data, out.size
-            w.rows, w.rows_cap, w.row_name, w.names, w.names_cap = rows.ctypes.data, len(rows), row_name.ctypes.data, names.ctypes.data, names.size
-            c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = load().mk_tag_bam_window(self._h, codec._h, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
-            if rc == MK_E_CAPACITY and (w.n_rows > len(rows) or w.n_names_bytes > names.size or w.out_len > out.size):
-                if w.n_rows > len(rows):
-                    rows, row_name = np.zeros(w.n_rows, dtype=ROW_DTYPE), np.zeros(w.n_rows, dtype=np.uint64)
-                if w.n_names_bytes > names.size:
-                    names = np.zeros(w.n_names_bytes, dtype=np.uint8)
-                if w.out_len > out.size:
-                    out = np.zeros(w.out_len, dtype=np.uint8)
-                continue
-            _check(rc)
-            break
-        nb = names[:w.n_names_bytes].tobytes()
-        out_rows = []
-        if logging and status.value == 0:
-            for k in range(w.n_rows):
-                a = int(row_name[k])
-                out_rows.append((nb[a:nb.index(b"\0", a)], int(rows[k]["rec"]), int(rows[k]["pat"]), int(rows[k]["pos"])))
-        return dict(status=status.value, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
-                    out=out[:w.out_len].tobytes(), out_text_bytes=w.out_text_bytes, rows=out_rows, counters=c2.as_dict(k2), ms=list(w.ms))
-
-    def tag_sam_window(self, head: bytes, text: bytes, last, tag=b"km", logging=True, filter_matching=False, invert=False, write=True):
-        """mk_tag_sam_window: head + text as SAM lines -> dict(status, n_window, n_used, n_rec, n_kept, tail, out (the kept lines with
-        their tag field appended), rows [(name, rec, pat, pos)], counters, ms)"""
-        hb, tb = np.frombuffer(head, dtype=np.uint8), np.frombuffer(text, dtype=np.uint8)
-        w = SamWindow()
-        w.head, w.n_head, w.text, w.n_text = (hb.ctypes.data if len(hb) else None), len(hb), (tb.ctypes.data if len(tb) else None), len(tb)
-        w.last, w.filter_matching, w.invert = int(bool(last)), int(bool(filter_matching)), int(bool(invert))
-        w.tag[0], w.tag[1] = tag[0], tag[1]
-        tail = np.zeros(max(64, len(hb) + len(tb)), dtype=np.uint8)
-        w.tail, w.tail_cap = tail.ctypes.data, tail.size
-        out = np.zeros(1 << 16, dtype=np.uint8)
-        rows = np.zeros(4096, dtype=ROW_DTYPE)
-        row_name = np.zeros(4096, dtype=np.uint64)
-        names = np.zeros(1 << 16, dtype=np.uint8)
-        status = C.c_uint32()
-        while True:
-            if write:
-                w.out, w.out_cap = out.ctypes.data, out.size
-            w.rows, w.rows_cap, w.row_name, w.names, w.names_cap = rows.ctypes.data, len(rows), row_name.ctypes.data, names.ctypes.data, names.size
-            c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = load().mk_tag_sam_window(self._h, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
-            if rc == MK_E_CAPACITY and (w.n_rows > len(rows) or w.n_names_bytes > names.size or w.out_len > out.size):
-                if w.n_rows > len(rows):
-                    rows, row_name = np.zeros(w.n_rows, dtype=ROW_DTYPE), np.zeros(w.n_rows, dtype=np.uint64)
-                if w.n_names_bytes > names.size:
-                    names = np.zeros(w.n_names_bytes, dtype=np.uint8)
-                if w.out_len > out.size:
-                    out = np.zeros(w.out_len, dtype=np.uint8)
-                continue
-            _check(rc)
-            break
-        nb = names[:w.n_names_bytes].tobytes()
-        out_rows = []
-        if logging and status.value == 0:
-            for k in range(w.n_rows):
-                a = int(row_name[k])
-                out_rows.append((nb[a:nb.index(b"\0", a)], int(rows[k]["rec"]), int(rows[k]["pat"]), int(rows[k]["pos"])))
-        return dict(status=status.value, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
-                    out=out[:w.out_len].tobytes() if write else b"", rows=out_rows, counters=c2.as_dict(k2), ms=list(w.ms))
-
-    def tag_sam_bam_window(self, codec, head: bytes, text: bytes, last, refs=(), tag=b"km", logging=True, filter_matching=False, invert=False,
-                           write=True, block_bytes=0):
-        """mk_tag_sam_bam_window: head + text as SAM lines, `refs` = the reference names (bytes) in header order -> dict(status, n_window,
-        n_used, n_rec, n_kept, tail, out (BGZF members of the kept lines as tagged BAM records), out_text_bytes, rows [(name, rec, pat,
-        pos)], counters, ms)"""
-        hb, tb = np.frombuffer(head, dtype=np.uint8), np.frombuffer(text, dtype=np.uint8)
-        ref_bytes = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8)
-        ref_off = np.zeros(len(refs) + 1, dtype=np.uint64)
-        ref_off[1:] = np.cumsum([len(r) for r in refs], dtype=np.uint64)
-        w = SamBamWindow()
-        w.head, w.n_head, w.text, w.n_text = (hb.ctypes.data if len(hb) else None), len(hb), (tb.ctypes.data if len(tb) else None), len(tb)
-        w.last, w.filter_matching, w.invert, w.block_bytes = int(bool(last)), int(bool(filter_matching)), int(bool(invert)), block_bytes
-        w.tag[0], w.tag[1] = tag[0], tag[1]
-        w.ref_names, w.ref_off, w.n_refs = ref_bytes.ctypes.data, ref_off.ctypes.data, len(refs)
-        tail = np.zeros(max(64, len(hb) + len(tb)), dtype=np.uint8)
-        w.tail, w.tail_cap = tail.ctypes.data, tail.size
-        out = np.zeros(1 << 16, dtype=np.uint8)
-        rows = np.zeros(4096, dtype=ROW_DTYPE)
-        row_name = np.zeros(4096, dtype=np.uint64)
-        names = np.zeros(1 << 16, dtype=np.uint8)
-        status = C.c_uint32()
-        while True:
-            if write:
-                w.out, w.out_cap = out.ctypes.data, out.size
-            w.rows, w.rows_cap, w.row_name, w.names, w.names_cap = rows.ctypes.data, len(rows), row_name.ctypes.data, names.ctypes.data, names.size
-            c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = load().mk_tag_sam_bam_window(self._h, codec._h, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
-            if rc == MK_E_CAPACITY and (w.n_rows > len(rows) or w.n_names_bytes > names.size or w.out_len > out.size):
-                if w.n_rows > len(rows):
-                    rows, row_name = np.zeros(w.n_rows, dtype=ROW_DTYPE), np.zeros(w.n_rows, dtype=np.uint64)
-                if w.n_names_bytes > names.size:
-                    names = np.zeros(w.n_names_bytes, dtype=np.uint8)
-                if w.out_len > out.size:
-                    out = np.zeros(w.out_len, dtype=np.uint8)
-                continue
-            _check(rc)
-            break
-        nb = names[:w.n_names_bytes].tobytes()
-        out_rows = []
-        if logging and status.value == 0:
-            for k in range(w.n_rows):
-                a = int(row_name[k])
-                out_rows.append((nb[a:nb.index(b"\0", a)], int(rows[k]["rec"]), int(rows[k]["pat"]), int(rows[k]["pos"])))
-        return dict(status=status.value, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
-                    out=out[:w.out_len].tobytes() if write else b"", out_text_bytes=w.out_text_bytes, rows=out_rows, counters=c2.as_dict(k2),
-                    ms=list(w.ms))
-
-    def tag_bam_sam_window(self, codec, head: bytes, blob: bytes, members, last, refs=(), tag=b"km", logging=True, filter_matching=False, invert=False,
-                           write=True, piece_bytes=0, out_cap=None, guard=0):
-        """mk_tag_bam_sam_window: head + the text of `members` (entries of bgzf_members(blob), out_off re-based to 0) as BAM records, `refs`
-        = the reference names (bytes) in header order -> dict(status, rc, n_window, n_used, n_rec, n_kept, tail, out (the kept records as SAM
-        lines with their tag field appended), out_len, rows [(name, rec, pat, pos)], counters, ms).  out_cap: the output buffer is exactly
-        that large and a call that asks for more is NOT repeated (rc = MK_E_CAPACITY is returned); `guard` bytes of 0xA5 lie behind it and
-        come back as `guard`."""
-        mem = members.copy()
-        if len(mem):
-            mem["out_off"] -= mem["out_off"][0]
-        hb, bb = np.frombuffer(head, dtype=np.uint8), np.frombuffer(blob, dtype=np.uint8)
-        n_text = len(head) + (int(mem["isize"].sum()) if len(mem) else 0)
-        ref_bytes = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8)
-        ref_off = np.zeros(len(refs) + 1, dtype=np.uint64)
-        ref_off[1:] = np.cumsum([len(r) for r in refs], dtype=np.uint64)
-        _check(load().mk_matcher_set_bam_piece(self._h, piece_bytes))
-        w = BamSamWindow()
-        w.head, w.n_head, w.bgzf, w.n_bgzf = (hb.ctypes.data if len(hb) else None), len(hb), (bb.ctypes.data if len(bb) else None), len(bb)
-        w.members, w.n_members = (mem.ctypes.data if len(mem) else None), len(mem)
-        w.last, w.filter_matching, w.invert = int(bool(last)), int(bool(filter_matching)), int(bool(invert))
-        w.tag[0], w.tag[1] = tag[0], tag[1]
-        w.ref_names, w.ref_off, w.n_refs = ref_bytes.ctypes.data, ref_off.ctypes.data, len(refs)
+    def _tag_window(self, w, fn, handles, n_text, logging, write, out_cap=None, guard=0):
+        """What the four tag_*_window wrappers share.  w: the window struct with its input fields set; fn(*handles, w, ...): its entry
+        point.  Gives the call a tail of n_text bytes, an output buffer (write) and rows / names, and repeats a call that asks for more
+        room -- but not for more output than a given out_cap: that call's MK_E_CAPACITY comes back as rc, with `guard` bytes of 0xA5
+        behind the buffer as they are afterwards.  -> (the result keys all four have, rc, guard)"""
         tail = np.zeros(max(64, n_text), dtype=np.uint8)
         w.tail, w.tail_cap = tail.ctypes.data, tail.size
         fixed = out_cap is not None
@@ -941,7 +789,7 @@ class Matcher:
                 w.out, w.out_cap = out.ctypes.data, cap
             w.rows, w.rows_cap, w.row_name, w.names, w.names_cap = rows.ctypes.data, len(rows), row_name.ctypes.data, names.ctypes.data, names.size
             c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = load().mk_tag_bam_sam_window(self._h, codec._h, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
+            rc = fn(*handles, C.byref(w), int(logging), C.byref(c2), k2.ctypes.data, C.byref(status))
             if rc == MK_E_CAPACITY and (w.n_rows > len(rows) or w.n_names_bytes > names.size or (w.out_len > cap and not fixed)):
                 if w.n_rows > len(rows):
                     rows, row_name = np.zeros(w.n_rows, dtype=ROW_DTYPE), np.zeros(w.n_rows, dtype=np.uint64)
@@ -960,9 +808,86 @@ class Matcher:
             for k in range(w.n_rows):
                 a = int(row_name[k])
                 out_rows.append((nb[a:nb.index(b"\0", a)], int(rows[k]["rec"]), int(rows[k]["pat"]), int(rows[k]["pos"])))
-        return dict(status=status.value, rc=rc, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
-                    out=out[:min(w.out_len, cap)].tobytes() if write and rc == MK_OK else b"", out_len=w.out_len, guard=out[cap:cap + guard].tobytes(),
-                    rows=out_rows, counters=c2.as_dict(k2), ms=list(w.ms))
+        res = dict(status=status.value, n_window=w.n_window, n_used=w.n_used, n_rec=w.n_rec, n_kept=w.n_kept, tail=tail[:w.n_tail].tobytes(),
+                   out=out[:min(w.out_len, cap)].tobytes() if rc == MK_OK else b"", rows=out_rows, counters=c2.as_dict(k2), ms=list(w.ms))
+        return res, rc, out[cap:cap + guard].tobytes()
+
+    # The input fields of a window struct, by what the struct has.  Each returns the arrays the struct points into: they must outlive the call.
+    def _window_common(self, w, head, last, tag, filter_matching, invert):
+        hb = np.frombuffer(head, dtype=np.uint8)
+        w.head, w.n_head = (hb.ctypes.data if len(hb) else None), len(hb)
+        w.last, w.filter_matching, w.invert = int(bool(last)), int(bool(filter_matching)), int(bool(invert))
+        w.tag[0], w.tag[1] = tag[0], tag[1]
+        return [hb]
+
+    def _window_members(self, w, blob, members, piece_bytes):
+        """`members` re-based to the first one's text -> (the arrays, bytes of text)"""
+        mem = members.copy()
+        if len(mem):
+            mem["out_off"] -= mem["out_off"][0]
+        bb = np.frombuffer(blob, dtype=np.uint8)
+        _check(load().mk_matcher_set_bam_piece(self._h, piece_bytes))
+        w.bgzf, w.n_bgzf = (bb.ctypes.data if len(bb) else None), len(bb)
+        w.members, w.n_members = (mem.ctypes.data if len(mem) else None), len(mem)
+        return [mem, bb], int(mem["isize"].sum()) if len(mem) else 0
+
+    def _window_text(self, w, text):
+        tb = np.frombuffer(text, dtype=np.uint8)
+        w.text, w.n_text = (tb.ctypes.data if len(tb) else None), len(tb)
+        return [tb], len(tb)
+
+    def _window_refs(self, w, refs):
+        ref_bytes = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8)
+        ref_off = np.zeros(len(refs) + 1, dtype=np.uint64)
+        ref_off[1:] = np.cumsum([len(r) for r in refs], dtype=np.uint64)
+        w.ref_names, w.ref_off, w.n_refs = ref_bytes.ctypes.data, ref_off.ctypes.data, len(refs)
+        return [ref_bytes, ref_off]
+
+    def tag_bam_window(self, codec, head: bytes, blob: bytes, members, last, tag=b"km", logging=True, filter_matching=False, invert=False,
+                       write=True, block_bytes=0, piece_bytes=0):
+        """mk_tag_bam_window: head + the text of `members` (entries of bgzf_members(blob), out_off re-based to 0) as BAM records ->
+        dict(status, n_window, n_used, n_rec, n_kept, tail, out (BGZF members of the tagged kept records), out_text_bytes, rows
+        [(name, rec, pat, pos)], counters, ms)"""
+        w = BamWindow()
+        hold = self._window_common(w, head, last, tag, filter_matching, invert)
+        held, n_body = self._window_members(w, blob, members, piece_bytes)
+        w.block_bytes = block_bytes
+        res, _, _ = self._tag_window(w, load().mk_tag_bam_window, (self._h, codec._h), len(head) + n_body, logging, write)
+        return dict(res, out_text_bytes=w.out_text_bytes)
+
+    def tag_sam_window(self, head: bytes, text: bytes, last, tag=b"km", logging=True, filter_matching=False, invert=False, write=True):
+        """mk_tag_sam_window: head + text as SAM lines -> dict(status, n_window, n_used, n_rec, n_kept, tail, out (the kept lines with
+        their tag field appended), rows [(name, rec, pat, pos)], counters, ms)"""
+        w = SamWindow()
+        hold = self._window_common(w, head, last, tag, filter_matching, invert)
+        held, n_body = self._window_text(w, text)
+        res, _, _ = self._tag_window(w, load().mk_tag_sam_window, (self._h,), len(head) + n_body, logging, write)
+        return dict(res, out=res["out"] if write else b"")
+
+    def tag_sam_bam_window(self, codec, head: bytes, text: bytes, last, refs=(), tag=b"km", logging=True, filter_matching=False, invert=False,
+                           write=True, block_bytes=0):
+        """mk_tag_sam_bam_window: head + text as SAM lines, `refs` = the reference names (bytes) in header order -> dict(status, n_window,
+        n_used, n_rec, n_kept, tail, out (BGZF members of the kept lines as tagged BAM records), out_text_bytes, rows [(name, rec, pat,
+        pos)], counters, ms)"""
+        w = SamBamWindow()
+        hold = self._window_common(w, head, last, tag, filter_matching, invert) + self._window_refs(w, refs)
+        held, n_body = self._window_text(w, text)
+        w.block_bytes = block_bytes
+        res, _, _ = self._tag_window(w, load().mk_tag_sam_bam_window, (self._h, codec._h), len(head) + n_body, logging, write)
+        return dict(res, out=res["out"] if write else b"", out_text_bytes=w.out_text_bytes)
+
+    def tag_bam_sam_window(self, codec, head: bytes, blob: bytes, members, last, refs=(), tag=b"km", logging=True, filter_matching=False, invert=False,
+                           write=True, piece_bytes=0, out_cap=None, guard=0):
+        """mk_tag_bam_sam_window: head + the text of `members` (entries of bgzf_members(blob), out_off re-based to 0) as BAM records, `refs`
+        = the reference names (bytes) in header order -> dict(status, rc, n_window, n_used, n_rec, n_kept, tail, out (the kept records as SAM
+        lines with their tag field appended), out_len, rows [(name, rec, pat, pos)], counters, ms).  out_cap: the output buffer is exactly
+        that large and a call that asks for more is NOT repeated (rc = MK_E_CAPACITY is returned); `guard` bytes of 0xA5 lie behind it and
+        come back as `guard`."""
+        w = BamSamWindow()
+        hold = self._window_common(w, head, last, tag, filter_matching, invert) + self._window_refs(w, refs)
+        held, n_body = self._window_members(w, blob, members, piece_bytes)
+        res, rc, guard_bytes = self._tag_window(w, load().mk_tag_bam_sam_window, (self._h, codec._h), len(head) + n_body, logging, write, out_cap, guard)
+        return dict(res, rc=rc, out=res["out"] if write else b"", out_len=w.out_len, guard=guard_bytes)
 
     def tag_value(self, found, existing=None) -> bytes:
         arr = np.asarray(list(found) + [0], dtype=np.uint32)

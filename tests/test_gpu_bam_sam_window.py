@@ -7,16 +7,15 @@ import gzip
 import os
 import random
 import struct
-import zlib
 
 import numpy as np
 import pytest
 
 import oracle_binding as ob
+from tag_windows import NIB, _bgzf, bam_record, patterns31
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NIB = b"=ACMGRSVTWYHKDBN"
 REFS = [b"chr1", b"2", b"a_rather_long_reference_name.17", b"MT"]
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
 
@@ -28,30 +27,6 @@ def mk():
     if native.device_count() < 1:
         pytest.fail("no HIP device visible: the gpu-marked tests need an MI355X")
     return native
-
-
-def _bgzf(data, block=0xff00, level=6):
-    out = bytearray()
-    for b in range(0, len(data), block):
-        chunk = data[b:b + block]
-        co = zlib.compressobj(level, zlib.DEFLATED, -15)
-        payload = co.compress(chunk) + co.flush()
-        out += bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0]) + struct.pack("<H", 18 + len(payload) + 8 - 1) + payload
-        out += struct.pack("<II", zlib.crc32(chunk), len(chunk))
-    return bytes(out)
-
-
-def bam_record(name, seq, qual=None, aux=b"", cigar=(), ref=0, pos=100, flag=0, mapq=60, nref=-1, npos=-1, tlen=0):
-    """block_size + one BAM record; seq in the 16-letter alphabet, qual = l_seq raw bytes (default: 30s)"""
-    l = len(seq)
-    packed = bytearray((l + 1) // 2)
-    for k, ch in enumerate(seq):
-        packed[k >> 1] |= NIB.index(ch) << (4 if k % 2 == 0 else 0)
-    qual = bytes([30] * l) if qual is None else qual
-    assert len(qual) == l
-    body = struct.pack("<iiBBHHHiiii", ref, pos, len(name) + 1, mapq, 4680, len(cigar), flag, l, nref, npos, tlen)
-    body += name + b"\0" + b"".join(struct.pack("<I", c) for c in cigar) + bytes(packed) + qual + aux
-    return struct.pack("<i", len(body)) + body
 
 
 # ---- the restatement
@@ -124,11 +99,6 @@ def expected(om, patterns, recs, refs, tag, logging, filter_matching, invert, ex
         if k:
             out += dec[i][0] + b"\t" + tag + b":Z:" + ob.tag_value(patterns, f, existing[i] if existing and existing[i] else None) + b"\n"
     return keep, [(dec[rec][1], rec, pat, pos) for (_, rec, pat, pos) in rows], c, bytes(out)
-
-
-def patterns31(mk, n=100, seed=3):
-    rnd = random.Random(seed)
-    return mk.parse_pattern_list(kmer_seq=[bytes(rnd.choice(b"ACGT") for _ in range(31)) for _ in range(n)])
 
 
 def check(r, keep, rows, c, out, logging=True):
@@ -250,7 +220,7 @@ def window(mk, recs, block=0xff00):
 def test_lines_match_the_restatement(mk, filter_matching, invert, logging):
     """every sequence length of the nibble parity and 16-lane step edges, every kind of quality, fixed and optional fields of every kind"""
     rnd = random.Random(11)
-    pats = patterns31(mk)
+    pats = patterns31(mk, 100)
     recs, existing = make(rnd, pats, 600)
     text, blob, members = window(mk, recs)
     m, codec = mk.Matcher(pats, device=0), mk.Codec(0)

@@ -7,16 +7,15 @@ import gzip
 import os
 import random
 import struct
-import zlib
 
 import numpy as np
 import pytest
 
 import oracle_binding as ob
+from tag_windows import NIB, _bgzf, bam_record, patterns31
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NIB = b"=ACMGRSVTWYHKDBN"
 
 
 @pytest.fixture(scope="module")
@@ -26,28 +25,6 @@ def mk():
     if native.device_count() < 1:
         pytest.fail("no HIP device visible: the gpu-marked tests need an MI355X")
     return native
-
-
-def _bgzf(data, block=0xff00, level=6):
-    out = bytearray()
-    for b in range(0, len(data), block):
-        chunk = data[b:b + block]
-        co = zlib.compressobj(level, zlib.DEFLATED, -15)
-        payload = co.compress(chunk) + co.flush()
-        out += bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0]) + struct.pack("<H", 18 + len(payload) + 8 - 1) + payload
-        out += struct.pack("<II", zlib.crc32(chunk), len(chunk))
-    return bytes(out)
-
-
-def bam_record(name, seq, aux=b"", cigar=(), ref=0, pos=100, flag=0, mapq=60):
-    """block_size + one BAM record; seq in the 16-letter alphabet"""
-    l = len(seq)
-    packed = bytearray((l + 1) // 2)
-    for k, ch in enumerate(seq):
-        packed[k >> 1] |= NIB.index(ch) << (4 if k % 2 == 0 else 0)
-    body = struct.pack("<iiBBHHHiiii", ref, pos, len(name) + 1, mapq, 4680, len(cigar), flag, l, -1, -1, 0)
-    body += name + b"\0" + b"".join(struct.pack("<I", c) for c in cigar) + bytes(packed) + bytes([30] * l) + aux
-    return struct.pack("<i", len(body)) + body
 
 
 def decode(rec):
@@ -94,7 +71,7 @@ def make_records(rnd, n, patterns, lens=(150,), hit=0.2, alpha=b"ACGT", aux_kind
             if pick >= 5:
                 aux += b"XAA" + b"q" + b"XHH" + b"0AFF\0" + b"XFf" + struct.pack("<f", 1.5) + b"XSs" + struct.pack("<h", -7)
         cigar = ((L << 4) | 0,) if L else ()
-        recs.append(bam_record(b"read%d_%d" % (i, rnd.randrange(10 ** 6)), bytes(s), aux, cigar, pos=rnd.randrange(10 ** 6)))
+        recs.append(bam_record(b"read%d_%d" % (i, rnd.randrange(10 ** 6)), bytes(s), aux=aux, cigar=cigar, pos=rnd.randrange(10 ** 6)))
     return recs
 
 
@@ -125,15 +102,6 @@ def run_windows(mk, m, codec, blob, members, cuts, **kw):
             break
         head = r["tail"]
     return res
-
-
-PATS31 = None
-
-
-def patterns31(mk, n=200, seed=3):
-    rnd = random.Random(seed)
-    raw = [bytes(rnd.choice(b"ACGT") for _ in range(31)) for _ in range(n)]
-    return mk.parse_pattern_list(kmer_seq=raw)
 
 
 @pytest.mark.parametrize("filter_matching,invert", [(False, False), (True, False), (False, True)])
@@ -234,19 +202,19 @@ def test_refusals(mk):
     # a kept record with a field of the tag's name that is not a string (the reference bails), whose value is not plain ASCII (the
     # reference checks UTF-8 first) or is very long: the host path's
     hit_seq = pats[0] + b"A" * 40
-    r = run(good + [bam_record(b"old", hit_seq, b"kmi" + struct.pack("<i", 5))] + good)
+    r = run(good + [bam_record(b"old", hit_seq, aux=b"kmi" + struct.pack("<i", 5))] + good)
     assert r["status"] == 4 and r["out"] == b""
-    r = run(good + [bam_record(b"old", hit_seq, b"kmZ" + "AAA,\u00e9".encode() + b"\0")])
+    r = run(good + [bam_record(b"old", hit_seq, aux=b"kmZ" + "AAA,\u00e9".encode() + b"\0")])
     assert r["status"] == 4
-    r = run(good + [bam_record(b"old", hit_seq, b"kmZ" + b"ACGT," * 500 + b"\0")])
+    r = run(good + [bam_record(b"old", hit_seq, aux=b"kmZ" + b"ACGT," * 500 + b"\0")])
     assert r["status"] == 4
     # ... but not when that record is dropped (-v drops records with a hit; the reference never looks at a dropped record's tags)
-    r = run(good + [bam_record(b"old", hit_seq, b"kmi" + struct.pack("<i", 5))], invert=True)
+    r = run(good + [bam_record(b"old", hit_seq, aux=b"kmi" + struct.pack("<i", 5))], invert=True)
     assert r["status"] == 0
     # optional fields that do not parse
-    r = run(good + [bam_record(b"odd", b"ACGT" * 10, b"XX?" + b"1234")])
+    r = run(good + [bam_record(b"odd", b"ACGT" * 10, aux=b"XX?" + b"1234")])
     assert r["status"] == 2
-    r = run(good + [bam_record(b"odd", b"ACGT" * 10, b"XXZ" + b"no terminator")])
+    r = run(good + [bam_record(b"odd", b"ACGT" * 10, aux=b"XXZ" + b"no terminator")])
     assert r["status"] == 2
     # a block_size below the fixed fields / sizes that do not add up: the serial parser's "truncated file"
     bad = bytearray(good[3])
@@ -299,7 +267,7 @@ def test_existing_tag_values_are_merged(mk):
             if i % 7 == 0:
                 aux += b"kmZ" + b"second,field" + b"\0"  # (only the first field of that name is looked at)
         aux += b"ASi" + struct.pack("<i", i)
-        recs.append(bam_record(b"e%d" % i, bytes(s), aux))
+        recs.append(bam_record(b"e%d" % i, bytes(s), aux=aux))
         existing.append(v)
     blob = _bgzf(b"".join(recs))
     members, _, _ = mk.bgzf_members(blob)
@@ -340,7 +308,7 @@ def test_names_that_look_like_records(mk):
     recs = []
     for i in range(400):
         aux = b"ZBB" + b"C" + struct.pack("<i", 4 * len(fake)) + fake * 4
-        recs.append(bam_record(b"n%d" % i, bytes(rnd.choice(b"ACGT") for _ in range(60)), aux))
+        recs.append(bam_record(b"n%d" % i, bytes(rnd.choice(b"ACGT") for _ in range(60)), aux=aux))
     text = b"".join(recs)
     blob = _bgzf(text)
     members, _, _ = mk.bgzf_members(blob)

@@ -3,7 +3,6 @@ The expected bytes come from `encode` below: a restatement of the SAM specificat
 entry point's contract in include/merkurio_hip.h, written here in Python with exact rational arithmetic for the floats -- it shares
 no code with the library.  The oracle's tag_records + tag_value supply keep, values, rows and counters, as in test_gpu_sam_window.py.
 Every input outside test_refusals is one the device takes: each test asserts status == 0."""
-import gzip
 import random
 import struct
 
@@ -11,9 +10,9 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+from tag_windows import existing_value, inflate, patterns31, records_of
 
 pytestmark = pytest.mark.gpu
-EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])
 REFS = [b"chr1", b"chr2", b"chrM", b"chr2", b"HLA-A*01:01", b"="]  # (a duplicate: the first one counts)
 
 
@@ -31,11 +30,6 @@ def codec(mk):
     c = mk.Codec(0)
     yield c
     c.close()
-
-
-def patterns31(mk, n=200, seed=3):
-    rnd = random.Random(seed)
-    return mk.parse_pattern_list(kmer_seq=[bytes(rnd.choice(b"ACGT") for _ in range(31)) for _ in range(n)])
 
 
 # ---- the BAM record of a SAM line (SAM specification 4.2, 4.2.4 for the optional fields, 5.3 for the bin)
@@ -213,27 +207,6 @@ def sam_line(rnd, i, patterns, lens=(150,), hit=0.2, alpha=b"ACGT", lower=0.0, e
     return b"\t".join(f) + eol
 
 
-def records_of(text, last=True):
-    used = len(text) if last or text.endswith(b"\n") else text.rfind(b"\n") + 1
-    out = []
-    for ln in text[:used].split(b"\n"):
-        if ln.endswith(b"\r"):
-            ln = ln[:-1]
-        if not ln or ln[:1] == b"@":
-            continue
-        f = ln.split(b"\t")
-        out.append((ln, f[0], b"" if f[9] == b"*" else bytes(c - 32 if 97 <= c <= 122 else c for c in f[9]), f[11:]))
-    return out, used
-
-
-def existing_value(aux, tag):
-    for f in aux:
-        if len(f) >= 5 and f[:2] == tag and f[2:3] == b":":
-            assert f[3:5] == b"Z:"
-            return f[5:]
-    return None
-
-
 def expected(om, patterns, text, tag, logging, fm, inv, refs=REFS, last=True):
     recs, _ = records_of(text, last)
     keep, rows, c, found = ob.tag_records(om, [r[2] for r in recs], logging=logging, filter_matching=fm, invert=inv)
@@ -243,10 +216,6 @@ def expected(om, patterns, text, tag, logging, fm, inv, refs=REFS, last=True):
             ex = existing_value(aux, tag)
             out += encode(ln + b"\t" + tag + b":Z:" + ob.tag_value(patterns, f, ex if ex else None), refs)
     return keep, [(recs[rec][1], rec, pat, pos) for (_, rec, pat, pos) in rows], c, bytes(out), len(recs)
-
-
-def inflate(members):
-    return gzip.decompress(members + EOF) if members else b""
 
 
 def first_difference(got, want):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+from tag_windows import existing_value, patterns31, records_of
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -22,37 +23,6 @@ def mk():
     if native.device_count() < 1:
         pytest.fail("no HIP device visible: the gpu-marked tests need an MI355X")
     return native
-
-
-def patterns31(mk, n=200, seed=3):
-    rnd = random.Random(seed)
-    raw = [bytes(rnd.choice(b"ACGT") for _ in range(31)) for _ in range(n)]
-    return mk.parse_pattern_list(kmer_seq=raw)
-
-
-def records_of(text, last=True):
-    """the line rule: -> [(line without its line end, name, SEQ as the matcher sees it, existing-field scan input)], bytes used"""
-    used = len(text) if last or text.endswith(b"\n") else text.rfind(b"\n") + 1
-    out = []
-    for ln in text[:used].split(b"\n"):
-        if ln.endswith(b"\r"):
-            ln = ln[:-1]
-        if not ln or ln[:1] == b"@":
-            continue
-        f = ln.split(b"\t")
-        assert len(f) >= 10
-        seq = b"" if f[9] == b"*" else bytes(c - 32 if 97 <= c <= 122 else c for c in f[9])
-        out.append((ln, f[0], seq, f[11:]))
-    return out, used
-
-
-def existing_value(aux, tag):
-    """SamFile::find_tag: the first optional field of at least 5 bytes that starts with tag ':' -> its value (None: no such field)"""
-    for f in aux:
-        if len(f) >= 5 and f[:2] == tag and f[2:3] == b":":
-            assert f[3:5] == b"Z:"
-            return f[5:]
-    return None
 
 
 def expected(ob_m, patterns, text, tag, logging, filter_matching, invert, last=True):

@@ -364,7 +364,7 @@ def test_bam_window_with_values_of_a_hundred_patterns(mk, carry):
     patterns = mk.parse_pattern_list(kmer_seq=raw)
     rnd = random.Random(21)
     existing = _existing_values(rnd, raw, len(seqs)) if carry else [None] * len(seqs)
-    recs = [bw.bam_record(b"read%d" % i, s, b"NMC\x01" + (b"kmZ" + v + b"\0" if v else b"") + b"ASi" + struct.pack("<i", i))
+    recs = [bw.bam_record(b"read%d" % i, s, aux=b"NMC\x01" + (b"kmZ" + v + b"\0" if v else b"") + b"ASi" + struct.pack("<i", i))
             for i, (s, v) in enumerate(zip(seqs, existing))]
     blob = bw._bgzf(b"".join(recs))
     members, used, _ = mk.bgzf_members(blob)
@@ -394,7 +394,7 @@ def test_bam_window_with_values_of_a_hundred_patterns(mk, carry):
     if carry:  # a value just above kBamMergeBytes (2 048): the window is handed back (status 4, no output), as test_refusals has it
         over = b",".join(raw[:64]) + b",A"
         assert len(over) == 2049
-        recs[0] = bw.bam_record(b"over", seqs[0], b"kmZ" + over + b"\0")
+        recs[0] = bw.bam_record(b"over", seqs[0], aux=b"kmZ" + over + b"\0")
         blob = bw._bgzf(b"".join(recs))
         members, _, _ = mk.bgzf_members(blob)
         r = m.tag_bam_window(codec, b"", blob, members, last=True)
