@@ -4,7 +4,8 @@ src/cmd_extract.rs:332-351) and BNDMq order (record, pattern, start -- src/cmd_e
 sets that walk every path of the device code: bins of consecutive records, re-binning on (record, end) for few
 huge records, the re-binning on the whole key, the library fallback, shuffled input, tuples of a batch the handle has not scanned, and every
 small size around the leaf-sort geometry.  The scan-produced tuples of real batches are covered by
-test_gpu_parity.py::test_emission_order_on_the_device and test_gpu_configs.py (10^8 tuples)."""
+test_gpu_parity.py::test_emission_order_on_the_device and test_gpu_configs.py (10^8 tuples).
+What happens to the ordered tuples next (pattern sets, counts, log rows, pair lists: sets.hip) is in test_gpu_sets.py."""
 import random
 
 import numpy as np
