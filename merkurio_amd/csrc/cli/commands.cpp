@@ -20,6 +20,7 @@
 #include "../../../include/merkurio_hip.h"
 #include "io.hpp"
 #include "extract_common.hpp"
+#include "tag_host.hpp"
 
 namespace cli {
 
@@ -112,28 +113,6 @@ static void open_loggers(const CommonArgs &a, Loggers &lg) {
         lg.has_json = true;
     }
     lg.active = a.out_log || a.json_log;
-}
-
-// ---- --gpus N: one matcher handle + one host thread per device, contiguous record ranges ---------
-// [lo, hi) of shard d of n units over `parts` shards, sizes differing by at most one (the same
-// rule as merkurio_amd/sharding.py): concatenating shard outputs in device order reproduces the
-// single-device output order (pairs are units, never split: src/cmd_extract.rs:463-468)
-static std::pair<size_t, size_t> shard_range(size_t n, size_t parts, size_t d) {
-    const size_t base = n / parts, rem = n % parts;
-    const size_t lo = d * base + std::min(d, rem);
-    return {lo, lo + base + (d < rem ? 1 : 0)};
-}
-
-// A window of n records (pairs) over the devices: fn(d, lo, hi, out[d]) scans shard_range(n, N, d) on device d's own host thread and
-// keeps its results in out[d]; they come back in device order = record order, to be emitted in that order.
-template <class Result, class F>
-static std::vector<Result> run_shards(size_t n, size_t n_dev, F fn) {
-    std::vector<Result> out(n_dev);
-    run_threads(n_dev, [&](size_t d) {
-        const auto [lo, hi] = shard_range(n, n_dev, d);
-        fn(d, lo, hi, out[d]);
-    });
-    return out;
 }
 
 // the scalars of src/cmd_extract.rs:285-290 / src/cmd_tag.rs:360-364 and pattern_hit_counts of every
@@ -616,7 +595,6 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
     }
     tm.mark("open + header");
     const std::vector<mk_matcher *> ms = fm.get();
-    mk_matcher *m = ms[0];
     std::future<void> comm_ready;  // (--gpus N: RCCL's set-up beside the job, as in extract)
     if (ms.size() > 1) comm_ready = std::async(std::launch::async, [&ms] { (void)mk_reduce_prepare(ms.data(), (int)ms.size()); });
     // from here on (the HIP runtime is up) the BGZF members of a BAM window are inflated by the device codec (mk_bgzf_inflate)
@@ -644,166 +622,17 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
     mk_counters c;
     memset(&c, 0, sizeof(c));
     std::vector<uint32_t> counts(pats.list.size(), 0);
-    const uint64_t batch_bytes = (uint64_t)a.batch_mb << 20;
     const uint64_t window_bytes = (uint64_t)a.window_mb << 20;
-    // The input is read a window at a time (--window-mb of SAM text / inflated BAM); inside a window,
-    // one batch = a slab of records whose sequences fill --batch-mb: gather (upper-case / un-nibble)
-    // -> mk_tag_records -> log rows -> tag + encode the kept records.  Only the input buffer and its
-    // record index are whole-file; device buffers, hit rows and matched-pattern sets are per batch.
-    // The results of a batch: its log rows and the encoded output of its kept records, in record order.
-    struct BatchOut {
-        std::vector<mk_row> rows;  // rec = global record index
-        std::vector<std::vector<uint8_t>> bin;  // BAM output: per-thread encoded records, in order
-        std::vector<std::string> txt;           // SAM output
-    };
-    std::mutex txt_pool_mu;
-    std::vector<std::string> txt_pool;
-    auto emit = [&](BatchOut &o) {  // (takes the batch's encoded records with it)
-        if (lg.active)
-            emit_log_rows(
-                lg, pats, o.rows.data(), o.rows.size(),
-                [&](const mk_row &r) {
-                    const auto &rec = sam.recs[r.rec];
-                    return std::pair<const char *, size_t>(sam.data + rec.off + (sam.is_bam ? 36 : 0), rec.name_len);
-                },
-                [&](const mk_row &) -> const std::string & { return in_name; });
-        for (auto &b : o.bin) bw.put_encoded(std::move(b));  // moved, not copied: the pieces are joined on the device
-        for (auto &t : o.txt) w.write(t);
-        {  // the text buffers go back to the encoder threads (pages mapped: a fresh one costs a fault per 4 KiB)
-            std::lock_guard<std::mutex> lk(txt_pool_mu);
-            for (auto &t : o.txt)
-                if (t.capacity() >= (1u << 20) && txt_pool.size() < 64) {
-                    t.clear();
-                    txt_pool.push_back(std::move(t));
-                }
-        }
-    };
-    // scan buffers of one device thread, reused by every batch of every window
-    struct TagBuffers {
-        std::vector<uint8_t> seq, keep;
-        std::vector<uint64_t> off, foff;
-        std::vector<uint32_t> fpat = std::vector<uint32_t>(1024);
-        std::vector<mk_row> rows = std::vector<mk_row>(4096);
-    };
-    std::vector<TagBuffers> dev_bufs(ms.size());
-    auto scan_range = [&](mk_matcher *mm, TagBuffers &TB, size_t r0, size_t r1, mk_counters &cc, std::vector<uint32_t> &cnts,
-                          size_t enc_threads, auto on_batch) {
-        std::vector<uint8_t> &seq = TB.seq, &keep = TB.keep;
-        std::vector<uint64_t> &off = TB.off, &foff = TB.foff;
-        std::vector<uint32_t> &fpat = TB.fpat;
-        std::vector<mk_row> &rows = TB.rows;
-        for (size_t b0 = r0; b0 < r1;) {
-            size_t b1 = b0;
-            uint64_t bytes = 0;
-            while (b1 < r1 && (bytes < batch_bytes || b1 == b0)) bytes += sam.recs[b1++].l_seq;
-            const size_t nb = b1 - b0;
-            sam.gather(b0, b1, seq, off);
-            if (ms.size() == 1) tm.mark("  batch: gather");
-            keep.assign(nb, 0);
-            foff.assign(nb + 1, 0);
-            uint64_t n_rows = 0;
-            for (;;) {
-                mk_counters cb;
-                memset(&cb, 0, sizeof(cb));
-                std::vector<uint32_t> cnt_b(cnts.size(), 0);
-                int rc = mk_tag_records(mm, seq.data(), off.data(), nb, lg.active, a.filter_matching, a.invert_match, keep.data(),
-                                        rows.data(), rows.size(), &n_rows, &cb, cnt_b.data(), foff.data(), fpat.data(), fpat.size());
-                if (rc == MK_E_CAPACITY && (n_rows > rows.size() || foff[nb] > fpat.size())) {
-                    rows.resize(std::max<uint64_t>(rows.size(), n_rows));
-                    fpat.resize(std::max<uint64_t>(fpat.size(), foff[nb]));
-                    continue;
-                }
-                mk_check(rc, "Error during matching");
-                add_counters(cc, cb);
-                add_counts(cnts, cnt_b);
-                break;
-            }
-            if (ms.size() == 1) tm.mark("  batch: mk_tag_records");
-            BatchOut out;
-            if (lg.active) {
-                out.rows.assign(rows.begin(), rows.begin() + n_rows);
-                for (auto &r : out.rows) r.rec += b0;
-            }
-            // tag + encode the kept records (src/cmd_tag.rs:457-497) on the host threads, in record order
-            std::vector<size_t> kept;
-            for (size_t k = 0; k < nb; ++k)
-                if (keep[k]) kept.push_back(k);
-            if (a.suppress_output) {  // the reference still validates existing tags of kept records
-                for (size_t k : kept) {
-                    std::string existing;
-                    if (sam.find_tag(b0 + k, a.tag, &existing) == 2) bail("Invalid tag value format. Expected string value.");
-                }
-            } else {
-                const size_t T = std::max<size_t>(1, std::min<size_t>(enc_threads, kept.size() / 4096 + 1));
-                out.bin.resize(to_bam ? T : 0);
-                out.txt.resize(to_bam ? 0 : T);
-                run_threads(T, [&](size_t t) {
-                    std::vector<char> val(4096);
-                    std::string line;
-                    {  // one allocation for the slice's output instead of a doubling series of copies
-                        size_t est = 0;
-                        for (size_t i = kept.size() * t / T; i < kept.size() * (t + 1) / T; ++i) est += sam.recs[b0 + kept[i]].len + 24 + a.tag.size();
-                        if (to_bam) {
-                            out.bin[t] = bw.take_buffer();  // (one the writer thread has written out, if there is one)
-                            out.bin[t].reserve(est);
-                        } else {
-                            {
-                                std::lock_guard<std::mutex> lk(txt_pool_mu);
-                                if (!txt_pool.empty()) {
-                                    out.txt[t] = std::move(txt_pool.back());
-                                    txt_pool.pop_back();
-                                }
-                            }
-                            out.txt[t].reserve(est);
-                        }
-                    }
-                    for (size_t i = kept.size() * t / T; i < kept.size() * (t + 1) / T; ++i) {
-                        const size_t k = kept[i], g = b0 + k;
-                        std::string existing;
-                        const int has = sam.find_tag(g, a.tag, &existing);
-                        if (has == 2) bail("Invalid tag value format. Expected string value.");
-                        size_t need = 0;
-                        for (;;) {
-                            int rc = mk_tag_value(mm, fpat.data() + foff[k], foff[k + 1] - foff[k], has == 1 ? existing.c_str() : nullptr,
-                                                  val.data(), val.size(), &need);
-                            if (rc == MK_E_CAPACITY) {
-                                val.resize(need + 1);
-                                continue;
-                            }
-                            mk_check(rc, "Error building tag value");
-                            break;
-                        }
-                        if (to_bam && sam.is_bam) {
-                            BamWriter::append_tagged_raw(sam.raw(g), sam.raw_len(g), a.tag, val.data(), need, out.bin[t]);
-                        } else if (to_bam) {
-                            line.clear();
-                            sam.append_line(g, line);
-                            line += '\t';
-                            line += a.tag;
-                            line += ":Z:";
-                            line.append(val.data(), need);
-                            bw.encode_record(line, out.bin[t]);
-                        } else {
-                            std::string &o = out.txt[t];
-                            sam.append_line(g, o);
-                            o += '\t';
-                            o += a.tag;
-                            o += ":Z:";
-                            o.append(val.data(), need);
-                            o += '\n';
-                        }
-                    }
-                });
-            }
-            if (ms.size() == 1) tm.mark("  batch: tag values + encode");
-            on_batch(std::move(out));
-            b0 = b1;
-        }
-    };
     // per-device counters of a --gpus N job (summed once, at the end, by RCCL)
     std::vector<mk_counters> dev_c(ms.size());
     std::vector<std::vector<uint32_t>> dev_counts(ms.size(), std::vector<uint32_t>(counts.size(), 0));
     for (auto &x : dev_c) memset(&x, 0, sizeof(x));
+    // the host loop (tag_host.cpp): the whole input where no window path applies, the rest of it where one handed over, and single
+    // windows the device refused in between (tag_windows.cpp)
+    std::vector<TagHandle> host_handles;
+    for (size_t d = 0; d < ms.size(); ++d)
+        host_handles.push_back(TagHandle{ms[d], devs[d], ms.size() == 1 ? &c : &dev_c[d], ms.size() == 1 ? &counts : &dev_counts[d]});
+    TagHostLoop host(a, sam, lg, pats, in_name, w, bw, to_bam, tm, host_handles);
     bool device_done = false;
     // BAM -> BAM (or no output at all): the records stay on the device between inflate and deflate
     // (tag_windows.cpp; two windows per device in flight, each on a handle of its own); false: a window was not for the device and the
@@ -838,44 +667,15 @@ int run_tag(const TagArgs &a, const std::vector<std::string> &argv) {
         for (int rep = 0; rep < (one_window ? 1 : 2); ++rep)
             for (size_t d = 0; d < ms.size(); ++d)
                 handles.push_back(TagHandle{rep ? seconds[d] : ms[d], devs[d], ms.size() == 1 ? &c : &dev_c[d], ms.size() == 1 ? &counts : &dev_counts[d]});
-        device_done = bam_windows       ? tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window)
-                      : bam_sam_windows ? tag_bam_sam_windows_on_device(a, sam, handles, lg, pats, in_name, w, dev_window)
-                      : to_bam          ? tag_sam_bam_windows_on_device(a, sam, handles, lg, pats, in_name, bw, dev_window)
-                                        : tag_sam_windows_on_device(a, sam, handles, lg, pats, in_name, a.suppress_output ? nullptr : &w, dev_window);
+        // (a window the device refuses is the host loop's, with the handle of the worker that had it)
+        const HostTurn turn = [&](const TagHandle &h) { host.run(&h); };
+        device_done = bam_windows       ? tag_bam_windows_on_device(a, sam, handles, lg, pats, in_name, to_bam ? &bw : nullptr, dev_window, turn)
+                      : bam_sam_windows ? tag_bam_sam_windows_on_device(a, sam, handles, lg, pats, in_name, w, dev_window, turn)
+                      : to_bam          ? tag_sam_bam_windows_on_device(a, sam, handles, lg, pats, in_name, bw, dev_window, turn)
+                                        : tag_sam_windows_on_device(a, sam, handles, lg, pats, in_name, a.suppress_output ? nullptr : &w, dev_window, turn);
         tm.mark(device_done ? "windows on the device" : "windows on the device (the rest: host reader)");
     }
-    // (the first window is small: nothing can run beside its read; the later, large ones are read beside their predecessors)
-    bool more_windows = !device_done && sam.fill(std::min<uint64_t>(window_bytes, 128ull << 20));
-    while (more_windows) {
-        const size_t n = sam.recs.size();
-        tm.mark("window: read (inflate) + index");
-        // the next window of a compressed input is inflated (device codec: the host threads are free for the batches
-        // below) and indexed beside this one; an error in it is reported after this window was written
-        std::future<void> next_window = std::async(std::launch::async, [&] { sam.prefetch(window_bytes); });
-        try {
-        if (ms.size() == 1) {
-            scan_range(m, dev_bufs[0], 0, n, c, counts, io_threads(), [&](BatchOut &&o) {
-                emit(o);
-                tm.mark("  batch: rows + write");
-            });
-        } else {
-            // --gpus N: device d scans and tags a contiguous record range of the window
-            auto outs = run_shards<std::vector<BatchOut>>(n, ms.size(), [&](size_t d, size_t lo, size_t hi, std::vector<BatchOut> &out) {
-                scan_range(ms[d], dev_bufs[d], lo, hi, dev_c[d], dev_counts[d], std::max<size_t>(1, io_threads() / ms.size()),
-                           [&](BatchOut &&o) { out.push_back(std::move(o)); });
-            });
-            tm.mark("window: scan + tag on all devices");
-            for (auto &v : outs)
-                for (auto &o : v) emit(o);
-        }
-        } catch (...) {
-            next_window.wait();  // it works on sam
-            throw;
-        }
-        tm.mark("window done");
-        next_window.get();
-        more_windows = sam.fill(window_bytes);
-    }
+    if (!device_done) host.run();
     if (ms.size() > 1) {
         comm_ready.get();
         reduce_device_counters(ms, devs, dev_c, dev_counts, c, counts);

@@ -3,6 +3,7 @@
 #pragma once
 #include <ctime>
 #include <cstdlib>
+#include <functional>
 #include <future>
 #include <string>
 #include <algorithm>
@@ -46,6 +47,28 @@ inline void add_counters(mk_counters &into, const mk_counters &from) {
 }
 inline void add_counts(std::vector<uint32_t> &into, const std::vector<uint32_t> &from) {
     for (size_t k = 0; k < from.size(); ++k) into[k] += from[k];
+}
+
+// ---- --gpus N: one matcher handle + one host thread per device, contiguous record ranges ---------
+// [lo, hi) of shard d of n units over `parts` shards, sizes differing by at most one (the same
+// rule as merkurio_amd/sharding.py): concatenating shard outputs in device order reproduces the
+// single-device output order (pairs are units, never split: src/cmd_extract.rs:463-468)
+inline std::pair<size_t, size_t> shard_range(size_t n, size_t parts, size_t d) {
+    const size_t base = n / parts, rem = n % parts;
+    const size_t lo = d * base + std::min(d, rem);
+    return {lo, lo + base + (d < rem ? 1 : 0)};
+}
+
+// A window of n records (pairs) over the devices: fn(d, lo, hi, out[d]) scans shard_range(n, N, d) on device d's own host thread and
+// keeps its results in out[d]; they come back in device order = record order, to be emitted in that order.
+template <class Result, class F>
+inline std::vector<Result> run_shards(size_t n, size_t n_dev, F fn) {
+    std::vector<Result> out(n_dev);
+    run_threads(n_dev, [&](size_t d) {
+        const auto [lo, hi] = shard_range(n, n_dev, d);
+        fn(d, lo, hi, out[d]);
+    });
+    return out;
 }
 
 struct Patterns {
@@ -110,6 +133,8 @@ struct WindowExtract {
 
 // tag_windows.cpp: BAM input whose records stay on the device (mk_tag_bam_window); bw == nullptr: no output (-S).
 // true: the whole input has been processed; false: `sam` has been positioned where the host reader has to carry on.
+// A window the device refuses is the host loop's alone: `sam` is given that window's bounds and `turn` runs the loop over them with
+// the handle of the worker that had the window, in the window's place of the output order; the windows behind it stay on the device.
 // handles: matchers with the device they live on and where their windows' counters are added (two handles per device keep two
 // windows per device in flight; window k runs on handle k mod handles.size()).
 struct SamFile;
@@ -120,19 +145,20 @@ struct TagHandle {
     mk_counters *counters;
     std::vector<uint32_t> *pattern_counts;
 };
+using HostTurn = std::function<void(const TagHandle &)>;
 bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes);
+                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes, const HostTurn &turn);
 // the same for plain (memory-mapped) SAM text -> SAM text (mk_tag_sam_window); out == nullptr: no output (-S).  The windows are cut at
 // line starts every ~window_bytes and are independent of each other.
 bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                               const std::string &in_name, Sink *out, uint64_t window_bytes);
+                               const std::string &in_name, Sink *out, uint64_t window_bytes, const HostTurn &turn);
 // the same for plain SAM text -> BAM (mk_tag_sam_bam_window): the kept lines come back as BGZF members of BAM records, encoded on the
 // device against bw's reference names (bw is open), and go to bw.put_members
 bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes);
+                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes, const HostTurn &turn);
 // BAM (BGZF members) -> SAM text / STDOUT (mk_tag_bam_sam_window): tag_bam_windows_on_device's windows, head chain and refusal (seek_bam);
 // the kept records come back as SAM lines formatted on the device and go to `out` in window order
 bool tag_bam_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                                   const std::string &in_name, Sink &out, uint64_t window_bytes);
+                                   const std::string &in_name, Sink &out, uint64_t window_bytes, const HostTurn &turn);
 
 }  // namespace cli

@@ -543,9 +543,10 @@ bool WindowSource::more_into(std::vector<char> &buf, uint64_t &buf_len, uint64_t
     if (want < (1u << 16)) want = 1u << 16;
     require_host_memory(buf_len + want + (buf_len + want) / 8, path);
     if (kind == BGZF) {
+        const size_t m_end = std::min(members.size(), member_end);
         size_t m1 = (size_t)src_pos;
         uint64_t add = 0;
-        while (m1 < members.size() && (add < want || m1 == (size_t)src_pos)) add += members[m1++].isize;
+        while (m1 < m_end && (add < want || m1 == (size_t)src_pos)) add += members[m1++].isize;
         if (buf.size() < buf_len + add) buf.resize(buf_len + add);
         std::vector<BgzfMember> part;
         uint64_t o = 0;
@@ -556,7 +557,7 @@ bool WindowSource::more_into(std::vector<char> &buf, uint64_t &buf_len, uint64_t
         if (!part.empty()) bgzf_inflate_range((const uint8_t *)src.p, part, 0, part.size(), buf.data() + buf_len, path);
         buf_len += add;
         src_pos = m1;
-        if (src_pos >= members.size()) src_eof = true;
+        if (src_pos >= m_end) src_eof = true;
         return true;
     }
     // GZIP: zlib streaming over the mapped file, concatenated members included
@@ -1200,14 +1201,15 @@ void SamFile::open(const std::string &path) {
     data = bytes();
 }
 
-void SamFile::seek_bam(size_t member, const char *head, uint64_t n_head) {
+void SamFile::seek_bam(size_t member, const char *head, uint64_t n_head, size_t end_member) {
     std::vector<char> b(head, head + n_head);  // (head may point into buf)
     buf.swap(b);
     buf_len = n_head;
     cursor = 0;
     recs.clear();
     have_next = false;
-    src.seek_member(member);
+    bam_bounded = end_member < src.n_bgzf_members();
+    src.seek_member(member, end_member);
     data = buf.data();
 }
 
@@ -1232,7 +1234,7 @@ bool SamFile::next_window(std::vector<char> &b, uint64_t &bl, uint64_t &cur, std
         SamFile part;  // (the parsers append to a SamFile's records)
         part.is_bam = is_bam;
         if (is_bam) {
-            cur = parse_bam_records(d, n, cur, std::min<uint64_t>(n, cur + window_bytes), !src.exhausted(), part);
+            cur = parse_bam_records(d, n, cur, std::min<uint64_t>(n, cur + window_bytes), !src.exhausted() || bam_bounded, part);
         } else {
             uint64_t stop = std::min(n, cur + window_bytes);
             if (stop < n) stop = std::min(line_end(d, n, stop > 0 ? stop - 1 : 0) + 1, n);  // first line start at or after
@@ -1249,8 +1251,8 @@ bool SamFile::next_window(std::vector<char> &b, uint64_t &bl, uint64_t &cur, std
         }
         if (src.exhausted() && cur >= n) return false;
         if (src.exhausted()) {  // bytes are left that are no record
-            if (is_bam) bail("Error during BAM record parsing: truncated file");
-            return false;
+            if (is_bam && !bam_bounded) bail("Error during BAM record parsing: truncated file");
+            return false;  // (BAM with an end: the record that crosses it stays behind `cur`)
         }
         src.more_into(b, bl, std::max<uint64_t>(window_bytes, bl));  // one record larger than the window
     }
@@ -1291,7 +1293,7 @@ bool SamFile::fill(uint64_t window_bytes) {
     recs.clear();
     for (;;) {
         const char *d = src.text();
-        const uint64_t n = src.text_size();
+        const uint64_t n = std::min<uint64_t>(src.text_size(), text_end);
         data = d;
         if (cursor >= n) return false;
         if (is_bam) {

@@ -3,6 +3,7 @@
 // (SURVEY.md §5): needletail 0.6.3 for FASTA/FASTQ (src/cmd_extract.rs:281,327-340,403) and
 // bam 0.1.4 for SAM/BAM (src/cmd_tag.rs:470-497,503-615).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <condition_variable>
 #include <deque>
@@ -150,9 +151,11 @@ struct WindowSource {
     void bgzf_member_at(size_t i, uint64_t *data_off, uint32_t *data_len, uint32_t *isize, uint32_t *crc) const {
         *data_off = members[i].data_off, *data_len = (uint32_t)members[i].data_len, *isize = members[i].isize, *crc = members[i].crc;
     }
-    void seek_member(size_t i) {
+    // (end: more_into() stops in front of member `end`, as if the file ended there)
+    void seek_member(size_t i, size_t end = ~(size_t)0) {
         src_pos = i;
-        src_eof = i >= members.size();
+        member_end = end;
+        src_eof = i >= std::min(members.size(), member_end);
     }
     size_t next_member() const { return (size_t)src_pos; }  // BGZF: the first member more_into() has not inflated yet
     ~WindowSource();
@@ -169,6 +172,7 @@ struct WindowSource {
     uint64_t src_pos = 0;  // GZIP: next compressed byte; BGZF: next member
     struct Member { uint64_t data_off, data_len; uint32_t isize, crc; };
     std::vector<Member> members;
+    size_t member_end = ~(size_t)0;  // BGZF: seek_member()'s end
 };
 
 // A FASTA/FASTQ input read window by window (needletail's parse_fastx_file streams records:
@@ -273,21 +277,24 @@ struct SamFile {
     // BAM input for a caller that keeps the records on the device (run_tag: mk_tag_bam_window takes windows of members as they are
     // stored).  After open(): the file and its member table (source()), the bytes open() inflated behind the header but has not
     // turned into records (the first window's head), and the first member it has not touched.  seek_bam() hands the input back to
-    // fill(): the records continue with head[0, n_head) followed by the text of member `member` onwards.
+    // fill(): the records continue with head[0, n_head) followed by the text of member `member` onwards -- up to member `end_member`
+    // where one is given: fill() then returns false in front of the record that crosses into it, which bam_pending() hands out
+    // (the next window's head); an end at or behind the last member is the end of the file, where such a record is an error.
     bool bam_on_bgzf() const { return is_bam && src.is_bgzf(); }
     const WindowSource &source() const { return src; }
     const char *bam_pending(uint64_t *n) const {
         *n = buf_len > cursor ? buf_len - cursor : 0;
         return buf.data() + cursor;
     }
-    void seek_bam(size_t member, const char *head, uint64_t n_head);
+    void seek_bam(size_t member, const char *head, uint64_t n_head, size_t end_member = ~(size_t)0);
     // plain SAM text for a caller that keeps the lines on the device (run_tag: mk_tag_sam_window takes slices of the mapping): after
     // open(), text_cursor() = the first byte behind the header lines; seek_text() hands the input back to fill(): the records
-    // continue at byte `offset` of the text (a line start).
+    // continue at byte `offset` of the text (a line start) and, where `end` is given (a line start too), end in front of it.
     bool sam_on_mapping() const { return !is_bam && src.mapped() && src.is_file_mapping(); }
     uint64_t text_cursor() const { return cursor; }
-    void seek_text(uint64_t offset) {
+    void seek_text(uint64_t offset, uint64_t end = ~0ull) {
         cursor = offset;
+        text_end = end;
         recs.clear();
     }
 
@@ -296,6 +303,8 @@ struct SamFile {
     std::vector<char> buf;  // compressed input: the window
     uint64_t buf_len = 0;
     uint64_t cursor = 0;    // mapped input: next unread byte; compressed: bytes of the window already turned into records
+    uint64_t text_end = ~0ull;  // mapped input: seek_text()'s end
+    bool bam_bounded = false;   // seek_bam() was given an end in front of the last member: an unfinished record there is no error
     const char *bytes() const { return src.mapped() ? src.text() : buf.data(); }
     uint64_t n_bytes() const { return src.mapped() ? src.text_size() : buf_len; }
     void drop_front(uint64_t k);

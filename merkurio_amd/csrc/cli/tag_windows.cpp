@@ -3,22 +3,29 @@
 // sides followed by one of two output sides; the library's entry point in between (mk_tag_bam_window, mk_tag_sam_window,
 // mk_tag_sam_bam_window, mk_tag_bam_sam_window) inflates or uploads, indexes the records, scans, tags and encodes on the device, so the
 // text crosses the host boundary once in each direction at most, and what comes back goes to the file as it is.  All four share one driver:
-// tag_windows cuts the windows, packs the reference names, makes a Worker<input, output, window struct> per handle and seeks the reader
-// on refusal; run_windows is the round-robin over the workers, the repeat of a call that asked for more room, the emit turn (results
-// leave in window order; the writer thread writes window k - 1 meanwhile), refusal and error bookkeeping, counters and log rows.
+// tag_windows cuts the windows, packs the reference names and makes a Worker<input, output, window struct> per handle; run_windows is
+// the round-robin over the workers, the repeat of a call that asked for more room, the emit turn (results leave in window order; the
+// writer thread writes window k - 1 meanwhile), the host turn of a refused window, error bookkeeping, counters and log rows.
+//
+// A WINDOW THE DEVICE REFUSES IS THE HOST LOOP'S, AND ONLY THAT WINDOW: when its emit turn comes, the reader is given the window's
+// bounds and the host loop (tag_host.cpp: the code of --host-ingest) runs over them with the worker's own handle; its output, counters
+// and log rows land where the window's would have, and the windows behind it stay on the device.  After kRefusedInARow = 4 refused
+// windows in a row the last of them gets no turn: the reader is put at its first byte and the host loop keeps the rest of the file.
 //
 // MemberInput (BAM): a window is a run of BGZF members AS THEY ARE STORED, copied into page-locked memory (a mapped file is not a DMA
 // source), behind a head: window k + 1 starts with the unfinished record window k ended with -- its TAIL, known right after k's record
 // index (on_tail).  Two windows per device are in flight, each on a handle (and stream) of its own (--gpus N: consecutive windows on
 // different devices), so k + 1's staging, upload and inflate run beside k's scan, tag and output.  A window the device refuses -- a
 // record that fails the parser's checks, optional fields that do not parse, a kept record whose field of the tag's name is not a plain
-// string, a damaged member -- hands the input back to the host reader AT THAT WINDOW'S FIRST BYTE, with the head it was given
-// (SamFile::seek_bam).  (The window behind it may have been started already: its results are dropped.)
+// string, a damaged member -- is read by the host loop from the head it was given to the record that crosses its end (SamFile::seek_bam
+// with an end member).  Window k + 1 never starts before its head is known: from on_tail, or, where window k was refused before its
+// record index, from the bytes window k's host turn stopped in front of.  So a window behind a refused one always ran with its true
+// head and stands.
 //
 // LineInput (plain SAM text): a window is a slice of the memory-mapped file cut at a line start (a '\n' can be found without reading
 // the lines), staged through a page-locked buffer: no heads or tails, the windows are INDEPENDENT.  A refused window (a line with fewer
-// than 10 fields, a kept record whose field of the tag's name is not a plain string) hands the input back to the host loop at its first
-// byte (SamFile::seek_text).
+// than 10 fields, a kept record whose field of the tag's name is not a plain string) is [wins[k].first, wins[k + 1].first) of the
+// mapping to the host loop (SamFile::seek_text with an end).
 //
 // MembersOutput (BAM, or nothing with -S on BAM input): the kept records come back as finished BGZF members in a buffer of the
 // BamWriter's and go to BamWriter::put_members.  From lines they are encoded on the device against the @SQ names the writer's header
@@ -50,30 +57,41 @@ void copy_in(const uint8_t *file, uint64_t lo, uint64_t hi, uint8_t *dst) {
 }
 
 // what the workers share: whose turn it is to emit, and how the job ends early
+constexpr size_t kRefusedInARow = 4;  // R: after so many refused windows in a row the rest of the file is the host loop's
+
 struct Pipe {
     std::mutex mu;
     std::condition_variable cv;
     size_t emit_turn = 0;         // windows before this one have been emitted
-    bool stop = false;            // a window was refused or failed: nothing further is emitted
-    size_t refused = ~(size_t)0;  // the window the host reader takes over at
+    bool stop = false;            // the job ends here (an error) or goes to the host loop (`refused`): nothing further is emitted
+    size_t refused = ~(size_t)0;  // the window the host loop takes the rest of the file over at (the R-th refused one in a row)
     std::string error;
+    size_t n_device = 0, n_host = 0;  // windows the device emitted | the host loop took: in turns, and behind a hand-over
+    size_t refused_in_a_row = 0;
+    struct Left {
+        size_t k;
+        int rc;  // what the window returned
+        uint32_t status;
+    };
+    std::vector<Left> left;  // the windows the device refused
     // BAM's head chain: window k + 1 starts with window k's tail, reported by the library as soon as it is known (on_tail)
     size_t heads_ready = 0;  // the head of window `heads_ready` is in `head` (windows before it have theirs already)
     std::vector<uint8_t> head;
-    std::vector<uint8_t> refused_head;  // the head the refused window was given
-    int refused_rc = MK_OK;  // what the refused window returned
-    uint32_t refused_status = 0;
+    std::vector<uint8_t> refused_head;  // the head window `refused` was given
 };
 
 // One worker per handle: window k runs on worker k mod n_workers (with the handles of several devices in a row, consecutive windows
 // go to different devices).  `make(id)` gives worker id its format's state W: W.w is the library's window struct (tag and keep rule
 // filled in here), W.load(k) puts window k's input where the device reads it (false: the job has been stopped), W.call(...) runs the
-// window, W.grow() makes the room for tail and output that a call asked for, W.write() hands the output on, W.refused(k, rc, status)
-// notes a window left to the host reader (pipe.mu held).  Results leave in window order, and after `stop` none do; a worker holds
-// one finished window at most while it waits for its turn.  Ends with bail() on the first error.
+// window, W.grow() makes the room for tail and output that a call asked for, W.write() hands the output on.  A window the device
+// refuses waits for its turn like any other and then has the host loop run over its bounds (W.host_turn) where its output would have
+// gone: the loop's bytes, counters, per-pattern counts and log rows land in window order, the workers behind go on.  The
+// kRefusedInARow-th refused window in a row is not run but noted (W.refused, pipe.mu held) and ends the windows: the host loop takes
+// the file from its first byte.  Results leave in window order, and after `stop` none do; a worker holds one finished window at most
+// while it waits for its turn.  The first error is left in pipe.error.
 template <class Make>
 void run_windows(const TagArgs &a, Pipe &pipe, size_t n_win, size_t n_workers, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                 const std::string &in_name, double (&t_dev)[8], Make make) {
+                 const std::string &in_name, double (&t_dev)[8], const HostTurn &turn, Make make) {
     auto worker = [&](size_t id) {
         auto W = make(id);
         std::vector<uint8_t> names(1u << 16);
@@ -111,13 +129,36 @@ void run_windows(const TagArgs &a, Pipe &pipe, size_t n_win, size_t n_workers, c
             std::unique_lock<std::mutex> lk(pipe.mu);
             pipe.cv.wait(lk, [&] { return pipe.stop || pipe.emit_turn == k; });
             if (pipe.stop) return;  // (an earlier window ended the job: this one's results are dropped)
-            if (refused || !err.empty()) {
-                pipe.stop = true;
-                if (refused) pipe.refused = k, W.refused(k, rc, status);
-                else pipe.error = err;
+            if (!err.empty()) {
+                pipe.stop = true, pipe.error = err;
                 pipe.cv.notify_all();
                 return;
             }
+            if (refused) {
+                pipe.left.push_back({k, rc, status});
+                if (++pipe.refused_in_a_row >= kRefusedInARow) {
+                    pipe.stop = true, pipe.refused = k, pipe.n_host += n_win - k;
+                    W.refused();
+                    pipe.cv.notify_all();
+                    return;
+                }
+                lk.unlock();
+                // (only the worker whose turn it is gets here: the reader, the loggers and the output are its alone)
+                std::string turn_err;
+                try {
+                    W.host_turn(k, [&] { turn(handles[id]); });
+                } catch (const Error &e) {
+                    turn_err = e.what()[0] ? e.what() : "error";
+                }
+                lk.lock();
+                ++pipe.n_host;
+                if (!turn_err.empty()) pipe.stop = true, pipe.error = turn_err;
+                pipe.emit_turn = k + 1;
+                pipe.cv.notify_all();
+                if (pipe.stop) return;
+                continue;
+            }
+            pipe.refused_in_a_row = 0;
             lk.unlock();
             // (only the worker whose turn it is gets here: the counters of its device, the loggers and the output are its alone)
             add_counters(*handles[id].counters, wc);
@@ -139,6 +180,7 @@ void run_windows(const TagArgs &a, Pipe &pipe, size_t n_win, size_t n_workers, c
             }
             lk.lock();
             if (!emit_err.empty()) pipe.stop = true, pipe.error = emit_err;
+            else ++pipe.n_device;
             pipe.emit_turn = k + 1;
             pipe.cv.notify_all();
             if (pipe.stop) return;
@@ -155,13 +197,13 @@ void run_windows(const TagArgs &a, Pipe &pipe, size_t n_win, size_t n_workers, c
             pipe.cv.notify_all();
         }
     });
-    if (!pipe.error.empty()) bail(pipe.error);
 }
 
 // ---- the input sides.  An input cuts the job's windows (cut), copies window k to where the device reads it (stage), fills the window
 // struct's input fields (fill; false: the job has been stopped), says how much text the window holds for the output's room (text_bytes),
-// places the tail (aim), follows a call (done: one that went well; grow: one that asked for more room; refused) and puts the reader
-// where the device stopped (seek; k = the refused window, ~0: none)
+// places the tail (aim), follows a call (done: one that went well; grow: one that asked for more room; refused: one that ends the
+// windows), gives the reader the bounds of a window that is the host loop's and runs it (host_turn) and puts the reader where the
+// windows stopped (seek; k = the window of the hand-over, ~0: none)
 struct TailCtx {
     Pipe *pipe;
     size_t k;
@@ -191,6 +233,7 @@ struct MemberInput {
     const Windows &wins;
     const uint8_t *file;
     Pipe &pipe;
+    SamFile &sam;
     HostBuffer stage_buf;  // the window's members (page-locked)
     std::vector<uint8_t> tail = std::vector<uint8_t>(1u << 20), head;
     TailCtx tctx{};
@@ -273,6 +316,21 @@ struct MemberInput {
         return true;
     }
     void refused() { pipe.refused_head = head; }  // (the head the window was given, not the current one)
+    // The head the window was given, then its members; the loop stops in front of the record that crosses the window's end.  That
+    // record's first bytes are window k + 1's head: where the device got as far as its record index they are the tail it has
+    // reported already (the same chain walked by the same rule: window k + 1 stands, and may be running), where it did not (a record
+    // chain it could not prove, an unfinished record, a damaged member) window k + 1 has been waiting for them.  Either way no
+    // window ever starts with a head that is not the true one, so none has to be run again.  (on_tail's `heads_ready != k` guard is
+    // what makes the second publication a no-op: once the device's tail has moved heads_ready to k + 1, window k + 1 may already
+    // have published window k + 2's head into pipe.head, and the bytes handed in here must not overwrite it.)
+    template <class Run>
+    void host_turn(size_t k, Run run) {
+        sam.seek_bam(wins[k].m0, (const char *)head.data(), head.size(), wins[k].m1);
+        run();
+        uint64_t n_left = 0;
+        const char *left = sam.bam_pending(&n_left);
+        on_tail(&tctx, (const uint8_t *)left, n_left);
+    }
 };
 
 // SAM text: windows cut at line starts have no heads or tails and are independent
@@ -283,6 +341,7 @@ struct LineInput {
     const Windows &wins;
     const uint8_t *file;
     Pipe &pipe;
+    SamFile &sam;
     HostBuffer stage_buf;  // the window's text (page-locked)
     uint8_t no_tail[8];
 
@@ -327,6 +386,11 @@ struct LineInput {
         return false;
     }
     void refused() {}
+    template <class Run>
+    void host_turn(size_t k, Run run) {
+        sam.seek_text(wins[k].first, wins[k].second);
+        run();
+    }
 };
 
 // ---- the output sides.  An output makes room for what `text` bytes of window text may turn into (room: a guess -- a window that does
@@ -449,9 +513,10 @@ struct Worker {
         const bool tail_grew = in.grow(w), out_grew = out.grow(w, In::error);
         return tail_grew || out_grew;
     }
-    void refused(size_t, int rc, uint32_t status) {
-        in.refused();
-        in.pipe.refused_rc = rc, in.pipe.refused_status = status;
+    void refused() { in.refused(); }
+    template <class Run>
+    void host_turn(size_t k, Run run) {
+        in.host_turn(k, run);
     }
     void write() { out.write(w); }
 };
@@ -472,6 +537,8 @@ const Direction kSamBam = {" SAM text -> BAM", {"upload", "line index + fields",
 const Direction kBamSam = {" BAM -> SAM text", {"upload", "inflate", "record index", "unpack + scan + sets", "tag + format", "download"}, "loop",
                            {"record chain", "a record the device does not format", "existing tag", "unfinished record"}};
 
+// (the row's first number is the windows the DEVICE emitted -- a window's host turn is not one of them --, and the rows are printed
+// before an error ends the job: a window whose turn bailed still has its `left to the host` row in front of the error message)
 void report(const Direction &D, const Pipe &pipe, size_t n_win, size_t n_workers, const double (&t_dev)[8]) {
     std::string row;
     char buf[64];
@@ -479,20 +546,26 @@ void report(const Direction &D, const Pipe &pipe, size_t n_win, size_t n_workers
         snprintf(buf, sizeof(buf), "%s %.3f", D.phases[i], t_dev[i] / 1e3);
         row += (i ? ", " : "") + std::string(buf);
     }
-    fprintf(stderr, "[timing] %llu of %llu%s windows on the device (%llu in flight): %s s (of these, growing device buffers: %.3f s)\n",
-            (unsigned long long)pipe.emit_turn, (unsigned long long)n_win, D.title, (unsigned long long)n_workers, row.c_str(), t_dev[7] / 1e3);
-    if (pipe.refused == ~(size_t)0) return;
-    const char *why = pipe.refused_rc == MK_E_CORRUPT ? "a damaged member" : D.reasons[3];
-    for (int bit = 2; bit >= 0 && pipe.refused_rc != MK_E_CORRUPT; --bit)
-        if ((pipe.refused_status >> bit & 1) && D.reasons[bit]) why = D.reasons[bit];
-    fprintf(stderr, "[timing] window %llu left to the host %s (%s)\n", (unsigned long long)pipe.refused, D.left_to, why);
+    fprintf(stderr,
+            "[timing] %llu of %llu%s windows on the device (%llu in flight): %s s (of these, growing device buffers: %.3f s); windows: %llu on the device, "
+            "%llu on the host\n",
+            (unsigned long long)pipe.n_device, (unsigned long long)n_win, D.title, (unsigned long long)n_workers, row.c_str(), t_dev[7] / 1e3,
+            (unsigned long long)pipe.n_device, (unsigned long long)pipe.n_host);
+    for (const Pipe::Left &x : pipe.left) {
+        const char *why = x.rc == MK_E_CORRUPT ? "a damaged member" : D.reasons[3];
+        for (int bit = 2; bit >= 0 && x.rc != MK_E_CORRUPT; --bit)
+            if ((x.status >> bit & 1) && D.reasons[bit]) why = D.reasons[bit];
+        fprintf(stderr, "[timing] window %llu left to the host %s (%s)%s\n", (unsigned long long)x.k, D.left_to, why,
+                x.k == pipe.refused ? " with every window behind it" : "");
+    }
 }
 
 // The driver of all four directions.  `target`: where the output side sends (nullptr: -S); names: the reference names the direction's
-// entry point takes (nullptr: none).  false: a window was not for the device and the reader stands at its first byte.
+// entry point takes (nullptr: none); turn: the host loop over what the reader has been bounded to (a refused window).  false: the
+// kRefusedInARow-th window in a row was not for the device and the reader stands at its first byte.
 template <class In, class Out, class Win, class Target>
 bool tag_windows(const Direction &D, const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                 const std::string &in_name, Target *target, const std::vector<std::string> *names, uint64_t window_bytes) {
+                 const std::string &in_name, Target *target, const std::vector<std::string> *names, uint64_t window_bytes, const HostTurn &turn) {
     const uint8_t *file = In::bytes(sam.source());
     Pipe pipe;
     const typename In::Windows wins = In::cut(sam, pipe, window_bytes);
@@ -507,12 +580,13 @@ bool tag_windows(const Direction &D, const TagArgs &a, SamFile &sam, const std::
     // (window k runs on handle k mod n_workers: with the handles of several devices in a row, consecutive windows go to different devices)
     const size_t n_workers = std::max<size_t>(1, std::min<size_t>(handles.size(), n_win));
     double t_dev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev, [&](size_t id) {
+    run_windows(a, pipe, n_win, n_workers, handles, lg, pats, in_name, t_dev, turn, [&](size_t id) {
         mk_codec *codec = nullptr;
         if (!std::is_same<Win, mk_sam_window>::value && mk_codec_create(handles[id].device, &codec) != MK_OK) bail(std::string(In::error) + mk_last_error());
-        return Worker<In, Out, Win>{In{wins, file, pipe}, Out(target, In::is_bam, !a.filter_matching && !a.invert_match), refs, handles[id].m, codec};
+        return Worker<In, Out, Win>{In{wins, file, pipe, sam}, Out(target, In::is_bam, !a.filter_matching && !a.invert_match), refs, handles[id].m, codec};
     });
     if (getenv("MERKURIO_TIMING")) report(D, pipe, n_win, n_workers, t_dev);
+    if (!pipe.error.empty()) bail(pipe.error);
     In::seek(sam, wins, pipe, pipe.refused);
     return pipe.refused == ~(size_t)0;
 }
@@ -520,23 +594,23 @@ bool tag_windows(const Direction &D, const TagArgs &a, SamFile &sam, const std::
 }  // namespace
 
 bool tag_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes) {
-    return tag_windows<MemberInput, MembersOutput, mk_bam_window>(kBamBam, a, sam, handles, lg, pats, in_name, bw, nullptr, window_bytes);
+                               const std::string &in_name, BamWriter *bw, uint64_t window_bytes, const HostTurn &turn) {
+    return tag_windows<MemberInput, MembersOutput, mk_bam_window>(kBamBam, a, sam, handles, lg, pats, in_name, bw, nullptr, window_bytes, turn);
 }
 
 bool tag_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                               const std::string &in_name, Sink *out_sink, uint64_t window_bytes) {
-    return tag_windows<LineInput, TextOutput, mk_sam_window>(kSamSam, a, sam, handles, lg, pats, in_name, out_sink, nullptr, window_bytes);
+                               const std::string &in_name, Sink *out_sink, uint64_t window_bytes, const HostTurn &turn) {
+    return tag_windows<LineInput, TextOutput, mk_sam_window>(kSamSam, a, sam, handles, lg, pats, in_name, out_sink, nullptr, window_bytes, turn);
 }
 
 bool tag_sam_bam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes) {
-    return tag_windows<LineInput, MembersOutput, mk_sam_bam_window>(kSamBam, a, sam, handles, lg, pats, in_name, &bw, &bw.ref_names, window_bytes);
+                                   const std::string &in_name, BamWriter &bw, uint64_t window_bytes, const HostTurn &turn) {
+    return tag_windows<LineInput, MembersOutput, mk_sam_bam_window>(kSamBam, a, sam, handles, lg, pats, in_name, &bw, &bw.ref_names, window_bytes, turn);
 }
 
 bool tag_bam_sam_windows_on_device(const TagArgs &a, SamFile &sam, const std::vector<TagHandle> &handles, Loggers &lg, const Patterns &pats,
-                                   const std::string &in_name, Sink &out_sink, uint64_t window_bytes) {
-    return tag_windows<MemberInput, TextOutput, mk_bam_sam_window>(kBamSam, a, sam, handles, lg, pats, in_name, &out_sink, &sam.ref_names, window_bytes);
+                                   const std::string &in_name, Sink &out_sink, uint64_t window_bytes, const HostTurn &turn) {
+    return tag_windows<MemberInput, TextOutput, mk_bam_sam_window>(kBamSam, a, sam, handles, lg, pats, in_name, &out_sink, &sam.ref_names, window_bytes, turn);
 }
 
 }  // namespace cli

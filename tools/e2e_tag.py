@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """End-to-end wall time of `merkurio tag` on synthetic SAM / BAM (host codec + PCIe + scan + write).
-usage: tools/e2e_tag.py [n_records] [n_patterns] [one record in N carries a k-mer, default 100] [--bam-sam REPS]
+usage: tools/e2e_tag.py [n_records] [n_patterns] [one record in N carries a k-mer, default 100] [--bam-sam REPS] [--odd]
 --bam-sam REPS: only the BAM -> SAM shapes (everything kept, -m, -m -j), each REPS times on the window path and with --host-ingest in
-turn; medians with ranges, and the window path's own [timing] row of each shape's last run (profiles/e2e_tag_bam_sam_window.txt)"""
+turn; medians with ranges, and the window path's own [timing] row of each shape's last run (profiles/e2e_tag_bam_sam_window.txt)
+--odd: one kept record in the middle of the second 240 MiB window carries XE:f:1e-05, a float the device does not format: that window
+is the host loop's, the others stay on the device (tools/e2e_tag_window_turn.py times that against the clean file)"""
 import os, statistics, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 bam_sam_reps = 0
+odd = "--odd" in sys.argv
+if odd:
+    sys.argv.remove("--odd")
 if "--bam-sam" in sys.argv:
     k = sys.argv.index("--bam-sam")
     bam_sam_reps = int(sys.argv[k + 1])
@@ -36,7 +41,12 @@ rec[:, P + L + 1:P + 2 * L + 1] = ord("I")
 rec[:, -1] = ord("\n")
 with open(sam, "wb") as f:
     f.write(b"@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:chr1\tLN:2000000\n")
-    rec.tofile(f)
+    # (--odd: a BAM record of these lines takes ~281 bytes; a record with a k-mer, so that -m keeps it)
+    odd_at = min(n - 1, int(1.5 * (240 << 20) / 281)) // every * every if odd else n
+    rec[:odd_at].tofile(f)
+    if odd:
+        f.write(rec[odd_at, :-1].tobytes() + b"\tXE:f:1e-05\n")
+        rec[odd_at + 1:].tofile(f)
 open(km, "wb").write(b"\n".join(p.tobytes() for p in pats) + b"\n")
 print(f"generated {n} records ({os.path.getsize(sam) / 1e6:.0f} MB SAM) in {time.time() - t0:.1f} s", flush=True)
 binp = os.environ.get("MERKURIO_BIN") or os.path.join(ROOT, "merkurio_amd", "lib", "merkurio")

@@ -3,7 +3,10 @@
 path (mk_tag_sam_window, the default) against --host-ingest (the host loop) in the same job, and the window path at several
 --window-mb.  Shapes: -m with one record in `every` carrying a k-mer, everything kept, -S -j.
 --bam: SAM -> BAM instead (mk_tag_sam_bam_window against the host loop; shapes: everything kept, -m, -m -j; sweep 64 / 128 / 240).
-usage: tools/e2e_tag_sam.py [n_records] [n_patterns] [every, default 5] [runs, default 5] [--sweep] [--bam] [--keep]"""
+--odd: one kept record in the middle of the second 64 MiB window is one the device refuses (SAM -> SAM: an existing km value of 2 049
+bytes; --bam: XF:f:1e-45): that window is the host loop's, the others stay on the device (tools/e2e_tag_window_turn.py times that
+against the clean file)
+usage: tools/e2e_tag_sam.py [n_records] [n_patterns] [every, default 5] [runs, default 5] [--sweep] [--bam] [--keep] [--odd]"""
 import os, statistics, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +39,12 @@ with open(sam, "wb") as f:
         rec[:, P + L + 1:P + 2 * L + 1] = ord("I")
         rec[:, P + 2 * L + 1:-1] = np.frombuffer(b"\tNM:i:0", dtype=np.uint8)
         rec[:, -1] = ord("\n")
+        odd_at = min(n - 1, int(1.5 * (64 << 20) / rec.shape[1])) // every * every if "--odd" in sys.argv else n
+        if c0 <= odd_at < c0 + m:
+            rec[:odd_at - c0].tofile(f)
+            f.write(rec[odd_at - c0, :-1].tobytes() + (b"\tXF:f:1e-45" if "--bam" in sys.argv else b"\tkm:Z:" + b"A" * 2049) + b"\n")
+            rec[odd_at - c0 + 1:].tofile(f)
+            continue
         rec.tofile(f)
 print(f"generated {n} records ({os.path.getsize(sam) / 1e6:.0f} MB SAM), one in {every} with a k-mer, {npat} 31-mers, in {time.time() - t0:.1f} s", flush=True)
 binp = os.environ.get("MERKURIO_BIN") or os.path.join(ROOT, "merkurio_amd", "lib", "merkurio")
