@@ -156,7 +156,12 @@ typedef struct {
     uint32_t force_stride;        /* 0 = geometry rule; else sampling stride 1, 2, 4, 8 or 16 */
     uint32_t force_global_filter; /* 1 = level-1 filter in global memory even for small sets */
     uint32_t gbloom_log2_blocks;  /* 0 = rule; else log2 of the number of 64-bit blocks of a global filter */
-    uint32_t tile_run;            /* 0 = rule; else 1..8 consecutive 31 KiB tiles a scan wave takes before it jumps ahead */
+    uint32_t tile_run;            /* 0 = rule; else R in 1..8: a scan wave's long tiles are 32 R - 1 KiB + a 1 KiB halo (mk_scan_tile_geometry).
+                                   * A test hook.  On a text so short that the grid is not full (fewer 31 KiB tiles than 16 waves per compute
+                                   * unit), a forced R > 1 launches only as many workgroups (of 16 waves) as the text has long tiles for,
+                                   * at least one, so that the forced length is what runs; on any longer text of less than one round of
+                                   * long tiles the grid stays full and all of it runs in 31 KiB tiles.  R is shortened where the device's wave
+                                   * count times the tile length would exceed 1 GiB (mk_matcher_scan_geometry reports what ran). */
     uint32_t gbloom_kib;          /* 0 = rule; else size of a global filter in KiB (any size, overrides gbloom_log2_blocks) */
     /* length classes (ABI 4).  A set whose shortest pattern is much shorter than the rest is split by length: the
      * short patterns get their own stride and q-gram table next to the main filter (one pass, one kernel). */
@@ -297,6 +302,26 @@ int mk_matcher_order_stats(const mk_matcher *m, uint64_t calls[4]);
  * launch geometry (for profiling / roofline bookkeeping) */
 const char *mk_matcher_kernel_name(const mk_matcher *m);
 int mk_matcher_launch_info(const mk_matcher *m, uint32_t *grid_blocks, uint32_t *block_threads, uint32_t *lds_bytes);
+/* How a scan launch cuts its text into wave tiles (host arithmetic only, no device needed).  Tile i belongs to scan
+ * wave i mod n_waves.  Tiles [0, n_long_tiles) are long_tile_bytes long and lie back to back from byte 0: a whole
+ * number of rounds (n_long_tiles is a multiple of n_waves).  Tiles [n_long_tiles, n_long_tiles + n_short_tiles) follow
+ * them, short_tile_bytes each (15 .. 31 KiB, the length that loads the busiest wave least): less than one round of long tiles.  [tail_start, n_bytes) is scanned with guarded loads,
+ * one 1 KiB chunk per wave.  A tile is fetched with *_tile_loads loads of 1 KiB, one more than it has KiB: the last
+ * one is the next tile's first KiB, so the scan streams n_bytes + 1 KiB per tile.  tile_run = R in 1..8: long tiles of
+ * 32 R - 1 KiB; R = 1 is one region of 31 KiB tiles (n_long_tiles = 0); 0 = the R that a scan picks by itself for this
+ * text and these waves (returned in tile_run). */
+typedef struct {
+    uint64_t n_waves;
+    uint64_t n_long_tiles, long_tile_bytes;
+    uint64_t n_short_tiles, short_tile_bytes;
+    uint64_t tail_start;
+    uint32_t long_tile_loads, short_tile_loads;
+    uint32_t tile_run;
+    uint32_t reserved;
+} mk_tile_geometry;
+int mk_scan_tile_geometry(uint64_t n_bytes, uint64_t n_waves, uint32_t tile_run, mk_tile_geometry *out);
+/* the geometry of the last mk_scan_device on this handle (tile_run: the R its rule picked, or the forced one) */
+int mk_matcher_scan_geometry(const mk_matcher *m, mk_tile_geometry *out);
 /* Per-launch kernel timing with hipEvents recorded on the launch stream immediately before
  * and after the scan kernel (not around the buffer clears).  enable_timing(slots) keeps the
  * last `slots` launches; kernel_times() waits for them, returns their durations in ms

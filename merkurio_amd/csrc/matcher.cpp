@@ -578,6 +578,34 @@ int mk_matcher_filter_mode(const mk_matcher *m, uint32_t *in_lds, uint64_t *filt
     return MK_OK;
 }
 
+static void export_geometry(const TileGeometry &g, uint64_t n_waves, uint32_t run, mk_tile_geometry *out) {
+    out->n_waves = n_waves;
+    out->n_long_tiles = g.n_long;
+    out->long_tile_bytes = g.long_bytes;
+    out->n_short_tiles = g.n_short;
+    out->short_tile_bytes = g.short_bytes;
+    out->tail_start = g.tail_start;
+    out->long_tile_loads = g.long_loads;
+    out->short_tile_loads = g.short_loads;
+    out->tile_run = run;
+    out->reserved = 0;
+}
+
+int mk_scan_tile_geometry(uint64_t n_bytes, uint64_t n_waves, uint32_t tile_run, mk_tile_geometry *out) {
+    if (!out) return fail(MK_E_INVALID_ARG, "null geometry");
+    if (n_waves == 0 || tile_run > kMaxTileRun)
+        return fail(MK_E_INVALID_ARG, "tile geometry: %llu waves, tile_run %u (0..8)", (unsigned long long)n_waves, tile_run);
+    if (tile_run == 0) tile_run = tile_run_rule(n_bytes, n_waves);
+    export_geometry(tile_geometry(n_bytes, n_waves, tile_run), n_waves, tile_run, out);
+    return MK_OK;
+}
+
+int mk_matcher_scan_geometry(const mk_matcher *m, mk_tile_geometry *out) {
+    if (!m || !out) return fail(MK_E_INVALID_ARG, "null argument");
+    export_geometry(m->last_geo, (uint64_t)m->last_grid * (kBlockThreads / 64), m->last_run, out);
+    return MK_OK;
+}
+
 int mk_scan_device(mk_matcher *m, const void *d_seq, uint64_t n_bytes, const void *d_seq_off, uint64_t n_rec,
                    uint32_t mode, void *d_rec_flags, void *d_hits, uint64_t hits_cap, void *d_n_hits,
                    void *d_counters, void *stream) {
@@ -639,11 +667,28 @@ int mk_scan_device(mk_matcher *m, const void *d_seq, uint64_t n_bytes, const voi
     if (blocks > (uint64_t)m->num_cus) blocks = m->num_cus;
     p.stage = m->d_stage;
     p.rec_per_byte = (double)n_rec / (double)n_bytes;
-    // tiles a wave scans back to back before it jumps ahead by n_waves * run tiles: runs of 4 keep a wave
-    // inside one 2 MiB page for 124 KiB (-4 % on 15 GB batches, profiles/r02_tile_run.txt); small batches
-    // keep runs short so that every wave still gets tiles
-    const uint64_t tiles_per_wave = n_tiles / (blocks * waves_per_block);
-    p.tile_run = m->tile_run ? m->tile_run : tiles_per_wave >= 16 ? 4 : tiles_per_wave >= 8 ? 2 : 1;
+    // Tile length of this launch: R = 8 makes a tile 255 scanned chunks + 1 halo chunk instead of 31 + 1, so a wave
+    // stays inside one 2 MiB page for 255 KiB and the halo chunks -- fetched twice -- are 1 KiB in 256 of the stream
+    // instead of 1 in 32.  R is picked from the 31-chunk tiles available per wave: small batches keep tiles short so
+    // that every wave still gets some.  Long tiles cover whole rounds only, what is left goes round in tiles of 15 .. 31
+    // chunks (tile_geometry.hpp), so no batch size ends on a round that few waves take part in.
+    uint32_t run = m->tile_run ? m->tile_run : tile_run_rule(n_bytes, blocks * waves_per_block);
+    // the kernel pushes its queued candidates on after every 1 GiB a wave advances, which keeps their 32-bit positions
+    // unambiguous only while a wave's consecutive tiles are at most 1 GiB apart (scan_kernel_impl.hpp): a forced R that
+    // this device's wave count makes longer than that (R = 8 on more than 4112 waves) is shortened until it holds
+    while (run > 1 && blocks * waves_per_block * ((uint64_t)(run * (kTileChunks + 1) - 1) * kChunkBytes) > (1ull << 30)) --run;
+    // a forced R on a text with fewer 31-chunk tiles than a full grid has waves (the rule never does that): as many
+    // workgroups as the text has long tiles for, so that the forced length is what runs
+    if (run > 1 && blocks < (uint64_t)m->num_cus) {
+        const uint64_t long_bytes = (uint64_t)(run * (kTileChunks + 1) - 1) * kChunkBytes;
+        blocks = std::min<uint64_t>(blocks, std::max<uint64_t>(1, n_bytes / (long_bytes * waves_per_block)));
+    }
+    const TileGeometry geo = tile_geometry(n_bytes, blocks * waves_per_block, run);
+    p.n_long_tiles = geo.n_long;
+    p.n_tiles = geo.n_long + geo.n_short;
+    p.tail_start = geo.tail_start;
+    p.long_groups = geo.long_loads / 4;
+    p.short_groups = geo.short_loads / 4;
     p.rec_index = nullptr;
     p.rec_len = rec_len;
     p.inv_rec_len = rec_len ? 1.0 / (double)rec_len : 0.0;
@@ -691,6 +736,8 @@ int mk_scan_device(mk_matcher *m, const void *d_seq, uint64_t n_bytes, const voi
     }
     m->kernel_name = name;
     m->last_grid = (int)blocks;
+    m->last_geo = geo;
+    m->last_run = run;
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

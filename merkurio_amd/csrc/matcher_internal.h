@@ -7,6 +7,7 @@
 
 #include "filter.hpp"
 #include "scan_kernel.h"
+#include "tile_geometry.hpp"
 #include "host_common.h"
 
 struct mk_matcher {
@@ -110,6 +111,8 @@ struct mk_matcher {
     float batch_ms[4] = {0, 0, 0, 0};
     const char *kernel_name = "";
     int last_grid = 0;
+    mk::TileGeometry last_geo{};  // tile geometry of the last mk_scan_device (mk_matcher_scan_geometry)
+    uint32_t last_run = 0;
     // optional per-launch kernel timing (hipEvents recorded on the launch stream, tightly
     // around the scan kernel): bench.py's roofline figure
     std::vector<hipEvent_t> ev_start, ev_stop;

@@ -38,7 +38,11 @@ struct ScanParams {
     uint32_t case_insensitive;
     uint32_t uniform_len;  // > 0: every pattern has this length (pattern i starts at i * uniform_len)
     double rec_per_byte;  // n_rec / n_bytes: record-index estimate for the lookup in resolve_one
-    uint32_t tile_run;    // consecutive tiles a wave takes before it jumps ahead (>= 1)
+    // tile geometry of this launch (tile_geometry.hpp): tiles [0, n_long_tiles) are long_groups four-load groups
+    // long and lie back to back from byte 0, tiles [n_long_tiles, n_tiles) are short_groups groups long and
+    // follow them; the guarded tail phase starts at tail_start
+    uint64_t n_long_tiles, n_tiles, tail_start;
+    uint32_t long_groups, short_groups;
     // records of unequal length: rec_index[k] = index of the record that contains byte k * 64 Ki (one more
     // entry behind the last); null = equal lengths, the quotient p * rec_per_byte is the record
     const uint32_t *rec_index;

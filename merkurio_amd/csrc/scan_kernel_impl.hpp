@@ -12,8 +12,9 @@
 //   * one persistent 1024-thread workgroup per CU (16 waves); level 1, the 128 KiB blocked
 //     q-gram Bloom filter of the pattern set, lives in LDS for the life of the workgroup
 //     (pattern sets too large for it use the same filter layout in global memory / L2: GF);
-//   * the concatenated text is cut into 31 KiB tiles dealt to the 4096 waves in short runs (1, 2 or 4
-//     consecutive tiles, then a jump of n_waves runs); a wave walks a tile in 1 KiB chunks: each lane issues ONE non-temporal global_load_dwordx4
+//   * the concatenated text is cut into tiles dealt round-robin to the 4096 waves: whole rounds of long tiles
+//     (32 R - 1 KiB scanned + a 1 KiB halo, R in 1..8 picked per launch), then less than one such round in tiles
+//     of 15 .. 31 KiB (tile_geometry.hpp); a wave walks a tile in 1 KiB chunks: each lane issues ONE non-temporal global_load_dwordx4
 //     (64 lanes x 16 B, fully coalesced) per chunk, four chunks (one group) are in flight while
 //     the previous group is filtered;
 //   * a lane 2-bit-packs its 16 bytes into one dword (11 VALU ops), gets the 32-base halo from
@@ -558,7 +559,6 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
     const uint64_t wave_id = (uint64_t)blockIdx.x * (kBlockThreads / 64) + wave_in_block;
     const uint64_t n_waves = (uint64_t)gridDim.x * (kBlockThreads / 64);
     constexpr int NS = G::kNS;
-    constexpr uint64_t kTileBytes = (uint64_t)kTileChunks * kChunkBytes;
     const uint32_t mask_lo = P.key_mask_lo, mask_hi = P.key_mask_hi;
     const uint8_t *__restrict__ seq = P.seq;
     const uint64_t n_bytes = P.n_bytes;
@@ -773,23 +773,34 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
         } while (__ballot(cand != 0));
     };
 
-    // ---- main phase: tiles whose 32 chunk loads (31 scanned + halo) lie inside the text.
+    // ---- main phase: tiles whose chunk loads (scanned chunks + halo) lie inside the text.
     // No bounds checks here; loads run one group (4 chunks = 4 KiB per wave, 64 KiB per CU)
     // ahead of their use.
-    const uint64_t n_main_tiles = n_bytes >= kChunkBytes ? (n_bytes - kChunkBytes) / kTileBytes : 0;
-    if (wave_id * (P.tile_run ? P.tile_run : 1u) < n_main_tiles) {
+    // Tile i of the launch belongs to wave i mod n_waves.  The first n_long_tiles tiles (whole rounds) are long_groups
+    // four-load groups long, the rest short_groups (tile_geometry.hpp); the loader cursor and the scan loop
+    // both map a tile index to its base and group count with the two wave-uniform compares below.
+    const uint64_t n_main_tiles = P.n_tiles;
+    const uint64_t n_long_tiles = P.n_long_tiles;
+    const uint32_t long_groups = P.long_groups;
+    const uint32_t short_groups = P.short_groups;
+    const uint64_t long_bytes = (uint64_t)(4u * long_groups - 1u) * kChunkBytes;
+    const uint64_t short_bytes = (uint64_t)(4u * short_groups - 1u) * kChunkBytes;
+    auto tile_base = [&](uint64_t t) __attribute__((always_inline)) -> uint64_t {
+        return t < n_long_tiles ? t * long_bytes : n_long_tiles * long_bytes + (t - n_long_tiles) * short_bytes;
+    };
+    auto tile_groups = [&](uint64_t t) __attribute__((always_inline)) -> uint32_t {
+        return t < n_long_tiles ? long_groups : short_groups;
+    };
+    if (wave_id < n_main_tiles) {
         // loader cursor (wave-uniform): pointer to the next chunk to fetch.  Past this wave's
         // last tile the pointer parks on the last main tile: the loads stay unconditional (a
         // branch around a load would force s_waitcnt vmcnt(0) at the join), their data unused.
-        // Tile dealing: a wave takes `run` consecutive tiles, then jumps ahead by n_waves * run tiles
-        // (run = 1: plain round-robin).  Longer runs keep a wave inside one 2 MiB page for several tiles.
-        const uint32_t run = P.tile_run ? P.tile_run : 1u;
-        const uint64_t jump = (n_waves - 1) * (uint64_t)run + 1;  // from the last tile of a run to the first of the next
-        uint64_t ld_tile = wave_id * run;
-        uint32_t ld_run = 0;
-        uint32_t ld_g = 0;  // group index inside the tile (a tile is 8 groups of 4 chunk loads)
+        // (a long tile keeps a wave inside one 2 MiB page for up to 256 KiB and fetches one halo chunk for all of it)
+        uint64_t ld_tile = wave_id;
+        uint32_t ld_g = 0;  // group index inside the tile (a tile is ld_groups groups of 4 chunk loads)
+        uint32_t ld_groups = tile_groups(ld_tile);
         const uint64_t last_tile = n_main_tiles - 1;
-        const uint8_t *ld_ptr = seq + (ld_tile < last_tile ? ld_tile : last_tile) * kTileBytes + lane * 16;
+        const uint8_t *ld_ptr = seq + tile_base(ld_tile) + lane * 16;
         auto nt_load = [](const uint8_t *p) -> uint4 {
             // NTL (the normal case): non-temporal, the text is read once; keep L2 for the exact table and
             // the filter image (-15 % kernel time).  Plain loads are the variant for hit-dense text, where
@@ -811,16 +822,12 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
             c = nt_load(ld_ptr + 2 * kChunkBytes);
             d = nt_load(ld_ptr + 3 * kChunkBytes);
             ld_ptr += 4 * kChunkBytes;
-            if (++ld_g == (uint32_t)(kTileChunks + 1) / 4) {  // next tile of this wave
+            if (++ld_g == ld_groups) {  // next tile of this wave
                 ld_g = 0;
-                if (++ld_run == run) {
-                    ld_run = 0;
-                    ld_tile += jump;
-                } else {
-                    ld_tile += 1;
-                }
+                ld_tile += n_waves;
                 const uint64_t t = ld_tile < last_tile ? ld_tile : last_tile;
-                ld_ptr = seq + t * kTileBytes + lane * 16;
+                ld_groups = tile_groups(t);
+                ld_ptr = seq + tile_base(t) + lane * 16;
             }
         };
         // Register pipeline, one group = 4 chunks deep.  A group (straight-line code, so the
@@ -850,15 +857,16 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
         };
         // Queued filter positives carry only the low 32 bits of their position, restored relative to
         // the wave's current position: none may stay queued while the wave advances 4 GiB.  A wave's
-        // runs of tiles are n_waves * run * 31 KiB <= 1 GiB apart, so after every 1 GiB of advance whatever
+        // tiles are at most n_waves * 255 KiB apart (the longest tile, R = 8; 4096 waves: 1020 MiB < 1 GiB, and
+        // mk_scan_device shortens R on a device with more waves; from its last long tile to its first short one it is less), so after every 1 GiB of advance whatever
         // is parked or queued is pushed on to level 2.  (Not 2 GiB: a push that finds a probe still pending
         // leaves the queued candidates for the NEXT push, and two intervals must stay below 4 GiB -- r02,
         // test_sparse_candidates_full_size caught exactly that.)  (Sparse candidates never reach the ring's
         // fill threshold by themselves: 1 pattern on 15 GB lost two hits in three before this).
         uint64_t last_push_base = 0;
-        uint32_t sc_run = 0;
-        for (uint64_t tile = wave_id * run; tile < n_main_tiles;) {
-            const uint64_t base = tile * kTileBytes;
+        for (uint64_t tile = wave_id; tile < n_main_tiles; tile += n_waves) {
+            const uint64_t base = tile_base(tile);
+            const int groups = (int)tile_groups(tile);  // the same mapping as the loader cursor's
             if constexpr (kCtx) {  // 16 bases in front of the tile (one address for the whole wave)
                 pk_tile_prev = 0;
                 if (base >= 16) pk_tile_prev = pack16(*reinterpret_cast<const uint4 *>(seq + base - 16));
@@ -870,7 +878,7 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
                 if (q_count && !pend_on) issue_probe(q_count < 64 ? q_count : 64);
             }
 #pragma unroll 1
-            for (int g = 0; g < (kTileChunks + 1) / 4; ++g) {
+            for (int g = 0; g < groups; ++g) {
                 const uint32_t p0 = pack16(r0), p1 = pack16(r1), p2 = pack16(r2), p3 = pack16(r3);
                 // pack BEFORE re-issuing the loads into the same registers: without this pin the
                 // compiler sinks the packs below the loads and keeps the raw data alive with 16
@@ -943,12 +951,6 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
                 }
                 pk_prev = p3;
             }
-            if (++sc_run == run) {  // the same sequence as the loader cursor's
-                sc_run = 0;
-                tile += jump;
-            } else {
-                tile += 1;
-            }
         }
         if constexpr (kPipe) {
             if (pd_on) test_pending();
@@ -956,14 +958,14 @@ __global__ __launch_bounds__(kBlockThreads) void mk_scan_kernel(const ScanParams
     }
     if (pend_on) consume_probe();
 
-    // ---- tail phase: the < 32 KiB behind the last main tile, with guarded loads.  One chunk per
+    // ---- tail phase: the < 32 KiB behind the second region's last tile, with guarded loads.  One chunk per
     // wave, dealt to the waves that come after the last main tile in the round-robin (they have
     // one tile less than the others): a single wave walking all <= 32 chunks exposes one memory
     // round trip per chunk and finishes up to 60 us after everybody else (r02: 10 M x 150 bp
     // batches ran at 0.65 of the roofline mostly because of it).
     {
-        const uint64_t tail_rank = (wave_id + n_waves - (n_main_tiles / (P.tile_run ? P.tile_run : 1u)) % n_waves) % n_waves;
-        for (uint64_t cpos = n_main_tiles * kTileBytes + tail_rank * kChunkBytes; cpos < n_bytes; cpos += n_waves * kChunkBytes) {
+        const uint64_t tail_rank = (wave_id + n_waves - n_main_tiles % n_waves) % n_waves;
+        for (uint64_t cpos = P.tail_start + tail_rank * kChunkBytes; cpos < n_bytes; cpos += n_waves * kChunkBytes) {
             const uint32_t pk_cur = pack16(load16(seq, cpos + lane * 16, n_bytes));
             const uint32_t pk_nxt = pack16(load16(seq, cpos + kChunkBytes + lane * 16, n_bytes));
             uint32_t h0 = 0, h1 = 0;

@@ -49,7 +49,7 @@ EXPORTS = [
     "mk_reverse_complement", "mk_canonical", "mk_recommend_aho_corasick", "mk_tune_q_value", "mk_generate_masks",
     "mk_free", "mk_matcher_create", "mk_matcher_create_ex", "mk_plan_geometry", "mk_matcher_destroy", "mk_matcher_algo", "mk_matcher_num_patterns",
     "mk_matcher_filter_info", "mk_matcher_class_info", "mk_matcher_filter_mode", "mk_scan_batch", "mk_scan_device", "mk_order_hits", "mk_order_hits_device", "mk_matcher_order_info", "mk_matcher_order_stats", "mk_matcher_kernel_name",
-    "mk_matcher_launch_info", "mk_matcher_enable_timing", "mk_matcher_kernel_times", "mk_matcher_hint_hit_density", "mk_matcher_hint_record_lengths", "mk_matcher_set_fixed_record_length", "mk_matcher_check_device",
+    "mk_matcher_launch_info", "mk_scan_tile_geometry", "mk_matcher_scan_geometry", "mk_matcher_enable_timing", "mk_matcher_kernel_times", "mk_matcher_hint_hit_density", "mk_matcher_hint_record_lengths", "mk_matcher_set_fixed_record_length", "mk_matcher_check_device",
     "mk_extract_single", "mk_extract_fastq_text", "mk_upload_text_ahead", "mk_host_alloc", "mk_host_free", "mk_extract_paired", "mk_tag_records", "mk_tag_value", "mk_matcher_batch_times", "mk_synth_reads_device",
     "mk_synth_reads_host", "mk_synth_reads_device_range", "mk_reduce_counters", "mk_reduce_prepare", "mk_comm_available", "mk_comm_unique_id", "mk_comm_init",
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
@@ -87,6 +87,16 @@ class MatcherOptions(C.Structure):
         super().__init__(C.sizeof(MatcherOptions), int(force_stride), int(bool(force_global_filter)),
                          int(gbloom_log2_blocks), int(tile_run), int(gbloom_kib),
                          1 if force_single_class else int(length_classes), int(force_split_len), int(force_stride2), int(force_q2))
+
+
+class TileGeometry(C.Structure):
+    """mk_tile_geometry (include/merkurio_hip.h): how a scan launch cuts its text into wave tiles"""
+    _fields_ = [("n_waves", C.c_uint64), ("n_long_tiles", C.c_uint64), ("long_tile_bytes", C.c_uint64), ("n_short_tiles", C.c_uint64),
+                ("short_tile_bytes", C.c_uint64), ("tail_start", C.c_uint64), ("long_tile_loads", C.c_uint32),
+                ("short_tile_loads", C.c_uint32), ("tile_run", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
 class WindowText(C.Structure):
@@ -236,6 +246,8 @@ def load(build_if_missing=True):
     L.mk_order_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.mk_matcher_order_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.mk_matcher_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mk_scan_tile_geometry.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(TileGeometry)]
+    L.mk_matcher_scan_geometry.argtypes = [C.c_void_p, C.POINTER(TileGeometry)]
     L.mk_matcher_enable_timing.argtypes = [C.c_void_p, C.c_uint32]
     L.mk_matcher_hint_hit_density.argtypes = [C.c_void_p, C.c_uint32]
     L.mk_matcher_hint_record_lengths.argtypes = [C.c_void_p, C.c_int]
@@ -429,6 +441,13 @@ def plan_geometry(lengths, options=None):
     return dict(zip(keys, (x.value for x in v)))
 
 
+def scan_tile_geometry(n_bytes, n_waves, tile_run):
+    """mk_scan_tile_geometry: the two tile regions and the tail of a scan of n_bytes by n_waves waves (host arithmetic)"""
+    g = TileGeometry()
+    _check(load().mk_scan_tile_geometry(int(n_bytes), int(n_waves), int(tile_run), C.byref(g)))
+    return g.as_dict()
+
+
 # ------------------------------------------------------------------ matcher handle
 class Matcher:
     """The matcher bundle the reference drivers hold (src/cmd_extract.rs:259): construction
@@ -481,6 +500,12 @@ class Matcher:
         g, b, l = C.c_uint32(), C.c_uint32(), C.c_uint32()
         _check(load().mk_matcher_launch_info(self._h, C.byref(g), C.byref(b), C.byref(l)))
         return {"grid_blocks": g.value, "block_threads": b.value, "lds_bytes": l.value}
+
+    def scan_geometry(self):
+        """tile geometry of the last mk_scan_device on this handle (mk_tile_geometry as a dict)"""
+        g = TileGeometry()
+        _check(load().mk_matcher_scan_geometry(self._h, C.byref(g)))
+        return g.as_dict()
 
     def batch_times_ms(self):
         """upload / device / download / host milliseconds of the last extract_single / tag_records call"""

@@ -27,7 +27,7 @@ for f in find("kt/**/*kernel_stats.csv") + find("kt*kernel_stats.csv"):
     for row in csv.DictReader(open(f)):
         print("  {Name:60.60s} calls={Calls} avg_ns={AverageNs} min_ns={MinNs} total_ns={TotalDurationNs} pct={Percentage}".format(**row))
 
-scan_name, scan_avg_us = None, None
+scan_name, scan_avg_us, scan_row = None, None, None
 for f in find("kt/**/*kernel_trace.csv") + find("kt*kernel_trace.csv"):
     d = defaultdict(list)
     scan_row = None  # a launch of the scan kernel: ITS resources are the ones worth printing (r03 printed the last launch's,
@@ -42,9 +42,9 @@ for f in find("kt/**/*kernel_trace.csv") + find("kt*kernel_trace.csv"):
         # sparse flavour during its warm-up and the dense one afterwards)
         if "mk_scan_kernel" in k and (scan_name is None or len(v) > len(d[scan_name])):
             scan_name, scan_avg_us = k, sum(v) / len(v) / 1e3
-    for key in ("VGPR_Count", "Accum_VGPR_Count", "SGPR_Count", "LDS_Block_Size", "Scratch_Size", "Workgroup_Size", "Grid_Size"):
+    for key in ("VGPR_Count", "Accum_VGPR_Count", "SGPR_Count", "LDS_Block_Size", "Scratch_Size", "Workgroup_Size_X", "Grid_Size_X"):
         if scan_row and key in scan_row:
-            print("  scan kernel launch {}={}  (as the trace reports it; the compiler's own figures: profiles/r04_isa_resources.txt)".format(key, scan_row[key]))
+            print("  scan kernel launch {}={}  (as the trace reports it; the compiler's own figures: profiles/r06_isa_resources.txt)".format(key, scan_row[key]))
 
 print("== PMC (per-launch average over the launches of %s)" % (scan_name or "kernels matching 'mk_scan'"))
 pmc = {}
@@ -75,12 +75,19 @@ if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc and scan_name:
         short += ">"
     fetch_kb, write_kb = pmc["FETCH_SIZE"], pmc["WRITE_SIZE"]
     # gfx950 tallies a wide coalesced streaming read at half its bytes (MI355X_MICROARCH.md, HBM): that correction
-    # applies to the kernel's TEXT STREAM only (16 B per lane, every byte once + one halo chunk per 31-chunk tile),
+    # applies to the kernel's TEXT STREAM only (16 B per lane, every byte once + one halo chunk per tile of either region),
     # not to its random 8- / 32-byte reads of filter blocks, table buckets and occurrence windows.  The stream's
     # bytes are known, so: hbm = FETCH_SIZE + stream / 2 + WRITE_SIZE (r03 doubled all of FETCH_SIZE, which inflated
     # the global-filter configuration, whose fetches are mostly random, from ~6.0 to 8.9 GB).
     n_text = a.records * a.read_len
-    stream = n_text * 32 // 31
+    # the tiles of the launch: mk_scan_tile_geometry for this text, the traced grid's waves and bench.py's --tile-run (0 = the rule)
+    from merkurio_amd import native
+    # (rocprofv3's kernel trace reports the grid in work-items: Grid_Size_X = workgroups x 1024 for the scan kernel)
+    assert scan_row and scan_row.get("Grid_Size_X") and int(scan_row["Grid_Size_X"]) % int(scan_row["Workgroup_Size_X"]) == 0, \
+        "no grid size for the scan kernel in the kernel trace: the stream's bytes depend on the number of scan waves"
+    n_waves = int(scan_row["Grid_Size_X"]) // 64
+    geo = native.scan_tile_geometry(n_text, n_waves, a.tile_run or 0)
+    stream = n_text + 1024 * (geo["n_long_tiles"] + geo["n_short_tiles"])
     fetch_b = fetch_kb * 1024
     stream_reported = min(fetch_b, stream / 2)
     j = {
@@ -91,8 +98,9 @@ if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc and scan_name:
         "records_per_gpu": a.records, "read_len": a.read_len, "patterns": a.patterns * (2 if a.rc else 1), "plant_every": a.plant_every,
         "FETCH_SIZE_KB_per_launch": fetch_kb, "WRITE_SIZE_KB_per_launch": write_kb,
         "correction": "gfx950 tallies 16 B/lane streaming reads at half size (MI355X_MICROARCH.md HBM section): the text stream "
-                      "(records x read_len x 32/31 bytes, known) is counted twice, the random reads (the rest of FETCH_SIZE) once; WRITE_SIZE exact",
+                      "(records x read_len bytes + 1 KiB per tile, known from tile_geometry) is counted twice, the random reads (the rest of FETCH_SIZE) once; WRITE_SIZE exact",
         "text_stream_bytes": stream,
+        "tile_geometry": geo,
         "random_fetch_bytes_per_launch": fetch_b - stream_reported,
         "hbm_bytes_per_launch": fetch_b + stream_reported + write_kb * 1024,
         "hbm_bytes_per_launch_all_doubled_r03": fetch_b * 2 + write_kb * 1024,
