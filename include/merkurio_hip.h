@@ -571,7 +571,7 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
                       uint32_t *pattern_hit_counts, uint32_t *status);
 
 /* -------------------------------------------------------------------------------------
- * One gzip member inflated in parallel on the device (v6) -- a .fastq.gz / .fasta.gz as plain gzip (or pigz, or zlib) writes it: ONE
+ * A gzip file inflated in parallel on the device (v6: one member; v7: a chain of members) -- a .fastq.gz / .fasta.gz as plain gzip (or pigz, or zlib) writes it: ONE
  * DEFLATE stream of thousands of blocks, which zlib can only walk from the front.  Replaces needletail's gzip reader under
  * `merkurio extract` (src/cmd_extract.rs:281-282) for such files.  The stream is cut where block starts can be FOUND (a dynamic
  * block's header is a pattern almost no bit position satisfies; a candidate is confirmed by decoding its block and meeting another
@@ -580,7 +580,8 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
  * CRC-32 and ISIZE (merkurio_amd/csrc/codec/gzip_segments.hpp).
  * gz[0, n) = the whole member.  *taken = 1: the text lies on the codec's device, *text_bytes long, until the next call or
  * mk_gzip_text_release; read it with mk_gzip_text_read (host copy of a range) or hand windows of it to mk_extract_window
- * (mk_window_source::device_text).  *taken = 0: not a file for this path -- several members, a stream without findable block starts
+ * (mk_window_source::device_text).  *taken = 0: not a file for this path -- several members (mk_gzip_members_inflate_device takes
+ * those), a stream that ends in front of its trailer, a stream without findable block starts
  * where they are needed, a piece that does not meet its neighbour, an unusually compressible stream the buffers do not hold, a
  * CRC-32 / ISIZE that does not match --: nothing is reported as an error, the caller inflates the file with zlib (which then also
  * words what is wrong with a damaged one).
@@ -589,8 +590,33 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
 int mk_gzip_text_read(mk_codec *c, uint64_t offset, uint8_t *out, uint64_t len);
 const void *mk_gzip_text_device(const mk_codec *c, uint64_t *text_bytes);
 int mk_gzip_text_release(mk_codec *c);
-/* pieces of the last mk_gzip_inflate_device and its phases in milliseconds: upload, block search, pieces, resolution, CRC-32 */
+/* pieces of the last mk_gzip_inflate_device / mk_gzip_members_inflate_device and its phases in milliseconds: upload, block search,
+ * pieces, resolution, CRC-32 */
 int mk_gzip_info(const mk_codec *c, uint32_t *segments, float ms[5]);
+
+/* (v7) A gzip file of SEVERAL members -- `cat a.gz b.gz`, a member per tile or per block without BGZF's BC field.  A member carries no
+ * compressed size: where it ends is known once it is decoded.  So the starts are guessed on the host and proved on the device.
+ * mk_gzip_member_guesses (host code, no device needed) reports every offset at which an RFC 1952 header parses inside gz[0, n): ID1
+ * ID2 CM = 1f 8b 08, reserved FLG bits clear, FEXTRA / FNAME / FCOMMENT / FHCRC walked, at least 2 bytes of stream and 8 of trailer
+ * behind it (and, behind offset 0, 8 bytes in front of it).  Offset 0 must be one, otherwise there are no guesses.  A guess is not a
+ * member: the three bytes and the flag test pass at a handful of places per GB of compressed data.  crc / isize are read from the 8
+ * bytes in front of the NEXT guess (the file's end for the last one).  *n_guesses = how many there are; table[0, min(cap, that)) is
+ * written (table may be NULL).
+ * mk_gzip_members_inflate_device: the whole file goes up, all candidate members are cut into pieces and decoded in ONE batch of
+ * launches, the 32 KiB context chain restarts at every member.  Member 0 starts at byte 0; a guess is PROVED a member start when the
+ * member in front of it decodes from its first bit to a final block that ends in the last byte in front of the trailer there, with
+ * that trailer's CRC-32 and ISIZE.  A candidate that does not is joined with the next one (its end was no member start) and the
+ * pieces are decoded again, four rounds in all.  *taken = 1 only when proved members cover gz[0, n) with nothing left over -- the
+ * chain zlib walks; the text of all members lies back to back where mk_gzip_inflate_device leaves its text (mk_gzip_text_read /
+ * _device / _release), *n_members says how many were proved.  *taken = 0 (MK_OK, nothing else touched): trailing bytes, a member of
+ * 4 GiB of text or more, more than 65 535 pieces, and everything mk_gzip_inflate_device hands back. */
+typedef struct mk_gzip_guess {
+    uint64_t header_off; /* where the header parses */
+    uint64_t data_off;   /* the first byte behind it: the member's DEFLATE stream, if this is a member */
+    uint32_t crc, isize; /* of the 8 bytes in front of the next guess */
+} mk_gzip_guess;
+int mk_gzip_member_guesses(const uint8_t *gz, uint64_t n, mk_gzip_guess *table, uint64_t cap, uint64_t *n_guesses);
+int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_members);
 
 /* -------------------------------------------------------------------------------------
  * `tag` on a window of a BAM file with the records RESIDENT ON THE DEVICE (v7) -- the reader loop, process_record and the writer

@@ -50,8 +50,8 @@ struct Input {
     std::string path;
     FastxStream s;
     bool bgzf_dev = false;  // its members go to the device as they are
-    // a plain gzip file whose ONE member the device has inflated in parallel pieces (mk_gzip_inflate_device): the text lies there,
-    // windows are ranges of it
+    // a plain gzip file whose member, or chain of members, the device has inflated in parallel pieces (mk_gzip_inflate_device /
+    // mk_gzip_members_inflate_device): the text lies there, windows are ranges of it
     bool gz_dev = false;
     mk_codec *gz_codec = nullptr;
     const uint8_t *gz_text = nullptr;
@@ -793,8 +793,10 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             J.bgzf_target = std::min<uint64_t>(J.bgzf_target, std::max<uint64_t>(64ull << 20, (uint64_t)free_b / (6 * (uint64_t)J.n_in)));
     }
     // a plain gzip input: ONE DEFLATE stream, which zlib walks from the front at 0.5 GB/s -- the device inflates it in parallel
-    // pieces (mk_gzip_inflate_device) and keeps the text; what it does not take (several members, no findable block starts, a
-    // stream the buffers do not hold, a damaged file) stays with the zlib reader, which also words the errors
+    // pieces (mk_gzip_inflate_device) and keeps the text; a file of several members (`cat a.gz b.gz`) goes to
+    // mk_gzip_members_inflate_device, which cuts all of them into pieces at once.  What neither takes (no findable block starts, a
+    // stream the buffers do not hold, bytes behind the last member, a damaged file) stays with the zlib reader, which also words
+    // the errors
     run_threads((size_t)J.n_in, [&](size_t ii) {  // (the two files of a pair side by side: a handle and a stream each)
         const int i = (int)ii;
         Input &I = J.in[i];
@@ -803,13 +805,21 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
         uint64_t text_bytes = 0;
         uint32_t taken = 0;
         const double t_gz = PhaseTimer::now();
-        mk_check(mk_gzip_inflate_device(I.gz_codec, I.s.source().file_bytes(), I.s.source().file_size(), &text_bytes, &taken), "Error inflating the input");
+        const uint8_t *gz = I.s.source().file_bytes();
+        const uint64_t gz_size = I.s.source().file_size();
+        mk_check(mk_gzip_inflate_device(I.gz_codec, gz, gz_size, &text_bytes, &taken), "Error inflating the input");
+        uint64_t members = taken ? 1 : 0, guesses = 0;
+        if (!taken && mk_gzip_member_guesses(gz, gz_size, nullptr, 0, &guesses) == MK_OK && guesses > 1) {
+            // (the codec rule: whatever this call reports other than "taken" -- an error of the device included -- the file is zlib's)
+            if (mk_gzip_members_inflate_device(I.gz_codec, gz, gz_size, &text_bytes, &taken, &members) != MK_OK) taken = 0;
+            if (!taken) members = 0;
+        }
         if (J.timing) {
             uint32_t seg = 0;
             float ms5[5] = {0, 0, 0, 0, 0};
             (void)mk_gzip_info(I.gz_codec, &seg, ms5);
-            fprintf(stderr, "[timing]   gzip input %d on the device: %s, %.3f s (%u pieces; upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms)\n", i,
-                    taken ? "taken" : "NOT taken (zlib reads it)", PhaseTimer::now() - t_gz, seg, ms5[0], ms5[1], ms5[2], ms5[3], ms5[4]);
+            fprintf(stderr, "[timing]   gzip input %d on the device: %s, %llu members proved, %.3f s (%u pieces; upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms)\n", i,
+                    taken ? "taken" : "NOT taken (zlib reads it)", (unsigned long long)members, PhaseTimer::now() - t_gz, seg, ms5[0], ms5[1], ms5[2], ms5[3], ms5[4]);
         }
         if (!taken) {
             mk_codec_destroy(I.gz_codec);

@@ -385,6 +385,19 @@ __global__ __launch_bounds__(256) void mk_bgzf_crc_kernel(const uint8_t *__restr
     if (lane == 0) crc[b] = c;
 }
 
+// the same over a table of ranges: crc[b] = CRC-32 of in[off[b], off[b] + len[b]) (the text of a gzip file's members, each cut into
+// blocks of its own: mk_gzip_members_inflate_device)
+__global__ __launch_bounds__(256) void mk_crc_ranges_kernel(const uint8_t *__restrict__ in, const unsigned long long *__restrict__ off,
+                                                            const uint32_t *__restrict__ len, uint32_t n_ranges, uint32_t *__restrict__ crc) {
+    __shared__ uint32_t t[4][256];
+    build_crc_tables(t);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_ranges) return;
+    const uint32_t c = wave_crc32(in + off[b], len[b], t, lane);
+    if (lane == 0) crc[b] = c;
+}
+
 __global__ __launch_bounds__(256) void mk_bgzf_crc_check_kernel(const uint8_t *__restrict__ out, const Member *__restrict__ members,
                                                                 uint32_t n_members, int32_t *__restrict__ status) {
     __shared__ uint32_t t[4][256];
@@ -447,6 +460,10 @@ uint32_t deflate_grid(uint32_t n_blocks, int num_cus) {
 void launch_crc(const uint8_t *in, uint64_t n, uint32_t block_bytes, uint32_t n_blocks, uint32_t *crc, hipStream_t s) {
     if (!n_blocks) return;
     hipLaunchKernelGGL(mk_bgzf_crc_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, s, in, n, block_bytes, n_blocks, crc);
+}
+void launch_crc_ranges(const uint8_t *in, const unsigned long long *off, const uint32_t *len, uint32_t n_ranges, uint32_t *crc, hipStream_t s) {
+    if (!n_ranges) return;
+    hipLaunchKernelGGL(mk_crc_ranges_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, s, in, off, len, n_ranges, crc);
 }
 void launch_crc_check(const uint8_t *out, const Member *members, uint32_t n_members, int32_t *status, hipStream_t s) {
     if (!n_members) return;

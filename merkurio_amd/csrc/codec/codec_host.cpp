@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <iterator>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -329,33 +330,43 @@ int mk_bgzf_members(const uint8_t *in, uint64_t n, mk_bgzf_member *members, uint
     return MK_OK;
 }
 
-// ---- one gzip member in parallel pieces (gzip_segments.hpp says how; kernels: gzip_inflate.hip) ---------------------------------
-int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t *text_bytes, uint32_t *taken) {
-    MK_ABI_BEGIN
-    if (!c || !text_bytes || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: NULL argument");
-    *text_bytes = 0, *taken = 0;
-    std::lock_guard<std::mutex> lock(c->mu);
-    c->gz_text_bytes = 0, c->gz_segments = 0;
-    for (float &x : c->gz_ms) x = 0;
-    // RFC 1952: the member's header, then the DEFLATE stream up to the 8 trailer bytes.  One member is what is taken; whether the
-    // stream really ends where the file does shows when the last segment meets its final block there.
-    if (n < 18 + 2 || gz[0] != 0x1f || gz[1] != 0x8b || gz[2] != 8 || (gz[3] & 0xE0)) return MK_OK;  // (not gzip / reserved flags: not taken)
-    uint64_t p = 10;
-    if (gz[3] & 4) {
-        if (p + 2 > n) return MK_OK;
+// ---- a gzip file in parallel pieces (gzip_segments.hpp says how; kernels: gzip_inflate.hip) -------------------------------------
+}  // extern "C"
+
+namespace {
+
+// RFC 1952: does a member's header parse at gz[b ...]?  -> the offset of the byte behind it (FEXTRA / FNAME / FCOMMENT / FHCRC
+// walked), with room for a DEFLATE stream (2 bytes at least) and the 8 trailer bytes inside the file; 0 = no header here
+uint64_t gzip_header_end(const uint8_t *gz, uint64_t n, uint64_t b) {
+    if (n - b < 10 + 2 + 8 || gz[b] != 0x1f || gz[b + 1] != 0x8b || gz[b + 2] != 8 || (gz[b + 3] & 0xE0)) return 0;
+    const uint8_t flg = gz[b + 3];
+    uint64_t p = b + 10;
+    if (flg & 4) {
+        if (p + 2 > n) return 0;
         p += 2 + (gz[p] | (uint64_t)gz[p + 1] << 8);
     }
     for (int bit = 3; bit <= 4; ++bit)
-        if (gz[3] & (1 << bit)) {
+        if (flg & (1 << bit)) {
             const void *z = p < n ? memchr(gz + p, 0, (size_t)(n - p)) : nullptr;
-            if (!z) return MK_OK;
+            if (!z) return 0;
             p = (uint64_t)((const uint8_t *)z - gz) + 1;
         }
-    if (gz[3] & 2) p += 2;
-    if (p + 8 + 2 > n) return MK_OK;
-    const uint64_t n_in = n - 8 - p;
-    uint32_t want_crc, want_isize;
-    memcpy(&want_crc, gz + n - 8, 4), memcpy(&want_isize, gz + n - 4, 4);
+    if (flg & 2) p += 2;
+    return p <= n && n - p >= 2 + 8 ? p : 0;
+}
+
+// a candidate member of the uploaded bytes: its DEFLATE stream is [pay, end), the trailer behind it says crc / isize
+struct GzMember {
+    uint64_t pay, end;
+    uint32_t crc, isize;
+};
+
+// up[0, n_up) goes to the device as it is; `mem` = the chain of candidate members in it, mem[0] a real one.  A candidate that does
+// not end on its final block in front of its trailer was cut at a guess that is no member start: the guess is dropped (the candidate
+// joined with the next one) and the pieces are decoded again, four rounds in all.  *taken = 1: every member left decoded from its
+// first bit to a final block that ends in its last payload byte, and its text has the trailer's CRC-32 and ISIZE -- the chain zlib
+// walks, since a DEFLATE stream decoded from a given bit has one end.  Called with the handle's mutex held.
+int gzip_inflate_chain(mk_codec *c, const uint8_t *up, uint64_t n_up, std::vector<GzMember> mem, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_members) {
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
     int rc;
     // nominal chunks of compressed bytes (a block of zlib's is 15-40 KiB of them).  A piece is decoded by one wave at that wave's pace
@@ -363,21 +374,26 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     // pieces make.  Cuts every 16 KiB give every block its own piece (no piece can be smaller); up to a round and a half of them
     // that is the fastest (61 MB of stream: 27 ms against 37); above, cuts every 64 KiB (pieces of ~2 blocks, a third of the
     // search waves) are (245 MB: 63 ms against 67).  At most 32 768 chunks (the prefix kernel's grid; a stream of more than 2 GiB
-    // gets larger chunks).
+    // gets larger chunks).  With the members' first bits the pieces are at most 65 535 (a grid dimension): more is not taken.
+    const uint64_t n_in = n_up;
     uint64_t chunk = c->gzip_chunk ? c->gzip_chunk : (n_in / (32u << 10) <= (uint64_t)c->num_cus * 17 * 3 / 2 ? 16u << 10 : 64u << 10);
     while (n_in / chunk > 32768) chunk *= 2;
     const uint32_t n_chunks = (uint32_t)std::max<uint64_t>(1, n_in / chunk);
+    constexpr uint64_t kMaxSegments = 65535;
+    if (mem.size() > kMaxSegments) return MK_OK;
     if ((rc = mk::ensure_device(&c->d_gz_in, &c->gz_in_cap, n_in + mkz::kPad + 16))) return rc;
-    // tables, all 64-bit: starts[n_chunks] | seg_bits[J + 1] | seg_off[J] | seg_cap[J] | n_out[J] | text_off[J] | status (i32) [J] | bad
-    const size_t tab_words = (size_t)n_chunks * 7 + 16;
+    // tables: starts[n_chunks] | per segment (J <= n_chunks + members of them), 64-bit: bits, end, lim, off, cap | n_out | text_off |
+    // 32-bit: first[J + 1], status[J] | bad
+    const size_t max_seg = (size_t)n_chunks + mem.size();
+    const size_t tab_words = (size_t)n_chunks + max_seg * 8 + 16;
     if ((rc = mk::ensure_device(&c->d_gz_tab, &c->gz_tab_cap, tab_words * 8))) return rc;
     unsigned long long *d_starts = (unsigned long long *)c->d_gz_tab;
     double t0 = now_ms();
-    if ((rc = upload(c, c->d_gz_in, gz + p, n_in))) return rc;
+    if ((rc = upload(c, c->d_gz_in, up, n_in))) return rc;
     MKC_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n_in, 0, mkz::kPad + 16, c->stream), "hipMemsetAsync");
     MKC_HIP(hipStreamSynchronize(c->stream), "upload of the stream");
     c->gz_ms[0] = (float)(now_ms() - t0);
-    // ---- block starts
+    // ---- block starts: searched over all the bytes as they lie there, headers and trailers included
     t0 = now_ms();
     std::vector<unsigned long long> starts(n_chunks, ~0ull);
     mkz::launch_gzip_find((const uint8_t *)c->d_gz_in, n_in, chunk, n_chunks, chunk, d_starts, c->stream);  // (a start behind the next cut is the next chunk's to find)
@@ -385,93 +401,155 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     if (n_chunks > 1) MKC_HIP(hipMemcpyAsync(starts.data() + 1, d_starts + 1, (n_chunks - 1) * 8ull, hipMemcpyDeviceToHost, c->stream), "download of the block starts");
     MKC_HIP(hipStreamSynchronize(c->stream), "gzip block search");
     c->gz_ms[1] = (float)(now_ms() - t0);
-    std::vector<unsigned long long> seg_bits{0ull};
+    std::vector<unsigned long long> found;  // (increasing)
     for (uint32_t k = 1; k < n_chunks; ++k)
-        if (starts[k] != ~0ull && starts[k] > seg_bits.back()) seg_bits.push_back(starts[k]);
-    uint32_t J = (uint32_t)seg_bits.size();
-    seg_bits.push_back(~0ull);
+        if (starts[k] != ~0ull && (found.empty() || starts[k] > found.back())) found.push_back(starts[k]);
     // ---- segments -> symbols.  Room per segment: 12 x its compressed bytes (FASTQ / FASTA / text: 3-6 x), then 48 x once more.
     // A start the search took for one and that is none (as good as never: gzip_segments.hpp) shows here: the piece in front of it
     // runs over it (kSegDesync, and says at which block boundary it stands).  Such starts are dropped and the pieces decoded
-    // again, a few times at most.
-    std::vector<unsigned long long> seg_off, seg_cap, n_out, text_off;
+    // again, a few times at most -- as are the member starts that are none.
+    std::vector<unsigned long long> tab, n_out, text_off;  // tab: bits | end | lim | off | cap, J of each
+    std::vector<uint32_t> seg_first, mem_first;            // segment -> first segment of its member; member -> its first segment (M + 1)
     std::vector<int32_t> status;
-    unsigned long long *d_bits = nullptr, *d_off = nullptr, *d_cap = nullptr, *d_nout = nullptr, *d_toff = nullptr;
+    unsigned long long *d_bits = nullptr, *d_end = nullptr, *d_lim = nullptr, *d_off = nullptr, *d_cap = nullptr, *d_nout = nullptr, *d_toff = nullptr;
+    uint32_t *d_first = nullptr, *d_bad = nullptr;
     int32_t *d_status = nullptr;
-    uint32_t *d_bad = nullptr;
-    uint64_t total = 0;
+    uint32_t J = 0;
     bool done = false;
     t0 = now_ms();
     // (ISIZE says how much text there is in all -- below 4 GiB of it: the first guess per piece is half as much again as the stream's
     // own ratio, which spares a 1.27 GB FASTQ two thirds of a 6 GB allocation; a stream of 4 GiB of text or more starts at 12)
-    const uint64_t whole_ratio = n_in ? (uint64_t)want_isize / n_in + 1 : 1;
-    uint64_t ratio = (n_in < (1ull << 29) && want_isize > n_in) ? std::min<uint64_t>(12, whole_ratio + whole_ratio / 2 + 1) : 12;
-    for (int attempt = 0, dropped_rounds = 0; attempt < 6 && !done; ++attempt) {
-        seg_off.assign(J, 0), seg_cap.assign(J, 0), n_out.assign(J, 0), status.assign(J, 0);
-        d_bits = d_starts + n_chunks, d_off = d_bits + (J + 1), d_cap = d_off + J, d_nout = d_cap + J, d_toff = d_nout + J;
-        d_status = (int32_t *)(d_toff + J);
-        d_bad = (uint32_t *)(d_status + J + (J & 1));
+    uint64_t said_text = 0;
+    for (const GzMember &m : mem) said_text += m.isize;
+    const uint64_t whole_ratio = n_in ? said_text / n_in + 1 : 1;
+    uint64_t ratio = (n_in < (1ull << 29) && said_text > n_in) ? std::min<uint64_t>(12, whole_ratio + whole_ratio / 2 + 1) : 12;
+    for (int dropped_rounds = 0, member_rounds = 0; !done;) {
+        // the table: every member's first bit is a start that is KNOWN; of the searched ones those inside its payload are kept (one in
+        // a header or a trailer is none)
+        const size_t M = mem.size();
+        std::vector<unsigned long long> bits, end, lim;
+        mem_first.assign(M + 1, 0), seg_first.clear();
+        size_t f = 0;
+        for (size_t m = 0; m < M; ++m) {
+            mem_first[m] = (uint32_t)bits.size();
+            const unsigned long long b0 = mem[m].pay * 8, b1 = mem[m].end * 8;
+            bits.push_back(b0);
+            while (f < found.size() && found[f] <= b0) ++f;
+            for (; f < found.size() && found[f] < b1; ++f) bits.push_back(found[f]);
+            for (size_t j = mem_first[m]; j < bits.size(); ++j) {
+                end.push_back(j + 1 < bits.size() ? bits[j + 1] : ~0ull);
+                lim.push_back(std::max(mem[m].end, mem[m].pay));  // (a guess inside the header in front of it leaves no room: such a member reads nothing and fails)
+                seg_first.push_back(mem_first[m]);
+            }
+        }
+        if (bits.size() > kMaxSegments) return MK_OK;
+        J = (uint32_t)bits.size();
+        mem_first[M] = J;
+        seg_first.push_back(J);  // (what the kernels compare the last segment's with)
+        tab.assign((size_t)J * 5, 0);
+        unsigned long long *seg_off = tab.data() + (size_t)J * 3, *seg_cap = seg_off + J;
+        std::copy(bits.begin(), bits.end(), tab.begin()), std::copy(end.begin(), end.end(), tab.begin() + J), std::copy(lim.begin(), lim.end(), tab.begin() + 2 * (size_t)J);
         uint64_t elems = 0;
         for (uint32_t j = 0; j < J; ++j) {
-            const uint64_t b0 = seg_bits[j] >> 3, b1 = j + 1 < J ? seg_bits[j + 1] >> 3 : n_in;
+            const uint64_t b0 = bits[j] >> 3, b1 = end[j] != ~0ull ? end[j] >> 3 : lim[j];
             seg_cap[j] = 65536 + ratio * (b1 - b0 + 1);
             seg_off[j] = elems;
             elems += mkz::kSegPrefix + seg_cap[j] + mkz::kSegSlack;
             elems = (elems + 7) & ~7ull;  // (16-byte aligned buffers)
         }
+        d_bits = d_starts + n_chunks, d_end = d_bits + J, d_lim = d_end + J, d_off = d_lim + J, d_cap = d_off + J, d_nout = d_cap + J, d_toff = d_nout + J;
+        d_first = (uint32_t *)(d_toff + J), d_status = (int32_t *)(d_first + J + 1), d_bad = (uint32_t *)(d_status + J);
+        n_out.assign(J, 0), status.assign(J, 0);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && elems * 2 > c->gz_sym_cap && elems * 2 - c->gz_sym_cap > free_b / 2) return MK_OK;  // not taken: too large for this device
         if ((rc = mk::ensure_device(&c->d_gz_sym, &c->gz_sym_cap, elems * 2 + 64))) return rc;
-        MKC_HIP(hipMemcpyAsync(d_bits, seg_bits.data(), (J + 1) * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the segment table");
-        MKC_HIP(hipMemcpyAsync(d_off, seg_off.data(), J * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the segment table");
-        MKC_HIP(hipMemcpyAsync(d_cap, seg_cap.data(), J * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the segment table");
-        mkz::launch_gzip_segments((const uint8_t *)c->d_gz_in, n_in, d_bits, d_off, d_cap, J, (uint16_t *)c->d_gz_sym, d_nout, d_status, c->num_cus, c->stream,
+        MKC_HIP(hipMemcpyAsync(d_bits, tab.data(), tab.size() * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the segment table");
+        mkz::launch_gzip_segments((const uint8_t *)c->d_gz_in, d_bits, d_end, d_lim, d_off, d_cap, J, (uint16_t *)c->d_gz_sym, d_nout, d_status, c->num_cus, c->stream,
                                   c->inflate_kernel == 1);
         MKC_HIP(hipGetLastError(), "gzip segment decode");
         MKC_HIP(hipMemcpyAsync(n_out.data(), d_nout, J * 8ull, hipMemcpyDeviceToHost, c->stream), "download");
         MKC_HIP(hipMemcpyAsync(status.data(), d_status, J * 4ull, hipMemcpyDeviceToHost, c->stream), "download");
         MKC_HIP(hipStreamSynchronize(c->stream), "gzip segment decode");
-        // the chain from the stream's first bit: a piece that ends on the next start proves that start; the first piece that runs
-        // over its end disproves every start in front of the block boundary it stands at (what lies behind is looked at next time)
-        bool overflow = false, failed = false;
-        uint32_t bad_from = J;
-        for (uint32_t j = 0; j < J && bad_from == J; ++j) {
-            if (status[j] == mkz::kSegDesync && j + 1 < J) bad_from = j;
-            else if (status[j] == mkz::kSegOverflow) overflow = true;
-            else if (status[j] != 0) failed = true;
+        c->gz_segments = J;
+        // Member by member from the file's first: a piece that ends on the next start proves that start; the first piece that runs
+        // over its end disproves every start in front of the block boundary it stands at (what lies behind is looked at next time).
+        // A member whose pieces do not add up otherwise ends somewhere else than at the guess behind it: that guess goes.  What
+        // follows a dropped guess says nothing until a member decodes whole again (a real one: the walk goes on from there, so that
+        // false guesses in several members cost one round, not one each).
+        bool overflow = false, starts_dropped = false, anchored = true;
+        std::vector<char> join(M, 0);  // member m ends at no member start: it is joined with member m + 1
+        std::vector<unsigned long long> gone;
+        for (size_t m = 0; m < M; ++m) {
+            if (m && join[m - 1]) continue;  // (it starts at the guess that has just gone)
+            int32_t st = 0;
+            uint32_t at = mem_first[m];
+            bool over = false;
+            for (; at < mem_first[m + 1] && st == 0; ++at) {
+                if (status[at] == mkz::kSegOverflow) over = true;
+                else st = status[at];
+            }
+            if (st == 0 && !over) {
+                anchored = true;
+                continue;
+            }
+            if (!anchored) continue;
+            if (st == 0) {
+                overflow = true;
+            } else if (st == mkz::kSegDesync && at < mem_first[m + 1]) {  // (at: behind the piece that ran over a start, not the member's last)
+                const unsigned long long stands_at = n_out[at - 1];
+                const size_t before = gone.size();
+                for (uint32_t j = at; j < mem_first[m + 1] && bits[j] < stands_at; ++j) gone.push_back(bits[j]);
+                if (gone.size() == before) return MK_OK;  // (nothing to drop: not what this is for)
+                starts_dropped = true;
+            } else {
+                if (m + 1 == M) return MK_OK;  // (no guess to drop: a stream that does not decode, or ends elsewhere -- zlib will say what this file is)
+                join[m] = 1, anchored = false;
+            }
         }
-        if (failed) return MK_OK;  // (a segment that does not decode, or a stream without its final block: zlib will say what this file is)
-        if (bad_from < J) {
+        if (starts_dropped) {
             if (++dropped_rounds > 3) return MK_OK;
-            const unsigned long long stands_at = n_out[bad_from];
-            std::vector<unsigned long long> kept(seg_bits.begin(), seg_bits.begin() + bad_from + 1);
-            for (uint32_t j = bad_from + 1; j < J; ++j)
-                if (seg_bits[j] >= stands_at) kept.push_back(seg_bits[j]);
-            if (kept.size() == J) return MK_OK;  // (nothing to drop: not what this is for)
-            J = (uint32_t)kept.size();
-            kept.push_back(~0ull);
-            seg_bits.swap(kept);
+            std::vector<unsigned long long> kept;
+            std::set_difference(found.begin(), found.end(), gone.begin(), gone.end(), std::back_inserter(kept));
+            found.swap(kept);
+        }
+        if (std::find(join.begin(), join.end(), 1) != join.end()) {
+            if (++member_rounds > 3) return MK_OK;
+            std::vector<GzMember> left;
+            for (size_t m = 0; m < M; ++m) {
+                if (m && join[m - 1]) left.back().end = mem[m].end, left.back().crc = mem[m].crc, left.back().isize = mem[m].isize;
+                else left.push_back(mem[m]);
+            }
+            mem.swap(left);
             continue;
         }
-        for (uint32_t j = 0; j < J; ++j) overflow = overflow || status[j] == mkz::kSegOverflow;
+        if (starts_dropped) continue;
         if (!overflow) done = true;
         else if (ratio == 48) break;
         else ratio = 48;
     }
-    c->gz_segments = J;
     c->gz_ms[2] = (float)(now_ms() - t0);
     if (!done) return MK_OK;
+    // every member's text: below 4 GiB, and as long as its trailer says
+    const size_t M = mem.size();
     text_off.assign(J, 0);
-    for (uint32_t j = 0; j < J; ++j) text_off[j] = total, total += n_out[j];
-    if ((uint32_t)total != want_isize) return MK_OK;
+    std::vector<uint64_t> mem_text(M, 0);
+    uint64_t total = 0;
+    uint32_t max_member_segs = 1;
+    for (size_t m = 0; m < M; ++m) {
+        for (uint32_t j = mem_first[m]; j < mem_first[m + 1]; ++j) text_off[j] = total, total += n_out[j], mem_text[m] += n_out[j];
+        if (mem_text[m] >> 32 || (uint32_t)mem_text[m] != mem[m].isize) return MK_OK;
+        max_member_segs = std::max(max_member_segs, mem_first[m + 1] - mem_first[m]);
+    }
     // ---- contexts, text, CRC-32
     t0 = now_ms();
     // (the contexts, and behind them two sets of J - 1 maps of 32 768 16-bit elements: launch_gzip_resolve)
     if ((rc = mk::ensure_device(&c->d_gz_ctx, &c->gz_ctx_cap, (size_t)J * mkz::kSegPrefix * 5 + 16))) return rc;
     if ((rc = mk::ensure_device(&c->d_gz_text, &c->gz_text_cap, total + 64))) return rc;
     MKC_HIP(hipMemcpyAsync(d_toff, text_off.data(), J * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the text offsets");
+    MKC_HIP(hipMemcpyAsync(d_first, seg_first.data(), (J + 1) * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the member table");
     MKC_HIP(hipMemsetAsync(d_bad, 0, 4, c->stream), "hipMemsetAsync");
-    mkz::launch_gzip_resolve((const uint16_t *)c->d_gz_sym, d_off, d_nout, d_toff, J, (uint8_t *)c->d_gz_ctx, (uint8_t *)c->d_gz_text, d_bad, c->stream);
+    mkz::launch_gzip_resolve((const uint16_t *)c->d_gz_sym, d_off, d_nout, d_toff, d_first, J, max_member_segs, (uint8_t *)c->d_gz_ctx, (uint8_t *)c->d_gz_text, d_bad,
+                             c->stream);
     MKC_HIP(hipGetLastError(), "gzip resolution");
     uint32_t bad = 0;
     MKC_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream), "download");
@@ -480,27 +558,40 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     if (bad) return MK_OK;
     t0 = now_ms();
     {
-        // CRC-32 of the text: per 65 280-byte block on the device (the BGZF writer's kernel), folded here:
-        // crc(A ++ B) = crc(A) * x^(8 |B|) mod P  ^  crc(B)
+        // CRC-32 of every member's text: per block of at most 65 280 bytes on the device (the BGZF writer's wave), the grid cut member
+        // by member, folded here: crc(A ++ B) = crc(A) * x^(8 |B|) mod P  ^  crc(B)
         const uint32_t bb = mkz::kMaxBlockBytes;
-        const uint32_t blocks = (uint32_t)((total + bb - 1) / bb);
-        if ((rc = mk::ensure_device(&c->d_crc, &c->crc_cap, blocks * 4ull + 16))) return rc;
-        mkz::launch_crc((const uint8_t *)c->d_gz_text, total, bb, blocks, (uint32_t *)c->d_crc, c->stream);
+        std::vector<unsigned long long> blk_off;
+        std::vector<uint32_t> blk_len;
+        for (size_t m = 0; m < M; ++m)
+            for (uint64_t at = 0; at < mem_text[m]; at += bb) blk_off.push_back(text_off[mem_first[m]] + at), blk_len.push_back((uint32_t)std::min<uint64_t>(bb, mem_text[m] - at));
+        const size_t blocks = blk_off.size();
+        if (blocks >> 32) return MK_OK;
+        if ((rc = mk::ensure_device(&c->d_crc, &c->crc_cap, blocks * 4ull + 16)) || (rc = mk::ensure_device(&c->d_off, &c->off_cap, blocks * 8ull + 16)) ||
+            (rc = mk::ensure_device(&c->d_len, &c->len_cap, blocks * 4ull + 16)))
+            return rc;
         std::vector<uint32_t> crcs(blocks);
-        MKC_HIP(hipGetLastError(), "CRC kernel");
-        if (blocks) MKC_HIP(hipMemcpyAsync(crcs.data(), c->d_crc, blocks * 4ull, hipMemcpyDeviceToHost, c->stream), "download of the CRCs");
+        if (blocks) {
+            MKC_HIP(hipMemcpyAsync(c->d_off, blk_off.data(), blocks * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
+            MKC_HIP(hipMemcpyAsync(c->d_len, blk_len.data(), blocks * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
+            mkz::launch_crc_ranges((const uint8_t *)c->d_gz_text, (const unsigned long long *)c->d_off, (const uint32_t *)c->d_len, (uint32_t)blocks, (uint32_t *)c->d_crc,
+                                   c->stream);
+            MKC_HIP(hipGetLastError(), "CRC kernel");
+            MKC_HIP(hipMemcpyAsync(crcs.data(), c->d_crc, blocks * 4ull, hipMemcpyDeviceToHost, c->stream), "download of the CRCs");
+        }
         MKC_HIP(hipStreamSynchronize(c->stream), "CRC kernel");
         const uint32_t shift_full = mkz::crc_x_pow_bytes(bb);
-        uint32_t crc = 0;
-        for (uint32_t b = 0; b < blocks; ++b) {
-            const uint64_t len = b + 1 < blocks ? bb : total - (uint64_t)b * bb;
-            crc = mkz::crc_mulmod(crc, len == bb ? shift_full : mkz::crc_x_pow_bytes(len)) ^ crcs[b];
+        size_t b = 0;
+        for (size_t m = 0; m < M; ++m) {
+            uint32_t crc = 0;
+            for (uint64_t at = 0; at < mem_text[m]; at += bb, ++b) crc = mkz::crc_mulmod(crc, blk_len[b] == bb ? shift_full : mkz::crc_x_pow_bytes(blk_len[b])) ^ crcs[b];
+            if (crc != mem[m].crc) return MK_OK;
         }
-        if (crc != want_crc) return MK_OK;
     }
     c->gz_ms[4] = (float)(now_ms() - t0);
     c->gz_text_bytes = total;
     *text_bytes = total, *taken = 1;
+    if (n_members) *n_members = M;
     // what is left to keep is the text: the symbols (24 x the compressed bytes) and the contexts go back to the device now
     for (void **q : {&c->d_gz_sym, &c->d_gz_ctx, &c->d_gz_in}) {
         if (*q) (void)hipFree(*q);
@@ -508,6 +599,71 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     }
     c->gz_sym_cap = c->gz_ctx_cap = c->gz_in_cap = 0;
     return MK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mk_gzip_member_guesses(const uint8_t *gz, uint64_t n, mk_gzip_guess *table, uint64_t cap, uint64_t *n_guesses) {
+    if (!n_guesses || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_member_guesses: NULL argument");
+    *n_guesses = 0;
+    if (n < 20 || !gzip_header_end(gz, n, 0)) return MK_OK;  // (not a gzip file: no guesses)
+    uint64_t k = 0;
+    auto trailer = [&](uint64_t member, uint64_t end) {  // the 8 bytes in front of `end` are what the member in front of it ends with
+        if (table && member < cap) memcpy(&table[member].crc, gz + end - 8, 4), memcpy(&table[member].isize, gz + end - 4, 4);
+    };
+    for (uint64_t b = 0; n - b >= 20;) {
+        const uint64_t p = gzip_header_end(gz, n, b);
+        if (p && (b == 0 || b >= 8)) {  // (behind the first one: with the room of a trailer in front of it)
+            if (k) trailer(k - 1, b);
+            if (table && k < cap) table[k] = mk_gzip_guess{b, p, 0, 0};
+            ++k;
+        }
+        const void *next = memchr(gz + b + 1, 0x1f, (size_t)(n - b - 1));  // (ID1: one byte in 256)
+        if (!next) break;
+        b = (uint64_t)((const uint8_t *)next - gz);
+    }
+    trailer(k - 1, n);
+    *n_guesses = k;
+    return MK_OK;
+}
+
+int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t *text_bytes, uint32_t *taken) {
+    MK_ABI_BEGIN
+    if (!c || !text_bytes || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: NULL argument");
+    *text_bytes = 0, *taken = 0;
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->gz_text_bytes = 0, c->gz_segments = 0;
+    for (float &x : c->gz_ms) x = 0;
+    // RFC 1952: the member's header, then the DEFLATE stream up to the 8 trailer bytes.  One member is what is taken here: the stream
+    // has to end where the file does, on the final block its last piece meets in front of the trailer (a file of several members
+    // does not: mk_gzip_members_inflate_device).  Not gzip / reserved flags / no room for a stream: not taken.
+    const uint64_t p = n ? gzip_header_end(gz, n, 0) : 0;
+    if (!p) return MK_OK;
+    GzMember one{0, n - 8 - p, 0, 0};
+    memcpy(&one.crc, gz + n - 8, 4), memcpy(&one.isize, gz + n - 4, 4);
+    return gzip_inflate_chain(c, gz + p, one.end, {one}, text_bytes, taken, nullptr);
+    MK_ABI_END
+}
+
+int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_members) {
+    MK_ABI_BEGIN
+    if (!c || !text_bytes || !taken || !n_members || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: NULL argument");
+    *text_bytes = 0, *taken = 0, *n_members = 0;
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->gz_text_bytes = 0, c->gz_segments = 0;
+    for (float &x : c->gz_ms) x = 0;
+    // the member starts as the host can guess them: every place where a header parses.  The file goes up whole; which guesses are
+    // member starts is what the decode proves (gzip_inflate_chain).  Bytes behind the last member cannot be proved away: not taken.
+    uint64_t n_guesses = 0;
+    int rc = mk_gzip_member_guesses(gz, n, nullptr, 0, &n_guesses);
+    if (rc || !n_guesses) return rc;
+    std::vector<mk_gzip_guess> guesses(n_guesses);
+    if ((rc = mk_gzip_member_guesses(gz, n, guesses.data(), n_guesses, &n_guesses))) return rc;
+    std::vector<GzMember> mem(n_guesses);
+    for (uint64_t k = 0; k < n_guesses; ++k) mem[k] = GzMember{guesses[k].data_off, (k + 1 < n_guesses ? guesses[k + 1].header_off : n) - 8, guesses[k].crc, guesses[k].isize};
+    return gzip_inflate_chain(c, gz, n, std::move(mem), text_bytes, taken, n_members);
     MK_ABI_END
 }
 

@@ -27,6 +27,8 @@ struct Member {
 
 // CRC-32 of every block_bytes-sized block of in[0, n) (the last one may be shorter) -> crc[b]
 void launch_crc(const uint8_t *in, uint64_t n, uint32_t block_bytes, uint32_t n_blocks, uint32_t *crc, hipStream_t s);
+// CRC-32 of in[off[b], off[b] + len[b]) -> crc[b], b < n_ranges (off, len: device memory)
+void launch_crc_ranges(const uint8_t *in, const unsigned long long *off, const uint32_t *len, uint32_t n_ranges, uint32_t *crc, hipStream_t s);
 // CRC-32 of the members' text out[out_off, out_off + isize) compared with Member::crc; status[i] |= 0x100 on a mismatch
 void launch_crc_check(const uint8_t *out, const Member *members, uint32_t n_members, int32_t *status, hipStream_t s);
 
@@ -52,21 +54,24 @@ void launch_inflate(const uint8_t *in, uint64_t n_in, const Member *members, uin
 void launch_inflate_wave(const uint8_t *in, uint64_t n_in, const Member *members, uint32_t n_members, uint8_t *out, int32_t *status, hipStream_t s,
                          uint32_t ring_bytes = 32768);
 
-// ---- one gzip member inflated in parallel pieces (gzip_inflate.hip, gzip_segments.hpp) ----
+// ---- a gzip file inflated in parallel pieces: one member, or a chain of them (gzip_inflate.hip, gzip_segments.hpp) ----
 // starts[c] (c = 1 .. n_chunks - 1) = bit position of the first confirmed block start at or behind byte c * chunk_bytes, searched
 // over search_bytes; ~0 = none
 void launch_gzip_find(const uint8_t *in, uint64_t n_in, uint64_t chunk_bytes, uint32_t n_chunks, uint64_t search_bytes, unsigned long long *starts,
                       hipStream_t s);
-// segment j = bits [seg_bits[j], seg_bits[j + 1]) (the last entry ~0: to the final block) -> 16-bit symbols in sym[seg_off[j] + 32768 ...],
-// at most seg_cap[j] of them; n_out[j], status[j]
-void launch_gzip_segments(const uint8_t *in, uint64_t n_in, const unsigned long long *seg_bits, const unsigned long long *seg_off,
-                          const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out, int32_t *status, int num_cus,
-                          hipStream_t s, bool lane_per_segment = false);
+// segment j = bits [seg_bits[j], seg_end[j]) of `in` (seg_end[j] = ~0: a member's last piece, to the final block), read no further than
+// byte seg_lim[j] (the end of its member's payload) -> 16-bit symbols in sym[seg_off[j] + 32768 ...], at most seg_cap[j] of them;
+// n_out[j], status[j]
+void launch_gzip_segments(const uint8_t *in, const unsigned long long *seg_bits, const unsigned long long *seg_end, const unsigned long long *seg_lim,
+                          const unsigned long long *seg_off, const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out,
+                          int32_t *status, int num_cus, hipStream_t s, bool lane_per_segment = false);
 // (the same with a wave per segment: gzip_segments_wave.hip; the place-holders must lie in front of every segment already)
-void launch_gzip_segments_wave(const uint8_t *in, uint64_t n_in, const unsigned long long *seg_bits, const unsigned long long *seg_off,
-                               const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out, int32_t *status, hipStream_t s);
-// contexts (n_seg x 32 KiB) and the text: text[text_off[j] ...] = segment j's bytes; *bad != 0: a symbol that is neither
+void launch_gzip_segments_wave(const uint8_t *in, const unsigned long long *seg_bits, const unsigned long long *seg_end, const unsigned long long *seg_lim,
+                               const unsigned long long *seg_off, const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out,
+                               int32_t *status, hipStream_t s);
+// contexts (n_seg x 32 KiB) and the text: text[text_off[j] ...] = segment j's bytes; *bad != 0: a symbol that is neither.  The chain of
+// contexts restarts at every member: seg_first[j] = the first segment of segment j's member, max_member_segs = the most segments a member has
 void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off, const unsigned long long *n_out, const unsigned long long *text_off,
-                         uint32_t n_seg, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s);
+                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s);
 
 }  // namespace mkz

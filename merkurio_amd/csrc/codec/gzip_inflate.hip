@@ -1,4 +1,4 @@
-// gzip_inflate.hip -- one gzip member (ONE DEFLATE stream) inflated in parallel on the device (r05): the kernels around the serial
+// gzip_inflate.hip -- a gzip file (ONE DEFLATE stream, or one per member) inflated in parallel on the device (r05): the kernels around the serial
 // pieces of gzip_segments.hpp, which says what the scheme is.  Replaces needletail's gzip reader under `merkurio extract`
 // (src/cmd_extract.rs:281-282) for files plain gzip wrote; mk_gzip_inflate_device (codec_host.cpp) drives it.
 //
@@ -132,9 +132,11 @@ __global__ __launch_bounds__(256) void mk_gzip_prefix_kernel(uint16_t *__restric
     sym[seg_off[j] + k] = (uint16_t)(kSegUnknown | k);
 }
 
-// seg_bits[j] = first bit of segment j; seg_bits[n_seg] = ~0 (the last one runs to the final block).  seg_off[j] = element offset of
-// its buffer in sym (prefix first), seg_cap[j] = its capacity.  -> n_out[j], status[j] (0, or a negative code)
-__global__ __launch_bounds__(64, 4) void mk_gzip_segments_kernel(const uint8_t *__restrict__ in, uint64_t n_in, const unsigned long long *__restrict__ seg_bits,
+// seg_bits[j] = first bit of segment j, seg_end[j] = the start behind it in the same member (~0: the member's last piece runs to the
+// final block), seg_lim[j] = the byte behind the member's payload (the reader's bound).  seg_off[j] = element offset of its buffer in
+// sym (prefix first), seg_cap[j] = its capacity.  -> n_out[j], status[j] (0, or a negative code)
+__global__ __launch_bounds__(64, 4) void mk_gzip_segments_kernel(const uint8_t *__restrict__ in, const unsigned long long *__restrict__ seg_bits,
+                                                                 const unsigned long long *__restrict__ seg_end, const unsigned long long *__restrict__ seg_lim,
                                                                  const unsigned long long *__restrict__ seg_off, const unsigned long long *__restrict__ seg_cap,
                                                                  uint32_t n_seg, uint16_t *__restrict__ sym, unsigned long long *__restrict__ n_out,
                                                                  int32_t *__restrict__ status) {
@@ -142,13 +144,12 @@ __global__ __launch_bounds__(64, 4) void mk_gzip_segments_kernel(const uint8_t *
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_seg) return;
     uint16_t *const t = reinterpret_cast<uint16_t *>(lanes + threadIdx.x * (kLaneTableU16 / 2));
-    const uint64_t end = seg_bits[j + 1];
+    const uint64_t end = seg_end[j], lim = seg_lim[j];
     uint64_t produced = 0, stop = 0;
     bool fin = false;
-    int rc = inflate_segment(in, n_in, seg_bits[j], end, 0, sym + seg_off[j] + kSegPrefix, seg_cap[j], t, &produced, &stop, &fin);
-    // both ends must be what the search said they are: the next start reached exactly (and not behind the final block), or the stream's end
-    if (rc == 0 && (end != ~0ull ? (stop != end || fin) : !fin)) rc = kSegDesync;
-    n_out[j] = rc == kSegDesync ? stop : produced;  // (a piece that ran over its end: where it stands, a block boundary)
+    int rc = inflate_segment(in, lim, seg_bits[j], end, 0, sym + seg_off[j] + kSegPrefix, seg_cap[j], t, &produced, &stop, &fin);
+    if (rc == 0) rc = seg_end_status(end, lim, stop, fin);
+    n_out[j] = rc == kSegDesync || rc == kSegEndsEarly ? stop : produced;  // (where it stands, a block boundary)
     status[j] = rc;
 }
 
@@ -161,22 +162,29 @@ __global__ __launch_bounds__(64, 4) void mk_gzip_segments_kernel(const uint8_t *
 // 32 KiB, place-holders of the context's own tail); composing it with map j - r (which gives ctx[j] when r = 1) puts it in terms of
 // a context r segments further back.  With r = 1, 2, 4, ... every map is in terms of ctx[0] after log2(segments) rounds: 12 rounds
 // of ~0.75 GB of traffic for 3 700 segments.
+// The chain restarts at every member: seg_first[j] = the first segment of segment j's member, whose context is nothing.  Map j is
+// composed no further back than that, and the map of a member's last segment (the context of nothing) is left alone.
 __global__ __launch_bounds__(256) void mk_gzip_maps_init_kernel(const uint16_t *__restrict__ sym, const unsigned long long *__restrict__ seg_off,
-                                                                const unsigned long long *__restrict__ n_out, uint16_t *__restrict__ maps) {
+                                                                const unsigned long long *__restrict__ n_out, const uint32_t *__restrict__ seg_first,
+                                                                uint16_t *__restrict__ maps) {
     const uint32_t j = blockIdx.y;
+    if (seg_first[j + 1] != seg_first[j]) return;
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;  // (gridDim.x = kSegPrefix / 256)
     const uint16_t *o = sym + seg_off[j] + kSegPrefix;
     const uint64_t n = n_out[j];
     const uint64_t keep = n >= kSegPrefix ? 0 : kSegPrefix - n;  // elements of the old context that survive
     maps[(uint64_t)j * kSegPrefix + k] = k >= keep ? o[n - (kSegPrefix - k)] : (uint16_t)(kSegUnknown | (uint32_t)(k + n));
 }
-// dst[j] = src[j] composed with src[j - r] (j >= r), else src[j].  8 elements per thread.
-__global__ __launch_bounds__(256) void mk_gzip_maps_step_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, uint32_t r) {
+// dst[j] = src[j] composed with src[j - r] (where j - r is a segment of the same member), else src[j].  8 elements per thread.
+__global__ __launch_bounds__(256) void mk_gzip_maps_step_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, const uint32_t *__restrict__ seg_first,
+                                                                uint32_t r) {
     const uint32_t j = blockIdx.y;
+    const uint32_t first = seg_first[j];
+    if (seg_first[j + 1] != first) return;
     const uint32_t k = (blockIdx.x * 256 + threadIdx.x) * 8;  // (gridDim.x = kSegPrefix / 2048)
     const uint4 v = *reinterpret_cast<const uint4 *>(src + (uint64_t)j * kSegPrefix + k);
     uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    if (j >= r) {
+    if (j >= first + r) {
         const uint16_t *back = src + (uint64_t)(j - r) * kSegPrefix;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -188,13 +196,13 @@ __global__ __launch_bounds__(256) void mk_gzip_maps_step_kernel(const uint16_t *
     }
     *reinterpret_cast<uint4 *>(dst + (uint64_t)j * kSegPrefix + k) = make_uint4(w[0], w[1], w[2], w[3]);
 }
-// ctx[j + 1] from map j, now in terms of ctx[0] = zeros (blockIdx.y = 0: ctx[0] itself).  8 elements per thread.  What is still a
-// place-holder of ctx[0] lies in front of the stream: the 0 written for it is never text -- the translation refuses the symbols
-// that would read it (seg_before_stream).
-__global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t *__restrict__ maps, uint8_t *__restrict__ ctx) {
+// ctx[j + 1] from map j, now in terms of the context of its member's first segment = zeros (that context itself: zeros).  8 elements
+// per thread.  What is still a place-holder lies in front of the member's stream: the 0 written for it is never text -- the
+// translation refuses the symbols that would read it (seg_before_stream).
+__global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t *__restrict__ maps, const uint32_t *__restrict__ seg_first, uint8_t *__restrict__ ctx) {
     const uint32_t k = (blockIdx.x * 256 + threadIdx.x) * 8;
     uint2 bytes = make_uint2(0, 0);
-    if (blockIdx.y) {
+    if (seg_first[blockIdx.y] != blockIdx.y) {
         const uint4 v = *reinterpret_cast<const uint4 *>(maps + (uint64_t)(blockIdx.y - 1) * kSegPrefix + k);
         auto two = [](uint32_t w) -> uint32_t {  // two elements -> two bytes (a place-holder of ctx[0]: 0)
             const uint32_t lo = w & 0xffffu, hi = w >> 16;
@@ -206,10 +214,10 @@ __global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t 
 }
 
 // text[text_off[j] + i] = the byte symbol i of segment j stands for.  bad: a symbol that is neither a byte nor a place-holder, or the
-// place-holder of a byte in front of the stream (a distance too far back, however many matches carried it here).
+// place-holder of a byte in front of the member's stream (a distance too far back, however many matches carried it here).
 __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t *__restrict__ sym, const unsigned long long *__restrict__ seg_off,
                                                                  const unsigned long long *__restrict__ n_out, const unsigned long long *__restrict__ text_off,
-                                                                 const uint8_t *__restrict__ ctx, uint32_t n_seg, uint8_t *__restrict__ text, uint32_t *__restrict__ bad) {
+                                                                 const uint32_t *__restrict__ seg_first, const uint8_t *__restrict__ ctx, uint32_t n_seg, uint8_t *__restrict__ text, uint32_t *__restrict__ bad) {
     __shared__ uint8_t c[kSegPrefix];
     const uint32_t j = blockIdx.x;
     if (j >= n_seg) return;
@@ -219,7 +227,7 @@ __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t 
     const uint16_t *o = sym + seg_off[j] + kSegPrefix;
     uint8_t *dst = text + text_off[j];
     const uint64_t n = n_out[j];
-    const uint32_t before = seg_context_before_stream(text_off[j]);
+    const uint32_t before = seg_context_before_stream(text_off[j] - text_off[seg_first[j]]);
     uint32_t wrong = 0;
     for (uint64_t i = threadIdx.x; i < n; i += 1024) {
         const uint16_t v = o[i];
@@ -235,34 +243,34 @@ void launch_gzip_find(const uint8_t *in, uint64_t n_in, uint64_t chunk_bytes, ui
         hipLaunchKernelGGL(mk_gzip_find_kernel, dim3(n_chunks - 1), dim3(64), 0, s, in, n_in, chunk_bytes, n_chunks, search_bytes, starts);
 }
 
-void launch_gzip_segments(const uint8_t *in, uint64_t n_in, const unsigned long long *seg_bits, const unsigned long long *seg_off,
-                          const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out, int32_t *status, int num_cus,
-                          hipStream_t s, bool lane_per_segment) {
+void launch_gzip_segments(const uint8_t *in, const unsigned long long *seg_bits, const unsigned long long *seg_end, const unsigned long long *seg_lim,
+                          const unsigned long long *seg_off, const unsigned long long *seg_cap, uint32_t n_seg, uint16_t *sym, unsigned long long *n_out,
+                          int32_t *status, int num_cus, hipStream_t s, bool lane_per_segment) {
     if (!n_seg) return;
     hipLaunchKernelGGL(mk_gzip_prefix_kernel, dim3(kSegPrefix / 256, n_seg), dim3(256), 0, s, sym, seg_off, n_seg);
     if (!lane_per_segment) {
-        launch_gzip_segments_wave(in, n_in, seg_bits, seg_off, seg_cap, n_seg, sym, n_out, status, s);
+        launch_gzip_segments_wave(in, seg_bits, seg_end, seg_lim, seg_off, seg_cap, n_seg, sym, n_out, status, s);
         return;
     }
     const uint32_t lanes = inflate_lanes(n_seg, num_cus);
-    hipLaunchKernelGGL(mk_gzip_segments_kernel, dim3((n_seg + lanes - 1) / lanes), dim3(lanes), lanes * (kLaneTableU16 / 2) * 4, s, in, n_in, seg_bits, seg_off,
-                       seg_cap, n_seg, sym, n_out, status);
+    hipLaunchKernelGGL(mk_gzip_segments_kernel, dim3((n_seg + lanes - 1) / lanes), dim3(lanes), lanes * (kLaneTableU16 / 2) * 4, s, in, seg_bits, seg_end,
+                       seg_lim, seg_off, seg_cap, n_seg, sym, n_out, status);
 }
 
 void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off, const unsigned long long *n_out, const unsigned long long *text_off,
-                         uint32_t n_seg, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s) {
+                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s) {
     if (!n_seg) return;
     // ctx: n_seg x 32 KiB of contexts, then two sets of n_seg - 1 maps (gzip_resolve_bytes)
     uint16_t *maps[2] = {reinterpret_cast<uint16_t *>(ctx + (uint64_t)n_seg * kSegPrefix), nullptr};
     maps[1] = maps[0] + (uint64_t)(n_seg - 1) * kSegPrefix;
     int cur = 0;
-    if (n_seg > 1) {
-        hipLaunchKernelGGL(mk_gzip_maps_init_kernel, dim3(kSegPrefix / 256, n_seg - 1), dim3(256), 0, s, sym, seg_off, n_out, maps[0]);
-        for (uint32_t r = 1; r < n_seg - 1; r *= 2, cur ^= 1)
-            hipLaunchKernelGGL(mk_gzip_maps_step_kernel, dim3(kSegPrefix / 2048, n_seg - 1), dim3(256), 0, s, maps[cur], maps[cur ^ 1], r);
+    if (max_member_segs > 1) {  // (the chains of the members side by side: as many rounds as the longest of them needs)
+        hipLaunchKernelGGL(mk_gzip_maps_init_kernel, dim3(kSegPrefix / 256, n_seg - 1), dim3(256), 0, s, sym, seg_off, n_out, seg_first, maps[0]);
+        for (uint32_t r = 1; r < max_member_segs - 1; r *= 2, cur ^= 1)
+            hipLaunchKernelGGL(mk_gzip_maps_step_kernel, dim3(kSegPrefix / 2048, n_seg - 1), dim3(256), 0, s, maps[cur], maps[cur ^ 1], seg_first, r);
     }
-    hipLaunchKernelGGL(mk_gzip_maps_final_kernel, dim3(kSegPrefix / 2048, n_seg), dim3(256), 0, s, maps[cur], ctx);
-    hipLaunchKernelGGL(mk_gzip_translate_kernel, dim3(n_seg), dim3(1024), 0, s, sym, seg_off, n_out, text_off, ctx, n_seg, text, bad);
+    hipLaunchKernelGGL(mk_gzip_maps_final_kernel, dim3(kSegPrefix / 2048, n_seg), dim3(256), 0, s, maps[cur], seg_first, ctx);
+    hipLaunchKernelGGL(mk_gzip_translate_kernel, dim3(n_seg), dim3(1024), 0, s, sym, seg_off, n_out, text_off, seg_first, ctx, n_seg, text, bad);
 }
 
 }  // namespace mkz

@@ -26,6 +26,8 @@
 // Anything that does not add up -- no block start found where one is needed, a segment that does not end exactly on the next start,
 // a buffer that is too small for an unusually compressible stream, a wrong CRC -- makes the whole call report "not taken": the
 // caller inflates that file with zlib, as before.  RFC 1951 / RFC 1952.
+// A file of SEVERAL members is the same scheme over all of them at once (mk_gzip_members_inflate_device, codec_host.cpp): every
+// member's first bit is a start that is known, a piece never reads behind its member's payload, the contexts restart at every member.
 #pragma once
 #include "inflate_serial.hpp"
 
@@ -36,7 +38,16 @@ constexpr uint16_t kSegUnknown = 0x8000u;  // | index into the 32 KiB in front o
 constexpr uint32_t kSegSlack = 16;         // elements a segment buffer holds behind its capacity (8-byte copy rounds overshoot)
 
 // error codes (negative; >= 0 are fine)
-constexpr int kSegDesync = -20, kSegOverflow = -21, kSegNoStart = -22;
+constexpr int kSegDesync = -20, kSegOverflow = -21, kSegNoStart = -22, kSegEndsEarly = -23;
+
+// What a piece that decoded cleanly says about its ends.  A piece in front of another start (bit_end) has met it exactly -- a final
+// block on the way is a member that ends in front of where it is said to (kSegEndsEarly).  A member's last piece (bit_end = ~0) runs
+// to the final block, which must end inside the last byte of the member's payload [.., lim): in front of it the member ends early
+// (bytes between the stream and the trailer: zlib reads the trailer there), behind it the reader's bound has cut the piece short.
+MKZ_HD int seg_end_status(uint64_t bit_end, uint64_t lim, uint64_t stop, bool fin) {
+    if (bit_end != ~0ull) return fin ? kSegEndsEarly : stop != bit_end ? kSegDesync : 0;
+    return !fin ? kSegDesync : stop + 8 <= lim * 8 ? kSegEndsEarly : 0;
+}
 
 // Element k of the context of a segment whose text starts at byte text_off of the whole text is byte text_off - 32 768 + k of it:
 // how many elements at the context's front lie in front of the stream's first byte.  A symbol that is the place-holder of one of

@@ -54,7 +54,7 @@ EXPORTS = [
     "mk_synth_reads_host", "mk_synth_reads_device_range", "mk_reduce_counters", "mk_reduce_prepare", "mk_comm_available", "mk_comm_unique_id", "mk_comm_init",
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
-    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_extract_fastq_bgzf", "mk_extract_window",
+    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_extract_fastq_bgzf", "mk_extract_window",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
@@ -286,6 +286,8 @@ def load(build_if_missing=True):
     L.mk_codec_set_gzip_chunk.argtypes = [C.c_void_p, C.c_uint64]
     L.mk_codec_set_inflate_kernel.argtypes = [C.c_void_p, C.c_int]
     L.mk_gzip_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.mk_gzip_member_guesses.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mk_gzip_members_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.mk_gzip_text_read.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     L.mk_gzip_text_device.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mk_gzip_text_device.restype = C.c_void_p
@@ -996,6 +998,21 @@ def bgzf_members(data):
     return mem, used.value, text.value
 
 
+GUESS_DTYPE = np.dtype([("header_off", "<u8"), ("data_off", "<u8"), ("crc", "<u4"), ("isize", "<u4")])
+
+
+def gzip_member_guesses(data):
+    """mk_gzip_member_guesses: every offset of a gzip byte string at which an RFC 1952 header parses (host code) -> table of
+    header_off, data_off and the crc / isize in front of the next guess.  Guesses, not members: the device proves them"""
+    L = load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n = C.c_uint64(0)
+    _check(L.mk_gzip_member_guesses(buf.ctypes.data if buf.size else None, buf.size, None, 0, C.byref(n)))
+    table = np.zeros(n.value, dtype=GUESS_DTYPE)
+    _check(L.mk_gzip_member_guesses(buf.ctypes.data if buf.size else None, buf.size, table.ctypes.data if table.size else None, table.size, C.byref(n)))
+    return table
+
+
 def bgzf_eof():
     return bytes(load().mk_bgzf_eof().contents)
 
@@ -1073,6 +1090,23 @@ class Codec:
         _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
         self.last_read_s = time.perf_counter() - t0
         return out.tobytes()
+
+    def gunzip_members(self, gz):
+        """mk_gzip_members_inflate_device + mk_gzip_text_read: a gzip file of one or more members, all of them inflated in one batch of
+        parallel pieces -> (text of all members, how many members were proved), or None when the device did not take the file"""
+        src = np.frombuffer(gz, dtype=np.uint8)
+        n, taken, members = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        t0 = time.perf_counter()
+        _check(self._L.mk_gzip_members_inflate_device(self._h, src.ctypes.data if src.size else None, src.size, C.byref(n), C.byref(taken), C.byref(members)))
+        self.last_call_s = time.perf_counter() - t0
+        seg, ms = C.c_uint32(0), (C.c_float * 5)()
+        _check(self._L.mk_gzip_info(self._h, C.byref(seg), ms))
+        self.gzip_info = (seg.value, tuple(round(x, 2) for x in ms))
+        if not taken.value:
+            return None
+        out = np.empty(n.value, dtype=np.uint8)
+        _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
+        return out.tobytes(), members.value
 
     def set_inflate_kernel(self, which=0):
         """0 = chosen per call, 1 = a lane per member, 2 = a wave per member (mk_codec_set_inflate_kernel)"""
