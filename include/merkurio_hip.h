@@ -571,6 +571,39 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
                       uint32_t *pattern_hit_counts, uint32_t *status);
 
 /* -------------------------------------------------------------------------------------
+ * BGZF members that end at record ends (v7 addition) -- the output side of `extract -z`: the kept records are deflated on the
+ * device, and every member is a FASTQ / FASTA fragment that parses on its own, so a reader that splits its work at member boundaries needs
+ * no head / tail chain.  (mk_bgzf_deflate cuts its text every block_bytes: a record may straddle two members.  The reference writes
+ * plain text only: src/cmd_extract.rs:297-318.)
+ *
+ * THE CUT RULE.  A text of T bytes whose records end at e[0] <= e[1] <= ... <= e[n-1] = T.  G = 49152 (the grid step), L = 65280 (the
+ * most text a member holds).  For k = 1 .. ceil(T / G) - 1, x = k * G: e* = the smallest record end >= x; snap(x) = e* if
+ * e* < x + (L - G), else x (a raw cut inside a record longer than L - G = 16128 bytes: a chromosome).  The cuts are 0, the distinct
+ * snap(k * G) in increasing order, and T; member i is the text between cut i and cut i + 1.  Consecutive cuts are more than 0 and at
+ * most L bytes apart; a grid point costs one binary search, no walk over the records; T = 0 gives one cut (0) and no member.  Since
+ * snap(x) lies in [x, x + (L - G)) and L - G <= G, two grid points never snap to the same place: the only cut that can coincide with
+ * another is the last grid point's with T.  A text that starts and ends at record ends gives members that do: concatenated outputs
+ * of several calls stay record-aligned.
+ *
+ * mk_bgzf_record_cuts (host code, no device): the rule -> cut[0, *n_cuts), at most ceil(T / G) + 1 of them.  rec_end must not
+ * decrease (MK_E_INVALID_ARG); cap too small: MK_E_CAPACITY with *n_cuts = the need.
+ * mk_bgzf_deflate_records: text[0, n) with rec_end[n_rec - 1] = n -> the members of the rule back to back in out, cut and deflated
+ * on the device (the cut kernel is checked against mk_bgzf_record_cuts by the tests).  *out_len = their bytes, *n_members how many;
+ * out_cap too small: MK_E_CAPACITY with *out_len = the exact need; out then holds nothing of use (the members of the device passes
+ * that still fitted may have been written to it).  No EOF member is appended.  Honours
+ * mk_codec_set_pass_limits (deflate_members).
+ * mk_codec_cut_times: members and milliseconds (cut kernel; CRC-32 + deflate + pack; download) of the handle's last
+ * mk_bgzf_deflate_records -- mk_codec_times reports the first two as one number, a caller that weighs the cut kernel against the deflate
+ * launch (`extract -z` under MERKURIO_TIMING) needs them apart.
+ * --------------------------------------------------------------------------------------- */
+#define MK_BGZF_CUT_GRID 49152u
+#define MK_BGZF_MEMBER_TEXT_MAX 65280u
+int mk_bgzf_record_cuts(const uint64_t *rec_end, uint64_t n_rec, uint64_t *cut, uint64_t cap, uint64_t *n_cuts);
+int mk_bgzf_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const uint64_t *rec_end, uint64_t n_rec, uint8_t *out, uint64_t out_cap,
+                            uint64_t *out_len, uint64_t *n_members);
+int mk_codec_cut_times(const mk_codec *c, uint64_t *n_members, float ms[3]);
+
+/* -------------------------------------------------------------------------------------
  * A gzip file inflated in parallel on the device (v6: one member; v7: a chain of members) -- a .fastq.gz / .fasta.gz as plain gzip (or pigz, or zlib) writes it: ONE
  * DEFLATE stream of thousands of blocks, which zlib can only walk from the front.  Replaces needletail's gzip reader under
  * `merkurio extract` (src/cmd_extract.rs:281-282) for such files.  The stream is cut where block starts can be FOUND (a dynamic

@@ -1,0 +1,75 @@
+// bgzf_out.cpp -- `extract -z` (bgzf_out.hpp).  The reference writes plain text only (src/cmd_extract.rs:297-318).
+#include "bgzf_out.hpp"
+
+#include <chrono>
+
+namespace cli {
+
+void RecordGzip::attach(Sink &sink, int device) {
+    sink_ = &sink, device_ = device;
+    sink.flush();
+    sink.z_text = &text_, sink.z_ends = &ends_;
+    sink.z_window = [this] { window_done(); };
+}
+
+void RecordGzip::window_done(bool force) {
+    if (!sink_ || text_.empty() || (!force && text_.size() < (64u << 20))) return;
+    if (ends_.empty() || ends_.back() != text_.size()) ends_.push_back(text_.size());  // (text behind the last marked record end: its own record)
+    FILE *f = sink_->f;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (device_ >= 0) {
+        if (!codec_) mk_check(mk_codec_create(device_, &codec_), "Error setting up the BGZF codec");
+        uint64_t need = 0, n_members = 0;
+        // (every member stored: its text + 31 bytes -- the call then never has to run twice)
+        out_.resize(std::max<size_t>(out_.size(), text_.size() + 31 * (text_.size() / MK_BGZF_CUT_GRID + 1)));
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            const int rc = mk_bgzf_deflate_records(codec_, (const uint8_t *)text_.data(), text_.size(), ends_.data(), ends_.size(), out_.data(), out_.size(), &need,
+                                                   &n_members);
+            if (rc == MK_E_CAPACITY && attempt == 0) {
+                out_.resize(need);
+                continue;
+            }
+            mk_check(rc, "Error compressing the output");
+            break;
+        }
+        float ms[3] = {0, 0, 0};
+        (void)mk_codec_cut_times(codec_, nullptr, ms);
+        cut_ms += ms[0], deflate_ms += ms[1], download_ms += ms[2];
+        members += n_members;
+        if (f && fwrite(out_.data(), 1, need, f) != need) bail("Error writing the compressed output");
+    } else {
+        uint64_t n_cuts = 0;
+        std::vector<uint64_t> cut(text_.size() / MK_BGZF_CUT_GRID + 3);
+        mk_check(mk_bgzf_record_cuts(ends_.data(), ends_.size(), cut.data(), cut.size(), &n_cuts), "Error compressing the output");
+        const size_t blocks = (size_t)n_cuts - 1;
+        std::vector<std::vector<uint8_t>> outs(blocks);
+        const size_t T = std::max<size_t>(1, std::min<size_t>(io_threads(), blocks));
+        std::vector<std::string> errs(T);
+        run_threads(T, [&](size_t t) {
+            try {
+                for (size_t i = t; i < blocks; i += T) bgzf_compress((const uint8_t *)text_.data() + cut[i], (size_t)(cut[i + 1] - cut[i]), outs[i]);
+            } catch (const Error &e) {
+                errs[t] = e.what()[0] ? e.what() : "error";
+            }
+        });
+        for (auto &e : errs)
+            if (!e.empty()) bail(e);
+        deflate_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        members += blocks;
+        for (auto &o : outs)
+            if (f && fwrite(o.data(), 1, o.size(), f) != o.size()) bail("Error writing the compressed output");
+    }
+    text_.clear(), ends_.clear();
+}
+
+void RecordGzip::finish() {
+    if (!sink_) return;
+    window_done(true);
+    if (sink_->f && fwrite(mk_bgzf_eof(), 1, 28, sink_->f) != 28) bail("Error writing the compressed output");
+    if (sink_->f) fflush(sink_->f);
+    sink_->z_text = nullptr, sink_->z_ends = nullptr, sink_->z_window = nullptr;
+    if (codec_ && !g_process_is_ending) mk_codec_destroy(codec_);
+    codec_ = nullptr, sink_ = nullptr;
+}
+
+}  // namespace cli

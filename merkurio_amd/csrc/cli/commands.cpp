@@ -21,6 +21,7 @@
 #include "io.hpp"
 #include "extract_common.hpp"
 #include "tag_host.hpp"
+#include "bgzf_out.hpp"
 
 namespace cli {
 
@@ -347,6 +348,7 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
     Sink w1, w2;
     if (a.out_fastx) {
         std::string p = with_extension(*a.out_fastx, identify_uncompressed_type(a.in_fastx));
+        if (a.bgzf_output) p += ".gz";  // (-z; the reference never compresses: its name is the derived one)
         if (paired) {
             w1.open(add_suffix_to_file_prefix(p, "_1"));
             w2.open(add_suffix_to_file_prefix(p, "_2"));
@@ -358,6 +360,12 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
     } else {
         w1.open("STDOUT");
         if (paired) w2.open("STDOUT");
+    }
+    // -z: what the sinks are given leaves as BGZF members that end at record ends
+    RecordGzip z1, z2;
+    if (a.bgzf_output) {
+        z1.attach(w1, a.host_codec ? -1 : devs[0]);
+        if (paired) z2.attach(w2, a.host_codec ? -1 : devs[0]);
     }
 
     mk_counters c;
@@ -380,8 +388,10 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
         for (uint64_t k = 0; k < nb; ++k)
             if (keep[k]) {
                 f1.write(b0 + k, w1);
-                if (paired) f2.write(b0 + k, w2);
+                w1.end_record();
+                if (paired) f2.write(b0 + k, w2), w2.end_record();
             }
+        w1.window_done(), w2.window_done();
     };
     // Scans records [r0, r1) on matcher `mm` in double-buffered batches: while batch k is on the GPU
     // and its results are consumed, a second thread gathers the sequences of batch k + 1.
@@ -535,9 +545,13 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
         reduce_device_counters(ms, devs, dev_c, dev_counts, c, counts);
         tm.mark("counter reduction (RCCL set-up began with the job)");
     }
+    z1.finish(), z2.finish();
     w1.flush();
     w2.flush();
     tm.mark("log rows + write records");
+    if (tm.on && a.bgzf_output)
+        fprintf(stderr, "[timing] BGZF output (%s): %llu members written, cut %.1f ms, deflate %.1f ms, download %.1f ms\n", a.host_codec ? "zlib, host" : "device codec",
+                (unsigned long long)(z1.members + z2.members), z1.cut_ms + z2.cut_ms, z1.deflate_ms + z2.deflate_ms, z1.download_ms + z2.download_ms);
     if (tm.on && (call_ms[0] + call_ms[1] + call_ms[2] + call_ms[3]) > 0)
         fprintf(stderr, "[timing] inside the batch calls: upload %.3f s, device %.3f s, download %.3f s, host loop %.3f s\n", call_ms[0] * 1e-3,
                 call_ms[1] * 1e-3, call_ms[2] * 1e-3, call_ms[3] * 1e-3);

@@ -40,6 +40,7 @@ struct ExtractArgs : CommonArgs {
     std::string in_fastx;                   // -i / -1
     std::optional<std::string> in_fastq_2;  // -2
     std::optional<std::string> out_fastx;   // -o
+    bool bgzf_output = false;               // -z: the kept records are written as BGZF members that end at record ends (output name + ".gz")
 };
 
 struct TagArgs : CommonArgs {

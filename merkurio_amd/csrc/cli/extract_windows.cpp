@@ -609,7 +609,7 @@ struct WindowExtract::Impl {
             if (!a.suppress_output)
                 for (uint64_t r = 0; r < n; ++r)
                     if (W.keep[r])
-                        for (int i = 0; i < n_in; ++i) W.side[i].parsed.write(r, *w[i]);
+                        for (int i = 0; i < n_in; ++i) W.side[i].parsed.write(r, *w[i]), w[i]->end_record();
             return;
         }
         // record r of side i in the text the writer holds: its own table for packed kept records
@@ -661,7 +661,9 @@ struct WindowExtract::Impl {
                 if (W.keep[r]) kept.push_back(r);
             const size_t T = std::max<size_t>(1, std::min<size_t>(io_threads(), kept.size() / 1024));
             std::vector<std::string> out[2];
-            out[0].resize(T), out[1].resize(T);
+            std::vector<std::vector<uint64_t>> out_ends[2];  // (-z: where every record ends in its buffer)
+            const bool mark_ends = w[0]->z_ends != nullptr;
+            for (int i = 0; i < 2; ++i) out[i].resize(T), out_ends[i].resize(T);
             run_threads(T, [&](size_t t) {
                 FastxFile one;
                 one.fastq = fastq;
@@ -691,11 +693,12 @@ struct WindowExtract::Impl {
                             o.append(sp.p + rec.raw_b, (size_t)(rec.raw_e - rec.raw_b)).append(eol, nl);
                             if (fastq) o.append("+", 1).append(eol, nl).append(sp.p + rec.qual_b, (size_t)(rec.qual_e - rec.qual_b)).append(eol, nl);
                         }
+                        if (mark_ends) out_ends[i][t].push_back(o.size());
                     }
                 }
             });
             for (size_t t = 0; t < T; ++t)
-                for (int i = 0; i < n_in; ++i) w[i]->write(out[i][t]);
+                for (int i = 0; i < n_in; ++i) w[i]->write_records(out[i][t], out_ends[i][t]);
         }
         tm.mark("window: records out");
     }
@@ -896,6 +899,7 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             add_counters(dev_c[W->dev], W->cb);
             add_counts(dev_counts[W->dev], W->cnt);
             J.write_window(*W, w1, w2, name1, name2, tm);
+            w1.window_done(), w2.window_done();
             {
                 std::lock_guard<std::mutex> lk(J.mu);
                 J.written = k + 1;

@@ -1464,7 +1464,7 @@ void BamWriter::put_members(HostBuffer &&buffer, size_t used) {
 }
 
 // one BGZF member: gzip header with the BC extra field, raw deflate, crc32, isize
-static void bgzf_compress(const uint8_t *in, size_t n, std::vector<uint8_t> &out) {
+void bgzf_compress(const uint8_t *in, size_t n, std::vector<uint8_t> &out) {
     out.resize(n + n / 8 + 1024);
     z_stream z;
     memset(&z, 0, sizeof(z));
@@ -1486,7 +1486,6 @@ static void bgzf_compress(const uint8_t *in, size_t n, std::vector<uint8_t> &out
     memcpy(out.data() + 22 + clen, &isize, 4);
     out.resize(clen + 26);
 }
-
 
 void BamWriter::writer_loop() {
     for (;;) {

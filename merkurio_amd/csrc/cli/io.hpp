@@ -314,6 +314,8 @@ struct SamFile {
     std::vector<Rec> nrecs;
     bool have_next = false, next_more = false;
 };
+// one BGZF member of in[0, n) (n <= 65 280) by zlib at level 6: gzip header with the BC extra field, raw deflate, CRC-32, ISIZE
+void bgzf_compress(const uint8_t *in, size_t n, std::vector<uint8_t> &out);
 // BAM writer (BGZF): encodes SAM text lines against the header's @SQ dictionary.  Used for
 // `tag -o out.bam` (src/cmd_tag.rs:254-271); output is checked by reading it back.
 // The uncompressed stream is kept as the pieces it arrives in (the per-thread record buffers of a batch are moved in,

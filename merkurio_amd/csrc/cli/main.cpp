@@ -23,7 +23,7 @@ const Spec kCommon[] = {{'s', "kmer-seq", 2},      {'f', "kmer-file", 1},    {'r
                         {'I', "case-insensitive", 0}, {'L', "lowercase", 0}, {'U', "uppercase", 0},          {'q', "q-size", 1},
                         {'a', "aho-corasick", 0},  {0, "device", 1},         {0, "batch-mb", 1},           {0, "gpus", 1},                 {0, "window-mb", 1},
                         {0, "host-ingest", 0},     {0, "host-codec", 0},     {0, "device-codec-always", 0}};
-const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}};
+const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}, {'z', "bgzf-output", 0}};
 const Spec kTag[] = {{'i', "in-file", 1}, {'o', "out-file", 1}, {'t', "tag", 1}, {'p', "threads", 1}, {'m', "filter-matching", 0}};
 
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -42,6 +42,7 @@ void print_help(const char *sub) {
              "  -i, -1, --in-fastx <PATH>    (compressed: gzip) FASTQ/A input\n  -2, --in-fastq-2 <PATH>      second FASTQ file (paired-end)\n"
              "  -s, --kmer-seq <SEQ>...      query sequences\n  -f, --kmer-file <PATH>       file with one k-mer per line\n"
              "  -o, --out-fastx <PATH>       output path (extension derived from the input)\n  -r, --reverse-complement     also search reverse complements\n"
+             "  -z, --bgzf-output            write the records bgzip'ed, members ending at record ends (output name + .gz; deflated on the GPU, --host-codec: zlib)\n"
              "  -c, --canonical              search canonical forms only\n  -l, --out-log [<PATH>]       text log (stdout without a value)\n"
              "  -j, --json-log [<PATH>]      JSON log\n  -S, --suppress-output        write no records (requires -l/-j)\n"
              "  -v, --invert-match           select non-matching records\n  -I, --case-insensitive       (always Aho-Corasick)\n"
@@ -243,6 +244,8 @@ int main(int argc, char **argv) {
             a.in_fastx = (*in)[0];
             if (auto v = p.get("in-fastq-2")) a.in_fastq_2 = (*v)[0];
             if (auto v = p.get("out-fastx")) a.out_fastx = (*v)[0];
+            a.bgzf_output = p.get("bgzf-output") != nullptr;
+            if (a.bgzf_output && p.get("suppress-output")) usage_error("the argument '--suppress-output' cannot be used with '--bgzf-output'");
             fill_common(p, a, (bool)a.out_fastx);
             g_process_is_ending = true;
             return leave(run_extract(a, all));

@@ -186,8 +186,18 @@ void Sink::open(const std::string &path) {
     }
 }
 void Sink::write(const char *p, size_t n) {
+    if (z_text) {
+        z_text->append(p, n);
+        return;
+    }
     buf.append(p, n);
     if (buf.size() >= (1u << 20)) flush();
+}
+void Sink::write_records(const std::string &s, const std::vector<uint64_t> &ends) {
+    if (!z_text) return write(s);
+    const uint64_t base = z_text->size();
+    z_text->append(s);
+    for (uint64_t e : ends) z_ends->push_back(base + e);
 }
 void Sink::flush() {
     if (f && !buf.empty()) fwrite(buf.data(), 1, buf.size(), f);

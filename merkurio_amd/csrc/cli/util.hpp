@@ -2,6 +2,7 @@
 // (src/helpers.rs:16-68), an ordered JSON value with serde_json-compatible pretty printing
 // (src/logger.rs:108-190), and the two loggers (src/logger.rs:11-191).
 #pragma once
+#include <functional>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -65,6 +66,18 @@ struct Sink {
     void write(const std::string &s) { write(s.data(), s.size()); }
     void write(const char *p, size_t n);
     void flush();
+    // extract -z (RecordGzip, bgzf_out.hpp): what is written is record text that leaves as BGZF members -- it gathers in *z_text, and the
+    // offset behind every record in *z_ends, until the compressor takes both
+    std::string *z_text = nullptr;
+    std::vector<uint64_t> *z_ends = nullptr;
+    void end_record() {  // what has been written since the last call is one record
+        if (z_ends) z_ends->push_back(z_text->size());
+    }
+    std::function<void()> z_window;
+    void window_done() {  // a window's records have been written: the compressor may take what has gathered
+        if (z_window) z_window();
+    }
+    void write_records(const std::string &s, const std::vector<uint64_t> &ends);  // whole records; ends: the offset in s behind each (used with -z only)
 };
 
 // logger::BufferedLogger (text log).  The reference keeps every row in memory as well

@@ -146,11 +146,29 @@ __device__ __forceinline__ void token_code(uint32_t t, const BlockCodes &c, uint
     bits |= (uint64_t)dxb << nb, nb += dnb;
 }
 
-__global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_kernel(const uint8_t *__restrict__ in, uint64_t n_bytes, uint32_t block_bytes,
-                                                             uint32_t n_blocks, const uint32_t *__restrict__ crc,
-                                                             uint32_t *__restrict__ tokens, uint8_t *__restrict__ slots,
-                                                             uint32_t *__restrict__ slot_len, uint32_t *__restrict__ next_block) {
-    __shared__ DeflateLds L;
+// How a wave finds the text of member b: every block_bytes of in[0, n_bytes) (mk_bgzf_deflate, the tag windows), or a table of
+// ranges (members that end at record ends: mk_bgzf_cuts_kernel below).  at(b) and len(b) are wave-uniform.
+struct UniformBlocks {
+    uint64_t n_bytes;
+    uint32_t block_bytes;
+    __device__ __forceinline__ uint64_t at(uint32_t b) const { return (uint64_t)b * block_bytes; }
+    __device__ __forceinline__ uint32_t len(uint32_t b) const {
+        const uint64_t a = at(b);
+        return (uint32_t)(n_bytes - a < block_bytes ? n_bytes - a : block_bytes);
+    }
+};
+struct RangeTable {
+    const unsigned long long *off;
+    const uint32_t *size;
+    __device__ __forceinline__ uint64_t at(uint32_t b) const { return off[b]; }
+    // (a member holds kMaxBlockBytes of text at most -- the token scratch and the slot are sized for that: a longer entry is cut short)
+    __device__ __forceinline__ uint32_t len(uint32_t b) const { return size[b] < kMaxBlockBytes ? size[b] : kMaxBlockBytes; }
+};
+
+template <class Ranges>
+__device__ __forceinline__ void deflate_members(DeflateLds &L, const uint8_t *__restrict__ in, const Ranges rg, uint32_t n_blocks,
+                                                const uint32_t *__restrict__ crc, uint32_t *__restrict__ tokens, uint8_t *__restrict__ slots,
+                                                uint32_t *__restrict__ slot_len, uint32_t *__restrict__ next_block) {
     const uint32_t lane = lane_id();
     uint32_t *const tok = tokens + (uint64_t)blockIdx.x * kTokensPerWave;
 
@@ -160,9 +178,8 @@ __global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_kernel(const uint8_t *_
         if (lane == 0) b = atomicAdd(next_block, 1u);
         b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
         if (b >= n_blocks) break;
-        const uint64_t at = (uint64_t)b * block_bytes;
-        const uint8_t *const src = in + at;
-        const uint32_t n = (uint32_t)(n_bytes - at < block_bytes ? n_bytes - at : block_bytes);
+        const uint8_t *const src = in + rg.at(b);
+        const uint32_t n = rg.len(b);
         uint8_t *const slot = slots + (uint64_t)b * kSlotBytes;
         uint32_t *const slot_w = reinterpret_cast<uint32_t *>(slot);
 
@@ -337,6 +354,53 @@ __global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_kernel(const uint8_t *_
     }
 }
 
+__global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_kernel(const uint8_t *__restrict__ in, uint64_t n_bytes, uint32_t block_bytes,
+                                                             uint32_t n_blocks, const uint32_t *__restrict__ crc,
+                                                             uint32_t *__restrict__ tokens, uint8_t *__restrict__ slots,
+                                                             uint32_t *__restrict__ slot_len, uint32_t *__restrict__ next_block) {
+    __shared__ DeflateLds L;
+    deflate_members(L, in, UniformBlocks{n_bytes, block_bytes}, n_blocks, crc, tokens, slots, slot_len, next_block);
+}
+// member b = in[off[b], off[b] + len[b])
+__global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_ranges_kernel(const uint8_t *__restrict__ in, const unsigned long long *__restrict__ off,
+                                                                    const uint32_t *__restrict__ len, uint32_t n_blocks,
+                                                                    const uint32_t *__restrict__ crc, uint32_t *__restrict__ tokens,
+                                                                    uint8_t *__restrict__ slots, uint32_t *__restrict__ slot_len,
+                                                                    uint32_t *__restrict__ next_block) {
+    __shared__ DeflateLds L;
+    deflate_members(L, in, RangeTable{off, len}, n_blocks, crc, tokens, slots, slot_len, next_block);
+}
+
+// ---- members that end at record ends: the cut rule of include/merkurio_hip.h (mk_bgzf_record_cuts is the same rule on the host) ----
+// rec_end[0, n_rec): the ends of the records of a text of T bytes, non-decreasing (a record that is not kept repeats the end in front
+// of it), rec_end[n_rec - 1] = T.  Grid point k (x = k * kCutGrid, k = 1 .. K - 1, K = ceil(T / kCutGrid)) snaps to the first record
+// end e >= x if e < x + kCutReach, and stays at x otherwise.  One lane per grid point, one binary search for its own cut and one for
+// the cut behind it: snap(x) lies in [x, x + kCutReach) and kCutReach <= kCutGrid, so the cuts of two grid points never meet -- the
+// only cut that can coincide with another is the last one with T, which is what lane K - 1 looks at.  Member k = [cut k, cut k + 1):
+// off[k], len[k]; *n_members = K, or K - 1 when the last grid point snapped to T.
+static_assert(kCutReach <= kCutGrid && kCutGrid + kCutReach == kMaxBlockBytes, "the cuts of two grid points cannot coincide; a member holds kMaxBlockBytes at most");
+__device__ __forceinline__ uint64_t snap_cut(const unsigned long long *__restrict__ rec_end, uint64_t n_rec, uint64_t x) {
+    uint64_t lo = 0, hi = n_rec;  // the first record end >= x: there is one, x < T = rec_end[n_rec - 1]
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (rec_end[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    const uint64_t e = lo < n_rec ? rec_end[lo] : x;
+    return e - x < kCutReach ? e : x;
+}
+__global__ __launch_bounds__(128) void mk_bgzf_cuts_kernel(const unsigned long long *__restrict__ rec_end, uint64_t n_rec, uint64_t T,
+                                                           uint32_t n_grid, unsigned long long *__restrict__ off, uint32_t *__restrict__ len,
+                                                           uint32_t *__restrict__ n_members) {
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n_grid; k += gridDim.x * blockDim.x) {
+        const uint64_t a = k ? snap_cut(rec_end, n_rec, (uint64_t)k * kCutGrid) : 0;
+        const uint64_t b = k + 1 < n_grid ? snap_cut(rec_end, n_rec, (uint64_t)(k + 1) * kCutGrid) : T;
+        off[k] = a;
+        len[k] = (uint32_t)(b - a);
+        if (k + 1 == n_grid) *n_members = b > a ? n_grid : n_grid - 1;
+    }
+}
+
 // ---- CRC-32 of each block: a piece per lane (slice-by-4), folded by the wave ------------------------------------
 __device__ __forceinline__ void build_crc_tables(uint32_t (*t)[256]) {
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) t[0][i] = crc_table_entry(i);
@@ -474,6 +538,18 @@ void launch_deflate(const uint8_t *in, uint64_t n, uint32_t block_bytes, uint32_
     if (!n_blocks) return;
     (void)hipMemsetAsync(next_block, 0, 4, s);
     hipLaunchKernelGGL(mk_bgzf_deflate_kernel, dim3(grid), dim3(64), 0, s, in, n, block_bytes, n_blocks, crc, tokens, slots, slot_len, next_block);
+}
+void launch_cuts(const unsigned long long *rec_end, uint64_t n_rec, uint64_t n_text, uint32_t n_grid, unsigned long long *off, uint32_t *len,
+                 uint32_t *n_members, hipStream_t s) {
+    if (!n_grid) return;
+    const uint32_t blocks = (n_grid + 127) / 128;
+    hipLaunchKernelGGL(mk_bgzf_cuts_kernel, dim3(blocks < kCutBlocks ? blocks : kCutBlocks), dim3(128), 0, s, rec_end, n_rec, n_text, n_grid, off, len, n_members);
+}
+void launch_deflate_ranges(const uint8_t *in, const unsigned long long *off, const uint32_t *len, uint32_t n_blocks, const uint32_t *crc, uint32_t *tokens,
+                           uint8_t *slots, uint32_t *slot_len, uint32_t *next_block, uint32_t grid, hipStream_t s) {
+    if (!n_blocks) return;
+    (void)hipMemsetAsync(next_block, 0, 4, s);
+    hipLaunchKernelGGL(mk_bgzf_deflate_ranges_kernel, dim3(grid), dim3(64), 0, s, in, off, len, n_blocks, crc, tokens, slots, slot_len, next_block);
 }
 void launch_pack(const uint8_t *slots, const uint32_t *slot_len, uint64_t *slot_off, uint64_t *total, uint32_t n_blocks, uint8_t *packed,
                  hipStream_t s) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../host_common.h"
+#include "bgzf_cuts.hpp"
 #include "codec_internal.h"
 #include "codec_kernels.h"
 #include "gzip_segments.hpp"
@@ -136,7 +137,141 @@ const uint8_t kEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 
 
 }  // namespace
 
+namespace mkz {
+
+int deflate_pass(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, uint32_t bb, const unsigned long long *off, const uint32_t *len,
+                 uint32_t blocks, void *d_packed, size_t packed_cap, void **d_members, uint64_t *total) {
+    int rc;
+    const uint32_t grid = deflate_grid(blocks, c->num_cus);
+    if ((rc = mk::ensure_device(&c->d_crc, &c->crc_cap, blocks * 4ull)) || (rc = mk::ensure_device(&c->d_tokens, &c->tokens_cap, (uint64_t)grid * kTokensPerWave * 4)) ||
+        (rc = mk::ensure_device(&c->d_slots, &c->slots_cap, (uint64_t)blocks * kSlotBytes)) || (rc = mk::ensure_device(&c->d_len, &c->len_cap, (blocks + 1) * 4ull)) ||
+        (rc = mk::ensure_device(&c->d_off, &c->off_cap, (blocks + 2) * 8ull)))
+        return rc;
+    // (a stored member: its text + 31 bytes)
+    const uint64_t bound = off ? std::min<uint64_t>((uint64_t)blocks * kMaxBlockBytes, n_text) + blocks * 31ull : mk_bgzf_deflate_bound(n_text, bb);
+    if (packed_cap < bound) {
+        if ((rc = mk::ensure_device(&c->d_out, &c->out_cap, bound))) return rc;
+        d_packed = c->d_out;
+    }
+    uint64_t *d_total = (uint64_t *)c->d_off + blocks;
+    if (off) {
+        launch_crc_ranges(d_text, off, len, blocks, (uint32_t *)c->d_crc, st);
+        launch_deflate_ranges(d_text, off, len, blocks, (const uint32_t *)c->d_crc, (uint32_t *)c->d_tokens, (uint8_t *)c->d_slots, (uint32_t *)c->d_len,
+                              (uint32_t *)(d_total + 1), grid, st);
+    } else {
+        launch_crc(d_text, n_text, bb, blocks, (uint32_t *)c->d_crc, st);
+        launch_deflate(d_text, n_text, bb, blocks, (const uint32_t *)c->d_crc, (uint32_t *)c->d_tokens, (uint8_t *)c->d_slots, (uint32_t *)c->d_len,
+                       (uint32_t *)(d_total + 1), grid, st);
+    }
+    launch_pack((const uint8_t *)c->d_slots, (const uint32_t *)c->d_len, (uint64_t *)c->d_off, d_total, blocks, (uint8_t *)d_packed, st);
+    *total = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return mk::fail(MK_E_HIP, "BGZF deflate on the device failed");
+    *d_members = d_packed;
+    return MK_OK;
+}
+
+// d_text[0, n_text) (kPad readable bytes behind it) whose records end at d_ends[0, n_ends) (device memory, non-decreasing, the last
+// one = n_text) -> BGZF members that end at record ends (the cut rule of include/merkurio_hip.h), in passes of members
+// (mk_codec_set_pass_limits).  *need = the bytes of all members, *n_members how many.  A pass's members are downloaded to out as long
+// as everything so far has fitted out_cap: *need > out_cap means out holds only the passes in front of the one that did not fit (the
+// caller reports MK_E_CAPACITY).  c->cut_ms: cut, deflate, download.  d_packed / packed_cap: as deflate_pass.
+static int deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, void *d_packed,
+                   size_t packed_cap, uint8_t *out, uint64_t out_cap, uint64_t *need, uint64_t *n_members) {
+    *need = 0, *n_members = 0;
+    c->cut_ms[0] = c->cut_ms[1] = c->cut_ms[2] = 0, c->cut_members = 0;
+    if (!n_text) return MK_OK;
+    const uint64_t grid64 = (n_text + kCutGrid - 1) / kCutGrid;
+    if (grid64 >= 0xFFFFFFFFull) return mk::fail(MK_E_UNSUPPORTED, "%llu output members", (unsigned long long)grid64);
+    const uint32_t n_grid = (uint32_t)grid64;
+    int rc;
+    // the range table: count | off[n_grid] | len[n_grid]
+    if ((rc = mk::ensure_device(&c->d_cut, &c->cut_cap, 16 + n_grid * 12ull))) return rc;
+    uint32_t *d_count = (uint32_t *)c->d_cut;
+    unsigned long long *d_off = (unsigned long long *)((uint8_t *)c->d_cut + 16);
+    uint32_t *d_len = (uint32_t *)(d_off + n_grid);
+    double t0 = now_ms();
+    launch_cuts(d_ends, n_ends, n_text, n_grid, d_off, d_len, d_count, st);
+    uint32_t members = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&members, d_count, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return mk::fail(MK_E_HIP, "the cut kernel failed");
+    if (members > n_grid || members + 1 < n_grid) return mk::fail(MK_E_HIP, "the cut kernel reports %u members of %u grid points", members, n_grid);
+    c->cut_ms[0] = (float)(now_ms() - t0);
+    // passes of members; a pass's members are downloaded as long as everything so far has fitted
+    const uint64_t pass = std::min<uint64_t>(c->deflate_pass_blocks ? c->deflate_pass_blocks : kDeflateChunkBlocks, 0x7FFFFFFFu);
+    uint64_t written = 0;
+    bool fits = true;
+    for (uint64_t m0 = 0; m0 < members; m0 += pass) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(pass, members - m0);
+        void *d_members = nullptr;
+        uint64_t total = 0;
+        t0 = now_ms();
+        if ((rc = deflate_pass(c, st, d_text, n_text, 0, d_off + m0, d_len + m0, cnt, d_packed, packed_cap, &d_members, &total))) return rc;
+        c->cut_ms[1] += (float)(now_ms() - t0);
+        fits = fits && written + total <= out_cap;
+        if (fits && total) {
+            t0 = now_ms();
+            if (hipMemcpyAsync(out + written, d_members, total, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+                return mk::fail(MK_E_HIP, "download of the members failed");
+            c->cut_ms[2] += (float)(now_ms() - t0);
+        }
+        written += total;
+    }
+    *need = written, *n_members = members, c->cut_members = members;
+    return MK_OK;
+}
+
+}  // namespace mkz
+
 extern "C" {
+
+int mk_bgzf_record_cuts(const uint64_t *rec_end, uint64_t n_rec, uint64_t *cut, uint64_t cap, uint64_t *n_cuts) {
+    if (!n_cuts || (n_rec && !rec_end) || (cap && !cut)) return mk::fail(MK_E_INVALID_ARG, "mk_bgzf_record_cuts: NULL argument");
+    *n_cuts = 0;
+    for (uint64_t r = 1; r < n_rec; ++r)
+        if (rec_end[r] < rec_end[r - 1]) return mk::fail(MK_E_INVALID_ARG, "mk_bgzf_record_cuts: record end %llu lies in front of the one before it", (unsigned long long)r);
+    const uint64_t k = mkz::record_cuts(rec_end, n_rec, cut, cap);
+    *n_cuts = k;
+    if (k > cap) return mk::fail(MK_E_CAPACITY, "mk_bgzf_record_cuts: %llu cuts, room for %llu", (unsigned long long)k, (unsigned long long)cap);
+    return MK_OK;
+}
+
+int mk_bgzf_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const uint64_t *rec_end, uint64_t n_rec, uint8_t *out, uint64_t out_cap,
+                            uint64_t *out_len, uint64_t *n_members) {
+    MK_ABI_BEGIN
+    if (!c || !out_len || !n_members || (n && (!text || !rec_end)) || (out_cap && !out)) return mk::fail(MK_E_INVALID_ARG, "mk_bgzf_deflate_records: NULL argument");
+    *out_len = 0, *n_members = 0;
+    if ((n_rec ? rec_end[n_rec - 1] : 0) != n) return mk::fail(MK_E_INVALID_ARG, "mk_bgzf_deflate_records: the last record does not end where the text does");
+    for (uint64_t r = 1; r < n_rec; ++r)
+        if (rec_end[r] < rec_end[r - 1]) return mk::fail(MK_E_INVALID_ARG, "mk_bgzf_deflate_records: record end %llu lies in front of the one before it", (unsigned long long)r);
+    std::lock_guard<std::mutex> lock(c->mu);
+    MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
+    c->ms[0] = c->ms[1] = c->ms[2] = 0;
+    if (!n) return MK_OK;
+    int rc;
+    if ((rc = mk::ensure_device(&c->d_in, &c->in_cap, n + mkz::kPad)) || (rc = mk::ensure_device(&c->d_ends, &c->ends_cap, n_rec * 8ull))) return rc;
+    const double t_up = now_ms();
+    if ((rc = upload(c, c->d_in, text, n)) || (rc = upload(c, c->d_ends, (const uint8_t *)rec_end, n_rec * 8ull))) return rc;
+    MKC_HIP(hipMemsetAsync((uint8_t *)c->d_in + n, 0, mkz::kPad, c->stream), "hipMemsetAsync");
+    MKC_HIP(hipStreamSynchronize(c->stream), "upload of the text");
+    c->ms[0] = (float)(now_ms() - t_up);
+    uint64_t need = 0;
+    if ((rc = mkz::deflate_ranges(c, c->stream, (const uint8_t *)c->d_in, n, (const unsigned long long *)c->d_ends, n_rec, nullptr, 0, out, out_cap, &need, n_members)))
+        return rc;
+    c->ms[1] = c->cut_ms[0] + c->cut_ms[1], c->ms[2] = c->cut_ms[2];
+    *out_len = need;
+    if (need > out_cap) return mk::fail(MK_E_CAPACITY, "mk_bgzf_deflate_records: the members take %llu bytes, room for %llu", (unsigned long long)need, (unsigned long long)out_cap);
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_codec_cut_times(const mk_codec *c, uint64_t *n_members, float ms[3]) {
+    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_codec_cut_times: NULL handle");
+    if (n_members) *n_members = c->cut_members;
+    if (ms)
+        for (int k = 0; k < 3; ++k) ms[k] = c->cut_ms[k];
+    return MK_OK;
+}
 
 int mk_codec_create(int device, mk_codec **out) {
     MK_ABI_BEGIN
@@ -165,7 +300,7 @@ void mk_codec_destroy(mk_codec *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *p : {c->d_in, c->d_crc, c->d_tokens, c->d_slots, c->d_len, c->d_off, c->d_out, c->d_aux, c->d_gz_in, c->d_gz_sym, c->d_gz_tab, c->d_gz_ctx, c->d_gz_text})
+    for (void *p : {c->d_in, c->d_crc, c->d_tokens, c->d_slots, c->d_len, c->d_off, c->d_out, c->d_aux, c->d_ends, c->d_cut, c->d_gz_in, c->d_gz_sym, c->d_gz_tab, c->d_gz_ctx, c->d_gz_text})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);

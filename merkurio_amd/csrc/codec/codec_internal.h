@@ -17,6 +17,11 @@ struct mk_codec {
     void *d_in = nullptr, *d_crc = nullptr, *d_tokens = nullptr, *d_slots = nullptr, *d_len = nullptr, *d_off = nullptr, *d_out = nullptr,
          *d_aux = nullptr;
     size_t in_cap = 0, crc_cap = 0, tokens_cap = 0, slots_cap = 0, len_cap = 0, off_cap = 0, out_cap = 0, aux_cap = 0;
+    // members that end at record ends: the record ends (u64), and the range table the cut kernel makes of them (codec_host.cpp: deflate_ranges)
+    void *d_ends = nullptr, *d_cut = nullptr;
+    size_t ends_cap = 0, cut_cap = 0;
+    float cut_ms[3] = {0, 0, 0};  // of the last such call: cut kernel, CRC-32 + deflate + pack, download
+    uint64_t cut_members = 0;
     // host buffers travel through two page-locked staging buffers, filled / emptied by the host threads beside the DMA (codec_host.cpp)
     void *h_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
@@ -33,3 +38,12 @@ struct mk_codec {
     uint64_t deflate_pass_blocks = 0, inflate_pass_text = 0;  // mk_codec_set_pass_limits; 0 = the defaults below
 };
 
+namespace mkz {
+// One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
+// output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on
+// stream st, with the codec's buffers (the caller holds c->mu).  Member b = d_text[b * bb ...] (off == nullptr; the last one ends at
+// n_text) or d_text[off[b], off[b] + len[b]) (device tables).  The members land back to back in d_packed when packed_cap holds
+// their bound, in c->d_out otherwise: *d_members says where, *total how many bytes (the stream has been waited for).
+int deflate_pass(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, uint32_t bb, const unsigned long long *off, const uint32_t *len,
+                 uint32_t blocks, void *d_packed, size_t packed_cap, void **d_members, uint64_t *total);
+}  // namespace mkz

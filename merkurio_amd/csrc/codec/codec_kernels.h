@@ -10,11 +10,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bgzf_cuts.hpp"
+
 namespace mkz {
 
 constexpr uint32_t kSlotBytes = 65536;       // a member never exceeds 64 KiB (BSIZE is 16 bits)
 constexpr uint32_t kMaxBlockBytes = 0xff00;  // input bytes per member (what htslib / the host writer use)
 constexpr uint32_t kTokensPerWave = 65536;   // token scratch of one resident deflate wave (u32 each)
+static_assert(kCutGrid + kCutReach == kMaxBlockBytes, "members that end at record ends hold kMaxBlockBytes at most (bgzf_cuts.hpp)");
+constexpr uint32_t kCutBlocks = 8;           // the cut kernel's grid: at most this many blocks of 128 lanes, which stride over the grid points
 constexpr uint32_t kPad = 128;               // readable bytes every input buffer needs behind its last byte (inflate_serial.hpp: kStreamPad)
 
 // one member of an inflate call (the host walks the BSIZE chain and fills these)
@@ -38,6 +42,15 @@ uint32_t deflate_grid(uint32_t n_blocks, int num_cus);
 // next_block: one u32 of device memory (the kernel's work counter; zeroed by the launcher)
 void launch_deflate(const uint8_t *in, uint64_t n, uint32_t block_bytes, uint32_t n_blocks, const uint32_t *crc, uint32_t *tokens,
                     uint8_t *slots, uint32_t *slot_len, uint32_t *next_block, uint32_t grid, hipStream_t s);
+// The same with member b = in[off[b], off[b] + len[b]) (off, len: device memory; len[b] <= kMaxBlockBytes): members that end where
+// the caller's table says, not every block_bytes.  `in` readable up to kPad bytes behind the last range.
+void launch_deflate_ranges(const uint8_t *in, const unsigned long long *off, const uint32_t *len, uint32_t n_blocks, const uint32_t *crc, uint32_t *tokens,
+                           uint8_t *slots, uint32_t *slot_len, uint32_t *next_block, uint32_t grid, hipStream_t s);
+// The range table of a text of n_text > 0 bytes whose records end at rec_end[0, n_rec) (device memory, non-decreasing, the last one =
+// n_text) by the cut rule of include/merkurio_hip.h: n_grid = ceil(n_text / kCutGrid) grid points -> off / len[0, *n_members),
+// *n_members = n_grid or n_grid - 1 (room for n_grid entries)
+void launch_cuts(const unsigned long long *rec_end, uint64_t n_rec, uint64_t n_text, uint32_t n_grid, unsigned long long *off, uint32_t *len,
+                 uint32_t *n_members, hipStream_t s);
 // slot_len[0, n_blocks) -> slot_off (exclusive sums, u64) and *total; then the members back to back
 void launch_pack(const uint8_t *slots, const uint32_t *slot_len, uint64_t *slot_off, uint64_t *total, uint32_t n_blocks, uint8_t *packed,
                  hipStream_t s);

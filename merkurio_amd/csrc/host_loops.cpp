@@ -1152,27 +1152,11 @@ int window_deflate(mk_matcher *m, mk_codec *codec, const WindowSide &W, DeviceLo
     const uint64_t blocks64 = (out_text + bb - 1) / bb;
     if (blocks64 >= 0xFFFFFFFFull) return fail(MK_E_UNSUPPORTED, "%s: %llu output members", who, (unsigned long long)blocks64);
     const uint32_t blocks = (uint32_t)blocks64;
-    const uint32_t grid = mkz::deflate_grid(blocks, codec->num_cus);
-    if ((rc = ensure_device(&codec->d_crc, &codec->crc_cap, blocks * 4ull)) ||
-        (rc = ensure_device(&codec->d_tokens, &codec->tokens_cap, (uint64_t)grid * mkz::kTokensPerWave * 4)) ||
-        (rc = ensure_device(&codec->d_slots, &codec->slots_cap, (uint64_t)blocks * mkz::kSlotBytes)) ||
-        (rc = ensure_device(&codec->d_len, &codec->len_cap, (blocks + 1) * 4ull)) || (rc = ensure_device(&codec->d_off, &codec->off_cap, (blocks + 2) * 8ull)))
-        return rc;
     // the packed members go where the window's text was: it has been read for the last time by the record output kernel (a buffer
     // of the output's size less to grow -- growing device buffers is what a job's first windows spend most of their time on)
-    void *d_packed = W.T->d_text;
-    if (W.T->d_text_cap < mk_bgzf_deflate_bound(out_text, bb)) {
-        if ((rc = ensure_device(&codec->d_out, &codec->out_cap, mk_bgzf_deflate_bound(out_text, bb)))) return rc;
-        d_packed = codec->d_out;
-    }
-    uint64_t *d_total = (uint64_t *)codec->d_off + blocks;
-    mkz::launch_crc((const uint8_t *)O.d_text, out_text, bb, blocks, (uint32_t *)codec->d_crc, st);
-    mkz::launch_deflate((const uint8_t *)O.d_text, out_text, bb, blocks, (const uint32_t *)codec->d_crc, (uint32_t *)codec->d_tokens, (uint8_t *)codec->d_slots,
-                        (uint32_t *)codec->d_len, (uint32_t *)(d_total + 1), grid, st);
-    mkz::launch_pack((const uint8_t *)codec->d_slots, (const uint32_t *)codec->d_len, (uint64_t *)codec->d_off, d_total, blocks, (uint8_t *)d_packed, st);
+    void *d_packed = nullptr;
     uint64_t total = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(MK_E_HIP, "BGZF deflate of the tagged records failed");
+    if ((rc = mkz::deflate_pass(codec, st, (const uint8_t *)O.d_text, out_text, bb, nullptr, nullptr, blocks, W.T->d_text, W.T->d_text_cap, &d_packed, &total))) return rc;
     *ms_deflate = (float)ms_since(t);
     *out_len = total;
     if (total > out_cap) return fail(MK_E_CAPACITY, "%s: the members take %llu bytes", who, (unsigned long long)total);

@@ -55,6 +55,7 @@ EXPORTS = [
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
     "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_extract_fastq_bgzf", "mk_extract_window",
+    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
@@ -115,6 +116,7 @@ class WindowSource(C.Structure):
 
 
 MK_TEXT_FASTQ, MK_TEXT_FASTA = 0, 1
+BGZF_CUT_GRID, BGZF_MEMBER_TEXT_MAX = 49152, 65280  # the cut rule of include/merkurio_hip.h
 
 
 class BamWindow(C.Structure):
@@ -298,6 +300,10 @@ def load(build_if_missing=True):
                                         C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_extract_window.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mk_bgzf_record_cuts.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mk_bgzf_deflate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]
+    L.mk_codec_cut_times.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
     L.mk_matcher_order_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mk_tag_bam_window.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BamWindow), C.c_int, C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_matcher_set_bam_piece.argtypes = [C.c_void_p, C.c_uint32]
@@ -1017,6 +1023,18 @@ def bgzf_eof():
     return bytes(load().mk_bgzf_eof().contents)
 
 
+def bgzf_record_cuts(rec_end):
+    """mk_bgzf_record_cuts (host code): where the members of a text end whose records end at rec_end -- the cut rule of
+    include/merkurio_hip.h -> uint64 array, first 0, last rec_end[-1] (no records: [0])"""
+    L = load()
+    ends = np.ascontiguousarray(rec_end, dtype=np.uint64)
+    total = int(ends[-1]) if ends.size else 0
+    cut = np.zeros((total + BGZF_CUT_GRID - 1) // BGZF_CUT_GRID + 1, dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(L.mk_bgzf_record_cuts(ends.ctypes.data if ends.size else None, ends.size, cut.ctypes.data, cut.size, C.byref(n)))
+    return cut[:n.value].copy()
+
+
 class Codec:
     """mk_codec: BGZF members deflated / inflated by the gfx950 kernels (no CPU path: without a device creation raises)"""
 
@@ -1056,6 +1074,30 @@ class Codec:
         _check(self._L.mk_bgzf_deflate_pieces(self._h, ptrs, sizes, len(arrs), block_bytes, out.ctypes.data if out.size else None, out.size,
                                               C.byref(n)))
         return out[:n.value].tobytes()
+
+    def deflate_records(self, text, rec_end, out_cap=None):
+        """mk_bgzf_deflate_records: BGZF members of `text` that end at record ends (rec_end[-1] == len(text)), cut and deflated on the
+        device.  out_cap (tests): the output buffer's size; too small raises MK_E_CAPACITY with self.last_need = the exact need.
+        self.last_members = how many members there are"""
+        src = np.frombuffer(text, dtype=np.uint8)
+        ends = np.ascontiguousarray(rec_end, dtype=np.uint64)
+        if out_cap is None:
+            out_cap = src.size + 31 * ((src.size + BGZF_CUT_GRID - 1) // BGZF_CUT_GRID)  # every member stored
+        out = np.empty(out_cap, dtype=np.uint8)
+        n, members = C.c_uint64(0), C.c_uint64(0)
+        t0 = time.perf_counter()
+        rc = self._L.mk_bgzf_deflate_records(self._h, src.ctypes.data if src.size else None, src.size, ends.ctypes.data if ends.size else None, ends.size,
+                                             out.ctypes.data if out.size else None, out.size, C.byref(n), C.byref(members))
+        self.last_call_s = time.perf_counter() - t0
+        self.last_need, self.last_members = n.value, members.value
+        _check(rc)
+        return out[:n.value].tobytes()
+
+    def cut_times(self):
+        """members and ms (cut kernel, CRC-32 + deflate + pack, download) of the last deflate_records call"""
+        n, ms = C.c_uint64(0), (C.c_float * 3)()
+        _check(self._L.mk_codec_cut_times(self._h, C.byref(n), ms))
+        return n.value, tuple(ms)
 
     def inflate(self, data, members=None, text_bytes=None):
         if members is None:
