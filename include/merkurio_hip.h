@@ -604,6 +604,57 @@ int mk_bgzf_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const 
 int mk_codec_cut_times(const mk_codec *c, uint64_t *n_members, float ms[3]);
 
 /* -------------------------------------------------------------------------------------
+ * A window's kept records as BGZF members (v7 addition) -- mk_extract_window whose kept records leave the device deflated: they
+ * are packed in their WRITTEN form on the device, cut by the rule above and deflated where they lie; only the members come down.
+ * Same arguments and outputs as mk_extract_window, plus one mk_window_members per source (paired: each source has members of its
+ * own).  Both entry points share one body.  `codec` is required and must be on the matcher's device (MK_E_INVALID_ARG); a source's
+ * `kept` buffer belongs to mk_extract_window (MK_E_INVALID_ARG here); logging with invert is MK_E_INVALID_ARG, because rows then
+ * name records that are not kept (use mk_extract_window's `all`).
+ *
+ * THE WRITTEN FORM.  The writer re-emits a kept record's lines (the reference's record.write(_, None), src/cmd_extract.rs:297-318),
+ * it does not copy its stored bytes.  eol = the line end of the record's HEADER line, "\r\n" or "\n".
+ *   FASTQ  '@' id eol sequence eol '+' eol quality eol     -- id, sequence, quality: the lines without their line ends; the '+'
+ *          line loses whatever it repeats; a last record without a line end gains one.  Every record the index accepts is written.
+ *   FASTA  the record's bytes up to its final line end, then eol -- the final line end becomes the header's kind, a last record
+ *          without one gains it; inner line ends stay as stored.  A kept FASTA record that this does not describe (no sequence
+ *          line, blank lines or a lone '\r' at its end) makes the call refuse member output for the window: *status = 2, every
+ *          mk_window_members reports 0 bytes (of two sources, the buffers of the one in front of the refusing one may have been
+ *          written to; nothing in them is of use), and the caller calls mk_extract_window for that window (with fresh counters).
+ * The record ends of the written text are the cut rule's e[]: every member starts at a record start, unless a record is longer
+ * than 16128 bytes.  No EOF member is written.  Nothing kept: 0 members, 0 bytes.
+ *
+ * in:  members / members_cap   where the members go, back to back
+ *      ids / ids_cap / id_end  with logging: the ids of the kept records (header lines without marker and line end) back to back
+ *                              in record order, id_end[q] = where the q-th kept record's id ends (room for rec_cap entries); the
+ *                              log rows then need no text.  May be NULL / 0 without logging.
+ *      text_below              > 0: a source whose written text is shorter than this many bytes comes back as that TEXT in
+ *                              `members` (as_text = 1, n_members = 0) -- for a caller that gathers small windows with their
+ *                              neighbours before it compresses.  0: always members.
+ * out: n_member_bytes (bytes in `members`: of the members, or of the text when as_text), n_members, n_written (bytes of the
+ *      written text), n_kept (records), n_id_bytes, as_text, written_ms (the two written-form kernels, select + gather, by stream
+ *      events; mk_codec_cut_times reports the cut, deflate and download of the codec handle's last such call, summed over sources).
+ * members_cap too small: MK_E_CAPACITY with n_member_bytes = the exact need; ids_cap too small: MK_E_CAPACITY with n_id_bytes = the
+ * need.  In mk_extract_window's order of "the first thing that does not fit" these two stand where `kept` stands: after tail and
+ * all, of every source at once, before rows.
+ * --------------------------------------------------------------------------------------- */
+typedef struct mk_window_members {
+    /* in */
+    uint8_t *members;
+    uint64_t members_cap;
+    uint8_t *ids;
+    uint64_t ids_cap;
+    uint64_t *id_end;
+    uint64_t text_below;
+    /* out */
+    uint64_t n_member_bytes, n_members, n_written, n_kept, n_id_bytes;
+    uint32_t as_text;
+    float written_ms;
+} mk_window_members;
+int mk_extract_window_members(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *sources,
+                              mk_window_members *members, int logging, int invert, uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep, mk_row *rows,
+                              uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status);
+
+/* -------------------------------------------------------------------------------------
  * A gzip file inflated in parallel on the device (v6: one member; v7: a chain of members) -- a .fastq.gz / .fasta.gz as plain gzip (or pigz, or zlib) writes it: ONE
  * DEFLATE stream of thousands of blocks, which zlib can only walk from the front.  Replaces needletail's gzip reader under
  * `merkurio extract` (src/cmd_extract.rs:281-282) for such files.  The stream is cut where block starts can be FOUND (a dynamic

@@ -10,6 +10,7 @@ void RecordGzip::attach(Sink &sink, int device) {
     sink.flush();
     sink.z_text = &text_, sink.z_ends = &ends_;
     sink.z_window = [this] { window_done(); };
+    sink.z_members = [this](const uint8_t *p, uint64_t n, uint64_t count) { put_members(p, n, count); };
 }
 
 void RecordGzip::window_done(bool force) {
@@ -62,12 +63,19 @@ void RecordGzip::window_done(bool force) {
     text_.clear(), ends_.clear();
 }
 
+void RecordGzip::put_members(const uint8_t *p, uint64_t n, uint64_t count) {
+    if (!sink_) return;
+    window_done(true);
+    if (sink_->f && n && fwrite(p, 1, n, sink_->f) != n) bail("Error writing the compressed output");
+    members += count;
+}
+
 void RecordGzip::finish() {
     if (!sink_) return;
     window_done(true);
     if (sink_->f && fwrite(mk_bgzf_eof(), 1, 28, sink_->f) != 28) bail("Error writing the compressed output");
     if (sink_->f) fflush(sink_->f);
-    sink_->z_text = nullptr, sink_->z_ends = nullptr, sink_->z_window = nullptr;
+    sink_->z_text = nullptr, sink_->z_ends = nullptr, sink_->z_window = nullptr, sink_->z_members = nullptr;
     if (codec_ && !g_process_is_ending) mk_codec_destroy(codec_);
     codec_ = nullptr, sink_ = nullptr;
 }

@@ -11,6 +11,9 @@ namespace cli {
 struct RecordGzip {
     void attach(Sink &sink, int device);  // device < 0: zlib on the host threads
     void window_done(bool force = false);
+    // members made on the device (mk_extract_window_members): whatever text has gathered is forced out first, so that record order
+    // holds, then the members are written through
+    void put_members(const uint8_t *p, uint64_t n, uint64_t count);
     void finish();
     uint64_t members = 0;
     double cut_ms = 0, deflate_ms = 0, download_ms = 0;  // device codec: summed over the calls; host codec: deflate_ms alone

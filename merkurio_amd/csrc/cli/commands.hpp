@@ -36,11 +36,16 @@ struct CommonArgs {
                                // (BAM records indexed and tagged on the host threads) where BAM -> BAM would keep them on the device
 };
 
+constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
+
 struct ExtractArgs : CommonArgs {
     std::string in_fastx;                   // -i / -1
     std::optional<std::string> in_fastq_2;  // -2
     std::optional<std::string> out_fastx;   // -o
     bool bgzf_output = false;               // -z: the kept records are written as BGZF members that end at record ends (output name + ".gz")
+    // --z-members-from: with -z on the window path, a window whose written kept records take this many bytes or more is cut and deflated
+    // where it lies and comes down as members (mk_extract_window_members); a smaller one comes down as text and gathers with its neighbours
+    uint64_t z_members_from = kZMembersFrom;
 };
 
 struct TagArgs : CommonArgs {

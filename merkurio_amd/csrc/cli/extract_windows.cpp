@@ -81,8 +81,13 @@ struct Side {  // one input's part of a window
     std::vector<uint64_t> rec_start;
     uint64_t n_window = 0, n_used = 0;
     std::vector<char> tail;       // the text behind the processed records: the next window's head
-    enum Layout { HEAD_BODY, PACKED_KEPT, WHOLE } layout = HEAD_BODY;
+    // MEMBERS / WRITTEN (-z, mk_extract_window_members): the kept records came down as BGZF members of their written form / as that
+    // text (a window below --z-members-from), the ids of the kept records beside them -- the writer needs no stored text
+    enum Layout { HEAD_BODY, PACKED_KEPT, WHOLE, MEMBERS, WRITTEN } layout = HEAD_BODY;
     std::vector<char> text;       // what the writer reads from unless HEAD_BODY: the kept records, the whole window, the host parser's text
+    std::vector<char> ids;        // MEMBERS / WRITTEN with logs: the kept records' ids back to back, id_end[q] = where the q-th one's ends
+    std::vector<uint64_t> id_end;
+    uint64_t n_members = 0;
     FastxFile parsed;             // host-parsed window: the records (parsed.data = text)
 };
 
@@ -97,6 +102,8 @@ struct Win {
     mk_counters cb;
     std::vector<uint32_t> cnt;
     bool by_host = false;
+    bool no_members = false;  // a window whose written form the device refused (*status = 2): its kept records come back as stored text
+    float z_ms[4] = {0, 0, 0, 0};  // -z on the device: written form (select, scan, gather), cut, deflate, download
 };
 
 }  // namespace
@@ -132,6 +139,15 @@ struct WindowExtract::Impl {
     bool failed = false;
     uint64_t last_head[2] = {0, 0};
     std::atomic<uint64_t> rec_cap_seen{0};
+    // -z: the kept records leave the device as BGZF members (mk_extract_window_members) -- not with --host-codec, and not with logs under
+    // -v, whose rows name records that are not kept
+    bool z_members = false;
+    // the last window's needs, carried forward as rec_cap_seen is: bytes of members (or of text, for a window that came back as text)
+    // and of ids per KiB of window text
+    std::atomic<uint64_t> members_share_seen{0}, ids_share_seen{0};
+    std::atomic<uint64_t> z_repeats{0};  // window calls made again because the members' or the ids' buffer was too small
+    uint64_t z_member_windows = 0, z_text_windows = 0;  // (the writer's)
+    double z_ms[4] = {0, 0, 0, 0};
 
     void fail_all(const std::string &msg) {
         std::lock_guard<std::mutex> lk(mu);
@@ -395,6 +411,9 @@ struct WindowExtract::Impl {
     void device_window(Win &W, mk_matcher *m, mk_codec *codec) {
         mk_window_source src[2];
         memset(src, 0, sizeof(src));
+        const bool use_members = z_members && !W.no_members;
+        mk_window_members mem[2];
+        memset(mem, 0, sizeof(mem));
         uint64_t cap_text = 0;
         bool any_bgzf = false;
         for (int i = 0; i < n_in; ++i) {
@@ -415,7 +434,12 @@ struct WindowExtract::Impl {
             }
             Q.ends_at_record = S.ends ? 1 : 0;
             cap_text = std::max(cap_text, S.head.size() + body);
-            if (in[i].dev_text()) {  // the host never sees this text: what it needs of it comes back
+            if (use_members) {  // only the tail comes back of the text
+                if (in[i].dev_text()) {
+                    S.tail.resize(std::max<size_t>(S.tail.size(), 1u << 20));
+                    Q.tail = (uint8_t *)S.tail.data(), Q.tail_cap = S.tail.size();
+                }
+            } else if (in[i].dev_text()) {  // the host never sees this text: what it needs of it comes back
                 if (whole_text) {
                     S.text.resize(S.head.size() + body + 16);
                     Q.all = (uint8_t *)S.text.data(), Q.all_cap = S.text.size();
@@ -430,7 +454,7 @@ struct WindowExtract::Impl {
             }
         }
         if (cap_text >= 0xFFFFFFF0ull) return host_window(W, m);  // (a FASTA record of 4 GiB or more: the host path's own limits apply)
-        // (a guess the call corrects: MK_E_CAPACITY comes back before anything is scanned)
+        // (a guess the call corrects: for rec_cap MK_E_CAPACITY comes back before anything is scanned)
         uint64_t rec_cap = std::max<uint64_t>(rec_cap_seen.load(), cap_text / (fastq ? 192 : 1024) + 16);
         W.rows.resize(std::max<size_t>(W.rows.size(), 4096));
         W.cnt.assign(pats->list.size(), 0);
@@ -443,9 +467,33 @@ struct WindowExtract::Impl {
             if (W.keep.size() < rec_cap) W.keep.resize(rec_cap);
             memset(&W.cb, 0, sizeof(W.cb));
             std::fill(W.cnt.begin(), W.cnt.end(), 0);
-            const int rc = mk_extract_window(m, any_bgzf ? codec : nullptr, fastq ? MK_TEXT_FASTQ : MK_TEXT_FASTA, (uint32_t)n_in, src, lg->active,
-                                             a.invert_match, rec_cap, &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb,
-                                             W.cnt.data(), &status);
+            for (int i = 0; i < n_in && use_members; ++i) {
+                Side &S = W.side[i];
+                if (attempt == 0) {
+                    // the members' and the ids' buffers are guessed, and a wrong guess is dear: their needs are known only after the scan,
+                    // the gather and the deflate, so MK_E_CAPACITY means the whole window is processed once more.  Under -v nearly
+                    // everything is kept: the written text's bound (a record grows by three line-end bytes at most), every member
+                    // stored.  Otherwise the share of its window's text that the last window needed, an eighth added -- the first window
+                    // is small, the ones behind it 16 times its size --, and never less than the text a window may come back as
+                    // (anything below --z-members-from, or the bound)
+                    const uint64_t bound = cap_text + 3 * rec_cap + 64;
+                    const uint64_t share = members_share_seen.load(), share_ids = ids_share_seen.load();
+                    uint64_t guess = a.invert_match ? bound + 31 * (bound / MK_BGZF_CUT_GRID + 1) : ((cap_text >> 10) + 1) * (share + (share >> 3));
+                    guess = std::max<uint64_t>(guess, std::min<uint64_t>(a.z_members_from, bound));
+                    S.text.resize(std::max<uint64_t>(1u << 20, guess));
+                    if (lg->active) S.ids.resize(std::max<uint64_t>(1u << 16, ((cap_text >> 10) + 1) * (share_ids + (share_ids >> 3))));
+                }
+                if (lg->active) S.id_end.resize(rec_cap);
+                mem[i].members = (uint8_t *)S.text.data(), mem[i].members_cap = S.text.size();
+                mem[i].ids = (uint8_t *)S.ids.data(), mem[i].ids_cap = S.ids.size(), mem[i].id_end = S.id_end.data();
+                mem[i].text_below = a.z_members_from;
+            }
+            const int rc = use_members ? mk_extract_window_members(m, codec, fastq ? MK_TEXT_FASTQ : MK_TEXT_FASTA, (uint32_t)n_in, src, mem, lg->active,
+                                                                   a.invert_match, rec_cap, &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(),
+                                                                   &W.n_rows, &W.cb, W.cnt.data(), &status)
+                                       : mk_extract_window(m, any_bgzf ? codec : nullptr, fastq ? MK_TEXT_FASTQ : MK_TEXT_FASTA, (uint32_t)n_in, src,
+                                                           lg->active, a.invert_match, rec_cap, &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(),
+                                                           &W.n_rows, &W.cb, W.cnt.data(), &status);
             if (rc == MK_E_CAPACITY && attempt < 8) {  // the call states every need: grow what was too small, once more
                 bool grown = false;
                 if (W.n_rec > rec_cap) rec_cap = W.n_rec + W.n_rec / 16, grown = true, rec_cap_seen = std::max<uint64_t>(rec_cap_seen.load(), rec_cap);
@@ -462,6 +510,10 @@ struct WindowExtract::Impl {
                         src[i].kept = (uint8_t *)S.text.data(), src[i].kept_cap = S.text.size();
                         grown = true;
                     }
+                    bool again = false;
+                    if (use_members && mem[i].n_member_bytes > mem[i].members_cap) S.text.resize(mem[i].n_member_bytes), again = true;
+                    if (use_members && mem[i].n_id_bytes > mem[i].ids_cap) S.ids.resize(mem[i].n_id_bytes + (mem[i].n_id_bytes >> 3)), again = true;
+                    if (again) grown = true, ++z_repeats;
                 }
                 if (grown) continue;
             }
@@ -478,11 +530,38 @@ struct WindowExtract::Impl {
             mk_check(rc, "Error during matching");
             break;
         }
+        if (status == 2) {  // a record whose written form the device does not make: this window's kept records come back as stored text
+            W.no_members = true;
+            for (int i = 0; i < n_in; ++i) W.side[i].text.clear(), W.side[i].ids.clear(), W.side[i].id_end.clear();
+            return device_window(W, m, codec);
+        }
         if (status != 0) return host_window(W, m);
+        if (use_members) {
+            if (codec) {
+                float ms3[3] = {0, 0, 0};
+                (void)mk_codec_cut_times(codec, nullptr, ms3);
+                for (int k = 0; k < 3; ++k) W.z_ms[k + 1] = ms3[k];
+            }
+            uint64_t most = 0, most_ids = 0;
+            for (int i = 0; i < n_in; ++i) {
+                most = std::max<uint64_t>(most, mem[i].n_member_bytes);
+                most_ids = std::max<uint64_t>(most_ids, mem[i].n_id_bytes);
+                W.z_ms[0] += mem[i].written_ms;
+            }
+            members_share_seen = most / ((cap_text >> 10) + 1) + 1;
+            ids_share_seen = most_ids / ((cap_text >> 10) + 1) + 1;
+        }
         for (int i = 0; i < n_in; ++i) {
             Side &S = W.side[i];
             S.n_window = src[i].n_window, S.n_used = src[i].n_used;
             S.rec_start.resize(W.n_rec + 1);
+            if (use_members) {
+                S.layout = mem[i].as_text ? Side::WRITTEN : Side::MEMBERS;
+                S.text.resize(mem[i].n_member_bytes);
+                S.ids.resize(mem[i].n_id_bytes);
+                S.id_end.resize(lg->active ? mem[i].n_kept : 0);
+                S.n_members = mem[i].n_members;
+            }
             if (in[i].dev_text()) {
                 S.tail.resize(src[i].n_tail);
                 if (S.layout == Side::PACKED_KEPT) S.text.resize(src[i].n_kept_bytes);
@@ -495,7 +574,7 @@ struct WindowExtract::Impl {
                 if (from < S.n_body) S.tail.insert(S.tail.end(), S.body + from, S.body + S.n_body);
                 // ... and what the writer will need of it -- the kept records (all of it when the rows name records that are not
                 // kept) -- is copied out here, so that the page-locked buffer goes back to the reader now, not after the write-out
-                pack_host_text(W, S);
+                if (!use_members) pack_host_text(W, S);
             }
         }
     }
@@ -593,6 +672,8 @@ struct WindowExtract::Impl {
         return Span{S.text.data(), S.text.size(), b, e};
     }
 
+    void write_members_window(Win &W, Sink **w, const std::string **names, PhaseTimer &tm);
+
     void write_window(Win &W, Sink &w1, Sink &w2, const std::string &name1, const std::string &name2, PhaseTimer &tm) {
         const uint64_t n = W.n_rec;
         Sink *w[2] = {&w1, &w2};
@@ -612,6 +693,7 @@ struct WindowExtract::Impl {
                         for (int i = 0; i < n_in; ++i) W.side[i].parsed.write(r, *w[i]), w[i]->end_record();
             return;
         }
+        if (W.side[0].layout == Side::MEMBERS || W.side[0].layout == Side::WRITTEN) return write_members_window(W, w, names, tm);
         // record r of side i in the text the writer holds: its own table for packed kept records
         std::vector<uint64_t> kept_of;               // window index of every kept record (PACKED_KEPT)
         std::vector<uint64_t> packed_start[2];
@@ -704,6 +786,46 @@ struct WindowExtract::Impl {
     }
 };
 
+// a window of the -z member path: log rows from the packed ids, then per output the members as they are, or -- a window below
+// --z-members-from -- the written text, which gathers with its neighbours' as the host writer's would (its record ends are found
+// again: every fourth line end of FASTQ, every header line of FASTA)
+void WindowExtract::Impl::write_members_window(Win &W, Sink **w, const std::string **names, PhaseTimer &tm) {
+    std::vector<uint64_t> kept_of;
+    if (lg->active)
+        for (uint64_t r = 0; r < W.n_rec; ++r)
+            if (W.keep[r]) kept_of.push_back(r);
+    auto id_of = [&](const mk_row &row) {
+        const Side &S = W.side[row.file];
+        const size_t q = (size_t)(std::lower_bound(kept_of.begin(), kept_of.end(), row.rec) - kept_of.begin());
+        if (q >= S.id_end.size() || kept_of[q] != row.rec) bail("Error during matching: a log row names a record whose id did not come back");
+        const uint64_t b = q ? S.id_end[q - 1] : 0;
+        return std::pair<const char *, size_t>(S.ids.data() + b, (size_t)(S.id_end[q] - b));
+    };
+    emit_log_rows(*lg, *pats, W.rows.data(), lg->active ? W.n_rows : 0, id_of, [&](const mk_row &r) -> const std::string & { return *names[r.file]; });
+    tm.mark("window: log rows");
+    bool any_members = false;
+    for (int i = 0; i < n_in; ++i) {
+        Side &S = W.side[i];
+        if (S.layout == Side::MEMBERS) {
+            any_members = true;
+            if (!S.text.empty()) w[i]->put_members((const uint8_t *)S.text.data(), S.text.size(), S.n_members);
+            continue;
+        }
+        std::vector<uint64_t> ends;
+        const char *p = S.text.data();
+        const uint64_t n = S.text.size();
+        uint64_t lines = 0;
+        for (const char *q = p; q < p + n && (q = (const char *)memchr(q, '\n', (size_t)(p + n - q))); ++q) {
+            const uint64_t at = (uint64_t)(q - p) + 1;
+            if (fastq ? (++lines % 4 == 0) : (at == n || p[at] == '>')) ends.push_back(at);
+        }
+        if (n) w[i]->write_records(std::string(p, (size_t)n), ends);
+    }
+    (any_members ? z_member_windows : z_text_windows) += 1;
+    for (int k = 0; k < 4; ++k) z_ms[k] += W.z_ms[k];
+    tm.mark("window: records out");
+}
+
 WindowExtract::~WindowExtract() {
     if (!impl) return;
     for (int i = 0; i < 2; ++i)
@@ -784,12 +906,16 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     J.queue.resize(N);
     bool any_bgzf = false;
     for (int i = 0; i < J.n_in; ++i) any_bgzf = any_bgzf || J.in[i].bgzf_dev;
-    if (any_bgzf) {
+    const bool logs = a.out_log || a.json_log;
+    J.z_members = a.bgzf_output && !a.host_codec && !a.host_ingest && !a.suppress_output && !(logs && a.invert_match);
+    if (any_bgzf || J.z_members) {  // (a codec per device: BGZF input is inflated, -z output deflated where its window is)
         for (size_t d = 0; d < N; ++d) {
             mk_codec *c = nullptr;
             mk_check(mk_codec_create(devs[d], &c), "Error setting up the BGZF codec");
             J.codecs.push_back(c);
         }
+    }
+    if (any_bgzf) {
         // a window's text, its sequences, its members and its tables all live on the device: keep it to a sixth of what is free there
         size_t free_b = 0, total_b = 0;
         if (hipSetDevice(devs[0]) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
@@ -914,6 +1040,13 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     for (auto &t : pin_threads) t.join();
     if (!writer_error.empty()) bail(writer_error);
     if (J.failed) bail(J.failure);
+    if (J.timing && a.bgzf_output) {
+        fprintf(stderr, "[timing] extract -z: %llu windows as members, %llu as text\n", (unsigned long long)J.z_member_windows,
+                (unsigned long long)J.z_text_windows);
+        if (J.z_member_windows + J.z_text_windows)
+            fprintf(stderr, "[timing] extract -z on the windows' devices: written form %.1f ms, cut %.1f ms, deflate %.1f ms, download %.1f ms; %llu calls repeated for a larger buffer\n",
+                    J.z_ms[0], J.z_ms[1], J.z_ms[2], J.z_ms[3], (unsigned long long)J.z_repeats.load());
+    }
 }
 
 }  // namespace cli

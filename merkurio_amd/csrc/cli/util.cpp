@@ -193,6 +193,11 @@ void Sink::write(const char *p, size_t n) {
     buf.append(p, n);
     if (buf.size() >= (1u << 20)) flush();
 }
+void Sink::put_members(const uint8_t *p, uint64_t n, uint64_t count) {
+    if (!z_members) bail("Error writing the compressed output: members for an output that is not compressed");
+    z_members(p, n, count);
+}
+
 void Sink::write_records(const std::string &s, const std::vector<uint64_t> &ends) {
     if (!z_text) return write(s);
     const uint64_t base = z_text->size();

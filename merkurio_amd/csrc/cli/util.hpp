@@ -78,6 +78,10 @@ struct Sink {
         if (z_window) z_window();
     }
     void write_records(const std::string &s, const std::vector<uint64_t> &ends);  // whole records; ends: the offset in s behind each (used with -z only)
+    // extract -z: BGZF members that hold whole records and were made elsewhere (on the device, mk_extract_window_members) go out
+    // behind everything written so far
+    std::function<void(const uint8_t *, uint64_t, uint64_t)> z_members;
+    void put_members(const uint8_t *p, uint64_t n, uint64_t count);
 };
 
 // logger::BufferedLogger (text log).  The reference keeps every row in memory as well

@@ -46,4 +46,9 @@ namespace mkz {
 // their bound, in c->d_out otherwise: *d_members says where, *total how many bytes (the stream has been waited for).
 int deflate_pass(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, uint32_t bb, const unsigned long long *off, const uint32_t *len,
                  uint32_t blocks, void *d_packed, size_t packed_cap, void **d_members, uint64_t *total);
+// d_text[0, n_text) (kPad readable bytes behind it) whose records end at d_ends[0, n_ends) (device memory, non-decreasing, the last one
+// = n_text) -> the members of the cut rule (include/merkurio_hip.h), cut and deflated in passes, downloaded to out as long as they
+// fit out_cap: *need = the bytes of all of them (> out_cap: the caller reports MK_E_CAPACITY), *n_members how many.  Sets c->cut_ms.
+int deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, void *d_packed,
+                   size_t packed_cap, uint8_t *out, uint64_t out_cap, uint64_t *need, uint64_t *n_members);
 }  // namespace mkz

@@ -640,6 +640,122 @@ int window_kept(mk_matcher *m, uint32_t format, WindowSide &W, uint64_t n, const
     return MK_OK;
 }
 
+
+// the kept records of side W in their written form (include/merkurio_hip.h), packed on the device, then cut and deflated there:
+// only the members come down -- or, below S.text_below bytes, the text.  With logging the ids of the kept records follow, packed by
+// the sequences' gather kernel.  *status = 2: a FASTA record the device does not write (nothing has been written to S's buffers).
+// The time of the codec's steps is ADDED to cut_ms / *cut_members (a paired window has two sides).
+int window_members(mk_matcher *m, mk_codec *codec, uint32_t format, WindowSide &W, uint64_t n, const uint8_t *d_keep, const std::vector<uint32_t> &rs,
+                   const uint8_t *keep_host, int logging, mk_window_members &S, DeviceLoop &dl, float cut_ms[3], uint64_t *cut_members, uint32_t *status) {
+    hipStream_t st = dl.st;
+    if (!n) return MK_OK;
+    int rc;
+    const bool fasta = format == MK_TEXT_FASTA;
+    const uint8_t *d_text = (const uint8_t *)W.T->d_text;
+    // scratch: written lengths | id starts | id lengths | refusal word | tile sums
+    const size_t n_tiles = n / ingest_scan_tile() + 2;
+    if ((rc = ensure_device(&m->d_aux, &m->d_aux_cap, 3 * (n + 2) * 4 + 16 + n_tiles * 8 + 64))) return rc;
+    uint32_t *d_len = (uint32_t *)m->d_aux, *d_id_start = d_len + n + 2, *d_id_len = d_id_start + n + 2, *d_refused = d_id_len + n + 2;
+    unsigned long long *d_tile = (unsigned long long *)(((uintptr_t)(d_refused + 1) + 15) & ~(uintptr_t)15);
+    if ((rc = ensure_device((void **)&m->d_off, &m->d_off_cap, (n + 1) * sizeof(uint64_t)))) return rc;
+    unsigned long long *d_off = (unsigned long long *)m->d_off;
+    // the two written-form kernels are timed by stream events (S.written_ms), read once the stream has been waited for anyway
+    struct Events {
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev;
+    for (hipEvent_t &x : ev.e)
+        if (hipEventCreate(&x) != hipSuccess) return fail(MK_E_HIP, "hipEventCreate failed");
+    bool gathered = false;
+    auto kernel_ms = [&] {  // (the stream is idle)
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, ev.e[0], ev.e[1]);
+        if (gathered) (void)hipEventElapsedTime(&b, ev.e[2], ev.e[3]);
+        S.written_ms = a + b;
+    };
+    uint32_t refused = 0;
+    unsigned long long total = 0;
+    if (hipMemsetAsync(d_refused, 0, 4, st) != hipSuccess || hipEventRecord(ev.e[0], st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
+    launch_ingest_written_select(d_text, d_keep, 0u, fasta, W.d_line, W.d_seq_len, W.d_rec_start, n, (uint32_t)W.n_used, d_len, logging ? d_id_start : nullptr,
+                                 logging ? d_id_len : nullptr, d_refused, st);
+    // (the refusal word comes down with the scan's total: one wait)
+    if (hipGetLastError() != hipSuccess || hipEventRecord(ev.e[1], st) != hipSuccess ||
+        hipMemcpyAsync(&refused, d_refused, 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(MK_E_HIP, "selection of the written records failed");
+    if ((rc = scan_offsets(d_len, n, d_tile, d_off, st, &total, "selection of the written records failed"))) return rc;
+    if (refused) {
+        *status = 2;
+        return MK_OK;
+    }
+    for (uint64_t r = 0; r < n; ++r) S.n_kept += keep_host[r] != 0;
+    S.n_written = total;
+    int cap_rc = MK_OK;
+    if (total) {
+        if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64 + mkz::kPad))) return rc;
+        // chromosome-sized FASTA records: one device copy each at their written offset, but for the last 16 stored bytes (the kernel's)
+        bool big = false;
+        for (uint64_t r = 0; fasta && r < n && !big; ++r) big = keep_host[r] && rs[r + 1] - rs[r] >= kBigRecord;
+        if (big) {
+            std::vector<unsigned long long> off(n + 1);
+            if (hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+                return fail(MK_E_HIP, "copy of the written offsets failed");
+            for (uint64_t r = 0; r < n; ++r) {
+                const uint64_t len = rs[r + 1] - rs[r];
+                if (keep_host[r] && len >= kBigRecord &&
+                    hipMemcpyAsync(m->d_seq + off[r], d_text + rs[r], len - 16, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return fail(MK_E_HIP, "copy of a kept record failed");
+            }
+        }
+        if (hipEventRecord(ev.e[2], st) != hipSuccess) return fail(MK_E_HIP, "hipEventRecord failed");
+        launch_ingest_written_gather(d_text, fasta, W.d_line, W.d_seq_len, W.d_rec_start, n, (uint32_t)W.n_used, d_len, d_off, m->d_seq,
+                                     fasta ? kBigRecord : 0xFFFFFFFFu, st);
+        // (no wait of its own: the download, or the cut kernel's count, waits for the stream)
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev.e[3], st) != hipSuccess || hipMemsetAsync(m->d_seq + total, 0, mkz::kPad, st) != hipSuccess)
+            return fail(MK_E_HIP, "gather of the written records failed");
+        gathered = true;
+        if (S.text_below && total < S.text_below) {  // a small window: its text, for the caller to gather with its neighbours'
+            S.as_text = 1;
+            S.n_member_bytes = total;
+            if (total > S.members_cap) {
+                if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "gather of the written records failed");
+                cap_rc = fail(MK_E_CAPACITY, "the written records take %llu bytes", total);
+            } else if (hipMemcpyAsync(S.members, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+                return fail(MK_E_HIP, "copy of the written records failed");
+            }
+        } else {
+            std::lock_guard<std::mutex> lock(codec->mu);
+            uint64_t need = 0, members = 0;
+            // (the codec times its steps by the host's clock: the gather must not run into the cut kernel's share)
+            if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "gather of the written records failed");
+            // the offsets scan is the record-end table: off[r + 1] = where record r's written form ends (a record that is not kept
+            // repeats the end in front of it)
+            if ((rc = mkz::deflate_ranges(codec, st, m->d_seq, total, d_off + 1, n, nullptr, 0, S.members, S.members_cap, &need, &members))) return rc;
+            for (int k = 0; k < 3; ++k) cut_ms[k] += codec->cut_ms[k];
+            *cut_members += members;
+            S.n_member_bytes = need, S.n_members = members;
+            if (need > S.members_cap) cap_rc = fail(MK_E_CAPACITY, "the members of the kept records take %llu bytes", (unsigned long long)need);
+        }
+    }
+    kernel_ms();
+    if (!logging || !S.n_kept) return cap_rc;
+    // ---- the ids of the kept records, packed the way the sequences are: start and length table, offsets scan, gather
+    if ((rc = scan_offsets(d_id_len, n, d_tile, d_off, st, &total, "selection of the ids failed"))) return rc;
+    S.n_id_bytes = total;
+    if (total > S.ids_cap) return fail(MK_E_CAPACITY, "the ids of the kept records take %llu bytes", total);
+    std::vector<unsigned long long> off(n + 1);
+    if ((rc = ensure_device((void **)&m->d_seq, &m->d_seq_cap, total + 64))) return rc;
+    launch_ingest_gather(d_text, d_id_start, d_id_len, d_off, 0, n, m->d_seq, st);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (total && hipMemcpyAsync(S.ids, m->d_seq, total, hipMemcpyDeviceToHost, st) != hipSuccess) || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MK_E_HIP, "copy of the ids failed");
+    uint64_t q = 0;
+    for (uint64_t r = 0; r < n; ++r)
+        if (keep_host[r]) S.id_end[q++] = off[r + 1];
+    return cap_rc;
+}
 }  // namespace
 
 extern "C" {
@@ -689,9 +805,14 @@ int mk_upload_text_ahead(mk_matcher *m, const uint8_t *text, uint64_t n_text) {
     MK_ABI_END
 }
 
-int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, int logging, int invert,
-                      uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
-                      uint32_t *counts, uint32_t *status) {
+}  // extern "C"
+
+namespace {
+
+// the body of mk_extract_window (mem == nullptr) and mk_extract_window_members (one mk_window_members per source)
+int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem, int logging,
+                        int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
+                        uint32_t *counts, uint32_t *status) {
     if (!m || !src || !n_rec_out || !status || !c || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
     if (n_sources < 1 || n_sources > 2) return fail(MK_E_INVALID_ARG, "mk_extract_window: one source (single file) or two (paired files)");
     if (format > MK_TEXT_FASTA) return fail(MK_E_INVALID_ARG, "mk_extract_window: unknown text format %u", format);
@@ -705,6 +826,17 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
             (S.kept_cap && !S.kept) ||
             (S.all_cap && !S.all) || (S.tail_cap && !S.tail))
             return fail(MK_E_INVALID_ARG, "mk_extract_window: a size without its buffer in source %u", k);
+        if (!mem) continue;
+        mk_window_members &M = mem[k];
+        M.n_member_bytes = M.n_members = M.n_written = M.n_kept = M.n_id_bytes = 0, M.as_text = 0, M.written_ms = 0;
+        if ((M.members_cap && !M.members) || (M.ids_cap && !M.ids) || (logging && !M.id_end))
+            return fail(MK_E_INVALID_ARG, "mk_extract_window_members: a size without its buffer in source %u", k);
+        if (S.kept || S.kept_cap) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the kept records leave as members, not as source %u's kept text", k);
+    }
+    if (mem) {
+        if (!codec) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the members need a codec handle");
+        if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the codec and the matcher are on different devices");
+        if (logging && invert) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: with logging and invert the rows name records that are not kept");
     }
     MK_ABI_BEGIN
     if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
@@ -819,10 +951,50 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
         }
         if (cap_rc) return cap_rc;
     }
+    if (mem) {
+        if ((rc = ensure_device((void **)&m->d_flags2, &m->d_flags2_cap, n + 8))) return rc;
+        if (hipMemcpyAsync(m->d_flags2, keep, n, hipMemcpyHostToDevice, st) != hipSuccess) return fail(MK_E_HIP, "upload of the keep flags failed");
+        int cap_rc = MK_OK;
+        float cut_ms[3] = {0, 0, 0};
+        uint64_t cut_members = 0;
+        for (uint32_t k = 0; k < n_sources && !*status; ++k) {
+            rc = window_members(m, codec, format, W[k], n, m->d_flags2, rs[k], keep, logging, mem[k], dl, cut_ms, &cut_members, status);
+            if (rc == MK_E_CAPACITY) cap_rc = rc;  // (every source reports its needs before the call returns)
+            else if (rc) return rc;
+        }
+        {
+            std::lock_guard<std::mutex> lock(codec->mu);
+            for (int k = 0; k < 3; ++k) codec->cut_ms[k] = cut_ms[k];
+            codec->cut_members = cut_members;
+        }
+        if (*status) {  // a record the device does not write: nothing of this window has left as members
+            for (uint32_t k = 0; k < n_sources; ++k)
+                mem[k].n_member_bytes = mem[k].n_members = mem[k].n_written = mem[k].n_kept = mem[k].n_id_bytes = 0, mem[k].as_text = 0;
+            return MK_OK;
+        }
+        if (cap_rc) return cap_rc;
+    }
     dl.finish();
     if (n_rows) *n_rows = total_rows;
     return check_rows_cap(logging, rows, rows_cap, total_rows);
     MK_ABI_END
+}
+
+}  // namespace
+
+extern "C" {
+
+int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, int logging, int invert,
+                      uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
+                      uint32_t *counts, uint32_t *status) {
+    return extract_window_body(m, codec, format, n_sources, src, nullptr, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+}
+
+int mk_extract_window_members(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem,
+                              int logging, int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap,
+                              uint64_t *n_rows, mk_counters *c, uint32_t *counts, uint32_t *status) {
+    if (!mem) return fail(MK_E_INVALID_ARG, "null argument");
+    return extract_window_body(m, codec, format, n_sources, src, mem, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 // (v4 / v5 entry points, kept: one FASTQ source whose window ends at a record end / one bgzip'ed FASTQ source with a head)

@@ -270,6 +270,124 @@ __global__ __launch_bounds__(256) void mk_ingest_select_kernel(const uint8_t *__
     sel_len[i] = ((flags[i] != 0) != (invert != 0)) ? end - rec_start[i] : 0u;
 }
 
+// ---- the WRITTEN form of the kept records (mk_extract_window_members; the rule: include/merkurio_hip.h) ------------------------
+// The writer does not emit a kept record's stored bytes, it re-emits its lines (cli/io.cpp: FastxFile::write): every line ends the
+// way the header line does, a FASTQ '+' line loses a repeated id, a last record without a line end gains one.  These two kernels
+// make that form on the device, so that the packed text can be cut and deflated where it lies.
+//   FASTQ, from the line table l0 .. l3 and the sequence length of mk_ingest_records_kernel:
+//     text[l0, e0) eol text[l1, l1 + len) eol '+' eol text[l3, l3 + len) eol       e0: the header's end without its line end
+//   FASTA, record [b, e) whose header line ends at h:
+//     text[b, p) eol       p: e without the record's final line end
+// eol = the header line's own line end.  A FASTA record whose form is not that (no sequence, blank lines or a lone '\r' at its end)
+// sets *refused: the caller leaves the window to the host writer.
+__device__ __forceinline__ uint32_t fq_header(const uint8_t *__restrict__ text, uint32_t l0, uint32_t l1, uint32_t *nl) {
+    uint32_t e0 = l1 - 1;  // (the records kernel has seen to l1 - l0 >= 2)
+    const bool crlf = e0 > l0 + 1 && text[e0 - 1] == '\r';
+    *nl = crlf ? 2u : 1u;
+    return e0 - (crlf ? 1u : 0u) - l0;  // marker + id
+}
+// the end of a FASTA record's body: e without at most one final line end; *k = the line-end bytes found there (3: more than one)
+__device__ __forceinline__ uint32_t fa_body_end(const uint8_t *__restrict__ text, uint32_t s, uint32_t e, uint32_t *k) {
+    uint32_t p = e, c = 0;
+    while (p > s && c < 3 && (text[p - 1] == '\n' || text[p - 1] == '\r')) --p, ++c;
+    *k = c;
+    return p;
+}
+__device__ __forceinline__ void put_eol(uint8_t *__restrict__ dst, uint32_t nl) {
+    if (nl == 2) dst[0] = '\r', dst[1] = '\n';
+    else dst[0] = '\n';
+}
+// src[0, len) -> dst by the 16 lanes of a record: four bytes per lane and step, the lane whose step is the first not to fit copies the rest
+__device__ __forceinline__ void copy16(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t len, uint32_t sub) {
+    uint32_t k = 4 * sub;
+    for (; k + 4 <= len; k += 64) {
+        uint32_t v;
+        __builtin_memcpy(&v, src + k, 4);
+        __builtin_memcpy(dst + k, &v, 4);
+    }
+    if (k < len)
+        for (uint32_t j = k; j < len; ++j) dst[j] = src[j];
+}
+
+// one lane per record: length of its written form if the record is kept, else 0; id_start / id_len (both or neither): the header
+// line without marker and line end of a kept record (length 0 otherwise) -- the table a second gather packs the log rows' ids by
+__global__ __launch_bounds__(256) void mk_ingest_written_select_kernel(const uint8_t *__restrict__ text, const uint8_t *__restrict__ flags, uint32_t invert,
+                                                                      uint32_t fasta, const uint32_t *__restrict__ line_start,
+                                                                      const uint32_t *__restrict__ seq_len, const uint32_t *__restrict__ rec_start,
+                                                                      uint64_t n_rec, uint32_t n_text, uint32_t *__restrict__ sel_len,
+                                                                      uint32_t *__restrict__ id_start, uint32_t *__restrict__ id_len,
+                                                                      uint32_t *__restrict__ refused) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec) return;
+    uint32_t w = 0, ids = 0, idl = 0;
+    if ((flags[i] != 0) != (invert != 0)) {
+        if (!fasta) {
+            const uint32_t l0 = line_start[4 * i], l1 = line_start[4 * i + 1];
+            uint32_t nl;
+            const uint32_t head = fq_header(text, l0, l1, &nl);
+            w = head + 2 * seq_len[i] + 1 + 4 * nl;
+            ids = l0 + 1, idl = head - 1;
+        } else {
+            const uint32_t b = rec_start[i], e = i + 1 < n_rec ? rec_start[i + 1] : n_text;
+            uint32_t h = b;
+            while (h < e && text[h] != '\n') ++h;
+            const uint32_t s = h + 1;  // first byte of the body
+            const bool crlf = h > b + 1 && h < e && text[h - 1] == '\r';
+            uint32_t k = 0;
+            const uint32_t p = s < e ? fa_body_end(text, s, e, &k) : s;
+            const bool ok = s < e && p > s && (k == 0 || (k == 1 && text[e - 1] == '\n') || (k == 2 && text[e - 2] == '\r' && text[e - 1] == '\n'));
+            if (ok) {
+                w = p - b + (crlf ? 2u : 1u);
+                ids = b + 1, idl = h - (crlf ? 1u : 0u) - (b + 1);
+            } else {
+                atomicOr(refused, 1u);
+            }
+        }
+    }
+    sel_len[i] = w;
+    if (id_start) id_start[i] = ids, id_len[i] = idl;
+}
+
+// written form of record i -> out[off[i], off[i] + sel_len[i]): 16 lanes per record, unaligned dwords.  A FASTA record of
+// big_from stored bytes and more has been copied by the caller but for its last 16 stored bytes: those and the line end are this
+// kernel's.
+__global__ __launch_bounds__(256) void mk_ingest_written_gather_kernel(const uint8_t *__restrict__ text, uint32_t fasta, const uint32_t *__restrict__ line_start,
+                                                                      const uint32_t *__restrict__ seq_len, const uint32_t *__restrict__ rec_start,
+                                                                      uint64_t n_rec, uint32_t n_text, const uint32_t *__restrict__ sel_len,
+                                                                      const unsigned long long *__restrict__ off, uint8_t *__restrict__ out,
+                                                                      uint32_t big_from) {
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t sub = threadIdx.x & 15u;
+    if (i >= n_rec) return;
+    const uint32_t w = sel_len[i];
+    if (!w) return;
+    uint8_t *__restrict__ dst = out + off[i];
+    if (!fasta) {
+        const uint32_t l0 = line_start[4 * i], l1 = line_start[4 * i + 1], l3 = line_start[4 * i + 3], len = seq_len[i];
+        uint32_t nl;
+        const uint32_t head = fq_header(text, l0, l1, &nl);
+        const uint32_t at_seq = head + nl, at_plus = at_seq + len + nl, at_qual = at_plus + 1 + nl;
+        copy16(dst, text + l0, head, sub);
+        copy16(dst + at_seq, text + l1, len, sub);
+        copy16(dst + at_qual, text + l3, len, sub);
+        if (sub == 15) {  // (the lane with the least to copy)
+            put_eol(dst + head, nl);
+            put_eol(dst + at_seq + len, nl);
+            dst[at_plus] = '+';
+            put_eol(dst + at_plus + 1, nl);
+            put_eol(dst + at_qual + len, nl);
+        }
+        return;
+    }
+    const uint32_t b = rec_start[i], e = i + 1 < n_rec ? rec_start[i + 1] : n_text;
+    uint32_t k;
+    const uint32_t body = fa_body_end(text, b + 1, e, &k) - b;  // (select has accepted the record: its body ends behind its header)
+    const uint32_t nl = w - body;
+    const uint32_t from = e - b >= big_from ? e - b - 16 : 0;
+    copy16(dst + from, text + b + from, body - from, sub);
+    if (sub == 15) put_eol(dst + body, nl);
+}
+
 // ---- FASTA (r05): '>' header lines, every other line is sequence; record.seq() is the sequence lines without their '\n' and '\r'
 // bytes (needletail strips both; cli/io.cpp: FastxFile::append_seq).  On the device that is a byte compaction of the window's text:
 // a byte is kept iff it lies in a sequence line and is neither '\n' nor '\r'.  Two passes over the text, a thread per 64 bytes:
@@ -442,6 +560,21 @@ void launch_ingest_select(const uint8_t *d_flags, uint32_t invert, const uint32_
     if (!n_rec) return;
     hipLaunchKernelGGL(mk_ingest_select_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_flags, invert, d_rec_start, n_rec, n_text,
                        d_sel_len);
+}
+
+void launch_ingest_written_select(const uint8_t *d_text, const uint8_t *d_flags, uint32_t invert, bool fasta, const uint32_t *d_line_start,
+                                  const uint32_t *d_seq_len, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
+                                  uint32_t *d_id_start, uint32_t *d_id_len, uint32_t *d_refused, hipStream_t st) {
+    if (!n_rec) return;
+    hipLaunchKernelGGL(mk_ingest_written_select_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_text, d_flags, invert, fasta ? 1u : 0u,
+                       d_line_start, d_seq_len, d_rec_start, n_rec, n_text, d_sel_len, d_id_start, d_id_len, d_refused);
+}
+void launch_ingest_written_gather(const uint8_t *d_text, bool fasta, const uint32_t *d_line_start, const uint32_t *d_seq_len, const uint32_t *d_rec_start,
+                                  uint64_t n_rec, uint32_t n_text, const uint32_t *d_sel_len, const unsigned long long *d_off, uint8_t *d_out,
+                                  uint32_t big_from, hipStream_t st) {
+    if (!n_rec) return;
+    hipLaunchKernelGGL(mk_ingest_written_gather_kernel, dim3((unsigned)((n_rec * 16 + 255) / 256)), dim3(256), 0, st, d_text, fasta ? 1u : 0u, d_line_start,
+                       d_seq_len, d_rec_start, n_rec, n_text, d_sel_len, d_off, d_out, big_from);
 }
 
 void launch_ingest_count(const uint8_t *d_text, uint64_t n, uint32_t *d_block_cnt, uint32_t *d_total, hipStream_t st) {

@@ -157,6 +157,15 @@ void launch_ingest_gather(const uint8_t *d_text, const uint32_t *d_seq_start, co
                           uint32_t fixed_len, uint64_t n_rec, uint8_t *d_seq, hipStream_t st, uint32_t skip_from = 0xFFFFFFFFu);
 void launch_ingest_select(const uint8_t *d_flags, uint32_t invert, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
                           hipStream_t st);
+// the written form of the kept records (mk_extract_window_members): lengths (+ the ids' table when d_id_start != nullptr; *d_refused |= 1
+// for a FASTA record the device does not write), then -- offsets scanned -- the bytes.  FASTA records of big_from stored bytes and
+// more: the caller copies all but their last 16 stored bytes.
+void launch_ingest_written_select(const uint8_t *d_text, const uint8_t *d_flags, uint32_t invert, bool fasta, const uint32_t *d_line_start,
+                                  const uint32_t *d_seq_len, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
+                                  uint32_t *d_id_start, uint32_t *d_id_len, uint32_t *d_refused, hipStream_t st);
+void launch_ingest_written_gather(const uint8_t *d_text, bool fasta, const uint32_t *d_line_start, const uint32_t *d_seq_len, const uint32_t *d_rec_start,
+                                  uint64_t n_rec, uint32_t n_text, const uint32_t *d_sel_len, const unsigned long long *d_off, uint8_t *d_out,
+                                  uint32_t big_from, hipStream_t st);
 void launch_ingest_fasta_count(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
                                unsigned long long *d_block64, hipStream_t st);
 void launch_ingest_fasta_emit(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,

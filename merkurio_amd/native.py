@@ -55,7 +55,7 @@ EXPORTS = [
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
     "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_extract_fastq_bgzf", "mk_extract_window",
-    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times",
+    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
@@ -113,6 +113,13 @@ class WindowSource(C.Structure):
                 ("reserved", C.c_uint32), ("rec_start", C.c_void_p), ("tail", C.c_void_p), ("tail_cap", C.c_uint64), ("kept", C.c_void_p),
                 ("kept_cap", C.c_uint64), ("all", C.c_void_p), ("all_cap", C.c_uint64), ("n_window", C.c_uint64), ("n_used", C.c_uint64),
                 ("n_tail", C.c_uint64), ("n_kept_bytes", C.c_uint64), ("n_rec_seen", C.c_uint64)]
+
+
+class WindowMembers(C.Structure):
+    """mk_window_members (include/merkurio_hip.h, v7): where one source's kept records go as BGZF members (mk_extract_window_members)"""
+    _fields_ = [("members", C.c_void_p), ("members_cap", C.c_uint64), ("ids", C.c_void_p), ("ids_cap", C.c_uint64), ("id_end", C.c_void_p),
+                ("text_below", C.c_uint64), ("n_member_bytes", C.c_uint64), ("n_members", C.c_uint64), ("n_written", C.c_uint64),
+                ("n_kept", C.c_uint64), ("n_id_bytes", C.c_uint64), ("as_text", C.c_uint32), ("written_ms", C.c_float)]
 
 
 MK_TEXT_FASTQ, MK_TEXT_FASTA = 0, 1
@@ -301,6 +308,9 @@ def load(build_if_missing=True):
     L.mk_extract_window.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_bgzf_record_cuts.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mk_extract_window_members.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Counters),
+                                            C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_bgzf_deflate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]
     L.mk_codec_cut_times.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
@@ -676,14 +686,10 @@ class Matcher:
         out_text = text[:io.n_text].tobytes() if whole_text else (tail[:io.n_tail].tobytes(), text[:io.n_kept_bytes].tobytes())
         return (status.value, out_text, io.n_used, rec_start[:n + 1].tolist(), [bool(k) for k in keep[:n]], out_rows, c2.as_dict(k2))
 
-    def extract_window(self, sources, fmt=MK_TEXT_FASTQ, logging=True, invert=False, codec=None, want=("tail",)):
-        """mk_extract_window.  sources: one dict per input file (one = single, two = paired) with keys
-             head (bytes, default b""), text (bytes) OR blob + members (bgzf_members entries), ends_at_record (bool)
-        want: which texts come back per source, any of "tail", "kept", "all".
-        -> dict(status, n_rec, keep, rows, counters, sources=[dict(n_window, n_used, n_rec_seen, rec_start, tail, kept, all)])"""
-        L = load()
-        n_src = len(sources)
-        arr = (WindowSource * n_src)()
+    @staticmethod
+    def _window_sources(sources):
+        """the mk_window_source array of extract_window's source dicts -> (array, what keeps its buffers alive, the longest window text)"""
+        arr = (WindowSource * len(sources))()
         hold = []
         bound = 0
         for k, sd in enumerate(sources):
@@ -711,6 +717,16 @@ class Matcher:
                 n_body = text.size
             S.ends_at_record = int(bool(sd.get("ends_at_record", True)))
             bound = max(bound, head.size + n_body)
+        return arr, hold, bound
+
+    def extract_window(self, sources, fmt=MK_TEXT_FASTQ, logging=True, invert=False, codec=None, want=("tail",)):
+        """mk_extract_window.  sources: one dict per input file (one = single, two = paired) with keys
+             head (bytes, default b""), text (bytes) OR blob + members (bgzf_members entries), ends_at_record (bool)
+        want: which texts come back per source, any of "tail", "kept", "all".
+        -> dict(status, n_rec, keep, rows, counters, sources=[dict(n_window, n_used, n_rec_seen, rec_start, tail, kept, all)])"""
+        L = load()
+        n_src = len(sources)
+        arr, hold, bound = self._window_sources(sources)
         cap = max(1, bound // (2 if fmt == MK_TEXT_FASTA else 8) + 2)
         bufs = []
         for k in range(n_src):
@@ -762,6 +778,70 @@ class Matcher:
                                    "tail": b["tail"][:S.n_tail].tobytes() if "tail" in want else None,
                                    "kept": b["kept"][:S.n_kept_bytes].tobytes() if "kept" in want else None,
                                    "all": b["all"][:S.n_window].tobytes() if "all" in want else None})
+        return out
+
+    def extract_window_members(self, sources, codec, fmt=MK_TEXT_FASTQ, logging=False, invert=False, text_below=0, caps=None):
+        """mk_extract_window_members: mk_extract_window whose kept records come back as BGZF members of their written form, one
+        stream per source.  sources: as extract_window.  caps: None = grow what the call names and ask again; else
+        dict(members=..., ids=...) taken as they are (MK_E_CAPACITY is raised).
+        -> extract_window's dict (sources: n_window, n_used, n_rec_seen, rec_start, tail) plus per source
+           members (bytes: the members, or the text when as_text), n_members, n_written, n_kept, as_text, ids (bytes), id_end (list),
+           written_ms"""
+        L = load()
+        n_src = len(sources)
+        arr, hold, bound = self._window_sources(sources)
+        cap = max(1, bound // (2 if fmt == MK_TEXT_FASTA else 8) + 2)
+        mem = (WindowMembers * n_src)()
+        bufs = []
+        for k in range(n_src):
+            b = {"rec_start": np.zeros(cap + 1, dtype=np.uint64), "tail": np.zeros(max(64, bound), dtype=np.uint8),
+                 "members": np.zeros((caps or {}).get("members", 65536), dtype=np.uint8), "ids": np.zeros((caps or {}).get("ids", 4096), dtype=np.uint8),
+                 "id_end": np.zeros(cap, dtype=np.uint64)}
+            bufs.append(b)
+            arr[k].rec_start = b["rec_start"].ctypes.data
+            arr[k].tail, arr[k].tail_cap = b["tail"].ctypes.data, b["tail"].size
+            M = mem[k]
+            M.members, M.members_cap = (b["members"].ctypes.data if b["members"].size else None), b["members"].size
+            M.ids, M.ids_cap = (b["ids"].ctypes.data if b["ids"].size else None), b["ids"].size
+            M.id_end, M.text_below = b["id_end"].ctypes.data, int(text_below)
+        n_rec, status, n_rows = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        keep = np.zeros(cap, dtype=np.uint8)
+        rows = np.zeros(4096, dtype=ROW_DTYPE)
+        for _ in range(8):
+            c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
+            rc = L.mk_extract_window_members(self._h, codec._h if codec else None, fmt, n_src, arr, mem, int(logging), int(invert), cap, C.byref(n_rec),
+                                             keep.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows), C.byref(c2), k2.ctypes.data, C.byref(status))
+            if rc == MK_E_CAPACITY and caps is None:
+                grown = False
+                if n_rows.value > len(rows):
+                    rows = np.zeros(n_rows.value, dtype=ROW_DTYPE)
+                    grown = True
+                for k in range(n_src):
+                    M, b = mem[k], bufs[k]
+                    if M.n_member_bytes > M.members_cap:
+                        b["members"] = np.zeros(M.n_member_bytes, dtype=np.uint8)
+                        M.members, M.members_cap = b["members"].ctypes.data, b["members"].size
+                        grown = True
+                    if M.n_id_bytes > M.ids_cap:
+                        b["ids"] = np.zeros(M.n_id_bytes, dtype=np.uint8)
+                        M.ids, M.ids_cap = b["ids"].ctypes.data, b["ids"].size
+                        grown = True
+                if grown:
+                    continue
+            _check(rc)
+            break
+        n = n_rec.value
+        out = {"status": status.value, "n_rec": n, "keep": [bool(x) for x in keep[:n]],
+               "rows": [(int(r["file"]), int(r["rec"]), int(r["pat"]), int(r["pos"])) for r in rows[:n_rows.value]] if logging else [],
+               "counters": c2.as_dict(k2), "sources": []}
+        for k in range(n_src):
+            S, M, b = arr[k], mem[k], bufs[k]
+            out["sources"].append({"n_window": S.n_window, "n_used": S.n_used, "n_rec_seen": S.n_rec_seen,
+                                   "rec_start": b["rec_start"][:n + 1].tolist() if not status.value else [],
+                                   "tail": b["tail"][:S.n_tail].tobytes(), "members": b["members"][:M.n_member_bytes].tobytes(),
+                                   "n_members": M.n_members, "n_written": M.n_written, "n_kept": M.n_kept, "as_text": bool(M.as_text),
+                                   "ids": b["ids"][:M.n_id_bytes].tobytes(), "id_end": b["id_end"][:M.n_kept].tolist() if logging else [],
+                                   "written_ms": float(M.written_ms)})
         return out
 
     def extract_paired(self, seqs1, seqs2, logging=True, invert=False):
