@@ -176,7 +176,7 @@ int deflate_pass(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_
 // (mk_codec_set_pass_limits).  *need = the bytes of all members, *n_members how many.  A pass's members are downloaded to out as long
 // as everything so far has fitted out_cap: *need > out_cap means out holds only the passes in front of the one that did not fit (the
 // caller reports MK_E_CAPACITY).  c->cut_ms: cut, deflate, download.  d_packed / packed_cap: as deflate_pass.  (Shared with
-// mk_extract_window_members, host_loops.cpp: the ends are then the offsets scan of a window's written lengths.)
+// mk_extract_window_members, extract_window.cpp: the ends are then the offsets scan of a window's written lengths.)
 int deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, void *d_packed,
                    size_t packed_cap, uint8_t *out, uint64_t out_cap, uint64_t *need, uint64_t *n_members) {
     *need = 0, *n_members = 0;

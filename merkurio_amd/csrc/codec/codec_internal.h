@@ -1,4 +1,4 @@
-// codec_internal.h -- the opaque mk_codec handle (codec_host.cpp; host_loops.cpp borrows its device buffers for
+// codec_internal.h -- the opaque mk_codec handle (codec_host.cpp; window_ingest.cpp borrows its device buffers for
 // mk_extract_fastq_bgzf, which inflates a window of members straight into the matcher's text buffer)
 #pragma once
 #include <hip/hip_runtime.h>

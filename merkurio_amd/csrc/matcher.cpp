@@ -1010,7 +1010,7 @@ int mk_order_hits(const mk_matcher *m, mk_hit *hits, uint64_t n_hits) {
 
 namespace mk {
 
-// ---- host-buffer batches, in steps (mk_scan_batch and the driver loops of host_loops.cpp) ----------------------
+// ---- host-buffer batches, in steps (mk_scan_batch and the driver loops of device_loop.hpp) ----------------------
 // argument checks of a host batch; *n_bytes = bytes of the batch
 int batch_check(const uint8_t *seq_bytes, const uint64_t *seq_off, uint64_t n_rec, uint64_t *n_bytes) {
     if (!seq_off) return fail(MK_E_INVALID_ARG, "null buffer");

@@ -71,7 +71,7 @@ struct mk_matcher {
     uint32_t order_path = 0, order_bins = 0, order_max_bin = 0;
     uint64_t order_path_calls[4] = {0, 0, 0, 0};  // successful ordering calls by path, over the handle's life (mk_matcher_order_stats)
     bool order_prepared = false;  // the ordering kernels' dynamic-LDS limit has been raised on this device
-    // scratch of the driver loops (host_loops.cpp): pattern sets, counters, rows
+    // scratch of the driver loops (device_loop.hpp): pattern sets, counters, rows
     void *d_aux = nullptr;
     size_t d_aux_cap = 0;
     void *d_pair = nullptr;  // paired extract: mate 1's tuples while mate 2 is scanned
@@ -123,7 +123,7 @@ struct mk_matcher {
 };
 
 namespace mk {
-// matcher.cpp: host-buffer batches in steps (mk_scan_batch, host_loops.cpp)
+// matcher.cpp: host-buffer batches in steps (mk_scan_batch, device_loop.hpp)
 int ensure_device(void **p, size_t *cap, size_t need);
 extern thread_local double g_alloc_ms, g_free_ms;
 int batch_check(const uint8_t *seq_bytes, const uint64_t *seq_off, uint64_t n_rec, uint64_t *n_bytes);

@@ -14,9 +14,9 @@
 //   mk_sam_taglen_kernel   keep / drop; of a kept record the first optional field of the tag's name, its value, the output length
 //   mk_sam_emit_kernel     line TAB tag ":Z:" value '\n' at its place in the output
 //   mk_sam_bam_len_kernel / _fields_kernel / _seq_kernel   SAM -> BAM: the kept lines as BAM records (the second half of this file)
-// (the keep rule and the value itself are tag_merge.hpp's, shared with bam.hip; the host side of both is host_loops.cpp: tag_scan / tag_keep)
+// (the keep rule and the value itself are tag_merge.hpp's, shared with bam.hip; the host side of both is tag_windows.cpp: tag_scan / tag_keep)
 // Every access is bounded by the line it belongs to: a load of 16 bytes starts inside the line and may run up to 15 bytes past its
-// end, which the text buffer's padding (64 bytes behind the window, host_loops.cpp: window_assemble) covers.
+// end, which the text buffer's padding (64 bytes behind the window, window_ingest.cpp: window_assemble) covers.
 #include "scan_kernel.h"
 #include "sam_numbers.hpp"
 #include "tag_merge.hpp"

@@ -147,7 +147,7 @@ void launch_pair_mark(mk_hit *d_hits, uint64_t n, uint32_t mate, bool ac, hipStr
 void launch_rows_pair(const mk_hit *d_hits, uint64_t n, bool ac, mk_row *d_rows, hipStream_t st);
 void launch_count_pair_heads(const mk_hit *d_hits, uint64_t n, uint32_t *d_counts, uint32_t n_bins, hipStream_t st);
 
-// ---- ingest.hip / bam.hip: a window's text -> record tables and sequences on the device (host_loops.cpp) ----------
+// ---- ingest.hip / bam.hip: a window's text -> record tables and sequences on the device (window_ingest.cpp) ----------
 void launch_ingest_count(const uint8_t *d_text, uint64_t n, uint32_t *d_block_cnt, uint32_t *d_total, hipStream_t st);
 void launch_ingest_records(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start,
                            uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start, uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st);
@@ -198,7 +198,7 @@ void launch_bam_sam_emit(const uint8_t *d_text, const uint32_t *d_rec_off, const
                          const uint32_t *d_found_pat, const uint8_t *d_pat_bytes, const uint32_t *d_pat_off, const uint32_t *d_ex_off, const uint8_t *d_ref_bytes,
                          const uint32_t *d_ref_off, uint32_t n_refs, uint64_t n_rec, uint32_t tag0, uint32_t tag1, uint8_t *d_out, hipStream_t st);
 // ---- sam.hip: a window of SAM text whose line table exists (launch_ingest_count + launch_ingest_lines) -> record tables, the
-// sequences as the matcher sees them, the kept lines with their tag appended (host_loops.cpp: mk_tag_sam_window)
+// sequences as the matcher sees them, the kept lines with their tag appended (tag_windows.cpp: mk_tag_sam_window)
 struct SamTables {  // one entry per line (or, compacted, per record)
     uint32_t *rec_start, *rec_len, *name_len, *seq_start, *seq_len, *aux_start;
 };

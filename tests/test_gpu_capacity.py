@@ -259,7 +259,7 @@ def _records_batch(kind, algo):
 
 def _overflows(kind, n_tuples, n_rec):
     """the batch is what its name says: the first scan of a fresh handle finds more tuples than the buffer it starts with
-    (host_loops.cpp, scan_flags: max(4096, n_rec / 8)) and is repeated inside the call"""
+    (device_loop.hpp, scan_flags: max(4096, n_rec / 8)) and is repeated inside the call"""
     return kind == "small" or n_tuples > max(4096, n_rec // 8)
 
 

@@ -255,6 +255,77 @@ def test_fasta_of_mixed_line_ends_gives_the_written_bytes_or_status_2(mk, codec,
         assert r["status"] == 0 and written_fasta(odd) == want
 
 
+# ---- records around the size from which a kept record is copied on its own (1 MiB of stored bytes) ----------------------------------
+BIG = 1 << 20
+
+
+def _one_line_fasta(rnd, rid, stored, hit):
+    """a single-line LF record of exactly `stored` bytes (header line + sequence line, line ends included)"""
+    rec = b">" + rid + b"\n" + _seq(rnd, stored - len(rid) - 3, hit) + b"\n"
+    assert len(rec) == stored
+    return rec
+
+
+@pytest.mark.parametrize("kept_big", ["below_and_above", "below_and_exactly"])
+def test_fasta_records_of_one_mebibyte_less_one_exactly_and_plus_one(mk, codec, matcher, kept_big):
+    """stored sizes 2^20 - 1, 2^20 and 2^20 + 1 among small records: the kernel's share and the one-by-one copies meet here.  Kept: the
+    2^20 - 1 record, one small record and either the 2^20 + 1 record (2^20 dropped) or the 2^20 record (2^20 + 1 dropped)."""
+    rnd = random.Random(101 if kept_big == "below_and_above" else 103)
+    exact, above = kept_big == "below_and_exactly", kept_big == "below_and_above"
+    recs = []
+    for i in range(3):
+        recs.append(_one_line_fasta(rnd, b"s%d" % i, rnd.choice([40, 100, 333]), False))
+    recs.append(_one_line_fasta(rnd, b"below", BIG - 1, True))
+    recs.append(_one_line_fasta(rnd, b"small and kept", 200, True))
+    recs.append(_one_line_fasta(rnd, b"small and dropped", 77, False))
+    recs.append(_one_line_fasta(rnd, b"exactly", BIG, exact))
+    recs.append(_one_line_fasta(rnd, b"between", 150, False))
+    recs.append(_one_line_fasta(rnd, b"above", BIG + 1, above))
+    for i in range(3):
+        recs.append(_one_line_fasta(rnd, b"t%d" % i, rnd.choice([40, 100, 333]), False))
+    keep = [False] * 3 + [True, True, False, exact, False, above] + [False] * 3
+    assert [len(recs[k]) for k in (3, 6, 8)] == [BIG - 1, BIG, BIG + 1]
+    text = b"".join(recs)
+    assert text.endswith(b"\n") and b"\r" not in text
+    stored = b"".join(x for x, k in zip(recs, keep) if k)
+    w = [written_fasta(x) for x, k in zip(recs, keep) if k]
+    assert None not in w and b"".join(w) == stored  # (LF line ends and a final line end: the written form is the stored one)
+    old = matcher.extract_window([{"text": text}], fmt=mk.MK_TEXT_FASTA, logging=False, want=("kept",))
+    assert old["status"] == 0 and old["n_rec"] == len(recs) and old["keep"] == keep
+    assert old["sources"][0]["kept"] == stored
+    r = matcher.extract_window_members([{"text": text}], codec, fmt=mk.MK_TEXT_FASTA, text_below=0)
+    assert r["status"] == 0 and r["keep"] == keep
+    check_members(mk, r["sources"][0], w)
+    r = matcher.extract_window_members([{"text": text}], codec, fmt=mk.MK_TEXT_FASTA, text_below=1 << 30)
+    S = r["sources"][0]
+    assert r["status"] == 0 and r["keep"] == keep
+    assert S["as_text"] and S["n_members"] == 0 and S["n_written"] == len(stored) and S["n_kept"] == len(w) and S["members"] == stored
+
+
+def test_fastq_record_of_just_over_one_mebibyte(mk, codec, matcher):
+    """a sequence of 2^19 bases: 2^20 + 9 stored bytes among small records.  The kept text copies it on its own; the members path
+    copies no FASTQ record on its own."""
+    rnd = random.Random(107)
+
+    def rec(rid, L, hit):
+        return b"@" + rid + b"\n" + _seq(rnd, L, hit) + b"\n+\n" + _rand(rnd, L, b"IJ#5F:,") + b"\n"
+
+    recs = [rec(b"q%d" % i, rnd.choice([36, 100, 151]), i % 2 == 0) for i in range(6)]
+    recs.insert(3, rec(b"big", 1 << 19, True))
+    keep = [True, False, True, True, False, True, False]
+    assert len(recs[3]) == BIG + 9
+    text = b"".join(recs)
+    stored = b"".join(x for x, k in zip(recs, keep) if k)
+    old = matcher.extract_window([{"text": text}], logging=False, want=("kept",))
+    assert old["status"] == 0 and old["n_rec"] == len(recs) and old["keep"] == keep
+    assert old["sources"][0]["kept"] == stored
+    r = matcher.extract_window_members([{"text": text}], codec)
+    assert r["status"] == 0 and r["keep"] == keep
+    w = [written_fastq(x) for x, k in zip(fastq_records(text), keep) if k]
+    assert b"".join(w) == stored
+    check_members(mk, r["sources"][0], w)
+
+
 # ---- two sources, the other body kinds ----------------------------------------------------------------------------------------------
 def _pair(n, seed):
     rnd = random.Random(seed)
