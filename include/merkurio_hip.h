@@ -702,6 +702,48 @@ typedef struct mk_gzip_guess {
 int mk_gzip_member_guesses(const uint8_t *gz, uint64_t n, mk_gzip_guess *table, uint64_t cap, uint64_t *n_guesses);
 int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_members);
 
+/* (v7) A gzip file of ANY size, inflated on the device window by window: nothing on the device is sized by the file, a member may hold
+ * 4 GiB of text or more.  mk_gzip_stream_begin: gz[0, n) = the whole file (the caller's -- the mapped file -- until _end);
+ * window_bytes = compressed bytes per window (0 = 256 MiB).  mk_gzip_member_guesses runs once over the file.  *taken = 0: not a gzip
+ * file, no stream is open.  mk_gzip_stream_next uploads the compressed bytes from the previous cut up to window_bytes further on,
+ * searches block starts in them, decodes the pieces and stops at the LAST start that the piece in front of it lands on exactly -- a
+ * cut that is proved, not guessed; the bytes behind it go up again with the next window.  The window's first bit is a known start,
+ * the 32 KiB of text in front of it are carried on the device from window to window (two buffers), the CRC-32 of a member that is
+ * open across windows is folded (mk_crc32_combine) and its length kept in 64 bits and compared with ISIZE modulo 2^32 (RFC 1952).
+ * Member starts inside a window are the guesses there, proved by the join / drop rounds of mk_gzip_members_inflate_device; a member
+ * whose trailer lies behind the upload stays open.  A window without a proved start (a huge stored block, a tiny window) is doubled
+ * and tried again as long as the device has the room.  At most 65 535 pieces per window.
+ * *state = 0: a window of text was produced, *text_bytes long: it is what mk_gzip_text_device / mk_gzip_text_read refer to, in one
+ *             of two text buffers -- window w's text stays valid until the call that produces window w + 2;
+ *          1: end of file: every member is proved, its CRC-32 and ISIZE agree; no text in this call;
+ *          2: handed back (MK_OK): this window produced nothing and the stream produces nothing more -- a desync the rounds do not
+ *             cure, an overflow at ratio 48, a distance in front of a member's first byte, a wrong CRC-32 or ISIZE, bytes behind the
+ *             last member, no room on the device, any device error.  The text delivered before it is what zlib gives for those bytes;
+ *             the caller's zlib takes the file from the front and skips stats.text_bytes.
+ * mk_gzip_stream_end closes the stream and frees what it held (the two text buffers included); the one-shot calls work as before.
+ * mk_gzip_stream_info may be called from another thread beside mk_gzip_stream_next (it takes the codec's lock, so it waits for the
+ * window in progress); without an open stream it is MK_OK with the last stream's figures, zeros if there was none.  While a stream is
+ * open the one-shot calls (mk_gzip_inflate_device, mk_gzip_members_inflate_device) return MK_E_INVALID_ARG, and mk_gzip_text_release
+ * ends the stream as mk_gzip_stream_end does.  A window drops at most three false member starts (three drop rounds): a window with
+ * four or more header look-alikes that are no member starts -- planted in a stored block, say -- is handed back (state 2).
+ * mk_crc32_combine (host code, no device): the CRC-32 of A ++ B from crc_a = CRC-32(A), crc_b = CRC-32(B) and len_b = |B|. */
+typedef struct mk_gzip_stream_stats {
+    uint64_t windows;           /* windows of text produced */
+    uint64_t members;           /* members proved (decoded to their final block, CRC-32 and ISIZE agree) */
+    uint64_t consumed_bytes;    /* compressed bytes in front of the next window's first bit */
+    uint64_t text_bytes;        /* text bytes delivered so far */
+    uint64_t windows_grown;     /* doublings of a window that had no proved start */
+    uint64_t rounds_repeated;   /* decodes of a window's pieces beyond the first (dropped starts, joined members, ratio 48) */
+    uint64_t peak_device_bytes; /* most device memory the stream has held */
+    float ms[5];                /* summed over the windows: upload, block search, pieces, resolution, CRC-32 */
+    uint32_t reserved;
+} mk_gzip_stream_stats;
+int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t window_bytes, uint32_t *taken);
+int mk_gzip_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state);
+int mk_gzip_stream_info(const mk_codec *c, mk_gzip_stream_stats *out);
+int mk_gzip_stream_end(mk_codec *c);
+uint32_t mk_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* -------------------------------------------------------------------------------------
  * `tag` on a window of a BAM file with the records RESIDENT ON THE DEVICE (v7) -- the reader loop, process_record and the writer
  * of src/cmd_tag.rs:503-615, :387-497, :254-271 for BAM -> BAM: only compressed members cross the host boundary, in both directions.

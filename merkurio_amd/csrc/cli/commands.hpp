@@ -38,6 +38,8 @@ struct CommonArgs {
 
 constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
 
+constexpr uint64_t kGzipWindow = 256ull << 20;  // (an unmeasured choice: README, "Gunzip window by window")
+
 struct ExtractArgs : CommonArgs {
     std::string in_fastx;                   // -i / -1
     std::optional<std::string> in_fastq_2;  // -2
@@ -46,6 +48,9 @@ struct ExtractArgs : CommonArgs {
     // --z-members-from: with -z on the window path, a window whose written kept records take this many bytes or more is cut and deflated
     // where it lies and comes down as members (mk_extract_window_members); a smaller one comes down as text and gathers with its neighbours
     uint64_t z_members_from = kZMembersFrom;
+    // --gzip-window: a plain gzip input of more compressed bytes than this is inflated on the device window by window (mk_gzip_stream_*),
+    // a smaller one in one piece (mk_gzip_inflate_device / mk_gzip_members_inflate_device)
+    uint64_t gzip_window = kGzipWindow;
 };
 
 struct TagArgs : CommonArgs {

@@ -56,6 +56,14 @@ struct Input {
     mk_codec *gz_codec = nullptr;
     const uint8_t *gz_text = nullptr;
     uint64_t gz_bytes = 0, gz_next = 0;
+    // ... or, a file of more compressed bytes than --gzip-window, window by window (mk_gzip_stream_*): gz_text / gz_bytes are the latest
+    // window's text, and where gz_next reaches its end the stream is asked for the next window.  Window w lies in text buffer w & 1
+    bool gz_stream = false;
+    uint64_t gz_windows = 0;                // windows the stream has produced
+    uint64_t gz_last_k[2] = {~0ull, ~0ull};  // the last text window whose body lies in either buffer
+    uint64_t gz_delivered = 0;              // text bytes of all its windows
+    bool gz_resume = false;                 // the stream handed the file back (state 2): zlib takes it from the chain's tail on
+    double gz_t0 = 0;
     bool dev_text() const { return bgzf_dev || gz_dev; }  // the host never holds this input's text: tails / kept records come back
     int fd = -1;            // plain file: windows are staged with pread()
     size_t next_member = 0;
@@ -77,6 +85,9 @@ struct Side {  // one input's part of a window
     const uint8_t *dev_body = nullptr;  // ... or a range of text that lies on the device
     uint64_t n_dev_body = 0, dev_off = 0;
     bool ends = true;             // the body ends at a record end
+    // the input was device text when this window was cut (Input::dev_text(); a streamed gzip input is device text up to where its stream
+    // hands the file back, host text behind): its tail and kept records come back from the device
+    bool on_device = false;
     // results
     std::vector<uint64_t> rec_start;
     uint64_t n_window = 0, n_used = 0;
@@ -133,6 +144,7 @@ struct WindowExtract::Impl {
     std::map<uint64_t, std::unique_ptr<Win>> done;        // finished windows by number
     std::map<uint64_t, std::vector<std::vector<char>>> tails;  // tails of finished windows (chained inputs)
     uint64_t written = 0;                                   // windows the writer is through with
+    uint64_t n_done = 0;                                    // windows the device loops are through with (chained inputs: in order)
     bool reader_done = false;
     uint64_t n_windows = 0;  // (valid once reader_done)
     std::string failure;
@@ -175,15 +187,84 @@ struct WindowExtract::Impl {
         });
     }
 
+    // the next window of input i's gzip stream; false: there is none -- the file has ended (I.exhausted), or the stream has handed it
+    // back (I.gz_resume: what does not add up, no room, any error of the device -- the codec rule).  Window w + 2 takes the text
+    // buffer of window w: not before every text window over w has left its device loop
+    bool next_gzip_window(int i, uint64_t k) {
+        Input &I = in[i];
+        for (;;) {
+            const uint64_t last = I.gz_last_k[I.gz_windows & 1];
+            if (last != ~0ull) {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return failed || n_done > last; });
+                if (failed) return false;
+            }
+            const double t0 = PhaseTimer::now();
+            uint64_t text_bytes = 0;
+            uint32_t state = 2;
+            if (mk_gzip_stream_next(I.gz_codec, &text_bytes, &state) != MK_OK) state = 2;
+            mk_gzip_stream_stats st;
+            memset(&st, 0, sizeof(st));
+            (void)mk_gzip_stream_info(I.gz_codec, &st);
+            if (state == 0) {
+                if (timing)
+                    fprintf(stderr, "[timing]   gzip input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu)\n",
+                            i, (unsigned long long)I.gz_windows, (unsigned long long)text_bytes, (unsigned long long)st.consumed_bytes,
+                            (PhaseTimer::now() - t0) * 1e3, (unsigned long long)k);
+                ++I.gz_windows;
+                I.gz_delivered += text_bytes;
+                I.gz_text = (const uint8_t *)mk_gzip_text_device(I.gz_codec, &I.gz_bytes);
+                I.gz_next = 0;
+                if (I.gz_bytes != text_bytes) state = 2;
+                else if (text_bytes) return true;
+                else continue;  // (a window of empty members)
+            }
+            if (timing)
+                fprintf(stderr, "[timing]   gzip input %d on the device, window by window: %llu windows, %llu members proved, %llu grown, %llu rounds repeated, handed back at %s, %.3f s (upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes)\n",
+                        i, (unsigned long long)st.windows, (unsigned long long)st.members, (unsigned long long)st.windows_grown,
+                        (unsigned long long)st.rounds_repeated, state == 1 ? "-" : std::to_string(I.gz_delivered).append(" text bytes (zlib reads on)").c_str(),
+                        PhaseTimer::now() - I.gz_t0, st.ms[0], st.ms[1], st.ms[2], st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
+            I.gz_bytes = I.gz_next = 0;
+            if (state == 1) I.exhausted = true;
+            else I.gz_resume = true;
+            return false;
+        }
+    }
+
+    // the stream of input i has handed the file back and every text window over its text is through: zlib reads the file from the
+    // front, drops what the windows have used -- all that was delivered but the chain's tail S.head, which starts at a record start --
+    // and is this input's reader from here on, through the host-text windows
+    void resume_with_zlib(int i, Side &S) {
+        Input &I = in[i];
+        const uint64_t at = I.gz_delivered - std::min<uint64_t>(I.gz_delivered, S.head.size());
+        S.head.clear();
+        last_head[i] = 0;
+        I.gz_resume = false, I.gz_dev = false, I.gz_text = nullptr;
+        (void)mk_gzip_stream_end(I.gz_codec);
+        if (at) {
+            I.have_first = false;
+            if (!I.s.raw_skip(at)) bail("Error while decompressing " + I.path);
+        }
+    }
+
     // the next body of input i into S; first: the window prepare() has read.  staged: page-locked staging + upload ahead are possible
-    void next_body(int i, Side &S, uint64_t target, bool staged, mk_matcher *m_ahead) {
+    void next_body(int i, uint64_t k, Side &S, uint64_t target, bool staged, mk_matcher *m_ahead) {
         Input &I = in[i];
         S.body = nullptr, S.n_body = 0, S.pin = -1, S.grp.clear(), S.ends = true, S.dev_body = nullptr, S.n_dev_body = 0;
+        S.on_device = I.dev_text();
         if (I.exhausted) return;
+        if (I.gz_resume) return;
         if (I.gz_dev) {
+            if (I.gz_stream && I.gz_next >= I.gz_bytes && !next_gzip_window(i, k)) return;  // (its end, or handed back)
             const uint64_t n = std::min<uint64_t>(target, I.gz_bytes - I.gz_next);
             S.dev_body = I.gz_text + I.gz_next, S.n_dev_body = n, S.dev_off = I.gz_next;
             I.gz_next += n;
+            if (I.gz_stream) {
+                // (that the text ends here is known only when the stream says so: the last window is then the chain's tail alone)
+                I.gz_last_k[(I.gz_windows - 1) & 1] = k;
+                S.ends = false;
+                return;
+            }
             I.exhausted = I.gz_next >= I.gz_bytes;
             S.ends = I.exhausted;
             return;
@@ -261,7 +342,7 @@ struct WindowExtract::Impl {
                 const uint64_t full = in[i].dev_text() ? bgzf_target : (k == 0 ? std::min(plain_target, kFirstWindow) : plain_target);
                 // (the previous window's leftovers count against this one: the two files of a pair then advance at the same rate)
                 const uint64_t target = std::max<uint64_t>(1u << 16, full > last_head[i] ? full - last_head[i] : 0);
-                next_body(i, W->side[i], target, k > 0, ms.empty() ? nullptr : ms[W->dev]);
+                next_body(i, k, W->side[i], target, k > 0 && !in[i].gz_stream, ms.empty() ? nullptr : ms[W->dev]);
                 any_body = any_body || W->side[i].n_body || !W->side[i].grp.empty() || W->side[i].n_dev_body;
             }
             bool any_head = false;
@@ -281,6 +362,15 @@ struct WindowExtract::Impl {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (failed) return;
+            }
+            for (int i = 0; i < n_in; ++i) {
+                if (!in[i].gz_resume) continue;
+                Side &S = W->side[i];
+                resume_with_zlib(i, S);
+                next_body(i, k, S, std::max<uint64_t>(1u << 16, std::min(plain_target, kFirstWindow)), false, nullptr);
+                any_body = any_body || S.n_body;
+                any_head = false;
+                for (int j = 0; j < n_in; ++j) any_head = any_head || !W->side[j].head.empty();
             }
             if (!any_body && !any_head) {
                 std::lock_guard<std::mutex> lk(mu);
@@ -329,7 +419,9 @@ struct WindowExtract::Impl {
         out.resize(S.head.size() + body);
         if (!S.head.empty()) memcpy(out.data(), S.head.data(), S.head.size());
         if (S.n_body) memcpy(out.data() + S.head.size(), S.body, S.n_body);
-        if (S.n_dev_body)
+        if (S.n_dev_body && in[i].gz_stream) {  // (mk_gzip_text_read refers to the stream's latest window, which this one may no longer be)
+            if (hipMemcpy(out.data() + S.head.size(), S.dev_body, S.n_dev_body, hipMemcpyDeviceToHost) != hipSuccess) bail("Error reading the inflated text back");
+        } else if (S.n_dev_body)
             mk_check(mk_gzip_text_read(in[i].gz_codec, S.dev_off, (uint8_t *)out.data() + S.head.size(), S.n_dev_body), "Error reading the inflated text back");
         if (!S.grp.empty())
             inflate_bgzf_members_host(in[i].s.source().file_bytes(), S.grp.data(), S.grp.size(), out.data() + S.head.size(), in[i].path);
@@ -435,11 +527,11 @@ struct WindowExtract::Impl {
             Q.ends_at_record = S.ends ? 1 : 0;
             cap_text = std::max(cap_text, S.head.size() + body);
             if (use_members) {  // only the tail comes back of the text
-                if (in[i].dev_text()) {
+                if (S.on_device) {
                     S.tail.resize(std::max<size_t>(S.tail.size(), 1u << 20));
                     Q.tail = (uint8_t *)S.tail.data(), Q.tail_cap = S.tail.size();
                 }
-            } else if (in[i].dev_text()) {  // the host never sees this text: what it needs of it comes back
+            } else if (S.on_device) {  // the host never sees this text: what it needs of it comes back
                 if (whole_text) {
                     S.text.resize(S.head.size() + body + 16);
                     Q.all = (uint8_t *)S.text.data(), Q.all_cap = S.text.size();
@@ -562,7 +654,7 @@ struct WindowExtract::Impl {
                 S.id_end.resize(lg->active ? mem[i].n_kept : 0);
                 S.n_members = mem[i].n_members;
             }
-            if (in[i].dev_text()) {
+            if (S.on_device) {
                 S.tail.resize(src[i].n_tail);
                 if (S.layout == Side::PACKED_KEPT) S.text.resize(src[i].n_kept_bytes);
                 if (S.layout == Side::WHOLE) S.text.resize(src[i].n_window);
@@ -656,6 +748,7 @@ struct WindowExtract::Impl {
                 tails[W->k] = std::move(t);
             }
             const uint64_t k = W->k;
+            n_done = std::max(n_done, k + 1);
             done[k] = std::move(W);
             cv.notify_all();
         }
@@ -926,6 +1019,18 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     // mk_gzip_members_inflate_device, which cuts all of them into pieces at once.  What neither takes (no findable block starts, a
     // stream the buffers do not hold, bytes behind the last member, a damaged file) stays with the zlib reader, which also words
     // the errors
+    // A streamed file holds, per window, its compressed bytes, 12 to 48 16-bit symbols per compressed byte and two text buffers of 12 to
+    // 48 bytes per compressed byte: about 50 times the window at the usual ratio.  Two windows' worth per streamed file must fit into
+    // half of what is free (the text windows' own buffers take a sixth per input, below), otherwise the window shrinks
+    uint64_t gzip_window = a.gzip_window;
+    {
+        uint64_t n_streamed = 0;
+        for (int i = 0; i < J.n_in; ++i)
+            if (!a.host_codec && J.in[i].s.raw_is_gzip() && J.in[i].s.source().file_size() > gzip_window) ++n_streamed;
+        size_t free_b = 0, total_b = 0;
+        if (n_streamed && hipSetDevice(devs[0]) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
+            while (gzip_window > (1u << 20) && n_streamed * 2 * 50 * gzip_window > (uint64_t)free_b / 2) gzip_window /= 2;
+    }
     run_threads((size_t)J.n_in, [&](size_t ii) {  // (the two files of a pair side by side: a handle and a stream each)
         const int i = (int)ii;
         Input &I = J.in[i];
@@ -936,6 +1041,21 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
         const double t_gz = PhaseTimer::now();
         const uint8_t *gz = I.s.source().file_bytes();
         const uint64_t gz_size = I.s.source().file_size();
+        if (gz_size > gzip_window) {
+            // more than one gzip window: inflated window by window as the text windows reach it (next_gzip_window); what the stream does
+            // not take, from whichever window on, is zlib's
+            I.gz_t0 = t_gz;
+            if (mk_gzip_stream_begin(I.gz_codec, gz, gz_size, gzip_window, &taken) != MK_OK) taken = 0;
+            if (!taken) {
+                if (J.timing) fprintf(stderr, "[timing]   gzip input %d on the device, window by window: NOT taken (zlib reads it)\n", i);
+                mk_codec_destroy(I.gz_codec);
+                I.gz_codec = nullptr;
+                return;
+            }
+            I.gz_dev = I.gz_stream = true;
+            I.gz_bytes = I.gz_next = 0;
+            return;
+        }
         mk_check(mk_gzip_inflate_device(I.gz_codec, gz, gz_size, &text_bytes, &taken), "Error inflating the input");
         uint64_t members = taken ? 1 : 0, guesses = 0;
         if (!taken && mk_gzip_member_guesses(gz, gz_size, nullptr, 0, &guesses) == MK_OK && guesses > 1) {

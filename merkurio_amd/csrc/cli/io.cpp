@@ -788,6 +788,25 @@ bool FastxStream::raw_fill(uint64_t window_bytes, const char **text, uint64_t *n
 
 void FastxStream::raw_consume() { cursor = raw_next; }
 
+bool FastxStream::raw_skip(uint64_t n) {
+    if (src.mapped()) {
+        cursor = std::min<uint64_t>(src.text_size(), n);
+        return cursor == n;
+    }
+    // (everything inflated so far is in front of the cursor or in bufs[cur] behind it: nothing has been consumed)
+    for (;;) {
+        const uint64_t have = lens[cur] > cursor ? lens[cur] - cursor : 0;
+        if (n <= have) {
+            cursor += n;
+            return true;
+        }
+        n -= have;
+        lens[cur] = 0, cursor = 0;
+        if (src.exhausted()) return false;
+        src.more_into(bufs[cur], lens[cur], std::min<uint64_t>(n, 64u << 20));
+    }
+}
+
 bool FastxStream::raw_rest(const char **text, uint64_t *n_out) {
     if (src.mapped()) {
         const uint64_t n = src.text_size();

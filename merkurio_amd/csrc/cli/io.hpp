@@ -202,6 +202,10 @@ struct FastxStream {
     // everything that is left of the input, as it is (after raw_fill() returned false: text that does not start like a record);
     // consumed.  false: nothing is left
     bool raw_rest(const char **text, uint64_t *n);
+    // gzip input whose first text_bytes bytes something else has read (the device's gzip stream, up to where it handed the file back):
+    // the reader inflates them too, from the front and at its own pace, and drops them; the next raw_fill() starts behind them, which
+    // has to be a record start.  A raw_fill() that was not consumed is forgotten.  false: the text is shorter than that
+    bool raw_skip(uint64_t text_bytes);
     // the raw windows are slices of a plain (memory-mapped) file: window = file[resume - n, resume)
     bool raw_is_plain() const { return src.mapped() && src.is_file_mapping(); }
     // after the first raw_fill(): the input is FASTQ ('@' records) or FASTA ('>' records)

@@ -133,6 +133,8 @@ double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+void gzip_stream_close(mk_codec *c);  // (below, with the stream)
+
 const uint8_t kEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 }  // namespace
@@ -301,6 +303,7 @@ void mk_codec_destroy(mk_codec *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    gzip_stream_close(c);  // (its text buffers are what d_gz_text points at)
     for (void *p : {c->d_in, c->d_crc, c->d_tokens, c->d_slots, c->d_len, c->d_off, c->d_out, c->d_aux, c->d_ends, c->d_cut, c->d_gz_in, c->d_gz_sym, c->d_gz_tab, c->d_gz_ctx, c->d_gz_text})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)
@@ -770,6 +773,7 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     if (!c || !text_bytes || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0;
     std::lock_guard<std::mutex> lock(c->mu);
+    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // RFC 1952: the member's header, then the DEFLATE stream up to the 8 trailer bytes.  One member is what is taken here: the stream
@@ -788,6 +792,7 @@ int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, u
     if (!c || !text_bytes || !taken || !n_members || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_members = 0;
     std::lock_guard<std::mutex> lock(c->mu);
+    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // the member starts as the host can guess them: every place where a header parses.  The file goes up whole; which guesses are
@@ -822,6 +827,7 @@ int mk_gzip_text_release(mk_codec *c) {
     if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_text_release: NULL handle");
     std::lock_guard<std::mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
+    gzip_stream_close(c);  // (an open stream's text is the text: the stream ends with it)
     for (void **p : {&c->d_gz_in, &c->d_gz_sym, &c->d_gz_tab, &c->d_gz_ctx, &c->d_gz_text}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -838,6 +844,427 @@ int mk_gzip_info(const mk_codec *c, uint32_t *segments, float ms[5]) {
         for (int k = 0; k < 5; ++k) ms[k] = c->gz_ms[k];
     return MK_OK;
 }
+
+}  // extern "C"
+
+// ---- a gzip file of any size, window by window (mk_gzip_stream_*) ------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kStreamWindow = 256ull << 20;  // the default window (an unmeasured choice: README)
+constexpr uint64_t kStreamMargin = 64;            // bytes uploaded behind the window: a trailer and the fixed part of the next header
+
+uint64_t stream_held(const mk_codec *c) {
+    return c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap + c->gz_ctx_cap + c->gzs.text_cap[0] + c->gzs.text_cap[1] + (c->gzs.d_carry[0] ? 2ull * mkz::kSegPrefix : 0);
+}
+
+// a candidate member of a window: its DEFLATE stream starts at bit `pay_bit` of the upload; closed: its trailer lies at byte `end`
+// of the upload (crc / isize read there); open: the trailer lies behind the upload, the member goes on in the next window
+struct WinMember {
+    uint64_t header, pay_bit, end;  // header: byte of the upload where its header parses (the continued member: 0, unused)
+    bool closed;
+};
+
+// One window: *state = 0 (c->gz_text_bytes of text in the current text buffer) or 2.  3 = grow the window and call again.  A return
+// other than MK_OK is a device error (the caller makes it state 2).  Called with the handle's mutex held.
+int gzip_stream_window(mk_codec *c, uint32_t *state) {
+    mk_gzip_stream &S = c->gzs;
+    *state = 2;
+    int rc;
+    const uint64_t base = S.pos_bit >> 3;
+    const uint64_t nominal = (S.window << S.grow) + kStreamMargin;
+    const uint64_t n_up = std::min<uint64_t>(S.n - base, nominal);
+    const bool is_last = base + n_up == S.n;
+    const uint8_t *up = S.gz + base;
+    // ---- the candidate members: the one the window continues or the header it starts at, then every guess inside the upload
+    std::vector<WinMember> mem;
+    if (S.in_member) {
+        mem.push_back(WinMember{0, S.pos_bit - base * 8, 0, false});
+    } else {
+        const uint64_t p = gzip_header_end(S.gz, S.n, base);
+        if (!p) return MK_OK;  // bytes behind the last member that are no member
+        if (p + 2 > base + n_up) {
+            *state = 3;
+            return MK_OK;
+        }
+        mem.push_back(WinMember{0, (p - base) * 8, 0, false});
+    }
+    {
+        const uint64_t from = base + (mem[0].pay_bit >> 3);
+        auto g = std::upper_bound(S.guesses.begin(), S.guesses.end(), from, [](uint64_t v, const mk_gzip_guess &x) { return v < x.header_off; });
+        for (; g != S.guesses.end() && g->data_off + 2 <= base + n_up; ++g) {
+            if (g->header_off < base + 8) continue;  // (no room for a trailer in front of it inside this upload)
+            mem.back().end = g->header_off - base - 8, mem.back().closed = true;
+            mem.push_back(WinMember{g->header_off - base, (g->data_off - base) * 8, 0, false});
+        }
+        if (is_last) mem.back().end = n_up - 8, mem.back().closed = true;
+    }
+    const uint64_t n_in = n_up;
+    uint64_t chunk = c->gzip_chunk ? c->gzip_chunk : (n_in / (32u << 10) <= (uint64_t)c->num_cus * 17 * 3 / 2 ? 16u << 10 : 64u << 10);
+    while (n_in / chunk > 32768) chunk *= 2;
+    const uint32_t n_chunks = (uint32_t)std::max<uint64_t>(1, n_in / chunk);
+    constexpr uint64_t kMaxSegments = 65535;
+    if (mem.size() + n_chunks > kMaxSegments) return MK_OK;
+    // buffers by the window's nominal size, so that every window of a file finds them there: nothing is sized by the file
+    const size_t seg_room = (size_t)std::max<uint64_t>(1, nominal / chunk) + 16;
+    if ((rc = mk::ensure_device(&c->d_gz_in, &c->gz_in_cap, nominal + mkz::kPad + 16))) return rc;
+    const size_t max_seg = std::max<size_t>(seg_room, (size_t)n_chunks + mem.size());
+    if ((rc = mk::ensure_device(&c->d_gz_tab, &c->gz_tab_cap, ((size_t)n_chunks + max_seg * 8 + 16) * 8))) return rc;
+    unsigned long long *d_starts = (unsigned long long *)c->d_gz_tab;
+    double t0 = now_ms();
+    if ((rc = upload(c, c->d_gz_in, up, n_in))) return rc;
+    MKC_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n_in, 0, mkz::kPad + 16, c->stream), "hipMemsetAsync");
+    MKC_HIP(hipStreamSynchronize(c->stream), "upload of the window");
+    S.stats.ms[0] += (float)(now_ms() - t0);
+    t0 = now_ms();
+    std::vector<unsigned long long> starts(n_chunks, ~0ull), found;
+    mkz::launch_gzip_find((const uint8_t *)c->d_gz_in, n_in, chunk, n_chunks, chunk, d_starts, c->stream);
+    MKC_HIP(hipGetLastError(), "gzip block search");
+    if (n_chunks > 1) MKC_HIP(hipMemcpyAsync(starts.data() + 1, d_starts + 1, (n_chunks - 1) * 8ull, hipMemcpyDeviceToHost, c->stream), "download of the block starts");
+    MKC_HIP(hipStreamSynchronize(c->stream), "gzip block search");
+    S.stats.ms[1] += (float)(now_ms() - t0);
+    for (uint32_t k = 1; k < n_chunks; ++k)
+        if (starts[k] != ~0ull && (found.empty() || starts[k] > found.back())) found.push_back(starts[k]);
+    // ---- pieces -> symbols, in rounds as gzip_inflate_chain runs them.  The last candidate of a window that is not the file's last
+    // is OPEN: its pieces end at found starts only, and the last of those is the cut -- no piece is decoded behind it.
+    std::vector<unsigned long long> tab, n_out, bits, end, lim;
+    std::vector<uint32_t> seg_first, mem_first;
+    std::vector<int32_t> status;
+    unsigned long long *d_bits = nullptr, *d_end = nullptr, *d_lim = nullptr, *d_off = nullptr, *d_cap = nullptr, *d_nout = nullptr, *d_toff = nullptr;
+    uint32_t *d_first = nullptr, *d_bad = nullptr;
+    int32_t *d_status = nullptr;
+    uint32_t J = 0;
+    uint64_t ratio = 12, cut_bit = ~0ull;  // cut_bit: the open member's last start (~0: it has none)
+    bool done = false;
+    t0 = now_ms();
+    for (int dropped_rounds = 0, member_rounds = 0, round = 0; !done; ++round) {
+        if (round) ++S.stats.rounds_repeated;
+        const size_t M = mem.size();
+        bits.clear(), end.clear(), lim.clear(), seg_first.clear();
+        mem_first.assign(M + 1, 0);
+        cut_bit = ~0ull;
+        size_t f = 0;
+        for (size_t m = 0; m < M; ++m) {
+            mem_first[m] = (uint32_t)bits.size();
+            const unsigned long long b0 = mem[m].pay_bit, b1 = mem[m].closed ? mem[m].end * 8 : n_in * 8;
+            std::vector<unsigned long long> at{b0};
+            while (f < found.size() && found[f] <= b0) ++f;
+            for (; f < found.size() && found[f] < b1; ++f) at.push_back(found[f]);
+            if (!mem[m].closed) {  // (the last start is where the window ends)
+                if (at.size() > 1) cut_bit = at.back();
+                at.pop_back();
+            }
+            for (size_t j = 0; j < at.size(); ++j) {
+                bits.push_back(at[j]);
+                end.push_back(j + 1 < at.size() ? at[j + 1] : mem[m].closed ? ~0ull : cut_bit);
+                lim.push_back(mem[m].closed ? std::max(mem[m].end, mem[m].pay_bit >> 3) : n_in);
+                seg_first.push_back(mem_first[m]);
+            }
+        }
+        if (bits.size() > kMaxSegments) return MK_OK;
+        J = (uint32_t)bits.size();
+        mem_first[M] = J;
+        seg_first.push_back(J);
+        if (!J) break;  // (one open member without a start: the window grows)
+        tab.assign((size_t)J * 5, 0);
+        unsigned long long *seg_off = tab.data() + (size_t)J * 3, *seg_cap = seg_off + J;
+        std::copy(bits.begin(), bits.end(), tab.begin()), std::copy(end.begin(), end.end(), tab.begin() + J), std::copy(lim.begin(), lim.end(), tab.begin() + 2 * (size_t)J);
+        uint64_t elems = 0;
+        for (uint32_t j = 0; j < J; ++j) {
+            const uint64_t b0 = bits[j] >> 3, b1 = end[j] != ~0ull ? end[j] >> 3 : lim[j];
+            seg_cap[j] = 65536 + ratio * (b1 - b0 + 1);
+            seg_off[j] = elems;
+            elems += mkz::kSegPrefix + seg_cap[j] + mkz::kSegSlack;
+            elems = (elems + 7) & ~7ull;
+        }
+        if (J > max_seg) return mk::fail(MK_E_HIP, "mk_gzip_stream_next: %u pieces, a table for %llu (internal error)", J, (unsigned long long)max_seg);
+        d_bits = d_starts + n_chunks, d_end = d_bits + J, d_lim = d_end + J, d_off = d_lim + J, d_cap = d_off + J, d_nout = d_cap + J, d_toff = d_nout + J;
+        d_first = (uint32_t *)(d_toff + J), d_status = (int32_t *)(d_first + J + 1), d_bad = (uint32_t *)(d_status + J);
+        n_out.assign(J, 0), status.assign(J, 0);
+        const uint64_t sym_need = std::max<uint64_t>(elems, seg_room * (uint64_t)(mkz::kSegPrefix + 65536 + mkz::kSegSlack + 8 + ratio) + ratio * nominal) * 2 + 64;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && sym_need > c->gz_sym_cap && sym_need - c->gz_sym_cap > free_b / 2) return MK_OK;  // no room on this device
+        if ((rc = mk::ensure_device(&c->d_gz_sym, &c->gz_sym_cap, sym_need))) return rc;
+        MKC_HIP(hipMemcpyAsync(d_bits, tab.data(), tab.size() * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the segment table");
+        mkz::launch_gzip_segments((const uint8_t *)c->d_gz_in, d_bits, d_end, d_lim, d_off, d_cap, J, (uint16_t *)c->d_gz_sym, d_nout, d_status, c->num_cus, c->stream,
+                                  c->inflate_kernel == 1);
+        MKC_HIP(hipGetLastError(), "gzip segment decode");
+        MKC_HIP(hipMemcpyAsync(n_out.data(), d_nout, J * 8ull, hipMemcpyDeviceToHost, c->stream), "download");
+        MKC_HIP(hipMemcpyAsync(status.data(), d_status, J * 4ull, hipMemcpyDeviceToHost, c->stream), "download");
+        MKC_HIP(hipStreamSynchronize(c->stream), "gzip segment decode");
+        c->gz_segments = J;
+        // the walk of gzip_inflate_chain; an open member has no last piece to judge, and every one of its pieces ends at a found start
+        bool overflow = false, starts_dropped = false, anchored = true;
+        std::vector<char> join(M, 0);
+        std::vector<unsigned long long> gone;
+        for (size_t m = 0; m < M; ++m) {
+            if (m && join[m - 1]) continue;
+            int32_t st = 0;
+            uint32_t at = mem_first[m];
+            bool over = false;
+            for (; at < mem_first[m + 1] && st == 0; ++at) {
+                if (status[at] == mkz::kSegOverflow) over = true;
+                else st = status[at];
+            }
+            if (st == 0 && !over) {
+                anchored = true;
+                continue;
+            }
+            if (!anchored) continue;
+            if (st == 0) {
+                overflow = true;
+            } else if (st == mkz::kSegDesync && (at < mem_first[m + 1] || !mem[m].closed)) {
+                const unsigned long long from = bits[at - 1], stands_at = n_out[at - 1], b1 = mem[m].closed ? mem[m].end * 8 : n_in * 8;
+                const size_t before = gone.size();
+                for (unsigned long long x : found)
+                    if (x > from && x < stands_at && x < b1) gone.push_back(x);
+                if (gone.size() == before) return MK_OK;
+                starts_dropped = true;
+            } else {
+                if (m + 1 == M) return MK_OK;  // (no guess to drop: a stream that does not decode, or ends elsewhere)
+                join[m] = 1, anchored = false;
+            }
+        }
+        if (starts_dropped) {
+            if (++dropped_rounds > 3) return MK_OK;
+            std::sort(gone.begin(), gone.end());
+            std::vector<unsigned long long> kept;
+            std::set_difference(found.begin(), found.end(), gone.begin(), gone.end(), std::back_inserter(kept));
+            found.swap(kept);
+        }
+        if (std::find(join.begin(), join.end(), 1) != join.end()) {
+            if (++member_rounds > 3) return MK_OK;
+            std::vector<WinMember> left;
+            for (size_t m = 0; m < M; ++m) {
+                if (m && join[m - 1]) left.back().end = mem[m].end, left.back().closed = mem[m].closed;
+                else left.push_back(mem[m]);
+            }
+            mem.swap(left);
+            continue;
+        }
+        if (starts_dropped) continue;
+        if (!overflow) done = true;
+        else if (ratio == 48) return MK_OK;
+        else ratio = 48;
+    }
+    S.stats.ms[2] += (float)(now_ms() - t0);
+    // ---- where the window ends
+    const size_t M = mem.size();
+    const WinMember &last = mem[M - 1];
+    uint64_t next_bit;
+    bool next_in_member;
+    if (last.closed) next_bit = S.n * 8, next_in_member = false;
+    else if (cut_bit != ~0ull) next_bit = base * 8 + cut_bit, next_in_member = true;
+    else if (M > 1) next_bit = (base + last.header) * 8, next_in_member = false;  // (the open member begins the next window, header first)
+    else next_bit = S.pos_bit, next_in_member = S.in_member;
+    if (next_bit <= S.pos_bit && !last.closed) {  // no proved start to stop at
+        *state = is_last ? 2 : 3;
+        return MK_OK;
+    }
+    // ---- every closed member's text is as long as its trailer says (modulo 2^32, of all its windows)
+    std::vector<unsigned long long> text_off(std::max<uint32_t>(J, 1), 0);
+    std::vector<uint64_t> mem_text(M, 0);
+    uint64_t total = 0;
+    uint32_t max_member_segs = 1;
+    for (size_t m = 0; m < M; ++m) {
+        for (uint32_t j = mem_first[m]; j < mem_first[m + 1]; ++j) text_off[j] = total, total += n_out[j], mem_text[m] += n_out[j];
+        if (mem[m].closed) {
+            uint32_t isize;
+            memcpy(&isize, up + mem[m].end + 4, 4);
+            const uint64_t len = mem_text[m] + (m == 0 && S.in_member ? S.open_len : 0);
+            if ((uint32_t)len != isize) return MK_OK;
+        }
+        max_member_segs = std::max(max_member_segs, mem_first[m + 1] - mem_first[m]);
+    }
+    t0 = now_ms();
+    void **d_text = &S.d_text[S.text_cur ^ 1];
+    size_t *text_cap = &S.text_cap[S.text_cur ^ 1];
+    if ((rc = mk::ensure_device(&c->d_gz_ctx, &c->gz_ctx_cap, std::max<size_t>(J, seg_room) * mkz::kSegPrefix * 5 + 16))) return rc;
+    if ((rc = mk::ensure_device(d_text, text_cap, std::max<uint64_t>(total, ratio * nominal) + 64))) return rc;
+    uint32_t bad = 0;
+    if (J) {
+        MKC_HIP(hipMemcpyAsync(d_toff, text_off.data(), J * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the text offsets");
+        MKC_HIP(hipMemcpyAsync(d_first, seg_first.data(), (J + 1) * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the member table");
+        MKC_HIP(hipMemsetAsync(d_bad, 0, 4, c->stream), "hipMemsetAsync");
+        mkz::launch_gzip_resolve((const uint16_t *)c->d_gz_sym, d_off, d_nout, d_toff, d_first, J, max_member_segs, (uint8_t *)c->d_gz_ctx, (uint8_t *)*d_text, d_bad,
+                                 c->stream, S.in_member ? (const uint8_t *)S.d_carry[S.carry_cur] : nullptr, S.carry_len);
+        MKC_HIP(hipGetLastError(), "gzip resolution");
+        MKC_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream), "download");
+        MKC_HIP(hipStreamSynchronize(c->stream), "gzip resolution");
+    }
+    S.stats.ms[3] += (float)(now_ms() - t0);
+    if (bad) return MK_OK;
+    // ---- CRC-32 per member of its text in this window, folded into what the member had before the window
+    t0 = now_ms();
+    std::vector<uint32_t> mem_crc(M, 0);
+    {
+        const uint32_t bb = mkz::kMaxBlockBytes;
+        std::vector<unsigned long long> blk_off;
+        std::vector<uint32_t> blk_len;
+        for (size_t m = 0; m < M; ++m)
+            for (uint64_t at = 0; at < mem_text[m]; at += bb) blk_off.push_back(text_off[mem_first[m]] + at), blk_len.push_back((uint32_t)std::min<uint64_t>(bb, mem_text[m] - at));
+        const size_t blocks = blk_off.size();
+        if (blocks >> 32) return MK_OK;
+        if ((rc = mk::ensure_device(&c->d_crc, &c->crc_cap, blocks * 4ull + 16)) || (rc = mk::ensure_device(&c->d_off, &c->off_cap, blocks * 8ull + 16)) ||
+            (rc = mk::ensure_device(&c->d_len, &c->len_cap, blocks * 4ull + 16)))
+            return rc;
+        std::vector<uint32_t> crcs(blocks);
+        if (blocks) {
+            MKC_HIP(hipMemcpyAsync(c->d_off, blk_off.data(), blocks * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
+            MKC_HIP(hipMemcpyAsync(c->d_len, blk_len.data(), blocks * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
+            mkz::launch_crc_ranges((const uint8_t *)*d_text, (const unsigned long long *)c->d_off, (const uint32_t *)c->d_len, (uint32_t)blocks, (uint32_t *)c->d_crc, c->stream);
+            MKC_HIP(hipGetLastError(), "CRC kernel");
+            MKC_HIP(hipMemcpyAsync(crcs.data(), c->d_crc, blocks * 4ull, hipMemcpyDeviceToHost, c->stream), "download of the CRCs");
+        }
+        MKC_HIP(hipStreamSynchronize(c->stream), "CRC kernel");
+        const uint32_t shift_full = mkz::crc_x_pow_bytes(bb);
+        size_t b = 0;
+        for (size_t m = 0; m < M; ++m) {
+            uint32_t crc = m == 0 && S.in_member ? S.open_crc : 0;
+            for (uint64_t at = 0; at < mem_text[m]; at += bb, ++b) crc = mkz::crc_mulmod(crc, blk_len[b] == bb ? shift_full : mkz::crc_x_pow_bytes(blk_len[b])) ^ crcs[b];
+            mem_crc[m] = crc;
+            if (mem[m].closed) {
+                uint32_t said;
+                memcpy(&said, up + mem[m].end, 4);
+                if (crc != said) return MK_OK;
+            }
+        }
+    }
+    S.stats.ms[4] += (float)(now_ms() - t0);
+    // ---- the window stands: what the next one starts from
+    if (next_in_member) {
+        const bool continued = M == 1 && S.in_member;  // the open member is the one this window continued
+        const uint8_t *prev = continued ? (const uint8_t *)S.d_carry[S.carry_cur] : nullptr;
+        const uint64_t t_open = mem_text[M - 1];
+        mkz::launch_gzip_carry((const uint8_t *)*d_text + (J && mem_first[M - 1] < J ? text_off[mem_first[M - 1]] : total), t_open, prev, (uint8_t *)S.d_carry[S.carry_cur ^ 1], c->stream);
+        MKC_HIP(hipGetLastError(), "gzip carry");
+        MKC_HIP(hipStreamSynchronize(c->stream), "gzip carry");
+        S.carry_len = (uint32_t)std::min<uint64_t>(mkz::kSegPrefix, (continued ? S.carry_len : 0) + t_open);
+        S.carry_cur ^= 1;
+        S.open_crc = mem_crc[M - 1];
+        S.open_len = (continued ? S.open_len : 0) + t_open;
+    } else {
+        S.carry_len = 0, S.open_crc = 0, S.open_len = 0;
+    }
+    for (size_t m = 0; m < M; ++m) S.stats.members += mem[m].closed;
+    S.pos_bit = next_bit, S.in_member = next_in_member;
+    S.text_cur ^= 1;
+    c->d_gz_text = *d_text, c->gz_text_cap = *text_cap, c->gz_text_bytes = total;
+    S.stats.windows += 1, S.stats.text_bytes += total, S.stats.consumed_bytes = S.pos_bit >> 3;
+    S.stats.peak_device_bytes = std::max<uint64_t>(S.stats.peak_device_bytes, stream_held(c));
+    *state = 0;
+    return MK_OK;
+}
+
+void gzip_stream_close(mk_codec *c) {
+    mk_gzip_stream &S = c->gzs;
+    if (!S.active) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (void **q : {&S.d_carry[0], &S.d_carry[1], &S.d_text[0], &S.d_text[1], &c->d_gz_sym, &c->d_gz_ctx, &c->d_gz_in, &c->d_gz_tab}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->gz_sym_cap = c->gz_ctx_cap = c->gz_in_cap = c->gz_tab_cap = 0;
+    c->d_gz_text = nullptr, c->gz_text_cap = 0, c->gz_text_bytes = 0;
+    S = mk_gzip_stream{};
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t mk_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return mkz::crc_mulmod(crc_a, mkz::crc_x_pow_bytes(len_b)) ^ crc_b; }
+
+int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t window_bytes, uint32_t *taken) {
+    MK_ABI_BEGIN
+    if (!c || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: NULL argument");
+    *taken = 0;
+    if (window_bytes && (window_bytes < 4096 || window_bytes > (1ull << 40))) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: a window of 4 KiB at least");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: the handle has an open stream (mk_gzip_stream_end)");
+    uint64_t n_guesses = 0;
+    int rc = mk_gzip_member_guesses(gz, n, nullptr, 0, &n_guesses);
+    if (rc || !n_guesses) return rc;  // (not a gzip file)
+    MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
+    // the one-shot text of an earlier call goes: d_gz_text is the stream's from here on
+    for (void **q : {&c->d_gz_in, &c->d_gz_sym, &c->d_gz_tab, &c->d_gz_ctx, &c->d_gz_text}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->gz_in_cap = c->gz_sym_cap = c->gz_tab_cap = c->gz_ctx_cap = c->gz_text_cap = 0;
+    c->gz_text_bytes = 0, c->gz_segments = 0;
+    mk_gzip_stream &S = c->gzs;
+    S = mk_gzip_stream{};
+    S.guesses.resize(n_guesses);
+    if ((rc = mk_gzip_member_guesses(gz, n, S.guesses.data(), n_guesses, &n_guesses))) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if (hipMalloc(&S.d_carry[k], mkz::kSegPrefix) != hipSuccess || hipMemsetAsync(S.d_carry[k], 0, mkz::kSegPrefix, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            S.active = true;
+            gzip_stream_close(c);
+            return MK_OK;  // (the codec rule: the device's trouble is "not taken")
+        }
+    }
+    S.active = true, S.gz = gz, S.n = n, S.window = window_bytes ? window_bytes : kStreamWindow;
+    *taken = 1;
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_gzip_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
+    MK_ABI_BEGIN
+    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_next: NULL argument");
+    *text_bytes = 0, *state = 2;
+    std::lock_guard<std::mutex> lock(c->mu);
+    mk_gzip_stream &S = c->gzs;
+    if (!S.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_next: no open stream (mk_gzip_stream_begin)");
+    if (S.dead) return MK_OK;
+    if (!S.in_member && (S.pos_bit >> 3) == S.n) {
+        *state = 1;
+        return MK_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) {
+        S.dead = true;
+        return MK_OK;
+    }
+    S.grow = 0;
+    for (;;) {
+        uint32_t st = 2;
+        const int rc = gzip_stream_window(c, &st);
+        if (rc != MK_OK) st = 2, (void)hipGetLastError();
+        if (st == 3) {  // no proved start inside the window: twice the window, as long as the file and the device have the room
+            const uint64_t base = S.pos_bit >> 3;
+            if (base + (S.window << S.grow) + kStreamMargin >= S.n || S.grow >= 24) st = 2;
+            else {
+                ++S.grow, ++S.stats.windows_grown;
+                continue;
+            }
+        }
+        if (st == 0) *text_bytes = c->gz_text_bytes;
+        else S.dead = true, c->gz_text_bytes = 0;
+        *state = st;
+        return MK_OK;
+    }
+    MK_ABI_END
+}
+
+int mk_gzip_stream_info(const mk_codec *c, mk_gzip_stream_stats *out) {
+    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_info: NULL argument");
+    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_gzip_stream_next writes them under it: a call beside it waits for the window)
+    *out = c->gzs.stats;  // (no stream open: what the last one left, zeros if there was none)
+    return MK_OK;
+}
+
+int mk_gzip_stream_end(mk_codec *c) {
+    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_end: NULL handle");
+    std::lock_guard<std::mutex> lock(c->mu);
+    gzip_stream_close(c);
+    return MK_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int mk_bgzf_inflate(mk_codec *c, const uint8_t *in, uint64_t n_in, const mk_bgzf_member *members, uint64_t n_members, uint8_t *out,
                     uint64_t out_cap, uint64_t *bad_member) {

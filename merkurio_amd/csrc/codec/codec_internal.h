@@ -4,8 +4,28 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <vector>
 
 #include "../host_common.h"
+
+// mk_gzip_stream_*: a gzip file in windows of its compressed bytes (codec_host.cpp).  The stream owns two text buffers (the handle's
+// d_gz_text points at the latest window's) and two carry buffers of 32 KiB; symbols, tables and contexts are the handle's, sized by
+// the window.
+struct mk_gzip_stream {
+    bool active = false, dead = false;  // dead: handed back (state 2), nothing more is produced
+    const uint8_t *gz = nullptr;
+    uint64_t n = 0, window = 0;
+    std::vector<mk_gzip_guess> guesses;  // of the whole file, once
+    uint64_t pos_bit = 0;    // first bit of the next window
+    bool in_member = false;  // pos_bit lies inside a member's DEFLATE stream (else: at a header, or at the file's end)
+    uint32_t open_crc = 0;   // of the open member's text so far
+    uint64_t open_len = 0;
+    uint32_t carry_len = 0, grow = 0;
+    int carry_cur = 0, text_cur = 0;
+    void *d_carry[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
+    size_t text_cap[2] = {0, 0};
+    mk_gzip_stream_stats stats{};
+};
 
 struct mk_codec {
     int device = 0, num_cus = 256;
@@ -36,6 +56,7 @@ struct mk_codec {
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size
     uint64_t deflate_pass_blocks = 0, inflate_pass_text = 0;  // mk_codec_set_pass_limits; 0 = the defaults below
+    mk_gzip_stream gzs;
 };
 
 namespace mkz {

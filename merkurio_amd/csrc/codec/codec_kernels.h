@@ -85,6 +85,12 @@ void launch_gzip_segments_wave(const uint8_t *in, const unsigned long long *seg_
 // contexts (n_seg x 32 KiB) and the text: text[text_off[j] ...] = segment j's bytes; *bad != 0: a symbol that is neither.  The chain of
 // contexts restarts at every member: seg_first[j] = the first segment of segment j's member, max_member_segs = the most segments a member has
 void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off, const unsigned long long *n_out, const unsigned long long *text_off,
-                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s);
+                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s,
+                         const uint8_t *carry = nullptr, uint32_t carry_len = 0);
+// a window of a stream (mk_gzip_stream_next).  launch_gzip_resolve with carry != nullptr: segment 0 continues a member whose last 32 KiB
+// of text in front of the window are carry[0, 32768) (carry_len of them real, at the buffer's end): its context, and what counts as
+// "inside the stream" for the member's segments.  launch_gzip_carry: next = the last 32 KiB of (prev ++ text[0, n)), prev = nullptr: of
+// text alone (zeros in front of it)
+void launch_gzip_carry(const uint8_t *text, uint64_t n, const uint8_t *prev, uint8_t *next, hipStream_t s);
 
 }  // namespace mkz

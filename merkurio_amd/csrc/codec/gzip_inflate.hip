@@ -199,25 +199,46 @@ __global__ __launch_bounds__(256) void mk_gzip_maps_step_kernel(const uint16_t *
 // ctx[j + 1] from map j, now in terms of the context of its member's first segment = zeros (that context itself: zeros).  8 elements
 // per thread.  What is still a place-holder lies in front of the member's stream: the 0 written for it is never text -- the
 // translation refuses the symbols that would read it (seg_before_stream).
-__global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t *__restrict__ maps, const uint32_t *__restrict__ seg_first, uint8_t *__restrict__ ctx) {
+// kCarried (a window of a stream, mk_gzip_stream_next): segment 0 continues a member that began in an earlier window, and `carry` is
+// the 32 KiB of text in front of it -- the context of segment 0, and what a place-holder that has survived composition back to
+// segment 0 stands for.  Members that start inside the window keep the context of nothing.
+template <bool kCarried>
+__global__ __launch_bounds__(256) void mk_gzip_maps_final_kernel(const uint16_t *__restrict__ maps, const uint32_t *__restrict__ seg_first, uint8_t *__restrict__ ctx,
+                                                                 const uint8_t *__restrict__ carry) {
     const uint32_t k = (blockIdx.x * 256 + threadIdx.x) * 8;
     uint2 bytes = make_uint2(0, 0);
     if (seg_first[blockIdx.y] != blockIdx.y) {
         const uint4 v = *reinterpret_cast<const uint4 *>(maps + (uint64_t)(blockIdx.y - 1) * kSegPrefix + k);
-        auto two = [](uint32_t w) -> uint32_t {  // two elements -> two bytes (a place-holder of ctx[0]: 0)
-            const uint32_t lo = w & 0xffffu, hi = w >> 16;
-            return ((lo & kSegUnknown) ? 0u : lo & 0xffu) | ((hi & kSegUnknown) ? 0u : hi & 0xffu) << 8;
-        };
-        bytes = make_uint2(two(v.x) | two(v.y) << 16, two(v.z) | two(v.w) << 16);
+        if constexpr (kCarried) {
+            const bool continued = seg_first[blockIdx.y] == 0;
+            auto two = [&](uint32_t w) -> uint32_t {  // (a place-holder of ctx[0]: the carry's byte)
+                const uint32_t lo = w & 0xffffu, hi = w >> 16;
+                const uint32_t a = (lo & kSegUnknown) ? (continued ? carry[lo & 0x7fffu] : 0u) : lo & 0xffu;
+                const uint32_t b = (hi & kSegUnknown) ? (continued ? carry[hi & 0x7fffu] : 0u) : hi & 0xffu;
+                return a | b << 8;
+            };
+            bytes = make_uint2(two(v.x) | two(v.y) << 16, two(v.z) | two(v.w) << 16);
+        } else {
+            auto two = [](uint32_t w) -> uint32_t {  // two elements -> two bytes (a place-holder of ctx[0]: 0)
+                const uint32_t lo = w & 0xffffu, hi = w >> 16;
+                return ((lo & kSegUnknown) ? 0u : lo & 0xffu) | ((hi & kSegUnknown) ? 0u : hi & 0xffu) << 8;
+            };
+            bytes = make_uint2(two(v.x) | two(v.y) << 16, two(v.z) | two(v.w) << 16);
+        }
+    } else if (kCarried && blockIdx.y == 0) {
+        bytes = *reinterpret_cast<const uint2 *>(carry + k);
     }
     *reinterpret_cast<uint2 *>(ctx + (uint64_t)blockIdx.y * kSegPrefix + k) = bytes;
 }
 
 // text[text_off[j] + i] = the byte symbol i of segment j stands for.  bad: a symbol that is neither a byte nor a place-holder, or the
 // place-holder of a byte in front of the member's stream (a distance too far back, however many matches carried it here).
+// kCarried: the member of segment 0 has carry_len bytes of text in front of the window (saturated at 32 768): they count as stream.
+template <bool kCarried>
 __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t *__restrict__ sym, const unsigned long long *__restrict__ seg_off,
                                                                  const unsigned long long *__restrict__ n_out, const unsigned long long *__restrict__ text_off,
-                                                                 const uint32_t *__restrict__ seg_first, const uint8_t *__restrict__ ctx, uint32_t n_seg, uint8_t *__restrict__ text, uint32_t *__restrict__ bad) {
+                                                                 const uint32_t *__restrict__ seg_first, const uint8_t *__restrict__ ctx, uint32_t n_seg, uint8_t *__restrict__ text, uint32_t *__restrict__ bad,
+                                                                 uint32_t carry_len) {
     __shared__ uint8_t c[kSegPrefix];
     const uint32_t j = blockIdx.x;
     if (j >= n_seg) return;
@@ -227,7 +248,9 @@ __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t 
     const uint16_t *o = sym + seg_off[j] + kSegPrefix;
     uint8_t *dst = text + text_off[j];
     const uint64_t n = n_out[j];
-    const uint32_t before = seg_context_before_stream(text_off[j] - text_off[seg_first[j]]);
+    uint64_t in_front = text_off[j] - text_off[seg_first[j]];
+    if constexpr (kCarried) in_front += seg_first[j] == 0 ? carry_len : 0u;
+    const uint32_t before = seg_context_before_stream(in_front);
     uint32_t wrong = 0;
     for (uint64_t i = threadIdx.x; i < n; i += 1024) {
         const uint16_t v = o[i];
@@ -235,6 +258,29 @@ __global__ __launch_bounds__(1024) void mk_gzip_translate_kernel(const uint16_t 
         dst[i] = (v & kSegUnknown) ? c[v & 0x7fffu] : (uint8_t)v;
     }
     if (wrong) atomicOr(bad, 1u);
+}
+
+// The outgoing carry of a window: next[k] = byte (n - 32 768 + k) of (prev ++ text[0, n)), text = what the member that stays open wrote
+// in this window, prev = the 32 KiB in front of it (nullptr: the member began in this window, nothing lies in front).  16 bytes per
+// thread; where the text is shorter than 32 KiB the front comes from prev (or is 0: in front of the member, never read as text).
+__global__ __launch_bounds__(256) void mk_gzip_carry_kernel(const uint8_t *__restrict__ text, uint64_t n, const uint8_t *__restrict__ prev, uint8_t *__restrict__ next) {
+    const uint32_t k = (blockIdx.x * 256 + threadIdx.x) * 16;  // (gridDim.x = kSegPrefix / 4096)
+    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 16; ++q) {
+        const uint64_t e = (uint64_t)k + q + n;  // element of (prev ++ text), prev being elements 0 .. 32 767
+        const uint32_t b = e >= kSegPrefix ? text[e - kSegPrefix] : prev ? prev[e] : 0u;
+        const uint32_t v = b << (8 * (q & 3));
+        if (q < 4) w0 |= v;
+        else if (q < 8) w1 |= v;
+        else if (q < 12) w2 |= v;
+        else w3 |= v;
+    }
+    *reinterpret_cast<uint4 *>(next + k) = make_uint4(w0, w1, w2, w3);
+}
+
+void launch_gzip_carry(const uint8_t *text, uint64_t n, const uint8_t *prev, uint8_t *next, hipStream_t s) {
+    hipLaunchKernelGGL(mk_gzip_carry_kernel, dim3(kSegPrefix / 4096), dim3(256), 0, s, text, n, prev, next);
 }
 
 void launch_gzip_find(const uint8_t *in, uint64_t n_in, uint64_t chunk_bytes, uint32_t n_chunks, uint64_t search_bytes, unsigned long long *starts,
@@ -258,7 +304,8 @@ void launch_gzip_segments(const uint8_t *in, const unsigned long long *seg_bits,
 }
 
 void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off, const unsigned long long *n_out, const unsigned long long *text_off,
-                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s) {
+                         const uint32_t *seg_first, uint32_t n_seg, uint32_t max_member_segs, uint8_t *ctx, uint8_t *text, uint32_t *bad, hipStream_t s, const uint8_t *carry,
+                         uint32_t carry_len) {
     if (!n_seg) return;
     // ctx: n_seg x 32 KiB of contexts, then two sets of n_seg - 1 maps (gzip_resolve_bytes)
     uint16_t *maps[2] = {reinterpret_cast<uint16_t *>(ctx + (uint64_t)n_seg * kSegPrefix), nullptr};
@@ -269,8 +316,13 @@ void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off,
         for (uint32_t r = 1; r < max_member_segs - 1; r *= 2, cur ^= 1)
             hipLaunchKernelGGL(mk_gzip_maps_step_kernel, dim3(kSegPrefix / 2048, n_seg - 1), dim3(256), 0, s, maps[cur], maps[cur ^ 1], seg_first, r);
     }
-    hipLaunchKernelGGL(mk_gzip_maps_final_kernel, dim3(kSegPrefix / 2048, n_seg), dim3(256), 0, s, maps[cur], seg_first, ctx);
-    hipLaunchKernelGGL(mk_gzip_translate_kernel, dim3(n_seg), dim3(1024), 0, s, sym, seg_off, n_out, text_off, seg_first, ctx, n_seg, text, bad);
+    if (carry) {  // (a window that continues a member: segment 0's context is the carry)
+        hipLaunchKernelGGL(mk_gzip_maps_final_kernel<true>, dim3(kSegPrefix / 2048, n_seg), dim3(256), 0, s, maps[cur], seg_first, ctx, carry);
+        hipLaunchKernelGGL(mk_gzip_translate_kernel<true>, dim3(n_seg), dim3(1024), 0, s, sym, seg_off, n_out, text_off, seg_first, ctx, n_seg, text, bad, carry_len);
+        return;
+    }
+    hipLaunchKernelGGL(mk_gzip_maps_final_kernel<false>, dim3(kSegPrefix / 2048, n_seg), dim3(256), 0, s, maps[cur], seg_first, ctx, carry);
+    hipLaunchKernelGGL(mk_gzip_translate_kernel<false>, dim3(n_seg), dim3(1024), 0, s, sym, seg_off, n_out, text_off, seg_first, ctx, n_seg, text, bad, 0u);
 }
 
 }  // namespace mkz
