@@ -678,6 +678,31 @@ int mk_gzip_text_release(mk_codec *c);
  * pieces, resolution, CRC-32 */
 int mk_gzip_info(const mk_codec *c, uint32_t *segments, float ms[5]);
 
+/* (v7) A .bz2 file decoded on the device, one wave per block (merkurio_amd/csrc/codec/bzip2_inflate.hip, bzip2_serial.hpp) -- what
+ * `merkurio extract` reads through needletail's bzip2 reader (src/cmd_extract.rs:281).  bz[0, n) is the whole file, which may hold
+ * several streams (pbzip2 output, `cat a.bz2 b.bz2`).  Every bit offset is tested on the device for the block magic 0x314159265359
+ * and the end-of-stream magic 0x177245385090; the host walks the sorted hits: "BZh" + level at byte 0, the first magic at bit 32,
+ * every block decoded from its magic must END exactly on the next magic of the table (the proof of a guessed start), behind an end
+ * magic and the stream's CRC comes padding to the byte, then the file's end or another "BZh" + level.  A block: header, code tables,
+ * Huffman symbols + zero runs + move-to-front on one wave, the inverse BWT vector by a counting sort across the wave, the walk of
+ * the vector on one lane, lengths, an offsets scan, the text written at each block's offset, bzip2's CRC-32 (polynomial 0x04c11db7,
+ * first bit on top) of every block in 64 folded pieces, the stream CRC folded on the host.  Blocks are decoded in passes whose
+ * scratch (4.5 bytes per symbol) is bounded: by the free memory, or by mk_codec_set_bzip2_pass_blocks (test hook; 0 = default;
+ * results do not depend on it).
+ * *taken = 1 only when proved blocks and streams cover bz[0, n) with nothing left over and every block and stream CRC agrees: the
+ * text of all streams then lies back to back where mk_gzip_inflate_device leaves its text (mk_gzip_text_read / _device / _release,
+ * mk_window_source::device_text), *n_blocks says how many blocks it came from (an empty stream: 0 blocks, 0 bytes).  *taken = 0
+ * (MK_OK, nothing else touched) means the caller runs libbz2, which also words the error: a `randomised` block, origPtr >= the
+ * block's symbols, nGroups outside 2..6, nSelectors 0 or above 18 002, a selector >= nGroups, a code length outside 1..20, a code
+ * under which a symbol does not decode (libbz2's own test of a code), more symbols than level x 100 000, a block that ends inside a
+ * run, data that ends early, a table of magics that does not chain, trailing bytes, a wrong CRC, text plus scratch beyond half of
+ * the free device memory, any device error.  With a gzip stream open on the handle: MK_E_INVALID_ARG.
+ * mk_bzip2_info: blocks of the last call and its phases in milliseconds: upload, marker search, block decode (symbols + vector),
+ * text (walk + expansion), CRC. */
+int mk_bzip2_inflate_device(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
+int mk_bzip2_info(const mk_codec *c, uint32_t *blocks, float ms[5]);
+int mk_codec_set_bzip2_pass_blocks(mk_codec *c, uint64_t blocks);
+
 /* (v7) A gzip file of SEVERAL members -- `cat a.gz b.gz`, a member per tile or per block without BGZF's BC field.  A member carries no
  * compressed size: where it ends is known once it is decoded.  So the starts are guessed on the host and proved on the device.
  * mk_gzip_member_guesses (host code, no device needed) reports every offset at which an RFC 1952 header parses inside gz[0, n): ID1

@@ -88,6 +88,33 @@ void inflate_bz2(const std::string &path, const unsigned char *d, size_t n, std:
     out.resize(used);
 }
 
+}  // namespace
+
+bool bz2_first_bytes(const unsigned char *d, size_t n, std::vector<char> &out, size_t want) {
+    out.clear();
+    void *h = open_any({"libbz2.so.1.0", "libbz2.so.1", "libbz2.so"});
+    if (!h) return false;
+    auto init = (int (*)(bz_stream *, int, int))dlsym(h, "BZ2_bzDecompressInit");
+    auto run = (int (*)(bz_stream *))dlsym(h, "BZ2_bzDecompress");
+    auto end = (int (*)(bz_stream *))dlsym(h, "BZ2_bzDecompressEnd");
+    if (!init || !run || !end) return false;
+    bz_stream s;
+    memset(&s, 0, sizeof(s));
+    if (init(&s, 0, 0) != BZ_OK) return false;
+    out.resize(want);
+    s.next_in = (char *)const_cast<unsigned char *>(d);
+    s.avail_in = (unsigned)std::min<size_t>(n, 1u << 30);
+    s.next_out = out.data();
+    s.avail_out = (unsigned)want;
+    int r = BZ_OK;
+    while (r == BZ_OK && s.avail_out != 0 && s.avail_in != 0) r = run(&s);  // (the first stream alone: an empty one yields nothing)
+    end(&s);
+    out.resize(want - s.avail_out);
+    return r == BZ_OK || r == BZ_STREAM_END;
+}
+
+namespace {
+
 // ---- xz (lzma/base.h, lzma/container.h) -------------------------------------------------------------
 struct lzma_stream {
     const uint8_t *next_in;

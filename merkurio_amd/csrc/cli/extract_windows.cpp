@@ -51,7 +51,8 @@ struct Input {
     FastxStream s;
     bool bgzf_dev = false;  // its members go to the device as they are
     // a plain gzip file whose member, or chain of members, the device has inflated in parallel pieces (mk_gzip_inflate_device /
-    // mk_gzip_members_inflate_device): the text lies there, windows are ranges of it
+    // mk_gzip_members_inflate_device), or a bzip2 file whose blocks it has decoded (mk_bzip2_inflate_device, which leaves
+    // its text in the same place): the text lies there, windows are ranges of it
     bool gz_dev = false;
     mk_codec *gz_codec = nullptr;
     const uint8_t *gz_text = nullptr;
@@ -970,11 +971,24 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     int kind[2] = {-1, -1};
     for (int i = 0; i < J.n_in; ++i) {
         Input &I = J.in[i];
-        I.s.open(I.path);
+        I.s.open(I.path, !a.host_codec);
         I.bgzf_dev = !a.host_codec && I.s.raw_is_bgzf();
+        if (I.s.raw_is_bzip2()) {
+            // not inflated here: run() hands the file to the device once the HIP runtime is up.  What its records are is read from
+            // the start of the first block's text (libbz2); where that does not say (an empty first stream, a damaged file), libbz2
+            // reads the whole file now, as under --host-codec, and words what is wrong with it
+            std::vector<char> first;
+            if (bz2_first_bytes(I.s.source().file_bytes(), I.s.source().file_size(), first, 1u << 16))
+                for (char ch : first)
+                    if (ch != '\n' && ch != '\r') {
+                        kind[i] = (unsigned char)ch;
+                        break;
+                    }
+            if (kind[i] != '@' && kind[i] != '>') kind[i] = -1, I.s.raw_settle();
+        }
         if (I.bgzf_dev) {
             kind[i] = first_text_byte_of_bgzf(I.s.source(), I.path);
-        } else {
+        } else if (!I.s.raw_is_bzip2()) {
             I.have_first = I.s.raw_fill(std::min(J.plain_target, kFirstWindow), &I.first_text, &I.first_n, &I.first_resume);
             if (I.have_first) kind[i] = I.s.raw_fastq() ? '@' : '>';
         }
@@ -985,7 +999,7 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     if (J.n_in == 2 && kind[0] != kind[1]) return false;
     J.fastq = kind[0] == '@';
     // (a plain gzip input may become device text once the HIP runtime is up, run(): its windows then end anywhere too)
-    J.chained = J.n_in == 2 || J.in[0].bgzf_dev || (!a.host_codec && J.in[0].s.raw_is_gzip());
+    J.chained = J.n_in == 2 || J.in[0].bgzf_dev || (!a.host_codec && J.in[0].s.raw_is_gzip()) || J.in[0].s.raw_is_bzip2();
     return true;
 }
 
@@ -1030,6 +1044,39 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
         size_t free_b = 0, total_b = 0;
         if (n_streamed && hipSetDevice(devs[0]) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
             while (gzip_window > (1u << 20) && n_streamed * 2 * 50 * gzip_window > (uint64_t)free_b / 2) gzip_window /= 2;
+    }
+    // a bzip2 input: its blocks are decoded on the device, a wave each (mk_bzip2_inflate_device), on a handle per file.
+    // The two files of a pair go ONE AFTER THE OTHER: a call sizes its passes and accepts its text by the memory that is free when it
+    // runs, so the second must find the first's text there already, not a sibling that is about to take the same half.  What a call
+    // does not take -- anything it refuses, a damaged file, no room, an error of the device -- libbz2 reads whole, as under --host-codec,
+    // and words the error; the job goes on with host text
+    for (int i = 0; i < J.n_in; ++i) {
+        Input &I = J.in[i];
+        if (!I.s.raw_is_bzip2()) continue;
+        const double t_bz = PhaseTimer::now();
+        uint64_t text_bytes = 0, blocks = 0;
+        uint32_t taken = 0;
+        if (mk_codec_create(devs[0], &I.gz_codec) != MK_OK) I.gz_codec = nullptr;
+        if (I.gz_codec && mk_bzip2_inflate_device(I.gz_codec, I.s.source().file_bytes(), I.s.source().file_size(), &text_bytes, &taken, &blocks) != MK_OK) taken = 0;
+        if (J.timing && taken) {
+            float ms5[5] = {0, 0, 0, 0, 0};
+            (void)mk_bzip2_info(I.gz_codec, nullptr, ms5);
+            fprintf(stderr, "[timing]   bzip2 on the device: %llu blocks, upload %.1f, marker search %.1f, block decode %.1f, text %.1f, CRC %.1f ms (input %d: %llu text bytes, %.3f s)\n",
+                    (unsigned long long)blocks, ms5[0], ms5[1], ms5[2], ms5[3], ms5[4], i, (unsigned long long)text_bytes, PhaseTimer::now() - t_bz);
+        } else if (J.timing) {
+            fprintf(stderr, "[timing]   bzip2 input %d: NOT taken by the device after %.3f s (libbz2 reads it)\n", i, PhaseTimer::now() - t_bz);
+        }
+        if (!taken) {
+            if (I.gz_codec) mk_codec_destroy(I.gz_codec);
+            I.gz_codec = nullptr;
+            I.s.raw_settle();
+            I.have_first = I.s.raw_fill(std::min(J.plain_target, kFirstWindow), &I.first_text, &I.first_n, &I.first_resume);
+            continue;
+        }
+        I.gz_dev = true;
+        I.gz_text = (const uint8_t *)mk_gzip_text_device(I.gz_codec, &I.gz_bytes);
+        I.gz_next = 0;
+        I.exhausted = I.gz_bytes == 0;
     }
     run_threads((size_t)J.n_in, [&](size_t ii) {  // (the two files of a pair side by side: a handle and a stream each)
         const int i = (int)ii;

@@ -501,14 +501,35 @@ WindowSource::~WindowSource() {
     }
 }
 
-void WindowSource::open(const std::string &p) {
+void WindowSource::settle() {
+    if (kind != BZIP2) return;
+    std::vector<char> out;
+    (void)inflate_by_magic(path, (const unsigned char *)src.p, (size_t)src.n, out);  // (raises on a damaged file)
+    munmap(src.map, src.map_len);
+    src.map = nullptr, src.map_len = 0;
+    src.owned = std::move(out);
+    src.p = src.owned.data(), src.n = src.owned.size();
+    kind = PLAIN;
+}
+
+void WindowSource::open(const std::string &p, bool defer_bzip2) {
     path = p;
     int fd = ::open(p.c_str(), O_RDONLY);
     if (fd < 0) bail("No such file or directory: " + p);
-    unsigned char magic[2] = {0, 0};
-    const ssize_t got = pread(fd, magic, 2, 0);
+    unsigned char magic[4] = {0, 0, 0, 0};
+    const ssize_t got = pread(fd, magic, 4, 0);
     struct stat st;
-    const bool gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+    const bool gz = got >= 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+    if (defer_bzip2 && got == 4 && !memcmp(magic, "BZh", 3) && fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
+        void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m != MAP_FAILED) {
+            close(fd);
+            src.map = m, src.map_len = (uint64_t)st.st_size;
+            src.p = (const char *)m, src.n = src.map_len;
+            kind = BZIP2;
+            return;
+        }
+    }
     if (gz && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
         void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
         close(fd);
@@ -633,6 +654,7 @@ void FastxStream::parse_window(const char *d, uint64_t n, uint64_t from, uint64_
 
 void FastxStream::prefetch(uint64_t window_bytes) {
     if (have_spare) return;
+    src.settle();
     if (window_bytes < (1u << 16)) window_bytes = 1u << 16;
     if (src.mapped()) {
         const uint64_t n = src.text_size();
@@ -717,6 +739,7 @@ void inflate_bgzf_members_host(const uint8_t *file, const mk_bgzf_member *member
 bool FastxStream::raw_fill(uint64_t window_bytes, const char **text, uint64_t *n_out, uint64_t *resume) {
     *resume = 0;
     if (window_bytes < (1u << 16)) window_bytes = 1u << 16;
+    src.settle();
     if (src.mapped()) {
         const char *d = src.text();
         const uint64_t n = src.text_size();
@@ -789,6 +812,7 @@ bool FastxStream::raw_fill(uint64_t window_bytes, const char **text, uint64_t *n
 void FastxStream::raw_consume() { cursor = raw_next; }
 
 bool FastxStream::raw_skip(uint64_t n) {
+    src.settle();
     if (src.mapped()) {
         cursor = std::min<uint64_t>(src.text_size(), n);
         return cursor == n;
@@ -808,6 +832,7 @@ bool FastxStream::raw_skip(uint64_t n) {
 }
 
 bool FastxStream::raw_rest(const char **text, uint64_t *n_out) {
+    src.settle();
     if (src.mapped()) {
         const uint64_t n = src.text_size();
         if (cursor >= n) return false;

@@ -80,6 +80,9 @@ void require_host_memory(uint64_t need, const std::string &path);
 // bzip2 / xz / zstd by magic bytes through the system's runtime libraries (bound with dlopen):
 // false = none of the three; raises cli::Error on corrupt input or a missing library
 bool inflate_by_magic(const std::string &path, const unsigned char *data, size_t n, std::vector<char> &out);
+// the first bytes of a bzip2 file's text, at most `want` of them, by libbz2 (the first block is decoded, no more): false if the library is
+// missing or the file is damaged before that many bytes have come out (the whole-file call then words the error)
+bool bz2_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
 
 // ---- FASTA / FASTQ ------------------------------------------------------------------------------
 // a whole input file in memory: mmap for plain files, an inflated copy for gzip
@@ -129,9 +132,14 @@ struct FastxFile {
 // memory-mapped: the "window" is the whole mapping and costs nothing.  gzip is inflated incrementally
 // (zlib streaming, concatenated members included), BGZF a group of members at a time on all host
 // threads; bzip2 / xz / zstd inputs are inflated whole (their libraries are bound through dlopen without
-// any block index) and then behave like plain text.
+// any block index) and then behave like plain text -- a bzip2 file opened with defer_bzip2 only when settle() is called.
 struct WindowSource {
-    void open(const std::string &path);
+    // defer_bzip2: a bzip2 file is mapped as stored and NOT inflated (is_bzip2()): the caller may decode file_bytes() elsewhere
+    // (extract's mk_bzip2_inflate_device path); settle() -- which every read of the text through FastxStream begins with -- inflates it
+    // with libbz2 after all, and from then on it is plain text like any other inflated bzip2 input
+    void open(const std::string &path, bool defer_bzip2 = false);
+    bool is_bzip2() const { return kind == BZIP2; }
+    void settle();
     bool mapped() const { return kind == PLAIN; }  // text()/text_size() is the complete text
     bool is_file_mapping() const { return kind == PLAIN && src.map != nullptr; }  // (not an inflated bzip2 / xz / zstd copy)
     const char *text() const { return src.p; }
@@ -144,7 +152,7 @@ struct WindowSource {
     // BGZF: the file as stored and its member table, for a caller that inflates on the device (extract's
     // mk_extract_fastq_bgzf path); seek_member() makes member i the next one more_into() inflates
     bool is_bgzf() const { return kind == BGZF; }
-    bool is_gzip() const { return kind == GZIP; }  // one or more plain gzip members: file_bytes() is the file as stored
+    bool is_gzip() const { return kind == GZIP; }  // one or more plain gzip members: file_bytes() is the file as stored (so it is for is_bzip2())
     const uint8_t *file_bytes() const { return (const uint8_t *)src.p; }
     uint64_t file_size() const { return src.n; }
     size_t n_bgzf_members() const { return members.size(); }
@@ -164,7 +172,7 @@ struct WindowSource {
     WindowSource &operator=(const WindowSource &) = delete;
 
    private:
-    enum Kind { PLAIN, GZIP, BGZF } kind = PLAIN;
+    enum Kind { PLAIN, GZIP, BGZF, BZIP2 } kind = PLAIN;
     std::string path;
     FileBytes src;  // the file as stored (PLAIN: the text itself, or inflated bzip2 / xz / zstd)
     bool src_eof = false;
@@ -182,7 +190,7 @@ struct WindowSource {
 //                    ...records [0, n) of s.view...; join; more = s.fill(W); }
 struct FastxStream {
     FastxFile view;  // the current window: view.data / view.recs / view.fastq; all FastxFile accessors work on it
-    void open(const std::string &path) { src.open(path); }
+    void open(const std::string &path, bool defer_bzip2 = false) { src.open(path, defer_bzip2); }
     // Makes the next window current: every complete record among the unconsumed bytes plus up to
     // `window_bytes` new ones (parsed here unless prefetch() already did).  false: no record is left.
     bool fill(uint64_t window_bytes);
@@ -213,6 +221,9 @@ struct FastxStream {
     // bgzip'ed input: the caller walks source()'s members itself and sends them to the device as they are
     bool raw_is_bgzf() const { return src.is_bgzf(); }
     bool raw_is_gzip() const { return src.is_gzip(); }
+    // a bzip2 input opened with defer_bzip2 that nothing has read yet: source().file_bytes() is the file as stored
+    bool raw_is_bzip2() const { return src.is_bzip2(); }
+    void raw_settle() { src.settle(); }  // libbz2 inflates it now
     const WindowSource &source() const { return src; }
 
    private:

@@ -54,7 +54,7 @@ void print_help(const char *sub) {
              "      --batch-mb <MB>          sequence bytes per GPU batch [128]\n"
              "      --window-mb <MB>         input text read and held per window [1024]\n"
              "      --host-ingest            parse FASTQ records on the host threads (default: a single FASTQ input is indexed on the GPU)\n"
-             "      --host-codec             bgzip'ed input inflated by zlib on the host threads (default: on the GPU)\n"
+             "      --host-codec             bgzip'ed input inflated by zlib, .bz2 input by libbz2 on the host (default: on the GPU)\n"
              "      --device-codec-always    BGZF members go through the GPU codec however few they are (default: from 8192 members per call)");
     } else {
         puts("Usage: merkurio tag [OPTIONS] --in-file <IN_FILE> <--kmer-seq <KMER_SEQ>...|--kmer-file <KMER_FILE>>\n\n"

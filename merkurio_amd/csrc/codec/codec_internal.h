@@ -52,6 +52,11 @@ struct mk_codec {
     uint64_t gz_text_bytes = 0;
     uint32_t gz_segments = 0;  // of the last call (diagnostic)
     float gz_ms[5] = {0, 0, 0, 0, 0};  // upload, block search, segments, resolve + translate, CRC
+    // mk_bzip2_inflate_device (its text is gz_text too; compressed file, bytes in front of the run-length step, tables and pass
+    // scratch borrow d_gz_in / d_gz_sym / d_gz_tab / d_gz_ctx)
+    uint32_t bz_blocks = 0;
+    float bz_ms[5] = {0, 0, 0, 0, 0};  // upload, marker search, block decode, text, CRC
+    uint64_t bz_pass_blocks = 0;       // mk_codec_set_bzip2_pass_blocks; 0 = by the free memory
     int inflate_kernel = 0;  // mk_codec_set_inflate_kernel: 0 = chosen per call, 1 = a lane per member, 2 = a wave per member
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size

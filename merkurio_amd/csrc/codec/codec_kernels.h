@@ -93,4 +93,20 @@ void launch_gzip_resolve(const uint16_t *sym, const unsigned long long *seg_off,
 // text alone (zeros in front of it)
 void launch_gzip_carry(const uint8_t *text, uint64_t n, const uint8_t *prev, uint8_t *next, hipStream_t s);
 
+// ---- a .bz2 file, a wave per block (bzip2_inflate.hip, bzip2_serial.hpp, bzip2_stream.hpp) ----
+// in[0, n) (zeros up to n_words dwords behind it) -> table[0, min(*count, cap)) = bit << 1 | kind of every block / end-of-stream magic, in no order
+void launch_bz2_markers(const uint8_t *in, uint64_t n, uint64_t n_words, unsigned long long *table, uint32_t cap, uint32_t *count, int num_cus, hipStream_t s);
+// blocks first .. first + count - 1 of the tables blk_bit / blk_level / blk_pre (device memory): header, symbols, inverse-BWT vector.
+// Block b's bytes go to pre + blk_pre[b] (cap = its level's symbols rounded up to 128 bytes, then cap / 8 bytes for the walk's count
+// bits), its selectors and vector to slot b - first of scratch (slot_bytes >= kBzSelBytes + 4 x cap); rep[b] = its Bz2Block
+void launch_bz2_decode(const uint8_t *in, uint64_t n, uint64_t n_words, const unsigned long long *blk_bit, const uint32_t *blk_level, const unsigned long long *blk_pre,
+                       uint8_t *pre, uint8_t *scratch, uint64_t slot_bytes, uint32_t first, uint32_t count, void *rep, hipStream_t s);
+// the same blocks' vectors walked from origPtr: the bytes in front of the run-length step and their count bits to pre, text_len[b]
+void launch_bz2_walk(const unsigned long long *blk_pre, const uint32_t *blk_level, uint8_t *pre, const uint8_t *scratch, uint64_t slot_bytes, uint32_t first,
+                     uint32_t count, void *rep, unsigned long long *text_len, hipStream_t s);
+// every block's text to text + text_off[b]; then bzip2's CRC-32 of it to crc[b]
+void launch_bz2_expand(const unsigned long long *blk_pre, const uint32_t *blk_level, const uint8_t *pre, const void *rep, const unsigned long long *text_off,
+                       uint8_t *text, uint32_t n_blocks, hipStream_t s);
+void launch_bz2_crc(const uint8_t *text, const unsigned long long *text_off, const unsigned long long *text_len, uint32_t *crc, uint32_t n_blocks, hipStream_t s);
+
 }  // namespace mkz

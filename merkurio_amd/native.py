@@ -54,7 +54,7 @@ EXPORTS = [
     "mk_synth_reads_host", "mk_synth_reads_device_range", "mk_reduce_counters", "mk_reduce_prepare", "mk_comm_available", "mk_comm_unique_id", "mk_comm_init",
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
-    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info",
+    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_codec_set_bzip2_pass_blocks",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
     "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
@@ -310,6 +310,9 @@ def load(build_if_missing=True):
     L.mk_gzip_text_device.restype = C.c_void_p
     L.mk_gzip_text_release.argtypes = [C.c_void_p]
     L.mk_gzip_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.mk_bzip2_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.mk_bzip2_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.mk_codec_set_bzip2_pass_blocks.argtypes = [C.c_void_p, C.c_uint64]
     L.mk_gzip_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
     L.mk_gzip_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.mk_gzip_stream_info.argtypes = [C.c_void_p, C.POINTER(GzipStreamStats)]
@@ -1226,6 +1229,30 @@ class Codec:
         _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
         self.last_read_s = time.perf_counter() - t0
         return out.tobytes()
+
+    def bunzip2(self, data):
+        """mk_bzip2_inflate_device + mk_gzip_text_read: a .bz2 file of one or more streams decoded on the device, a wave per block ->
+        (taken, text, n_blocks); taken = False (text None): the device handed the file back and the caller's libbz2 decodes it"""
+        src = np.frombuffer(data, dtype=np.uint8)
+        n, taken, blocks = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        t0 = time.perf_counter()
+        _check(self._L.mk_bzip2_inflate_device(self._h, src.ctypes.data if src.size else None, src.size, C.byref(n), C.byref(taken), C.byref(blocks)))
+        self.last_call_s = time.perf_counter() - t0
+        if not taken.value:
+            return False, None, 0
+        out = np.empty(n.value, dtype=np.uint8)
+        _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
+        return True, out.tobytes(), blocks.value
+
+    def bunzip2_info(self):
+        """mk_bzip2_info: (blocks of the last bunzip2, ms of upload / marker search / block decode / text / CRC)"""
+        blocks, ms = C.c_uint32(0), (C.c_float * 5)()
+        _check(self._L.mk_bzip2_info(self._h, C.byref(blocks), ms))
+        return blocks.value, tuple(round(x, 3) for x in ms)
+
+    def set_bzip2_pass_blocks(self, blocks):
+        """blocks per device pass of bunzip2 (mk_codec_set_bzip2_pass_blocks); 0 = by the free memory"""
+        _check(self._L.mk_codec_set_bzip2_pass_blocks(self._h, blocks))
 
     def gunzip_members(self, gz):
         """mk_gzip_members_inflate_device + mk_gzip_text_read: a gzip file of one or more members, all of them inflated in one batch of
