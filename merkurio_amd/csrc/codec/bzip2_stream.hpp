@@ -1,6 +1,6 @@
 // bzip2_stream.hpp -- the host's walk over a .bz2 file: from the table of magics found in it (every bit offset tested: the marker
 // kernel of bzip2_inflate.hip, or bz2_find_markers below for the test harness) to the blocks and streams that table implies.  Shared
-// by mk_bzip2_inflate_device (codec_host.cpp) and tests/helpers/bzip2_harness.cpp.  Host code only.
+// by mk_bzip2_inflate_device (bzip2_host.cpp) and tests/helpers/bzip2_harness.cpp.  Host code only.
 //
 // The file is "BZh" + level at byte 0, the first magic at bit 32, then magic after magic: a block magic opens a block that must end
 // exactly on the next magic of the table (which the decode proves or disproves), an end magic is followed by the stream's CRC, padding

@@ -1,5 +1,6 @@
-// codec_internal.h -- the opaque mk_codec handle (codec_host.cpp; window_ingest.cpp borrows its device buffers for
-// mk_extract_fastq_bgzf, which inflates a window of members straight into the matcher's text buffer)
+// codec_internal.h -- the opaque mk_codec handle and what the codec's host files share: codec_host.cpp (the handle, the staging
+// copies), bgzf_host.cpp, gzip_host.cpp, bzip2_host.cpp (a format each).  window_ingest.cpp borrows the handle's device buffers for
+// mk_extract_fastq_bgzf, which inflates a window of members straight into the matcher's text buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,8 +8,20 @@
 #include <vector>
 
 #include "../host_common.h"
+#include "gzip_chain.hpp"
 
-// mk_gzip_stream_*: a gzip file in windows of its compressed bytes (codec_host.cpp).  The stream owns two text buffers (the handle's
+namespace mk {
+int hip_fail(hipError_t e, const char *what);
+int ensure_device(void **p, size_t *cap, size_t need);
+}  // namespace mk
+
+#define MKC_HIP(call, what)                                   \
+    do {                                                      \
+        const hipError_t e_ = (call);                         \
+        if (e_ != hipSuccess) return mk::hip_fail(e_, what);  \
+    } while (0)
+
+// mk_gzip_stream_*: a gzip file in windows of its compressed bytes (gzip_host.cpp).  The stream owns two text buffers (the handle's
 // d_gz_text points at the latest window's) and two carry buffers of 32 KiB; symbols, tables and contexts are the handle's, sized by
 // the window.
 struct mk_gzip_stream {
@@ -16,11 +29,8 @@ struct mk_gzip_stream {
     const uint8_t *gz = nullptr;
     uint64_t n = 0, window = 0;
     std::vector<mk_gzip_guess> guesses;  // of the whole file, once
-    uint64_t pos_bit = 0;    // first bit of the next window
-    bool in_member = false;  // pos_bit lies inside a member's DEFLATE stream (else: at a header, or at the file's end)
-    uint32_t open_crc = 0;   // of the open member's text so far
-    uint64_t open_len = 0;
-    uint32_t carry_len = 0, grow = 0;
+    mkz::GzStreamPos at;                 // where the next window starts, and what the open member has so far (gzip_chain.hpp)
+    uint32_t grow = 0;
     int carry_cur = 0, text_cur = 0;
     void *d_carry[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
     size_t text_cap[2] = {0, 0};
@@ -37,7 +47,7 @@ struct mk_codec {
     void *d_in = nullptr, *d_crc = nullptr, *d_tokens = nullptr, *d_slots = nullptr, *d_len = nullptr, *d_off = nullptr, *d_out = nullptr,
          *d_aux = nullptr;
     size_t in_cap = 0, crc_cap = 0, tokens_cap = 0, slots_cap = 0, len_cap = 0, off_cap = 0, out_cap = 0, aux_cap = 0;
-    // members that end at record ends: the record ends (u64), and the range table the cut kernel makes of them (codec_host.cpp: deflate_ranges)
+    // members that end at record ends: the record ends (u64), and the range table the cut kernel makes of them (bgzf_host.cpp: deflate_ranges)
     void *d_ends = nullptr, *d_cut = nullptr;
     size_t ends_cap = 0, cut_cap = 0;
     float cut_ms[3] = {0, 0, 0};  // of the last such call: cut kernel, CRC-32 + deflate + pack, download
@@ -65,6 +75,24 @@ struct mk_codec {
 };
 
 namespace mkz {
+// ---- codec_host.cpp: host buffers <-> device through the handle's two page-locked staging buffers
+void parallel_copy(uint8_t *dst, const uint8_t *src, uint64_t n);
+// src[0, n) -> d_dst, enqueued on the handle's stream; the host side of it is done when this returns
+int upload(mk_codec *c, void *d_dst, const uint8_t *src, uint64_t n);
+// d_src[0, n) -> dst; waits for the stream (everything enqueued before it included)
+int download(mk_codec *c, uint8_t *dst, const void *d_src, uint64_t n);
+double now_ms();
+inline float elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+}
+// ---- gzip_host.cpp: the buffers of the gzip / bzip2 paths.  gz_release: all five and their caps (the text included: gz_text_bytes = 0).
+// gz_keep_text: what is left to keep is the text -- the compressed bytes, the symbols and the contexts go back to the device.
+// gzip_stream_close: an open stream ends, with its text buffers (which are what d_gz_text points at) and the handle's scratch
+void gz_release(mk_codec *c);
+void gz_keep_text(mk_codec *c);
+void gzip_stream_close(mk_codec *c);
+// ---- bgzf_host.cpp
 // One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
 // output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on
 // stream st, with the codec's buffers (the caller holds c->mu).  Member b = d_text[b * bb ...] (off == nullptr; the last one ends at

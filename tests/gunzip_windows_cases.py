@@ -12,7 +12,7 @@ import deflate_craft as craft
 import gunzip_members_cases as gm
 
 WINDOWS = (16 << 10, 64 << 10, 256 << 10)
-MARGIN = 64  # bytes a window uploads behind its nominal size (codec_host.cpp: kStreamMargin)
+MARGIN = 64  # bytes a window uploads behind its nominal size (codec/gzip_chain.hpp: kGzStreamMargin)
 SYNC_FLUSH_EVERY = 3 << 10  # bytes of text between two Z_SYNC_FLUSH of "sync-flush-every-3k": zlib's blocks are dynamic at this interval
 
 
