@@ -5,7 +5,9 @@
 //
 //   bzip2_harness IN.bz2 OUT
 // writes the text to OUT and prints one line: "taken=1 blocks=B streams=S unaligned=U runend=R bytes=N" (U: blocks whose magic is not
-// byte-aligned, R: blocks whose last symbol is a run's count) or "taken=0 why=WORD [status=K]".
+// byte-aligned, R: blocks whose last symbol is a run's count) or "taken=0 why=WORD status=K".  WORD: chain (the table of magics does not
+// chain: status 0 = the walk over it says so, status 1 = a block decodes but does not end on the magic behind it, which is how a magic
+// too many inside a block's data shows), block (K = the decoder's status), walk (K likewise), block-crc, stream-crc.
 // Exit status 0 either way (a sanitizer report is what makes it non-zero).
 #include <stdint.h>
 #include <stdio.h>
@@ -70,7 +72,7 @@ int main(int argc, char **argv) {
         }
         if (h.end_bit != blocks[k].end_bit) {
             delete T, fclose(out);
-            return refuse("end");
+            return refuse("chain", 1);
         }
         unaligned += (blocks[k].bit & 7) != 0;
         bz2_prefix(T->hist);

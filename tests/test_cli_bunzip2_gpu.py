@@ -1,7 +1,9 @@
 """`merkurio extract` on .bz2 inputs whose blocks are decoded on the device (mk_bzip2_inflate_device; the windows are
 ranges of the text there) against `--host-codec` (libbz2 inflates the file at load): the kept records, the text log and the JSON log
 byte for byte.  The [timing] row must name the device path with the number of blocks that the host harness counts: without that row
-these tests would pass on a build that never leaves libbz2.  A damaged file is handed back to libbz2, which words the error."""
+these tests would pass on a build that never leaves libbz2.  A damaged file is handed back to libbz2, which words the error; so is a
+file that libbz2 takes and the device documents that it does not (a block magic inside a block's data), and the run ends as it does
+under --host-codec."""
 import bz2
 import os
 import subprocess
@@ -9,6 +11,7 @@ import subprocess
 import pytest
 
 import bzip2_cases as cases
+import bzip2_craft as craft
 from test_cli_gpu import BIN, json_stable, log_body
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +64,7 @@ def inputs(tmp_path_factory):
     return d, blocks
 
 
-def compare(inputs, tmp_path, names, extra=()):
+def compare(inputs, tmp_path, names, extra=(), device_takes=True):
     d, blocks = inputs
     run_dir = tmp_path / "runs"
     run_dir.mkdir()
@@ -95,6 +98,9 @@ def compare(inputs, tmp_path, names, extra=()):
             assert json_stable(d_dir / f)[:2] == json_stable(h_dir / f)[:2]
         else:
             assert a == b, f
+    if not device_takes:
+        assert "NOT taken by the device" in err and "bzip2 on the device: " not in err, err
+        return dev, err, d_dir
     rows = [ln for ln in err.split("\n") if "bzip2 on the device: " in ln]
     assert [ln.split("bzip2 on the device: ")[1].split(" blocks,")[0] for ln in rows] == [str(blocks[n]) for n in names], err
     assert all("block decode" in ln and "CRC" in ln for ln in rows), err
@@ -140,3 +146,21 @@ def test_a_flipped_data_bit_is_libbz2s_error(inputs, tmp_path):
     dev, err, o = compare(inputs, tmp_path, ["damaged.fastq.bz2"])
     assert dev.returncode != 0 and "Error while decompressing" in err
     assert "NOT taken by the device" in err and "bzip2 on the device: " not in err
+
+
+def test_a_block_magic_in_a_blocks_data_is_libbz2s_file_end_to_end(inputs, tmp_path):
+    """a file libbz2 takes and the device hands back: a libbz2 stream that ends inside the last record's quality line, a hand-made
+    stream whose symbols spell the block magic (its 14 bytes of text are quality values), and a libbz2 stream with the line's end"""
+    d, _ = inputs
+    name = "host-block-magic-in-the-symbols-nibble-aligned"
+    crafted, tail = craft.CASES[name][0], craft.text_of(name)
+    assert len(tail) == 14 and len(craft.find_magics(crafted)) == 3 and set(tail) <= set(range(65, 79))
+    head = cases.fastq(400, seed=13) + b"@last lane=1\n" + b"ACGTAC" * 25 + b"\n+\n" + b"F" * 136
+    blob = bz2.compress(head, 1) + crafted + bz2.compress(b"\n", 9)
+    text = head + tail + b"\n"
+    assert cases.libbz2_says(blob) == craft.libbz2_says(blob) == text and text.count(b"\n") == 4 * 401
+    (d / "magic.fastq.bz2").write_bytes(blob)
+    dev, err, o = compare(inputs, tmp_path, ["magic.fastq.bz2"], device_takes=False)
+    assert dev.returncode == 0
+    kept = (o / "out.fastq").read_bytes()
+    assert kept.endswith(b"F" * 136 + tail + b"\n") and 10 < kept.count(b"\n") // 4 < 401  # the last record holds the pattern
