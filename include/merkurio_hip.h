@@ -888,7 +888,7 @@ int mk_tag_sam_window(mk_matcher *m, mk_sam_window *w, int logging, mk_counters 
  * its lines, the scan, the keep rule, the tag's value, rows, names, counters, tail and n_used are mk_tag_sam_window's; what leaves is
  * mk_tag_bam_window's: every kept record as  block_size | BAM record,  back to back in record order (out_text_bytes of them),
  * deflated into BGZF members of block_bytes of text (0 = 65280) in out[0, out_len).  The members inflate to exactly the bytes the
- * CLI's host path writes for these records: it appends TAB tag ":Z:" value to the line and encodes the line (cli/io.cpp:
+ * CLI's host path writes for these records: it appends TAB tag ":Z:" value to the line and encodes the line (cli/bam_out.cpp:
  * BamWriter::encode_record), which is the definition.  Restated:
  *   refID / next_refID: the index of RNAME / RNEXT among the n_refs reference names ref_names[ref_off[i], ref_off[i + 1]) (the @SQ
  *     lines' SN, in the order of the BAM header; of equal names the first), -1 for "*" or a name not among them; RNEXT "=" = refID.
@@ -950,7 +950,7 @@ int mk_tag_sam_bam_window(mk_matcher *m, mk_codec *codec, mk_sam_bam_window *w, 
  * the window, its members, head and tail, on_tail, the record index, the scan, the keep rule, the tag's value, rows, names and counters
  * are mk_tag_bam_window's; what leaves is mk_tag_sam_window's: every kept record as  line TAB tag ":Z:" value "\n",  back to back in
  * record order in out[0, out_len) -- only these lines are downloaded.  The line is what the CLI's host path writes for the record
- * (cli/io.cpp: SamFile::append_line), which is the definition.  Restated, tab-separated:
+ * (cli/sam_in.cpp: SamFile::append_line), which is the definition.  Restated, tab-separated:
  *   QNAME: read_name without its NUL;  FLAG, MAPQ: decimal;
  *   RNAME: reference name refID -- ref_names[ref_off[i], ref_off[i + 1]), the names of the BAM header in its order -- when
  *     0 <= refID < n_refs, else "*";  RNEXT: "*" when next_refID < 0, "=" when it equals refID, its name when it is < n_refs, else "*";

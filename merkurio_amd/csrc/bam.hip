@@ -14,7 +14,7 @@
 // and the guesses are PROVED by the host from two small arrays: piece 0 starts at a record start by contract, and if
 // every walk lands exactly on the next piece's start, every start is one (induction) and the table is the serial
 // walk's.  A start that is not met is replaced by the landing and the walks run again (a false guess costs a round; no
-// guess survives the check).  The walk applies the checks of the CLI's serial parser (cli/io.cpp:
+// guess survives the check).  The walk applies the checks of the CLI's serial parser (cli/sam_in.cpp:
 // parse_bam_records_serial); a record that fails them raises a status bit and the caller's host reader takes over, which
 // also words the error.
 #include <algorithm>
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void mk_bam_emit_kernel(const uint8_t *__restr
 }
 
 // ---- BAM record -> SAM line (mk_tag_bam_sam_window; the mirror of sam.hip's SAM -> BAM half): the bytes SamFile::append_line
-// (cli/io.cpp: bam_record_to_sam + aux_to_text) writes for the record, then TAB tag ":Z:" value "\n".  One walk, bam_sam_line<kWrite>,
+// (cli/bam_text.cpp: bam_record_to_sam + aux_to_text) writes for the record, then TAB tag ":Z:" value "\n".  One walk, bam_sam_line<kWrite>,
 // sizes a line (mk_bam_sam_len_kernel) and writes everything of it that is not SEQ / QUAL (mk_bam_sam_fields_kernel): the same code
 // advances the same position in both, so the sizes of the first are the bytes of the second.  The walk is serial and short -- a few
 // dozen bytes per record -- so it is one lane per record; SEQ and QUAL, three quarters of a line, are 16 lanes per record

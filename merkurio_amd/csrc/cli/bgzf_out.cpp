@@ -45,16 +45,9 @@ void RecordGzip::window_done(bool force) {
         const size_t blocks = (size_t)n_cuts - 1;
         std::vector<std::vector<uint8_t>> outs(blocks);
         const size_t T = std::max<size_t>(1, std::min<size_t>(io_threads(), blocks));
-        std::vector<std::string> errs(T);
         run_threads(T, [&](size_t t) {
-            try {
-                for (size_t i = t; i < blocks; i += T) bgzf_compress((const uint8_t *)text_.data() + cut[i], (size_t)(cut[i + 1] - cut[i]), outs[i]);
-            } catch (const Error &e) {
-                errs[t] = e.what()[0] ? e.what() : "error";
-            }
+            for (size_t i = t; i < blocks; i += T) bgzf_compress((const uint8_t *)text_.data() + cut[i], (size_t)(cut[i + 1] - cut[i]), outs[i]);
         });
-        for (auto &e : errs)
-            if (!e.empty()) bail(e);
         deflate_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         members += blocks;
         for (auto &o : outs)

@@ -271,20 +271,11 @@ struct WindowExtract::Impl {
             return;
         }
         if (I.bgzf_dev) {
-            const WindowSource &ws = I.s.source();
-            const size_t nm = ws.n_bgzf_members();
-            uint64_t text = 0;
-            size_t g = I.next_member;
-            while (g < nm && (text < target || g == I.next_member)) {
-                mk_bgzf_member e{};
-                ws.bgzf_member_at(g, &e.data_off, &e.data_len, &e.isize, &e.crc);
-                e.out_off = text;
-                text += e.isize;
-                S.grp.push_back(e);
-                ++g;
-            }
+            const std::vector<mk_bgzf_member> &mem = I.s.source().bgzf_members();
+            const size_t g0 = I.next_member, g = bgzf_run_end(mem, g0, mem.size(), target);
+            if (g > g0) S.grp = bgzf_rebased(mem.data() + g0, g - g0, 0, mem[g0].out_off);  // (data_off stays absolute in the file)
             I.next_member = g;
-            I.exhausted = g >= nm;
+            I.exhausted = g >= mem.size();
             S.ends = I.exhausted;
             return;
         }
@@ -935,11 +926,10 @@ WindowExtract::~WindowExtract() {
 
 // the first byte of a bgzip'ed text that is not a line end: zlib on its first members, here
 static int first_text_byte_of_bgzf(const WindowSource &ws, const std::string &path) {
-    for (size_t g = 0; g < ws.n_bgzf_members() && g < 64; ++g) {
-        mk_bgzf_member e{};
-        ws.bgzf_member_at(g, &e.data_off, &e.data_len, &e.isize, &e.crc);
-        e.out_off = 0;
-        if (!e.isize) continue;
+    const std::vector<mk_bgzf_member> &mem = ws.bgzf_members();
+    for (size_t g = 0; g < mem.size() && g < 64; ++g) {
+        if (!mem[g].isize) continue;
+        const mk_bgzf_member e = bgzf_rebased(&mem[g], 1, 0, mem[g].out_off)[0];
         std::vector<char> out(e.isize);
         inflate_bgzf_members_host(ws.file_bytes(), &e, 1, out.data(), path);
         for (char ch : out)

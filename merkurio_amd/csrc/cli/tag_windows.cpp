@@ -246,24 +246,17 @@ struct MemberInput {
         uint64_t n_pending = 0;
         const char *pend = sam.bam_pending(&n_pending);
         pipe.head.assign(pend, pend + n_pending);
-        const size_t n_mem = src.n_bgzf_members();
+        const std::vector<mk_bgzf_member> &mem = src.bgzf_members();
+        const size_t n_mem = mem.size();
         Windows wins;
         for (size_t m0 = src.next_member(); m0 < n_mem;) {
             WindowMembers W;
-            W.m0 = m0;
-            size_t m1 = m0;
-            while (m1 < n_mem && (W.text < window_bytes || m1 == m0)) {
-                uint64_t off;
-                uint32_t len, isize, crc;
-                src.bgzf_member_at(m1, &off, &len, &isize, &crc);
-                if (m1 == m0) W.file_lo = off;
-                W.file_hi = off + len;
-                W.mem.push_back(mk_bgzf_member{off - W.file_lo, W.text, len, isize, crc, 0});
-                W.text += isize;
-                ++m1;
-            }
-            W.m1 = m1;
-            m0 = m1;
+            W.m0 = m0, W.m1 = bgzf_run_end(mem, m0, n_mem, window_bytes);
+            const mk_bgzf_member &last = mem[W.m1 - 1];
+            W.file_lo = mem[m0].data_off, W.file_hi = last.data_off + last.data_len;
+            W.text = last.out_off + last.isize - mem[m0].out_off;
+            W.mem = bgzf_rebased(mem.data() + m0, W.m1 - m0, W.file_lo, mem[m0].out_off);
+            m0 = W.m1;
             wins.push_back(std::move(W));
         }
         if (wins.empty() && !pipe.head.empty()) {

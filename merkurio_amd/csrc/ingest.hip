@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void mk_ingest_select_kernel(const uint8_t *__
 }
 
 // ---- the WRITTEN form of the kept records (mk_extract_window_members; the rule: include/merkurio_hip.h) ------------------------
-// The writer does not emit a kept record's stored bytes, it re-emits its lines (cli/io.cpp: FastxFile::write): every line ends the
+// The writer does not emit a kept record's stored bytes, it re-emits its lines (cli/fastx.cpp: FastxFile::write): every line ends the
 // way the header line does, a FASTQ '+' line loses a repeated id, a last record without a line end gains one.  These two kernels
 // make that form on the device, so that the packed text can be cut and deflated where it lies.
 //   FASTQ, from the line table l0 .. l3 and the sequence length of mk_ingest_records_kernel:
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void mk_ingest_written_gather_kernel(const uin
 }
 
 // ---- FASTA (r05): '>' header lines, every other line is sequence; record.seq() is the sequence lines without their '\n' and '\r'
-// bytes (needletail strips both; cli/io.cpp: FastxFile::append_seq).  On the device that is a byte compaction of the window's text:
+// bytes (needletail strips both; cli/fastx.cpp: FastxFile::append_seq).  On the device that is a byte compaction of the window's text:
 // a byte is kept iff it lies in a sequence line and is neither '\n' nor '\r'.  Two passes over the text, a thread per 64 bytes:
 // count (kept bytes, header lines) per thread -> per block -> exclusive scan; then the same walk writes the kept bytes to their
 // place in the scan buffer and, at every header line, the record's text offset and sequence offset.  The state "my first byte lies

@@ -1,7 +1,7 @@
 // sam.hip -- a window of SAM text on the device: its lines become a record table, the SEQ fields become the text the matcher scans,
 // and the kept lines leave with their `km` field appended -- what the reference's reader thread, record loop and text writer do
 // one record at a time (src/cmd_tag.rs:559-612 `for record in reader`, :387-497 process_record) and what the CLI's host path does
-// on its threads (cli/io.cpp: parse_sam_text, SamFile::gather, SamFile::find_tag), which is the definition these kernels follow.
+// on its threads (cli/sam_in.cpp: parse_sam_text, SamFile::gather, SamFile::find_tag), which is the definition these kernels follow.
 //
 // The line table is ingest.hip's (one u32 per line start).  The text is then read three times -- fields, SEQ gather, emit -- and
 // nothing else is large, so each pass gives a line to 16 lanes that take 16 (gather: 8) consecutive bytes each per step: a line
@@ -138,7 +138,7 @@ __device__ __forceinline__ unsigned long long sam_upper8(unsigned long long v) {
     return v ^ (lower >> 2);
 }
 
-// SEQ of record i -> seq[fixed_len ? i * fixed_len : off[i]] as the matcher sees it (cli/io.cpp: SamFile::gather); 16 lanes per record,
+// SEQ of record i -> seq[fixed_len ? i * fixed_len : off[i]] as the matcher sees it (cli/sam_in.cpp: SamFile::gather); 16 lanes per record,
 // eight bytes per lane and step
 __global__ __launch_bounds__(256) void mk_sam_gather_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ seq_start,
                                                            const uint32_t *__restrict__ seq_len, const unsigned long long *__restrict__ off, uint32_t fixed_len,
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void mk_sam_name_ends_kernel(const uint32_t *_
 // Per record: keep or drop (src/cmd_tag.rs:457-467), and for a kept one the size of the line it leaves as -- line + TAB + tag + ":Z:"
 // + value + '\n', the value being its distinct matched patterns joined by ',' (:484-490), merged with the record's existing value of
 // that name if it has one (:470-485).  The optional fields of a kept record (fields 12 ...) are searched for the FIRST field of at
-// least five bytes that starts with the tag and ':' (cli/io.cpp: SamFile::find_tag): 16 lanes look at the tabs of 16 bytes each, a
+// least five bytes that starts with the tag and ':' (cli/sam_in.cpp: SamFile::find_tag): 16 lanes look at the tabs of 16 bytes each, a
 // field starts behind every tab.  A field of that name that is not "Z:" (the reference refuses it) or whose value is not plain ASCII
 // or very long sets status bit 4 -- the caller's host path then does this window.  ex_off[i] = where the value starts, 0 = none.
 __global__ __launch_bounds__(256) void mk_sam_taglen_kernel(const uint8_t *__restrict__ text, SamTables R, const unsigned long long *__restrict__ found_off,
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void mk_sam_emit_kernel(const uint8_t *__restr
 }
 
 // ---- SAM line -> BAM record (mk_tag_sam_bam_window): what the CLI's host path does with a kept line -- line TAB tag ":Z:" value handed
-// to BamWriter::encode_record (cli/io.cpp), which is the definition: the same bytes, or the window is refused (st[0] |= 1: a kept line
+// to BamWriter::encode_record (cli/bam_out.cpp), which is the definition: the same bytes, or the window is refused (st[0] |= 1: a kept line
 // with fewer than 11 fields; |= 2: a field that does not encode -- include/merkurio_hip.h lists them) and the host path does it.
 // Two passes over the kept lines.  SEQ and QUAL, three quarters of a record, go across 16 lanes per line as above: 16 bases become 8
 // bytes of nibbles, 16 quality bytes less 33 stay 16 bytes (mk_sam_bam_seq_kernel).  The short fields in front of SEQ, the CIGAR and the

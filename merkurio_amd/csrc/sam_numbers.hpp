@@ -2,7 +2,7 @@
 // Compiled by hipcc for the kernels and by g++ for the CPU harness that checks it against strtoll / strtof
 // (tests/helpers/sam_numbers_harness.cpp), the way codec/inflate_serial.hpp is.
 //
-// The host path's field_int / field_float (cli/io.cpp) are strtoll-like and strtof: they take junk and wrap on overflow.  These do
+// The host path's field_int / field_float (cli/bam_out.cpp) are strtoll-like and strtof: they take junk and wrap on overflow.  These do
 // not imitate that: each converts ONE plain spelling and says "not converted" for everything else -- the window is then the host's.
 //   sam_int        [+-] 1-18 digits, nothing else                      -> the value (fits a signed 64-bit integer: 10^18 < 2^63)
 //   sam_cigar_len  1-9 digits                                          -> the value (999 999 999 < 2^32: no wrap to imitate)

@@ -1,4 +1,4 @@
-// test harness: SAM text -> BAM through the CLI's BamWriter (merkurio_amd/csrc/cli/io.cpp) WITHOUT a device: records are
+// test harness: SAM text -> BAM through the CLI's BamWriter (merkurio_amd/csrc/cli/bam_out.cpp) WITHOUT a device: records are
 // encoded (BamWriter::encode_record), handed over in pieces of <piece> records (put_encoded: moved, never copied together),
 // cut into BGZF members by the writer's queue + writer thread and deflated by zlib on the host threads (the --host-codec
 // path; the device path shares everything but the deflate call).

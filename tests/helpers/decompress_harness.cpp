@@ -19,5 +19,5 @@ int main(int argc, char **argv) {
         } catch (const Error &e) { printf("%s: error %s\n", argv[i], e.what()); }
     }
 }
-// the harness links decompress.cpp alone: the memory check lives in io.cpp
+// the harness links decompress.cpp alone: the memory check lives in host_mem.cpp
 namespace cli { void require_host_memory(uint64_t, const std::string &) {} }

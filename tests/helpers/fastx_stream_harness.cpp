@@ -1,5 +1,5 @@
 // test harness: reads a FASTA/FASTQ file through the CLI's windowed reader (FastxStream,
-// merkurio_amd/csrc/cli/io.cpp) and prints one line per record -- id, sequence (line breaks squeezed
+// merkurio_amd/csrc/cli/fastx.cpp) and prints one line per record -- id, sequence (line breaks squeezed
 // out), quality -- plus the number of windows; tests/test_cli_cpu.py compares with a Python parse.
 // usage: harness <file> <window bytes> [consume at most N records per window (0 = all)] [digest | raw]
 // digest: one line per record with id, sequence length and FNV-1a hash instead of the text

@@ -1,5 +1,5 @@
 // test harness: reads a SAM / BAM file through the CLI's windowed reader (SamFile::open / fill,
-// merkurio_amd/csrc/cli/io.cpp) and prints the header, then one line per record: name, the sequence as
+// merkurio_amd/csrc/cli/sam_in.cpp) and prints the header, then one line per record: name, the sequence as
 // the matcher sees it, the value of an existing km tag, the record as SAM text.
 // usage: harness <file> <window bytes> [prefetch]   (prefetch: the next window is read by SamFile::prefetch on a second thread
 //        while the current one is printed, as `merkurio tag` does)

@@ -1,6 +1,6 @@
 """mk_tag_bam_sam_window without a GPU: the entry point is declared, listed, exported and refuses a NULL window; the ctypes struct
 follows the header; and the number formatting the kernels use (merkurio_amd/csrc/bam_numbers.hpp), compiled for the host, gives
-std::to_string's and snprintf("%g")'s bytes -- the host path's own calls (cli/io.cpp: aux_to_text) -- for every value it takes, and
+std::to_string's and snprintf("%g")'s bytes -- the host path's own calls (cli/bam_text.cpp: aux_to_text) -- for every value it takes, and
 refuses exactly the floats "%g" writes in exponent notation (and inf / nan).
 
 The float check is EXHAUSTIVE: every positive float of the 34 binades the rule can take and of two more on each side (3.2e8 values, on

@@ -3,8 +3,12 @@
 log-flag conflict check (src/helpers.rs:172-200) and path helpers.  Runs without a GPU."""
 import os
 import subprocess
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cli_sources import reader_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "merkurio_amd", "lib", "merkurio")
@@ -140,8 +144,7 @@ def test_windowed_fastx_reader(tmp_path):
     cli_dir = os.path.join(ROOT, "merkurio_amd/csrc/cli")
     exe = str(tmp_path / "fs")
     subprocess.run(["g++", "-std=c++17", *_HARNESS_FLAGS, "-w", "-I", cli_dir, "-o", exe, os.path.join(ROOT, "tests/helpers/fastx_stream_harness.cpp"),
-                    os.path.join(cli_dir, "io.cpp"), os.path.join(cli_dir, "decompress.cpp"), os.path.join(cli_dir, "util.cpp"),
-                    "-lz", "-ldl", "-lpthread"], check=True)
+                    *reader_sources()], check=True)
 
     def bgzf(data, block=0xff00):
         out = bytearray()
@@ -197,8 +200,7 @@ def test_fasta_records_longer_than_a_parse_piece(tmp_path):
     cli_dir = os.path.join(ROOT, "merkurio_amd/csrc/cli")
     exe = str(tmp_path / "fs")
     subprocess.run(["g++", "-std=c++17", "-O1", "-w", "-I", cli_dir, "-o", exe, os.path.join(ROOT, "tests/helpers/fastx_stream_harness.cpp"),
-                    os.path.join(cli_dir, "io.cpp"), os.path.join(cli_dir, "decompress.cpp"), os.path.join(cli_dir, "util.cpp"),
-                    "-lz", "-ldl", "-lpthread"], check=True)
+                    *reader_sources()], check=True)
     g = np.random.default_rng(4)
     lens = [36 << 20, 100, 40 << 20, 33 << 20, 7]
     seqs = [np.frombuffer(b"ACGT", dtype=np.uint8)[g.integers(0, 4, n)] for n in lens]
@@ -238,8 +240,7 @@ def test_windowed_sam_bam_reader(tmp_path, golden):
     cli_dir = os.path.join(ROOT, "merkurio_amd/csrc/cli")
     exe = str(tmp_path / "ss")
     subprocess.run(["g++", "-std=c++17", *_HARNESS_FLAGS, "-w", "-I", cli_dir, "-o", exe, os.path.join(ROOT, "tests/helpers/sam_stream_harness.cpp"),
-                    os.path.join(cli_dir, "io.cpp"), os.path.join(cli_dir, "decompress.cpp"), os.path.join(cli_dir, "util.cpp"),
-                    "-lz", "-ldl", "-lpthread"], check=True)
+                    *reader_sources()], check=True)
     rnd = random.Random(9)
     n = 8000
     seqs = ["".join(rnd.choice("ACGTacgtN") for _ in range(rnd.choice((1, 36, 100, 151)))) for _ in range(n)]
@@ -333,7 +334,7 @@ def test_bam_writer_pieces_queue_encoder_and_members(tmp_path):
     import random
     import struct
     cli_dir = os.path.join(ROOT, "merkurio_amd/csrc/cli")
-    common = [os.path.join(cli_dir, "io.cpp"), os.path.join(cli_dir, "decompress.cpp"), os.path.join(cli_dir, "util.cpp"), "-lz", "-ldl", "-lpthread"]
+    common = reader_sources()
     wexe, rexe = str(tmp_path / "bw"), str(tmp_path / "ss")
     subprocess.run(["g++", "-std=c++17", *_HARNESS_FLAGS, "-w", "-I", cli_dir, "-o", wexe, os.path.join(ROOT, "tests/helpers/bam_writer_harness.cpp"), *common], check=True)
     subprocess.run(["g++", "-std=c++17", *_HARNESS_FLAGS, "-w", "-I", cli_dir, "-o", rexe, os.path.join(ROOT, "tests/helpers/sam_stream_harness.cpp"), *common], check=True)

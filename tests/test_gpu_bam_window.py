@@ -415,7 +415,7 @@ def test_fuzz_windows_against_the_oracle(mk, seed):
 
 
 def _serial_walk(text, last):
-    """the CLI's serial parser (cli/io.cpp: parse_bam_records_serial) in Python: -> (records, bytes used) or None where it bails"""
+    """the CLI's serial parser (cli/sam_in.cpp: parse_bam_records_serial) in Python: -> (records, bytes used) or None where it bails"""
     recs, p, n = [], 0, len(text)
     while p < n:
         if n - p < 4:

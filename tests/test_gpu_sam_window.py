@@ -1,5 +1,5 @@
 """`tag` on windows of SAM text that stay on the device (mk_tag_sam_window, an addition to ABI v7; kernels: sam.hip) against the
-oracle's restatement of process_record (src/cmd_tag.rs:387-497) and the line rule of the CLI's host path (cli/io.cpp: parse_sam_text,
+oracle's restatement of process_record (src/cmd_tag.rs:387-497) and the line rule of the CLI's host path (cli/sam_in.cpp: parse_sam_text,
 SamFile::gather, SamFile::find_tag): lines split at '\\n' with one '\\r' stripped, '@' and empty lines skipped, SEQ = field 10
 upper-cased for the matcher, a kept line leaves as line TAB tag ":Z:" value '\\n'.  Expected bytes are built here from the oracle's
 answers; the inputs are valid, so no test but test_refusals accepts a refused window."""

@@ -77,7 +77,7 @@ def _fasta(recs, width, eol=b"\n", final_eol=True):
 
 
 def _parse_fasta(text):
-    """what needletail makes of it (cli/io.cpp restates the same): record starts, ids, sequences without '\\n' / '\\r'"""
+    """what needletail makes of it (cli/fastx.cpp restates the same): record starts, ids, sequences without '\\n' / '\\r'"""
     starts, ids, seqs = [], [], []
     pos = 0
     for line in text.split(b"\n"):

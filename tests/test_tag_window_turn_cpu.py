@@ -13,6 +13,7 @@ import sys
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cli_sources import reader_sources
 from tag_windows import EOF, NIB, _bgzf, bam_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,8 +29,7 @@ def job(tmp_path_factory):
     cli_dir = os.path.join(ROOT, "merkurio_amd/csrc/cli")
     exe = str(d / "tag_turn_harness")
     subprocess.run(["g++", "-std=c++17", *_FLAGS, "-w", "-I", cli_dir, "-o", exe, os.path.join(ROOT, "tests/helpers/tag_turn_harness.cpp"),
-                    os.path.join(cli_dir, "tag_host.cpp"), os.path.join(cli_dir, "io.cpp"), os.path.join(cli_dir, "decompress.cpp"),
-                    os.path.join(cli_dir, "util.cpp"), "-lz", "-ldl", "-lpthread"], check=True)
+                    os.path.join(cli_dir, "tag_host.cpp"), *reader_sources()], check=True)
     rnd = random.Random(11)
     lines, recs = [], bytearray()
     for i in range(N):
