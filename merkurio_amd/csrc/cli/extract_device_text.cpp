@@ -1,0 +1,192 @@
+// extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
+// inflated in one piece or member by member, or of a bzip2 file (windows are ranges of it), and a gzip file inflated window by window
+// (mk_gzip_stream_*), which may hand the file back to zlib mid-way.  Owns the step that tries the device for an input and the
+// "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
+#include <hip/hip_runtime_api.h>
+
+#include "extract_sources.hpp"
+
+namespace cli {
+namespace xw {
+
+uint64_t device_free_bytes(int device) {
+    size_t free_b = 0, total_b = 0;
+    return hipSetDevice(device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : 0;
+}
+
+namespace {
+
+struct DeviceText : Source {
+    mk_codec *codec;
+    const uint8_t *text = nullptr;  // (of a stream: the latest window's)
+    uint64_t bytes = 0, at = 0;     // windows are text[at, ...) in turn
+    explicit DeviceText(mk_codec *c) : codec(c) {}
+    // (codec handles, like the page-locked buffers, are not released at the end of the run: that costs more than the process has left to live)
+    ~DeviceText() override {
+        if (!g_process_is_ending) mk_codec_destroy(codec);
+    }
+    bool on_device() const override { return true; }
+    bool ended() const override { return at >= bytes; }
+    void cut(Side &S, uint64_t target) {
+        const uint64_t n = std::min<uint64_t>(target, bytes - at);
+        S.dev_body = text + at, S.n_dev_body = n, S.dev_off = at;
+        at += n;
+    }
+    void next(uint64_t, Side &S, uint64_t target, mk_matcher *) override {
+        if (ended()) return;
+        cut(S, target);
+        S.ends = ended();
+    }
+    void body_to_host(const Side &S, char *dst) const override {
+        mk_check(mk_gzip_text_read(codec, S.dev_off, (uint8_t *)dst, S.n_dev_body), "Error reading the inflated text back");
+    }
+};
+
+// Window w of the stream lies in text buffer w & 1
+struct GzipStream : DeviceText {
+    InputFile &f;
+    const int i;
+    Gate &g;
+    uint64_t windows = 0;                 // windows the stream has produced
+    uint64_t last_k[2] = {~0ull, ~0ull};  // the last text window whose body lies in either buffer
+    uint64_t delivered = 0;               // text bytes of all its windows
+    enum { RUNNING, ENDED, HANDED_BACK } state = RUNNING;  // HANDED_BACK (the stream's state 2): zlib takes the file from the chain's tail on
+    const double t0;
+    GzipStream(mk_codec *c, InputFile &f_, int i_, Gate &g_, double t0_) : DeviceText(c), f(f_), i(i_), g(g_), t0(t0_) {}
+    bool ended() const override { return state == ENDED; }
+
+    // the next window of the stream; false: there is none -- the file has ended, or the stream has handed it back (what does not add
+    // up, no room, any error of the device -- the codec rule).  Window w + 2 takes the text buffer of window w: not before every text
+    // window over w has left its device loop
+    bool next_window(uint64_t k) {
+        for (;;) {
+            const uint64_t last = last_k[windows & 1];
+            if (last != ~0ull) {
+                std::unique_lock<std::mutex> lk(g.mu);
+                g.cv.wait(lk, [&] { return g.failed || g.n_done > last; });
+                if (g.failed) return false;
+            }
+            const double t_win = PhaseTimer::now();
+            uint64_t text_bytes = 0;
+            uint32_t st_now = 2;
+            if (mk_gzip_stream_next(codec, &text_bytes, &st_now) != MK_OK) st_now = 2;
+            mk_gzip_stream_stats st;
+            memset(&st, 0, sizeof(st));
+            (void)mk_gzip_stream_info(codec, &st);
+            if (st_now == 0) {
+                if (g.timing)
+                    fprintf(stderr, "[timing]   gzip input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu)\n",
+                            i, (unsigned long long)windows, (unsigned long long)text_bytes, (unsigned long long)st.consumed_bytes,
+                            (PhaseTimer::now() - t_win) * 1e3, (unsigned long long)k);
+                ++windows;
+                delivered += text_bytes;
+                text = (const uint8_t *)mk_gzip_text_device(codec, &bytes);
+                at = 0;
+                if (bytes != text_bytes) st_now = 2;
+                else if (text_bytes) return true;
+                else continue;  // (a window of empty members)
+            }
+            if (g.timing)
+                fprintf(stderr, "[timing]   gzip input %d on the device, window by window: %llu windows, %llu members proved, %llu grown, %llu rounds repeated, handed back at %s, %.3f s (upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes)\n",
+                        i, (unsigned long long)st.windows, (unsigned long long)st.members, (unsigned long long)st.windows_grown,
+                        (unsigned long long)st.rounds_repeated, st_now == 1 ? "-" : std::to_string(delivered).append(" text bytes (zlib reads on)").c_str(),
+                        PhaseTimer::now() - t0, st.ms[0], st.ms[1], st.ms[2], st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
+            bytes = at = 0;
+            state = st_now == 1 ? ENDED : HANDED_BACK;
+            return false;
+        }
+    }
+
+    void next(uint64_t k, Side &S, uint64_t target, mk_matcher *) override {
+        if (state != RUNNING) return;
+        if (at >= bytes && !next_window(k)) return;  // (its end, or handed back)
+        cut(S, target);
+        // (that the text ends here is known only when the stream says so: the last window is then the chain's tail alone)
+        last_k[(windows - 1) & 1] = k;
+        S.ends = false;
+    }
+    // (mk_gzip_text_read refers to the stream's latest window, which S's may no longer be)
+    void body_to_host(const Side &S, char *dst) const override {
+        if (hipMemcpy(dst, S.dev_body, S.n_dev_body, hipMemcpyDeviceToHost) != hipSuccess) bail("Error reading the inflated text back");
+    }
+    // every text window over the stream's text is through: zlib reads the file from the front, drops what the windows have used -- all
+    // that was delivered but the chain's tail S.head, which starts at a record start -- and is this input's reader from here on
+    std::unique_ptr<Source> hand_back(Side &S) override {
+        if (state != HANDED_BACK) return nullptr;
+        const uint64_t used = delivered - std::min<uint64_t>(delivered, S.head.size());
+        S.head.clear();
+        (void)mk_gzip_stream_end(codec);
+        if (used) {
+            f.have_first = false;
+            if (!f.s.raw_skip(used)) bail("Error while decompressing " + f.path);
+        }
+        return host_text_source(f, i, g);
+    }
+};
+
+}  // namespace
+
+std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t gzip_window, Gate &g) {
+    const bool bz = f.s.raw_is_bzip2();
+    if (!bz && !f.s.raw_is_gzip()) return nullptr;
+    const uint8_t *z = f.s.source().file_bytes();
+    const uint64_t n = f.s.source().file_size();
+    double t0 = PhaseTimer::now();
+    mk_codec *codec = nullptr;
+    uint64_t text_bytes = 0;
+    uint32_t taken = 0;
+    // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
+    if (bz) {
+        // its blocks are decoded on the device, a wave each.  What the call does not take -- anything it refuses, a damaged file, no room
+        // -- libbz2 reads whole, as under --host-codec, and words the error
+        uint64_t blocks = 0;
+        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        if (codec && mk_bzip2_inflate_device(codec, z, n, &text_bytes, &taken, &blocks) != MK_OK) taken = 0;
+        if (g.timing && taken) {
+            float ms5[5] = {0, 0, 0, 0, 0};
+            (void)mk_bzip2_info(codec, nullptr, ms5);
+            fprintf(stderr, "[timing]   bzip2 on the device: %llu blocks, upload %.1f, marker search %.1f, block decode %.1f, text %.1f, CRC %.1f ms (input %d: %llu text bytes, %.3f s)\n",
+                    (unsigned long long)blocks, ms5[0], ms5[1], ms5[2], ms5[3], ms5[4], i, (unsigned long long)text_bytes, PhaseTimer::now() - t0);
+        } else if (g.timing) {
+            fprintf(stderr, "[timing]   bzip2 input %d: NOT taken by the device after %.3f s (libbz2 reads it)\n", i, PhaseTimer::now() - t0);
+        }
+    } else if (n > gzip_window) {
+        // more than one gzip window: inflated window by window as the text windows reach it; what the stream does not take, from
+        // whichever window on, is zlib's
+        mk_check(mk_codec_create(device, &codec), "Error setting up the gzip codec");
+        t0 = PhaseTimer::now();
+        if (mk_gzip_stream_begin(codec, z, n, gzip_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new GzipStream(codec, f, i, g, t0));
+        if (g.timing) fprintf(stderr, "[timing]   gzip input %d on the device, window by window: NOT taken (zlib reads it)\n", i);
+    } else {
+        // ONE DEFLATE stream, which zlib walks from the front at 0.5 GB/s -- the device inflates it in parallel pieces and keeps the
+        // text; a file of several members (`cat a.gz b.gz`) goes to mk_gzip_members_inflate_device, which cuts all of them into pieces
+        // at once.  What neither takes (no findable block starts, a stream the buffers do not hold, bytes behind the last member, a
+        // damaged file) stays with the zlib reader, which also words the errors
+        mk_check(mk_codec_create(device, &codec), "Error setting up the gzip codec");
+        t0 = PhaseTimer::now();
+        mk_check(mk_gzip_inflate_device(codec, z, n, &text_bytes, &taken), "Error inflating the input");
+        uint64_t members = taken ? 1 : 0, guesses = 0;
+        if (!taken && mk_gzip_member_guesses(z, n, nullptr, 0, &guesses) == MK_OK && guesses > 1) {
+            if (mk_gzip_members_inflate_device(codec, z, n, &text_bytes, &taken, &members) != MK_OK) taken = 0;
+            if (!taken) members = 0;
+        }
+        if (g.timing) {
+            uint32_t seg = 0;
+            float ms5[5] = {0, 0, 0, 0, 0};
+            (void)mk_gzip_info(codec, &seg, ms5);
+            fprintf(stderr, "[timing]   gzip input %d on the device: %s, %llu members proved, %.3f s (%u pieces; upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms)\n", i,
+                    taken ? "taken" : "NOT taken (zlib reads it)", (unsigned long long)members, PhaseTimer::now() - t0, seg, ms5[0], ms5[1], ms5[2], ms5[3], ms5[4]);
+        }
+    }
+    if (!taken) {
+        if (codec) mk_codec_destroy(codec);
+        return nullptr;
+    }
+    std::unique_ptr<DeviceText> d(new DeviceText(codec));
+    d->text = (const uint8_t *)mk_gzip_text_device(codec, &d->bytes);
+    return d;
+}
+
+}  // namespace xw
+}  // namespace cli
