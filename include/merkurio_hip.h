@@ -696,12 +696,58 @@ int mk_gzip_info(const mk_codec *c, uint32_t *segments, float ms[5]);
  * block's symbols, nGroups outside 2..6, nSelectors 0 or above 18 002, a selector >= nGroups, a code length outside 1..20, a code
  * under which a symbol does not decode (libbz2's own test of a code), more symbols than level x 100 000, a block that ends inside a
  * run, data that ends early, a table of magics that does not chain, trailing bytes, a wrong CRC, text plus scratch beyond half of
- * the free device memory, any device error.  With a gzip stream open on the handle: MK_E_INVALID_ARG.
+ * the free device memory, any device error.  With a gzip or bzip2 stream open on the handle: MK_E_INVALID_ARG.  Everything here is
+ * sized by the file; a larger file: mk_bzip2_stream_*.
  * mk_bzip2_info: blocks of the last call and its phases in milliseconds: upload, marker search, block decode (symbols + vector),
  * text (walk + expansion), CRC. */
 int mk_bzip2_inflate_device(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
 int mk_bzip2_info(const mk_codec *c, uint32_t *blocks, float ms[5]);
 int mk_codec_set_bzip2_pass_blocks(mk_codec *c, uint64_t blocks);
+
+/* (v7) A .bz2 file of ANY size, decoded on the device window by window: nothing on the device is sized by the file.  The contract is
+ * mk_gzip_stream_*'s (below).  mk_bzip2_stream_begin: bz[0, n) = the whole file (the caller's -- the mapped file -- until _end);
+ * window_bytes = compressed bytes per window (0 = 256 MiB, an unmeasured choice: profiles/e2e_bunzip2_windows.txt).  *taken = 0: no
+ * "BZh1-9" at byte 0, no stream is open.  mk_bzip2_stream_next uploads the compressed bytes from the byte that holds the previous
+ * cut's bit up to window_bytes further on, searches them for the two magics, walks the hits into blocks and stream ends, decodes
+ * every block whose closing magic lies inside the upload (in passes, mk_codec_set_bzip2_pass_blocks applies), proves each (status
+ * 0, it ends exactly on the next magic), walks, expands and CRC-checks them.  The cut is the LAST magic of the window -- proved, not
+ * guessed --; the bytes behind it go up again with the next window.  An end-of-stream magic is consumed only when its 32 CRC bits,
+ * the padding to the byte and either the file's end or the next "BZh" + level + first magic lie inside the upload; otherwise it is
+ * the cut.  Blocks need nothing of each other: carried between windows are the next bit, whether a stream is open, its level, its
+ * CRC folded so far, and the totals.  A window with fewer than two magics (a block longer than the window) is doubled and tried again
+ * as long as the file has more bytes and the device the room (windows_grown).  Text is not bounded by compressed bytes (a block may
+ * expand to 46 MB): the text buffers are sized by the blocks' text lengths once those are known and grow within half of the free
+ * memory; a window whose text does not fit is delivered as SEVERAL text windows, each a prefix of whole blocks, at least one (the
+ * bytes in front of the run-length step stay on the device for the rest).  mk_codec_set_bzip2_text_cap bounds a text window's bytes
+ * (test hook; 0 = by the free memory; results do not depend on it).
+ * *state = 0: a window of text was produced, *text_bytes long (0 for a window of empty streams): it is what mk_gzip_text_device /
+ *             mk_gzip_text_read refer to, in one of two text buffers -- text window w stays valid until the call that produces w + 2;
+ *          1: end of file: every block CRC and every stream's folded CRC agree; no text in this call;
+ *          2: handed back (MK_OK): no text in this call and the stream produces nothing more -- a table that does not chain, a block
+ *             that does not end on its magic, a status of the decoder (mk_bzip2_inflate_device lists them), a wrong block or stream
+ *             CRC, bytes behind the last stream, data that ends early, more than 2^20 magics in a window, no room, any device error.
+ *             The whole blocks in front of the fault are delivered first (state 0), so the text delivered before state 2 is a prefix
+ *             of what libbz2 gives before it refuses: the caller's libbz2 reads the file from the front and skips stats.text_bytes.
+ * mk_bzip2_stream_end closes the stream and frees what it held (the two text buffers included).  mk_bzip2_stream_info takes the
+ * codec's lock and may be called beside mk_bzip2_stream_next; without an open stream: the last stream's figures.  While a bzip2
+ * stream is open the one-shot gzip and bzip2 calls and mk_gzip_stream_begin return MK_E_INVALID_ARG -- and mk_bzip2_stream_begin
+ * does while a gzip stream is --, and mk_gzip_text_release ends the stream as mk_bzip2_stream_end does. */
+typedef struct mk_bzip2_stream_stats {
+    uint64_t windows;           /* windows of text produced */
+    uint64_t streams;           /* streams closed: their folded CRC agrees */
+    uint64_t blocks;            /* blocks delivered: proved, their CRC agrees */
+    uint64_t consumed_bytes;    /* compressed bytes in front of the next window's first bit */
+    uint64_t text_bytes;        /* text bytes delivered so far */
+    uint64_t windows_grown;     /* doublings of a window that held no whole block */
+    uint64_t peak_device_bytes; /* most device memory the stream has held */
+    float ms[5];                /* summed over the windows: upload, marker search, block decode, text (walk + expansion), CRC */
+    uint32_t reserved;
+} mk_bzip2_stream_stats;
+int mk_bzip2_stream_begin(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t window_bytes, uint32_t *taken);
+int mk_bzip2_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state);
+int mk_bzip2_stream_info(const mk_codec *c, mk_bzip2_stream_stats *out);
+int mk_bzip2_stream_end(mk_codec *c);
+int mk_codec_set_bzip2_text_cap(mk_codec *c, uint64_t text_bytes);
 
 /* (v7) A gzip file of SEVERAL members -- `cat a.gz b.gz`, a member per tile or per block without BGZF's BC field.  A member carries no
  * compressed size: where it ends is known once it is decoded.  So the starts are guessed on the host and proved on the device.
@@ -748,7 +794,8 @@ int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, u
  * mk_gzip_stream_end closes the stream and frees what it held (the two text buffers included); the one-shot calls work as before.
  * mk_gzip_stream_info may be called from another thread beside mk_gzip_stream_next (it takes the codec's lock, so it waits for the
  * window in progress); without an open stream it is MK_OK with the last stream's figures, zeros if there was none.  While a stream is
- * open the one-shot calls (mk_gzip_inflate_device, mk_gzip_members_inflate_device) return MK_E_INVALID_ARG, and mk_gzip_text_release
+ * open the one-shot calls (mk_gzip_inflate_device, mk_gzip_members_inflate_device, mk_bzip2_inflate_device) and
+ * mk_bzip2_stream_begin return MK_E_INVALID_ARG, and mk_gzip_text_release
  * ends the stream as mk_gzip_stream_end does.  A window drops at most three false member starts (three drop rounds): a window with
  * four or more header look-alikes that are no member starts -- planted in a stored block, say -- is handed back (state 2).
  * mk_crc32_combine (host code, no device): the CRC-32 of A ++ B from crc_a = CRC-32(A), crc_b = CRC-32(B) and len_b = |B|. */

@@ -39,6 +39,7 @@ struct CommonArgs {
 constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
 
 constexpr uint64_t kGzipWindow = 256ull << 20;  // (an unmeasured choice: README, "Gunzip window by window")
+constexpr uint64_t kBzip2Window = 256ull << 20;  // (an unmeasured choice: README, "Bunzip2 window by window"; profiles/e2e_bunzip2_windows.txt)
 
 struct ExtractArgs : CommonArgs {
     std::string in_fastx;                   // -i / -1
@@ -51,6 +52,8 @@ struct ExtractArgs : CommonArgs {
     // --gzip-window: a plain gzip input of more compressed bytes than this is inflated on the device window by window (mk_gzip_stream_*),
     // a smaller one in one piece (mk_gzip_inflate_device / mk_gzip_members_inflate_device)
     uint64_t gzip_window = kGzipWindow;
+    // --bzip2-window: likewise for a .bz2 input (mk_bzip2_stream_*; a smaller one: mk_bzip2_inflate_device)
+    uint64_t bzip2_window = kBzip2Window;
 };
 
 struct TagArgs : CommonArgs {

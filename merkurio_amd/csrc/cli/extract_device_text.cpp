@@ -1,6 +1,6 @@
 // extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
-// inflated in one piece or member by member, or of a bzip2 file (windows are ranges of it), and a gzip file inflated window by window
-// (mk_gzip_stream_*), which may hand the file back to zlib mid-way.  Owns the step that tries the device for an input and the
+// inflated in one piece or member by member, or of a bzip2 file (windows are ranges of it), and a gzip or bzip2 file decoded window by
+// window (mk_gzip_stream_*, mk_bzip2_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
 // "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
 #include <hip/hip_runtime_api.h>
 
@@ -42,17 +42,55 @@ struct DeviceText : Source {
     }
 };
 
-// Window w of the stream lies in text buffer w & 1
-struct GzipStream : DeviceText {
+// What differs between the two formats the device decodes window by window: the library calls, and the wording of the [timing] rows
+struct StreamCalls {
+    const char *format, *host_library;  // "gzip" / "zlib"
+    int (*next)(mk_codec *, uint64_t *text_bytes, uint32_t *state);
+    int (*end)(mk_codec *);
+    // the stream's own figures: compressed bytes consumed, what it counted, its phases and its peak
+    void (*figures)(mk_codec *, uint64_t *consumed, std::string *counts, std::string *phases);
+};
+
+template <class... A>
+std::string fmt(const char *f, A... a) {
+    char buf[512];
+    snprintf(buf, sizeof buf, f, a...);
+    return buf;
+}
+
+const StreamCalls kGzipCalls = {"gzip", "zlib", mk_gzip_stream_next, mk_gzip_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+                                    mk_gzip_stream_stats st;
+                                    memset(&st, 0, sizeof(st));
+                                    (void)mk_gzip_stream_info(c, &st);
+                                    *consumed = st.consumed_bytes;
+                                    *counts = fmt("%llu windows, %llu members proved, %llu grown, %llu rounds repeated", (unsigned long long)st.windows, (unsigned long long)st.members,
+                                                  (unsigned long long)st.windows_grown, (unsigned long long)st.rounds_repeated);
+                                    *phases = fmt("upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
+                                                  st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
+                                }};
+const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_next, mk_bzip2_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+                                     mk_bzip2_stream_stats st;
+                                     memset(&st, 0, sizeof(st));
+                                     (void)mk_bzip2_stream_info(c, &st);
+                                     *consumed = st.consumed_bytes;
+                                     *counts = fmt("%llu windows, %llu streams closed, %llu blocks, %llu grown", (unsigned long long)st.windows, (unsigned long long)st.streams,
+                                                   (unsigned long long)st.blocks, (unsigned long long)st.windows_grown);
+                                     *phases = fmt("upload %.1f, marker search %.1f, block decode %.1f, text %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
+                                                   st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
+                                 }};
+
+// A file the device decodes window by window (mk_gzip_stream_*, mk_bzip2_stream_*).  Window w of the stream lies in text buffer w & 1
+struct DeviceStream : DeviceText {
+    const StreamCalls &calls;
     InputFile &f;
     const int i;
     Gate &g;
     uint64_t windows = 0;                 // windows the stream has produced
     uint64_t last_k[2] = {~0ull, ~0ull};  // the last text window whose body lies in either buffer
     uint64_t delivered = 0;               // text bytes of all its windows
-    enum { RUNNING, ENDED, HANDED_BACK } state = RUNNING;  // HANDED_BACK (the stream's state 2): zlib takes the file from the chain's tail on
+    enum { RUNNING, ENDED, HANDED_BACK } state = RUNNING;  // HANDED_BACK (the stream's state 2): the host library takes the file from the chain's tail on
     const double t0;
-    GzipStream(mk_codec *c, InputFile &f_, int i_, Gate &g_, double t0_) : DeviceText(c), f(f_), i(i_), g(g_), t0(t0_) {}
+    DeviceStream(const StreamCalls &calls_, mk_codec *c, InputFile &f_, int i_, Gate &g_, double t0_) : DeviceText(c), calls(calls_), f(f_), i(i_), g(g_), t0(t0_) {}
     bool ended() const override { return state == ENDED; }
 
     // the next window of the stream; false: there is none -- the file has ended, or the stream has handed it back (what does not add
@@ -67,30 +105,28 @@ struct GzipStream : DeviceText {
                 if (g.failed) return false;
             }
             const double t_win = PhaseTimer::now();
-            uint64_t text_bytes = 0;
+            uint64_t text_bytes = 0, consumed = 0;
             uint32_t st_now = 2;
-            if (mk_gzip_stream_next(codec, &text_bytes, &st_now) != MK_OK) st_now = 2;
-            mk_gzip_stream_stats st;
-            memset(&st, 0, sizeof(st));
-            (void)mk_gzip_stream_info(codec, &st);
+            if (calls.next(codec, &text_bytes, &st_now) != MK_OK) st_now = 2;
+            std::string counts, phases;
+            calls.figures(codec, &consumed, &counts, &phases);
             if (st_now == 0) {
                 if (g.timing)
-                    fprintf(stderr, "[timing]   gzip input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu)\n",
-                            i, (unsigned long long)windows, (unsigned long long)text_bytes, (unsigned long long)st.consumed_bytes,
-                            (PhaseTimer::now() - t_win) * 1e3, (unsigned long long)k);
+                    fprintf(stderr, "[timing]   %s input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu)\n",
+                            calls.format, i, (unsigned long long)windows, (unsigned long long)text_bytes, (unsigned long long)consumed, (PhaseTimer::now() - t_win) * 1e3,
+                            (unsigned long long)k);
                 ++windows;
                 delivered += text_bytes;
                 text = (const uint8_t *)mk_gzip_text_device(codec, &bytes);
                 at = 0;
                 if (bytes != text_bytes) st_now = 2;
                 else if (text_bytes) return true;
-                else continue;  // (a window of empty members)
+                else continue;  // (a window of empty members / streams)
             }
             if (g.timing)
-                fprintf(stderr, "[timing]   gzip input %d on the device, window by window: %llu windows, %llu members proved, %llu grown, %llu rounds repeated, handed back at %s, %.3f s (upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes)\n",
-                        i, (unsigned long long)st.windows, (unsigned long long)st.members, (unsigned long long)st.windows_grown,
-                        (unsigned long long)st.rounds_repeated, st_now == 1 ? "-" : std::to_string(delivered).append(" text bytes (zlib reads on)").c_str(),
-                        PhaseTimer::now() - t0, st.ms[0], st.ms[1], st.ms[2], st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
+                fprintf(stderr, "[timing]   %s input %d on the device, window by window: %s, handed back at %s, %.3f s (%s)\n", calls.format, i, counts.c_str(),
+                        st_now == 1 ? "-" : std::to_string(delivered).append(" text bytes (").append(calls.host_library).append(" reads on)").c_str(), PhaseTimer::now() - t0,
+                        phases.c_str());
             bytes = at = 0;
             state = st_now == 1 ? ENDED : HANDED_BACK;
             return false;
@@ -109,13 +145,15 @@ struct GzipStream : DeviceText {
     void body_to_host(const Side &S, char *dst) const override {
         if (hipMemcpy(dst, S.dev_body, S.n_dev_body, hipMemcpyDeviceToHost) != hipSuccess) bail("Error reading the inflated text back");
     }
-    // every text window over the stream's text is through: zlib reads the file from the front, drops what the windows have used -- all
-    // that was delivered but the chain's tail S.head, which starts at a record start -- and is this input's reader from here on
+    // every text window over the stream's text is through: the host library reads the file from the front (a bzip2 file: libbz2
+    // inflates it now, whole), drops what the windows have used -- all that was delivered but the chain's tail S.head, which starts at a
+    // record start -- and is this input's reader from here on
     std::unique_ptr<Source> hand_back(Side &S) override {
         if (state != HANDED_BACK) return nullptr;
         const uint64_t used = delivered - std::min<uint64_t>(delivered, S.head.size());
         S.head.clear();
-        (void)mk_gzip_stream_end(codec);
+        (void)calls.end(codec);
+        f.s.raw_settle();
         if (used) {
             f.have_first = false;
             if (!f.s.raw_skip(used)) bail("Error while decompressing " + f.path);
@@ -126,7 +164,7 @@ struct GzipStream : DeviceText {
 
 }  // namespace
 
-std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t gzip_window, Gate &g) {
+std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t stream_window, Gate &g) {
     const bool bz = f.s.raw_is_bzip2();
     if (!bz && !f.s.raw_is_gzip()) return nullptr;
     const uint8_t *z = f.s.source().file_bytes();
@@ -136,7 +174,15 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (bz) {
+    if (bz && n > stream_window) {
+        // more than one bzip2 window: decoded window by window as the text windows reach it, device memory bounded by the window; what
+        // the stream does not take, from whichever window on, is libbz2's
+        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        t0 = PhaseTimer::now();
+        if (codec && mk_bzip2_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new DeviceStream(kBzip2Calls, codec, f, i, g, t0));
+        if (g.timing) fprintf(stderr, "[timing]   bzip2 input %d on the device, window by window: NOT taken (libbz2 reads it)\n", i);
+    } else if (bz) {
         // its blocks are decoded on the device, a wave each.  What the call does not take -- anything it refuses, a damaged file, no room
         // -- libbz2 reads whole, as under --host-codec, and words the error
         uint64_t blocks = 0;
@@ -150,13 +196,13 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
         } else if (g.timing) {
             fprintf(stderr, "[timing]   bzip2 input %d: NOT taken by the device after %.3f s (libbz2 reads it)\n", i, PhaseTimer::now() - t0);
         }
-    } else if (n > gzip_window) {
+    } else if (n > stream_window) {
         // more than one gzip window: inflated window by window as the text windows reach it; what the stream does not take, from
         // whichever window on, is zlib's
         mk_check(mk_codec_create(device, &codec), "Error setting up the gzip codec");
         t0 = PhaseTimer::now();
-        if (mk_gzip_stream_begin(codec, z, n, gzip_window, &taken) != MK_OK) taken = 0;
-        if (taken) return std::unique_ptr<Source>(new GzipStream(codec, f, i, g, t0));
+        if (mk_gzip_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new DeviceStream(kGzipCalls, codec, f, i, g, t0));
         if (g.timing) fprintf(stderr, "[timing]   gzip input %d on the device, window by window: NOT taken (zlib reads it)\n", i);
     } else {
         // ONE DEFLATE stream, which zlib walks from the front at 0.5 GB/s -- the device inflates it in parallel pieces and keeps the

@@ -4,7 +4,7 @@
 //   host text      a plain file staged with pread() into page-locked buffers, or text the host inflated      (extract_sources.cpp)
 //   BGZF members   the members go to the device as they are                                                  (extract_sources.cpp)
 //   device text    a gzip file (one member or several) or a bzip2 file whose text the device has made        (extract_device_text.cpp)
-//   gzip stream    a gzip file the device inflates window by window, and may hand back to zlib mid-way        (extract_device_text.cpp)
+//   device stream  a gzip or bzip2 file the device decodes window by window, and may hand back mid-way       (extract_device_text.cpp)
 // No HIP header here: everything but extract_device_text.cpp compiles for a CPU test (tests/helpers/extract_windows_harness.cpp).
 #pragma once
 #include <condition_variable>
@@ -136,10 +136,10 @@ std::unique_ptr<Source> members_source(InputFile &f);
 
 // ---- extract_device_text.cpp (a CPU harness brings its own: no device, nothing taken)
 uint64_t device_free_bytes(int device);  // 0: unknown
-// Once the HIP runtime is up: tries to make input i's text on `device` -- a bzip2 file's blocks, a gzip file of more compressed bytes
-// than gzip_window window by window, a smaller one in one piece or member by member -- and prints the [timing] rows.  -> the device
-// source, or nothing: the host library reads the file
-std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t gzip_window, Gate &g);
+// Once the HIP runtime is up: tries to make input i's text on `device` -- a gzip or bzip2 file of more compressed bytes than
+// stream_window (the window of its format: --gzip-window, --bzip2-window) window by window, a smaller one in one call -- and prints the
+// [timing] rows.  -> the device source, or nothing: the host library reads the file
+std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t stream_window, Gate &g);
 
 }  // namespace xw
 }  // namespace cli

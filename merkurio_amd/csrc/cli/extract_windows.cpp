@@ -235,6 +235,12 @@ void WindowExtract::Impl::bound_device_windows() {
         bgzf_target = std::min<uint64_t>(bgzf_target, std::max<uint64_t>(64ull << 20, free_b / (6 * (uint64_t)n_in)));
 }
 
+// libbz2 inflates the file after all, whole, and the first window is read from its text
+void WindowExtract::Impl::settle_bzip2(xw::InputFile &I) {
+    I.s.raw_settle();
+    I.have_first = I.s.raw_fill(std::min(plain_target, kFirstWindow), &I.first_text, &I.first_n, &I.first_resume);
+}
+
 // Once the HIP runtime is up: the inputs whose text the device can make become device sources (xw::take_on_device); handles on devs[0]
 void WindowExtract::Impl::take_inputs_on_device() {
     // A streamed gzip file holds, per window, its compressed bytes, 12 to 48 16-bit symbols per compressed byte and two text buffers of 12
@@ -245,20 +251,35 @@ void WindowExtract::Impl::take_inputs_on_device() {
         if (!a.host_codec && in[i].s.raw_is_gzip() && in[i].s.source().file_size() > gzip_window) ++n_streamed;
     if (const uint64_t free_b = n_streamed ? xw::device_free_bytes(devs[0]) : 0)
         while (gzip_window > (1u << 20) && n_streamed * 2 * 50 * gzip_window > free_b / 2) gzip_window /= 2;
-    // The two bzip2 files of a pair go ONE AFTER THE OTHER: a call sizes its passes and accepts its text by the memory that is free when
-    // it runs, so the second must find the first's text there already, not a sibling that is about to take the same half.  A file the
-    // device does not take is libbz2's, whole, and the job goes on with host text
+    // A streamed bzip2 file holds, per window, its compressed bytes, 1.125 bytes per symbol in front of the run-length step and two text
+    // buffers; at 8 bytes of text per compressed byte (FASTQ: 4 to 5) that is 1 + 1.125 * 8 + 2 * 8 = 26 times the window.  The pass
+    // scratch (4.5 bytes per symbol of a block in flight) takes what is left and shrinks its passes when that is little.  The factor is
+    // an estimate for FULL blocks and is not measured: the library reserves a block's room by its level's capacity, not by its symbols,
+    // so many short streams at level 9 take far more per compressed byte -- there the library decodes the prefix of a window's blocks
+    // that fits and leaves the rest to the next window, which keeps the bound whatever this factor is.  Same rule
+    uint64_t bzip2_window = a.bzip2_window, n_bz_streamed = 0;
+    for (int i = 0; i < n_in; ++i)
+        if (bzip2_streamed(i)) ++n_bz_streamed;
+    if (const uint64_t free_b = n_bz_streamed ? xw::device_free_bytes(devs[0]) : 0)
+        while (bzip2_window > (1u << 20) && n_bz_streamed * 2 * 26 * bzip2_window > free_b / 2) bzip2_window /= 2;
+    // The two bzip2 files of a pair that go up WHOLE go ONE AFTER THE OTHER: a one-shot call sizes its passes and accepts its text by the
+    // memory that is free when it runs, so the second must find the first's text there already, not a sibling that is about to take the
+    // same half.  A file the device does not take is libbz2's, whole, and the job goes on with host text
     for (int i = 0; i < n_in; ++i) {
         xw::InputFile &I = in[i];
-        if (!I.s.raw_is_bzip2()) continue;
-        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], gzip_window, gate)) {
+        if (!I.s.raw_is_bzip2() || bzip2_streamed(i)) continue;
+        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], a.bzip2_window, gate)) {  // (at or below the window: in one call)
             src[i] = std::move(dev);
             continue;
         }
-        I.s.raw_settle();
-        I.have_first = I.s.raw_fill(std::min(plain_target, kFirstWindow), &I.first_text, &I.first_n, &I.first_resume);
+        settle_bzip2(I);
     }
-    run_threads((size_t)n_in, [&](size_t i) {  // (the two gzip files of a pair side by side: a handle and a stream each)
+    run_threads((size_t)n_in, [&](size_t i) {  // (the two streamed files of a pair side by side: a handle and a stream each, sized by their windows)
+        if (bzip2_streamed((int)i)) {
+            if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], bzip2_window, gate)) src[i] = std::move(dev);
+            else settle_bzip2(in[i]);
+            return;
+        }
         if (a.host_codec || !in[i].s.raw_is_gzip()) return;
         if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], gzip_window, gate)) src[i] = std::move(dev);
     });

@@ -52,6 +52,9 @@ struct WindowExtract::Impl {
     bool members_input(int i) const { return !a.host_codec && in[i].s.raw_is_bgzf(); }
     void bound_device_windows();
     void take_inputs_on_device();
+    // a .bz2 input of more compressed bytes than --bzip2-window: decoded window by window (under --host-codec no input is_bzip2)
+    bool bzip2_streamed(int i) const { return in[i].s.raw_is_bzip2() && in[i].s.source().file_size() > a.bzip2_window; }
+    void settle_bzip2(xw::InputFile &I);
     void reader_loop();
     void device_loop(size_t d);
     // ---- extract_window_call.cpp

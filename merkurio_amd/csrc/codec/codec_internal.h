@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../host_common.h"
+#include "bzip2_chain.hpp"
 #include "gzip_chain.hpp"
 
 namespace mk {
@@ -35,6 +36,20 @@ struct mk_gzip_stream {
     void *d_carry[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
     size_t text_cap[2] = {0, 0};
     mk_gzip_stream_stats stats{};
+};
+
+// mk_bzip2_stream_*: a .bz2 file in windows of its compressed bytes (bzip2_host.cpp).  What is decided about a window is mkz::BzStream's
+// (bzip2_chain.hpp); here what the stream owns on the device: two text buffers (the handle's d_gz_text points at the latest text
+// window's).  Compressed bytes, the bytes in front of the run-length step, tables and pass scratch are the handle's d_gz_in /
+// d_gz_sym / d_gz_tab / d_gz_ctx, sized by the window's blocks.
+struct mk_bzip2_stream {
+    bool active = false;
+    mkz::BzStream s;
+    int text_cur = 0;
+    void *d_text[2] = {nullptr, nullptr};
+    size_t text_cap[2] = {0, 0};
+    uint64_t n_up = 0;  // bytes of the latest upload
+    size_t n_tab = 0;   // blocks the device tables of the decoded window are laid out for
 };
 
 struct mk_codec {
@@ -67,11 +82,14 @@ struct mk_codec {
     uint32_t bz_blocks = 0;
     float bz_ms[5] = {0, 0, 0, 0, 0};  // upload, marker search, block decode, text, CRC
     uint64_t bz_pass_blocks = 0;       // mk_codec_set_bzip2_pass_blocks; 0 = by the free memory
+    uint64_t bz_text_cap = 0;          // mk_codec_set_bzip2_text_cap: bytes per text window of a bzip2 stream; 0 = by the free memory
     int inflate_kernel = 0;  // mk_codec_set_inflate_kernel: 0 = chosen per call, 1 = a lane per member, 2 = a wave per member
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size
     uint64_t deflate_pass_blocks = 0, inflate_pass_text = 0;  // mk_codec_set_pass_limits; 0 = the defaults below
     mk_gzip_stream gzs;
+    mk_bzip2_stream bzs;
+    bool stream_open() const { return gzs.active || bzs.active; }  // one stream per handle, and no one-shot call beside it
 };
 
 namespace mkz {
@@ -92,6 +110,8 @@ inline float elapsed(hipEvent_t a, hipEvent_t b) {
 void gz_release(mk_codec *c);
 void gz_keep_text(mk_codec *c);
 void gzip_stream_close(mk_codec *c);
+// ---- bzip2_host.cpp: an open bzip2 stream ends likewise
+void bzip2_stream_close(mk_codec *c);
 // ---- bgzf_host.cpp
 // One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
 // output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on

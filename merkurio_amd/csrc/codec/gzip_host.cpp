@@ -295,7 +295,7 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     if (!c || !text_bytes || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // RFC 1952: the member's header, then the DEFLATE stream up to the 8 trailer bytes.  One member is what is taken here: the stream
@@ -312,7 +312,7 @@ int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, u
     if (!c || !text_bytes || !taken || !n_members || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_members = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // the member starts as the host can guess them: every place where a header parses.  The file goes up whole; which guesses are
@@ -348,6 +348,7 @@ int mk_gzip_text_release(mk_codec *c) {
     std::lock_guard<std::mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
     mkz::gzip_stream_close(c);  // (an open stream's text is the text: the stream ends with it)
+    mkz::bzip2_stream_close(c);
     mkz::gz_release(c);
     return MK_OK;
 }
@@ -368,7 +369,7 @@ int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t wi
     *taken = 0;
     if (window_bytes && (window_bytes < 4096 || window_bytes > (1ull << 40))) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: a window of 4 KiB at least");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->gzs.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: the handle has an open stream (mk_gzip_stream_end)");
     const uint64_t n_guesses = mkz::gzip_member_guesses(gz, n, nullptr, 0);
     if (!n_guesses) return MK_OK;  // (not a gzip file)
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");

@@ -9,9 +9,15 @@ against another build's binary that inflates .bz2 with libbz2 at load (the paren
          (mk_bzip2_info) as medians, and the share of the call that is its "text" phase (the chain walk on one lane plus the
          expansion).  The plain big.fastq goes through both binaries the same way: the control row, which must not move.
 
+  sweep  --bzip2-window at 64, 128, 256, 512 MiB and 1 GiB (mk_bzip2_stream_*; a file at or below the window takes the one-shot
+         call) beside the one-shot call alone (a window above any file), on big.fastq.bz2 and on that file --concat times behind
+         itself (4: more than the largest window), every setting once per round, --runs rounds, medians with ranges; per setting the
+         stream's own summary row.  Prints the table of profiles/e2e_bunzip2_windows.txt.
+
 Prints the table of profiles/e2e_bunzip2.txt.  Example:
   tools/e2e_bunzip2.py make --dir /tmp/bz
   tools/e2e_bunzip2.py run --dir /tmp/bz --parent-bin /path/to/parent/merkurio --runs 5
+  tools/e2e_bunzip2.py sweep --dir /tmp/bz --runs 5
 """
 import argparse
 import bz2
@@ -119,6 +125,42 @@ def run(a):
             raise SystemExit(1)
 
 
+STREAM = re.compile(r"bzip2 input 0 on the device, window by window: (\d+) windows, (\d+) streams closed, (\d+) blocks, (\d+) grown, handed back at (\S+).*?\((.*)\)")
+SWEEP_MIB = (64, 128, 256, 512, 1024)
+
+
+def sweep(a):
+    patterns = os.path.join(a.dir, "patterns.txt")
+    big = os.path.join(a.dir, "big.fastq.bz2")
+    cat = os.path.join(a.dir, f"big_x{a.concat}.fastq.bz2")
+    if not os.path.exists(cat):
+        with open(cat, "wb") as out, open(big, "rb") as src:
+            blob = src.read()
+            for _ in range(a.concat):
+                out.write(blob)
+    for path in (big, cat):
+        configs = [("one-shot", ["--bzip2-window", str(1 << 40)])] + [(f"{m} MiB", ["--bzip2-window", str(m << 20)]) for m in SWEEP_MIB]
+        times, rows, sizes = {n: [] for n, _ in configs}, {}, set()
+        with tempfile.TemporaryDirectory() as d:
+            for r in range(a.runs):  # (in alternation: every setting once per round)
+                for name, extra in configs:
+                    dt, err, size = run_once(BIN, path, patterns, os.path.join(d, "out.fastq"), extra)
+                    times[name].append(dt)
+                    sizes.add(size)
+                    m, one = STREAM.search(err), PHASES.search(err)
+                    rows[name] = (f"{m.group(1)} windows, {m.group(3)} blocks, {m.group(4)} grown, handed back at {m.group(5)}; {m.group(6)}" if m
+                                  else "one-shot call" if one else "NOT taken by the device")
+                    print(f"# {os.path.basename(path)} round {r} {name}: {dt:.3f} s", flush=True)
+        print(f"{os.path.basename(path)}: {os.path.getsize(path)} bytes as stored, medians of {a.runs} in alternation; kept records of {sorted(sizes)} bytes"
+              f" ({'EQUAL' if len(sizes) == 1 else 'DIFFER'})")
+        for name, _ in configs:
+            t = times[name]
+            print(f"  --bzip2-window {name:9s} median {statistics.median(t):8.3f} s   range {min(t):.3f} - {max(t):.3f} s   [{rows[name]}]")
+        sys.stdout.flush()
+        if len(sizes) != 1:
+            raise SystemExit(1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -131,8 +173,12 @@ def main():
     r.add_argument("--runs", type=int, default=5)
     r.add_argument("--parent-bin", default=None)
     r.add_argument("--with-default", action="store_true", help="also this build with --host-codec (libbz2)")
+    w = sub.add_parser("sweep")
+    w.add_argument("--dir", required=True)
+    w.add_argument("--runs", type=int, default=5)
+    w.add_argument("--concat", type=int, default=4, help="copies of big.fastq.bz2 behind each other in the second file")
     a = ap.parse_args()
-    (make if a.cmd == "make" else run)(a)
+    {"make": make, "run": run, "sweep": sweep}[a.cmd](a)
 
 
 if __name__ == "__main__":
