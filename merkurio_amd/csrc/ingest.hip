@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void mk_ingest_records_kernel(const uint8_t *_
         if (e3 > l3 && e3 - 1 < n && text[e3 - 1] == '\r') --e3;
         len = e1 - l1;
         bad |= text[l0] != '@';
-        bad |= l1 - l0 < 2;  // "@\n": no id at all is left to the host reader
+        bad |= l1 - l0 < 3;  // "@\n" (l1 - l0 == 2): no id at all is left to the host reader; "@\r\n" is taken, its id is empty
         bad |= (l3 - l2 < 2) || text[l2] != '+';
         bad |= (e3 - l3) != len;
         rec_start[i] = l0;
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void mk_ingest_select_kernel(const uint8_t *__
 // eol = the header line's own line end.  A FASTA record whose form is not that (no sequence, blank lines or a lone '\r' at its end)
 // sets *refused: the caller leaves the window to the host writer.
 __device__ __forceinline__ uint32_t fq_header(const uint8_t *__restrict__ text, uint32_t l0, uint32_t l1, uint32_t *nl) {
-    uint32_t e0 = l1 - 1;  // (the records kernel has seen to l1 - l0 >= 2)
+    uint32_t e0 = l1 - 1;  // (the records kernel has seen to l1 - l0 >= 3)
     const bool crlf = e0 > l0 + 1 && text[e0 - 1] == '\r';
     *nl = crlf ? 2u : 1u;
     return e0 - (crlf ? 1u : 0u) - l0;  // marker + id
