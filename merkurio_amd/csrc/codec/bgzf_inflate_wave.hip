@@ -15,6 +15,8 @@
 //     all lanes from the canonical description (limits / bases / symbols by length), which also decodes the rare longer codewords;
 //   * the tables are built in parallel -- counts per length by lane, symbol ranks by ballot -- so that a block header costs
 //     microseconds; nothing of the decoder lives in private memory (0 bytes of scratch).
+// The tables (WaveTables) and their builders are inflate_wave_common.hpp's, shared with the gunzip's piece decoder
+// (gzip_segments_wave.hpp); the bit reader and the block set-up are this file's own copy -- that header says what sharing them cost.
 // With the whole 32 KiB in LDS a wave takes 36.1 KiB: 4 waves per CU, one per SIMD -- nothing fills the waits of a token turn's
 // ~150 (literal) to ~500 (match) cycles of dependent LDS latency.  The kernel is a template on the ring's size: with the most
 // recent 8 KiB (12.4 KiB per wave, 12 waves per CU, 3 072 members in flight on an MI355X) the same member takes as long but three
@@ -40,15 +42,7 @@ namespace {
 template <uint32_t kRing>
 struct WaveLds {
     uint8_t ring[kRing];
-    // direct tables for codewords of <= 10 / 9 bits (else 0), everything a token turn needs in ONE read (r05: the kernel is bound by
-    // its scalar instructions -- 107 per token, 1 M per member, one scalar unit per CU --, so what can be looked up is not computed):
-    // ll_fast: a literal or end-of-block = symbol << 4 | codeword length (< 0x8000); a length symbol = 0x8000 | (base - 3) << 7 |
-    // extra bits << 4 | codeword length.  d_fast: distance base << 8 | extra bits << 4 | codeword length.
-    uint16_t ll_fast[1 << kFastLl];
-    uint32_t d_fast[1 << kFastD];
-    uint16_t ll_limit[16], ll_base[16], d_limit[16], d_base[16];
-    uint16_t ll_sorted[288], d_sorted[32];
-    uint8_t lens[320];  // code lengths of the block being set up: literal / length [0, 288), distance [288, 320)
+    WaveTables T;  // (inflate_wave_common.hpp)
 };
 static_assert(sizeof(WaveLds<32768>) <= 40 * 1024, "four waves per CU");
 static_assert(sizeof(WaveLds<8192>) <= 14 * 1024, "eleven waves per CU");
@@ -64,6 +58,7 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
     constexpr uint32_t kRingMask = kRing - 1;
     extern __shared__ uint8_t lds_raw[];
     WaveLds<kRing> &S = *reinterpret_cast<WaveLds<kRing> *>(lds_raw);
+    WaveTables &T = S.T;
     const uint32_t lane = lane_id();
     const uint32_t mi = blockIdx.x;
     if (mi >= n_members) return;
@@ -156,9 +151,9 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
             restart(pos + len);
             continue;
         }
-        // ---- code lengths of the block -> S.lens
+        // ---- code lengths of the block -> T.lens
         if (type == 1) {
-            for (uint32_t i = lane; i < 320; i += 64) S.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
+            for (uint32_t i = lane; i < 320; i += 64) T.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
         } else {
             const uint32_t hlit = ((uint32_t)bitbuf & 31u) + 257, hdist = ((uint32_t)(bitbuf >> 5) & 31u) + 1, hclen = ((uint32_t)(bitbuf >> 10) & 15u) + 4;
             MKW_TAKE(14);
@@ -167,18 +162,19 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
                 break;
             }
             // the code-length code: 19 lengths of 3 bits in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15 (5 bits each, packed)
-            if (lane < (uint32_t)kCl) S.lens[lane] = 0;
+            // (cl_order_at() of deflate_common.hpp, written out: through the call the 8 KiB ring measured 3-4 % slower, inflate_wave_common.hpp)
+            if (lane < (uint32_t)kCl) T.lens[lane] = 0;
             constexpr uint64_t kOrderLo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 |
                                           5ull << 45 | 11ull << 50 | 4ull << 55;
             constexpr uint64_t kOrderHi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
             for (uint32_t i = 0; i < hclen; ++i) {
                 MKW_NEED32();
                 const uint32_t sym = (uint32_t)((i < 12 ? kOrderLo >> (5 * i) : kOrderHi >> (5 * (i - 12))) & 31u);
-                if (lane == 0) S.lens[sym] = (uint8_t)((uint32_t)bitbuf & 7u);
+                if (lane == 0) T.lens[sym] = (uint8_t)((uint32_t)bitbuf & 7u);
                 MKW_TAKE(3);
             }
             // (the code-length code borrows the literal tables)
-            if (wave_build_tables(S.lens, kCl, S.ll_sorted, S.ll_limit, S.ll_base, false)) {
+            if (wave_build_tables(T.lens, kCl, T.ll_sorted, T.ll_limit, T.ll_base, false)) {
                 status = kInfBadLengths;
                 break;
             }
@@ -189,7 +185,7 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
                     status = kInfTruncated;
                     break;
                 }
-                const uint32_t e = decode_codeword((uint32_t)bitbuf, S.ll_sorted, S.ll_limit, S.ll_base);
+                const uint32_t e = decode_codeword((uint32_t)bitbuf, T.ll_sorted, T.ll_limit, T.ll_base);
                 if (e == 0 || (e & 15u) > (uint32_t)kMaxClBits) {
                     status = kInfBadLengths;
                     break;
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
                 const uint32_t sym = e >> 4;
                 if (sym < 16) {
                     // (lengths of the distance alphabet are stored where they belong at once: [288, 288 + hdist))
-                    if (lane == 0) S.lens[i < hlit ? i : 288 + (i - hlit)] = (uint8_t)sym;
+                    if (lane == 0) T.lens[i < hlit ? i : 288 + (i - hlit)] = (uint8_t)sym;
                     prev_len = sym, ++i;
                     continue;
                 }
@@ -224,37 +220,37 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
                 }
                 if (lane < rep) {
                     const uint32_t j = i + lane;  // (rep <= 138: three rounds of lanes at most)
-                    S.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
+                    T.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
                 }
                 if (lane + 64 < rep) {
                     const uint32_t j = i + lane + 64;
-                    S.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
+                    T.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
                 }
                 if (lane + 128 < rep) {
                     const uint32_t j = i + lane + 128;
-                    S.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
+                    T.lens[j < hlit ? j : 288 + (j - hlit)] = (uint8_t)val;
                 }
                 prev_len = val, i += rep;
             }
             if (status) break;
             // each alphabet padded with zeros to its full size
-            for (uint32_t k = hlit + lane; k < 288; k += 64) S.lens[k] = 0;
-            if (lane + hdist < 32) S.lens[288 + hdist + lane] = 0;
+            for (uint32_t k = hlit + lane; k < 288; k += 64) T.lens[k] = 0;
+            if (lane + hdist < 32) T.lens[288 + hdist + lane] = 0;
             __builtin_amdgcn_wave_barrier();
-            if (S.lens[256] == 0) {  // no end-of-block codeword
+            if (T.lens[256] == 0) {  // no end-of-block codeword
                 status = kInfBadLengths;
                 break;
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (wave_build_tables(S.lens, 288, S.ll_sorted, S.ll_limit, S.ll_base, true) ||
-            wave_build_tables(S.lens + 288, type == 1 ? 32 : 30, S.d_sorted, S.d_limit, S.d_base, true)) {
+        if (wave_build_tables(T.lens, 288, T.ll_sorted, T.ll_limit, T.ll_base, true) ||
+            wave_build_tables(T.lens + 288, type == 1 ? 32 : 30, T.d_sorted, T.d_limit, T.d_base, true)) {
             status = kInfBadLengths;
             break;
         }
         __builtin_amdgcn_wave_barrier();
-        wave_fill_fast_ll(S.ll_fast, S.ll_sorted, S.ll_limit, S.ll_base);
-        wave_fill_fast_d(S.d_fast, S.d_sorted, S.d_limit, S.d_base);
+        wave_fill_fast_ll(T.ll_fast, T.ll_sorted, T.ll_limit, T.ll_base);
+        wave_fill_fast_d(T.d_fast, T.d_sorted, T.d_limit, T.d_base);
         __builtin_amdgcn_wave_barrier();
 
         // ---- the symbols of the block: one token per turn, the same turn on every lane.  The turn is kept short (the scalar unit is
@@ -264,9 +260,9 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
         uint32_t flush_at = flushed + kFlush;
         for (;;) {
             MKW_NEED32();
-            uint32_t e = S.ll_fast[(uint32_t)bitbuf & ((1u << kFastLl) - 1)];
+            uint32_t e = T.ll_fast[(uint32_t)bitbuf & ((1u << kFastLl) - 1)];
             if (e == 0) {  // a codeword longer than the table's reach (or none)
-                e = pack_ll(decode_codeword((uint32_t)bitbuf, S.ll_sorted, S.ll_limit, S.ll_base));
+                e = pack_ll(decode_codeword((uint32_t)bitbuf, T.ll_sorted, T.ll_limit, T.ll_base));
                 if (e == 0) {
                     status = kInfBadSymbol;
                     break;
@@ -284,9 +280,9 @@ __global__ __launch_bounds__(64) void mk_bgzf_inflate_wave_kernel(const uint8_t 
                 const uint32_t len = ((e >> 7) & 255u) + 3u + ((uint32_t)bitbuf & ((1u << leb) - 1));
                 MKW_TAKE(leb);
                 MKW_NEED32();
-                uint32_t d = S.d_fast[(uint32_t)bitbuf & ((1u << kFastD) - 1)];
+                uint32_t d = T.d_fast[(uint32_t)bitbuf & ((1u << kFastD) - 1)];
                 if (d == 0) {
-                    d = pack_d(decode_codeword((uint32_t)bitbuf, S.d_sorted, S.d_limit, S.d_base));
+                    d = pack_d(decode_codeword((uint32_t)bitbuf, T.d_sorted, T.d_limit, T.d_base));
                     if (d == 0) {
                         status = kInfBadSymbol;
                         break;

@@ -7,11 +7,10 @@
 // where the caller has laid place-holders; and only the most recent 2 048 symbols live in LDS (4 KiB: 9.3 KiB per wave, 17 waves per
 // CU) -- a match that reaches further reads symbols back from global memory, where they went with a flush (or where the place-holders
 // lie).  kDry: nothing is stored or copied, the bit stream alone is checked, max_symbols of it at most (the block-start search looks at
-// a candidate with it).  Users: gzip_segments_wave.hip (the pieces), gzip_inflate.hip (the search).  RFC 1951.
+// a candidate with it).  The tables and their builders are inflate_wave_common.hpp's, shared with the BGZF kernel; the bit reader
+// (64-bit positions here) and the block set-up are a copy of that kernel's -- that header says what sharing them cost.  Users: gzip_segments_wave.hip (the pieces), gzip_inflate.hip (the search).  RFC 1951.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#include <type_traits>
 
 #include "gzip_segments.hpp"
 #include "inflate_wave_common.hpp"
@@ -19,14 +18,6 @@
 namespace mkz {
 namespace {
 
-// MK_SEG_PAIRS=1 (a measurement build): table entries of 32 bits that hold TWO literals where the entry's bits do, taken in one turn.
-// Measured on gzip -6 FASTQ: 14 instead of 17 waves per CU, pieces 31 -> 43 ms.  DNA text is not literals to DEFLATE: three tokens of
-// four are matches of ~12 bases found thousands of positions back (any 8-mer has occurred in the last 32 KiB), and what a wave waits
-// for is those matches' sources coming back from device memory -- hidden by the other waves of the CU, so waves per CU count.
-#ifndef MK_SEG_PAIRS
-#define MK_SEG_PAIRS 0
-#endif
-constexpr bool kSegPairs = MK_SEG_PAIRS != 0;
 #ifndef MK_SEG_RING
 #define MK_SEG_RING 2048  // (a measurement build may take another power of two >= 1024; 1024 = 21 waves per CU: pieces 31.2 -> 32.7 ms, small streams 15.5 -> 16.6)
 #endif
@@ -35,16 +26,8 @@ constexpr uint64_t kSegCapMax = 0xfff00000ull;  // (the decoder counts symbols i
 constexpr int kSegCutShort = 1;                // (dry) max_symbols were decoded without an error: not an error
 constexpr uint64_t kSegConfirmSymbols = 2048;  // what the search decodes of a candidate's block (a multiple of kSegFlush)
 
-struct SegWaveTables {
-    // ll_fast as bgzf_inflate_wave.hip has it (one codeword); kSegPairs: that is the low half, and the high half, if not 0, says that
-    // the stream bits of this entry hold TWO literals -- second literal << 4 | length of both codewords
-    std::conditional_t<kSegPairs, uint32_t, uint16_t> ll_fast[1 << kFastLl];
-    uint32_t d_fast[1 << kFastD];
-    uint16_t ll_limit[16], ll_base[16], d_limit[16], d_base[16];
-    uint16_t ll_sorted[288], d_sorted[32];
-    uint8_t lens[320];
-};
-static_assert(kSegRing != 2048 || sizeof(SegWaveTables) + 2 * kSegRing <= (kSegPairs ? 11648 : 9728), "fourteen (without pairs: seventeen) waves per CU");
+using SegWaveTables = WaveTables;  // (inflate_wave_common.hpp)
+static_assert(kSegRing != 2048 || sizeof(SegWaveTables) + 2 * kSegRing <= 9728, "seventeen waves per CU");
 static_assert(kSegRing >= 1024 && (kSegRing & (kSegRing - 1)) == 0, "the flush writes 512 symbols a step");
 
 // All lanes call it with the same arguments and get the same results.  ring: kSegRing elements of LDS, 16-byte aligned (kDry: unused).
@@ -164,13 +147,9 @@ __device__ __forceinline__ int wave_inflate_segment(const uint8_t *__restrict__ 
                     break;
                 }
                 if (lane < (uint32_t)kCl) S.lens[lane] = 0;
-                constexpr uint64_t kOrderLo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 |
-                                              5ull << 45 | 11ull << 50 | 4ull << 55;
-                constexpr uint64_t kOrderHi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
                 for (uint32_t i = 0; i < hclen; ++i) {
                     MKS_NEED32();
-                    const uint32_t s_ = (uint32_t)((i < 12 ? kOrderLo >> (5 * i) : kOrderHi >> (5 * (i - 12))) & 31u);
-                    if (lane == 0) S.lens[s_] = (uint8_t)((uint32_t)bitbuf & 7u);
+                    if (lane == 0) S.lens[cl_order_at(i)] = (uint8_t)((uint32_t)bitbuf & 7u);
                     MKS_TAKE(3);
                 }
                 // (the code-length code borrows the literal tables)
@@ -239,24 +218,8 @@ __device__ __forceinline__ int wave_inflate_segment(const uint8_t *__restrict__ 
                 break;
             }
             __builtin_amdgcn_wave_barrier();
-            // one codeword per entry ...
-            for (uint32_t e = lane; e < (1u << kFastLl); e += 64) {
-                const uint32_t r = decode_codeword(e, S.ll_sorted, S.ll_limit, S.ll_base);
-                S.ll_fast[e] = (r & 15u) <= (uint32_t)kFastLl ? pack_ll(r) : 0u;
-            }
+            wave_fill_fast_ll(S.ll_fast, S.ll_sorted, S.ll_limit, S.ll_base);
             __builtin_amdgcn_wave_barrier();
-            if constexpr (kSegPairs) {
-                // ... and where that is a literal and what follows it in the entry's bits is a whole literal too, the two of them (only
-                // the high halves are written here, only the low halves read)
-                for (uint32_t e = lane; e < (1u << kFastLl); e += 64) {
-                    const uint32_t a = reinterpret_cast<const uint16_t *>(S.ll_fast)[2 * e];
-                    const uint32_t la = a & 15u;
-                    if (a != 0 && a < 0x1000u && la < (uint32_t)kFastLl) {
-                        const uint32_t b = reinterpret_cast<const uint16_t *>(S.ll_fast)[2 * (e >> la)];  // (the bits behind the first, zeros above)
-                        if (b != 0 && b < 0x1000u && la + (b & 15u) <= (uint32_t)kFastLl) reinterpret_cast<uint16_t *>(S.ll_fast)[2 * e + 1] = (uint16_t)((b & 0xff0u) | (la + (b & 15u)));
-                    }
-                }
-            }
             wave_fill_fast_d(S.d_fast, S.d_sorted, S.d_limit, S.d_base);
             __builtin_amdgcn_wave_barrier();
 
@@ -265,69 +228,58 @@ __device__ __forceinline__ int wave_inflate_segment(const uint8_t *__restrict__ 
             for (;;) {
                 MKS_NEED32();
                 uint32_t e = S.ll_fast[(uint32_t)bitbuf & ((1u << kFastLl) - 1)];
-                if (kSegPairs && e > 0xffffu) {  // two literals
-                    if constexpr (!kDry) {
-                        ring[op & kSegRingMask] = (uint16_t)((e >> 4) & 0xffu);
-                        ring[(op + 1) & kSegRingMask] = (uint16_t)(e >> 20);
-                    }
-                    MKS_TAKE((e >> 16) & 15u);
-                    op += 2;
-                    if (op < flush_at) continue;
-                    e = 0x10000u;  // (the flush point's questions, then on)
-                } else if (e == 0) {
+                if (e == 0) {
                     e = pack_ll(decode_codeword((uint32_t)bitbuf, S.ll_sorted, S.ll_limit, S.ll_base));
                     if (e == 0) {
                         status = kInfBadSymbol;
                         break;
                     }
                 }
-                if (e != 0x10000u) {
-                    MKS_TAKE(e & 15u);
-                    if (e < 0x1000u) {
-                        if constexpr (!kDry) ring[op & kSegRingMask] = (uint16_t)(e >> 4);
-                        ++op;
-                        if (op < flush_at) continue;
-                    } else if (e < 0x8000u) {
-                        break;
-                    } else {
-                        const uint32_t leb = (e >> 4) & 7u;
-                        const uint32_t len = ((e >> 7) & 255u) + 3u + ((uint32_t)bitbuf & ((1u << leb) - 1));
-                        MKS_TAKE(leb);
-                        MKS_NEED32();
-                        uint32_t d = S.d_fast[(uint32_t)bitbuf & ((1u << kFastD) - 1)];
+                MKS_TAKE(e & 15u);
+                if (e < 0x1000u) {
+                    if constexpr (!kDry) ring[op & kSegRingMask] = (uint16_t)(e >> 4);
+                    ++op;
+                    if (op < flush_at) continue;
+                } else if (e < 0x8000u) {
+                    break;
+                } else {
+                    const uint32_t leb = (e >> 4) & 7u;
+                    const uint32_t len = ((e >> 7) & 255u) + 3u + ((uint32_t)bitbuf & ((1u << leb) - 1));
+                    MKS_TAKE(leb);
+                    MKS_NEED32();
+                    uint32_t d = S.d_fast[(uint32_t)bitbuf & ((1u << kFastD) - 1)];
+                    if (d == 0) {
+                        d = pack_d(decode_codeword((uint32_t)bitbuf, S.d_sorted, S.d_limit, S.d_base));
                         if (d == 0) {
-                            d = pack_d(decode_codeword((uint32_t)bitbuf, S.d_sorted, S.d_limit, S.d_base));
-                            if (d == 0) {
-                                status = kInfBadSymbol;
-                                break;
-                            }
+                            status = kInfBadSymbol;
+                            break;
                         }
-                        MKS_TAKE(d & 15u);
-                        const uint32_t deb = (d >> 4) & 15u;
-                        const uint32_t dist = (d >> 8) + ((uint32_t)bitbuf & ((1u << deb) - 1));
-                        MKS_TAKE(deb);
-                        if constexpr (!kDry) {
-                            // symbol i of the match = symbol (i mod distance) of the `distance` symbols in front of it.  A distance is at most
-                            // 32 768 = kSegPrefix: a source in front of the piece is a place-holder the caller has laid there
-                            const uint32_t src0 = op - dist;  // (wraps where the source lies in front of the piece: the far path's case)
-                            if (dist + len > kSegRing || dist > op) {
-                                // the source has (partly) left the ring, or never was in it: symbols below `flushed` come from global memory
-                                // (past the CU's L1: a line may have been cached before its last symbols were stored), the rest from the ring
-                                for (uint32_t i = lane; i < len; i += 64) {
-                                    const long long p = (long long)op - (long long)dist + (dist >= len ? i : i % dist);
-                                    const uint16_t v = p < (long long)flushed ? __hip_atomic_load(out + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                                                               : ring[(uint64_t)p & kSegRingMask];
-                                    ring[(op + i) & kSegRingMask] = v;
-                                }
-                            } else if (dist >= len) {
-                                for (uint32_t i = lane; i < len; i += 64) ring[(op + i) & kSegRingMask] = ring[(src0 + i) & kSegRingMask];
-                            } else {
-                                for (uint32_t i = lane; i < len; i += 64) ring[(op + i) & kSegRingMask] = ring[(src0 + i % dist) & kSegRingMask];
-                            }
-                        }
-                        op += len;
-                        if (op < flush_at) continue;
                     }
+                    MKS_TAKE(d & 15u);
+                    const uint32_t deb = (d >> 4) & 15u;
+                    const uint32_t dist = (d >> 8) + ((uint32_t)bitbuf & ((1u << deb) - 1));
+                    MKS_TAKE(deb);
+                    if constexpr (!kDry) {
+                        // symbol i of the match = symbol (i mod distance) of the `distance` symbols in front of it.  A distance is at most
+                        // 32 768 = kSegPrefix: a source in front of the piece is a place-holder the caller has laid there
+                        const uint32_t src0 = op - dist;  // (wraps where the source lies in front of the piece: the far path's case)
+                        if (dist + len > kSegRing || dist > op) {
+                            // the source has (partly) left the ring, or never was in it: symbols below `flushed` come from global memory
+                            // (past the CU's L1: a line may have been cached before its last symbols were stored), the rest from the ring
+                            for (uint32_t i = lane; i < len; i += 64) {
+                                const long long p = (long long)op - (long long)dist + (dist >= len ? i : i % dist);
+                                const uint16_t v = p < (long long)flushed ? __hip_atomic_load(out + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                                                           : ring[(uint64_t)p & kSegRingMask];
+                                ring[(op + i) & kSegRingMask] = v;
+                            }
+                        } else if (dist >= len) {
+                            for (uint32_t i = lane; i < len; i += 64) ring[(op + i) & kSegRingMask] = ring[(src0 + i) & kSegRingMask];
+                        } else {
+                            for (uint32_t i = lane; i < len; i += 64) ring[(op + i) & kSegRingMask] = ring[(src0 + i % dist) & kSegRingMask];
+                        }
+                    }
+                    op += len;
+                    if (op < flush_at) continue;
                 }
                 if (op > cap32) {
                     status = kSegOverflow;
@@ -374,8 +326,9 @@ __device__ __forceinline__ int wave_inflate_segment(const uint8_t *__restrict__ 
 // a plausible header at `bit` (the same on every lane): is it a block start?  The block is decoded dry by the whole wave, kSegConfirmSymbols
 // symbols of it at most: the few headers that pass seg_header_plausible() without being one (3 in 5.7 G bit positions of gzip-written
 // FASTQ) give codes whose first codewords are no symbols, or whose block ends after a handful of symbols in front of something that
-// is no header.  A block that ends within the bound is asked what seg_confirm_block_start() of gzip_segments.hpp asks.  (The first
-// version decoded every candidate's WHOLE block: a second decode of a quarter to all of the stream, 8-16 ms of the search.)
+// is no header.  A block that ends within the bound is asked what seg_confirm_block_start() of gzip_segments.hpp asks: does a header
+// follow (seg_next_header_plausible)?  (The first version decoded every candidate's WHOLE block: a second decode of a quarter to all
+// of the stream, 8-16 ms of the search.)
 __device__ __forceinline__ bool wave_confirm_block_start(const uint8_t *__restrict__ in, uint64_t n_in, uint64_t bit, SegWaveTables &S) {
     uint64_t n_out = 0, stop = 0;
     bool fin = false;
@@ -383,23 +336,7 @@ __device__ __forceinline__ bool wave_confirm_block_start(const uint8_t *__restri
     if (rc == kSegCutShort) return true;
     if (rc != 0) return false;
     if (n_out == 0 || fin) return false;  // (the block at a nominal cut is neither empty nor the last one)
-    if (stop + 3 > n_in * 8) return false;
-    SegReader r;
-    r.in = in, r.n_in = n_in;
-    sr_seek(r, stop);
-    const uint32_t type = ((uint32_t)r.bitbuf >> 1) & 3u;
-    if (type == 2) {
-        sr_take(r, 3);
-        return seg_dynamic_header(r, nullptr) == 0;
-    }
-    if (type == 0) {  // stored: LEN and its complement must agree
-        sr_take(r, 3);
-        sr_take(r, r.bitcnt & 7);
-        sr_need32(r);
-        const uint32_t len = (uint32_t)r.bitbuf & 0xffffu, nlen = ((uint32_t)(r.bitbuf >> 16)) & 0xffffu;
-        return (len ^ nlen) == 0xffffu;
-    }
-    return false;  // (a fixed block behind it proves nothing, type 3 is none)
+    return seg_next_header_plausible(in, n_in, stop);
 }
 
 }  // namespace

@@ -21,6 +21,10 @@
 //     next decode.  A long match occupies its own lane for several turns instead of stalling all 64.
 // 836 bytes of LDS per lane (an odd number of dwords: the lanes' blocks start in different banks), 52 KiB per wave.
 // Nothing sits in private memory (r05: a block header is decoded twice instead of keeping its code lengths in an array).
+//
+// How a block BEGINS is here once for both lane decoders: dynamic_header() and fixed_tables() run over any bit reader with
+// LaneReader's members -- the LDS-ring reader of inflate_stream below, or SegReader of gzip_segments.hpp under inflate_segment and
+// the gunzip's block-start test.  (The two wave decoders still carry a header reader each: inflate_wave_common.hpp says why.)
 #pragma once
 #include "deflate_common.hpp"
 
@@ -54,7 +58,7 @@ MKZ_HD uint32_t load_le32(const uint8_t *p) {
 // The canonical description of a prefix code, as the decoders use it: sorted[] = the symbols in (length, symbol) order; limit[l] =
 // the first left-aligned 15-bit value behind the codewords of length l (ascending in l); base[l] = (rank of the first symbol of
 // length l) - (its first codeword), mod 2^16.  Built by tables_from_counts below (one lane, no arrays) and by wave_build_tables
-// (bgzf_inflate_wave.hip: a whole wave).  A code is refused when it is over-subscribed, or incomplete and not one of the two shapes
+// (inflate_wave_common.hpp: a whole wave).  A code is refused when it is over-subscribed, or incomplete and not one of the two shapes
 // zlib's inflate_table accepts: no codeword at all, or -- literal / length and distance codes -- exactly one codeword of length 1.
 
 MKZ_HD uint32_t bit_reverse32(uint32_t v) {
@@ -195,166 +199,204 @@ MKZ_HD uint32_t cl_decode(uint32_t bits, const ClCode &t) {
     return sym << 4 | l;
 }
 
+// ---- the lane's bit reader: the stream through a ring of kWinWords dwords in the lane's table block ------------------------------
+// wpos = stream offset of the next dword to load, wr / rd = dwords loaded / handed to the bit buffer.  Dwords behind n_in + 8 are
+// not loaded (zeros stand for them): a stream that takes one of those has run out, a valid one never does.  The ring is topped up
+// by the token loop's cadence (every 8th turn, all lanes together); need32() tops it up itself only when it finds it empty.
+// The header functions below take any reader with these members (SegReader of gzip_segments.hpp is the other one); when a stream
+// has run out is each reader's own rule.
+struct LaneReader {
+    uint32_t *win;
+    const uint8_t *in;
+    uint32_t n_in;
+    uint32_t wpos, wr, rd;
+    uint64_t bitbuf;
+    uint32_t bitcnt;
+
+    MKZ_HD void topup() {
+        for (int k = 0; k < kWinWords; ++k)
+            if (wr - rd < (uint32_t)kWinWords) {
+                win[wr & (kWinWords - 1)] = wpos <= n_in + 8 ? load_le32(in + wpos) : 0u;
+                ++wr, wpos += 4;
+            }
+    }
+    MKZ_HD void need32() {  // >= 32 valid bits in the buffer
+        if (bitcnt < 32) {
+            if (rd == wr) topup();
+            bitbuf |= (uint64_t)win[rd & (kWinWords - 1)] << bitcnt;
+            ++rd, bitcnt += 32;
+        }
+    }
+    MKZ_HD void take(uint32_t n) { bitbuf >>= n, bitcnt -= n; }
+    MKZ_HD uint32_t taken() const { return wpos - 4 * (wr - rd); }  // stream bytes handed to the bit buffer
+    MKZ_HD bool ran_out() const { return taken() > n_in + 8; }
+    MKZ_HD uint64_t bitpos() const { return (uint64_t)taken() * 8 - bitcnt; }  // bits consumed so far
+    MKZ_HD void seek(uint64_t bit) {
+        bitbuf = 0, bitcnt = 0, wpos = (uint32_t)(bit >> 3), wr = 0, rd = 0;
+        need32();
+        take((uint32_t)bit & 7u);
+    }
+};
+
+// completeness of a code from its counts per length (Pack15 fields): 0 complete, 1 over-subscribed, 2 incomplete
+MKZ_HD int p15_kraft(uint64_t a, uint64_t b, uint64_t c) {
+    int left = 1;
+    for (uint32_t l = 1; l <= (uint32_t)kMaxBits; ++l) {
+        left = (left << 1) - (int)p15_get(a, b, c, l);
+        if (left < 0) return 1;
+    }
+    return left > 0 ? 2 : 0;
+}
+
+// A dynamic block's header at the reader's position (behind BFINAL / BTYPE), the two passes described above.  t != nullptr: the
+// decode tables are built into t (the layout above) with the decoder's rules (zlib's).  t == nullptr: only checked, registers only,
+// one pass -- strict: what a block start must look like for the gunzip's search to believe it (complete codes).  Returns 0 or a
+// negative kInf* code.  (HLIT / HDIST / HCLEN are in the bit buffer already: the caller took BFINAL / BTYPE off 32 bits, or off
+// what a seek left.)
+template <class Reader>
+MKZ_HD int dynamic_header(Reader &r, uint16_t *t) {
+    const uint32_t hlit = ((uint32_t)r.bitbuf & 31u) + 257, hdist = ((uint32_t)(r.bitbuf >> 5) & 31u) + 1, hclen = ((uint32_t)(r.bitbuf >> 10) & 15u) + 4;
+    r.take(14);
+    if (hlit > 286 || hdist > 30) return kInfBadLengths;
+    uint64_t cl = 0;  // the code-length code: 19 lengths of 3 bits, indexed by symbol
+    for (uint32_t i = 0; i < hclen; ++i) {
+        r.need32();
+        cl |= (uint64_t)((uint32_t)r.bitbuf & 7u) << (3 * cl_order_at(i));
+        r.take(3);
+    }
+    ClCode clc;
+    if (cl_build(cl, clc)) return kInfBadLengths;
+    if (!t && cl == 0) return kInfBadLengths;  // (a block start without any code-length codeword is not one)
+    const uint64_t lens_at = r.bitpos();       // where the code lengths begin: pass 2 starts here again
+    uint64_t la = 0, lb = 0, lc = 0, da = 0, db = 0, dc = 0;  // (Pack15 each) pass 1: codewords per length; pass 2: the next free rank of every length
+    uint32_t ll_used = 0, d_used = 0;
+    bool has_eob = false;
+    uint16_t *const ll_sorted = t ? t + kOffLlSorted : nullptr, *const d_sorted = t ? t + kOffDSorted : nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            if (!has_eob) return kInfBadLengths;  // no end-of-block codeword
+            if (!t) {  // a block start: both codes as a compressor writes them
+                if (p15_kraft(la, lb, lc) != 0) return kInfBadLengths;
+                if (d_used > 1 && p15_kraft(da, db, dc) != 0) return kInfBadLengths;
+                if (d_used == 1 && p15_get(da, db, dc, 1) != 1) return kInfBadLengths;
+                return 0;
+            }
+            if (tables_from_counts(la, lb, lc, ll_used, t + kOffLlLimit, t + kOffLlBase, true)) return kInfBadLengths;
+            if (tables_from_counts(da, db, dc, d_used, t + kOffDLimit, t + kOffDBase, true)) return kInfBadLengths;
+            r.seek(lens_at);
+        }
+        uint32_t i = 0, prev = 0;
+        while (i < hlit + hdist) {
+            r.need32();
+            if (r.ran_out()) return kInfTruncated;
+            const uint32_t e = cl_decode((uint32_t)r.bitbuf, clc);
+            if (e == 0) return kInfBadLengths;
+            r.take(e & 15u);
+            const uint32_t sym = e >> 4;
+            uint32_t rep = 1, val = sym;
+            if (sym == 16) {
+                if (i == 0) return kInfBadLengths;
+                val = prev;
+                rep = 3 + ((uint32_t)r.bitbuf & 3u);
+                r.take(2);
+            } else if (sym == 17) {
+                val = 0;
+                rep = 3 + ((uint32_t)r.bitbuf & 7u);
+                r.take(3);
+            } else if (sym == 18) {
+                val = 0;
+                rep = 11 + ((uint32_t)r.bitbuf & 127u);
+                r.take(7);
+            }
+            if (i + rep > hlit + hdist) return kInfBadLengths;
+            if (val) {  // (rep <= 6 here: runs of a non-zero length come from symbol 16 or are single)
+                for (uint32_t j = i; j < i + rep; ++j) {
+                    const bool lit = j < hlit;
+                    const uint32_t symbol = lit ? j : j - hlit;
+                    if (pass == 0) {
+                        if (lit) ++ll_used, has_eob = has_eob || symbol == 256;
+                        else ++d_used;
+                    } else if (lit) {
+                        ll_sorted[p15_get(la, lb, lc, val)] = (uint16_t)symbol;
+                    } else {
+                        d_sorted[p15_get(da, db, dc, val)] = (uint16_t)symbol;
+                    }
+                    if (lit) p15_add(la, lb, lc, val, 1);  // (pass 1 counts, pass 2 moves on to the next rank: the same step)
+                    else p15_add(da, db, dc, val, 1);
+                }
+            }
+            prev = val, i += rep;
+        }
+    }
+    return 0;
+}
+
+// the tables of the fixed code (RFC 1951 3.2.6) into t: lengths 7 (256..279), 8 (0..143, 280..287), 9 (144..255); 32 distance
+// codewords of 5 bits (symbols 30 and 31 complete the code and are refused when met)
+MKZ_HD void fixed_tables(uint16_t *t) {
+    uint64_t ca = 0, cb = 0, cc = 0;
+    p15_add(ca, cb, cc, 7, 24), p15_add(ca, cb, cc, 8, 152), p15_add(ca, cb, cc, 9, 112);
+    (void)tables_from_counts(ca, cb, cc, 288, t + kOffLlLimit, t + kOffLlBase, true);
+    // rank k -> symbol: 256..279, then 0..143, then 280..287, then 144..255
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+    for (uint32_t k = 0; k < 288; ++k) t[kOffLlSorted + k] = (uint16_t)(k < 24 ? 256 + k : k < 168 ? k - 24 : k < 176 ? k + 112 : k - 32);
+    ca = cb = cc = 0;
+    p15_add(ca, cb, cc, 5, 32);
+    (void)tables_from_counts(ca, cb, cc, 32, t + kOffDLimit, t + kOffDBase, true);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+    for (uint32_t k = 0; k < 32; ++k) t[kOffDSorted + k] = (uint16_t)k;
+}
+
 // in[0, n_in): the raw DEFLATE stream (readable up to in + n_in + kStreamPad); out[0, n_out): exactly what it must
 // inflate to (ISIZE of the BGZF member), readable up to out + n_out + 8 (match copies load whole 8-byte words; nothing is
 // written outside out[0, n_out)).  t: this decoder's kLaneTableU16 16-bit words (4-byte aligned).
 MKZ_HD int inflate_stream(const uint8_t *in, uint32_t n_in, uint8_t *out, uint32_t n_out, uint16_t *t) {
-    uint16_t *const ll_sorted = t + kOffLlSorted, *const d_sorted = t + kOffDSorted, *const ll_limit = t + kOffLlLimit, *const ll_base = t + kOffLlBase,
-                    *const d_limit = t + kOffDLimit, *const d_base = t + kOffDBase;
-    uint32_t *const win = reinterpret_cast<uint32_t *>(t + kOffWin);
+    const uint16_t *const ll_sorted = t + kOffLlSorted, *const d_sorted = t + kOffDSorted, *const ll_limit = t + kOffLlLimit, *const ll_base = t + kOffLlBase,
+                          *const d_limit = t + kOffDLimit, *const d_base = t + kOffDBase;
     uint8_t *op = out, *const out_end = out + n_out;
-    uint64_t bitbuf = 0;
-    uint32_t bitcnt = 0;
-    // the window: a ring of kWinWords dwords of the stream.  wpos = stream offset of the next dword to load, wr / rd =
-    // dwords loaded / handed to the bit buffer.  Dwords behind n_in + 8 are not loaded (zeros stand for them): a stream
-    // that takes one of those has run out (MKZ_RAN_OUT), a valid one never does.
-    uint32_t wpos = 0, wr = 0, rd = 0;
+    LaneReader r;
+    r.win = reinterpret_cast<uint32_t *>(t + kOffWin), r.in = in, r.n_in = n_in;
+    r.bitbuf = 0, r.bitcnt = 0, r.wpos = 0, r.wr = 0, r.rd = 0;
     uint32_t turn = 0;  // token turns of this stream: the window is topped up by all lanes together every 8th
-#define MKZ_TOPUP()                                                                                   \
-    do {                                                                                              \
-        for (int k_ = 0; k_ < kWinWords; ++k_)                                                        \
-            if (wr - rd < (uint32_t)kWinWords) {                                                      \
-                win[wr & (kWinWords - 1)] = wpos <= n_in + 8 ? load_le32(in + wpos) : 0u;             \
-                ++wr, wpos += 4;                                                                      \
-            }                                                                                         \
-    } while (0)
-// >= 32 valid bits in the buffer (the top-up inside is the exception: the cadence of the token loop keeps the ring filled)
-#define MKZ_NEED32()                                            \
-    do {                                                        \
-        if (bitcnt < 32) {                                      \
-            if (rd == wr) MKZ_TOPUP();                          \
-            bitbuf |= (uint64_t)win[rd & (kWinWords - 1)] << bitcnt; \
-            ++rd, bitcnt += 32;                                 \
-        }                                                       \
-    } while (0)
-#define MKZ_TAKEN() (wpos - 4 * (wr - rd))  // stream bytes handed to the bit buffer
-#define MKZ_RAN_OUT() (MKZ_TAKEN() > n_in + 8)
-#define MKZ_TAKE(n) (bitbuf >>= (n), bitcnt -= (n))
     for (;;) {
-        MKZ_NEED32();
-        if (MKZ_RAN_OUT()) return kInfTruncated;
-        const uint32_t final_block = (uint32_t)bitbuf & 1u, type = ((uint32_t)bitbuf >> 1) & 3u;
-        MKZ_TAKE(3);
+        r.need32();
+        if (r.ran_out()) return kInfTruncated;
+        const uint32_t final_block = (uint32_t)r.bitbuf & 1u, type = ((uint32_t)r.bitbuf >> 1) & 3u;
+        r.take(3);
         if (type == 0) {  // stored: skip to the byte boundary, LEN, ~LEN, bytes
-            MKZ_TAKE(bitcnt & 7);
-            MKZ_NEED32();
-            const uint32_t len = (uint32_t)bitbuf & 0xffffu, nlen = ((uint32_t)(bitbuf >> 16)) & 0xffffu;
-            MKZ_TAKE(32);
+            r.take(r.bitcnt & 7);
+            r.need32();
+            const uint32_t len = (uint32_t)r.bitbuf & 0xffffu, nlen = ((uint32_t)(r.bitbuf >> 16)) & 0xffffu;
+            r.take(32);
             if ((len ^ nlen) != 0xffffu) return kInfBadStored;
             // the bytes follow in the stream: what the bit buffer was handed, minus what it still holds
-            const uint32_t pos = MKZ_TAKEN() - (bitcnt >> 3);
-            if (MKZ_RAN_OUT() || pos > n_in || len > n_in - pos) return kInfTruncated;
+            const uint32_t pos = r.taken() - (r.bitcnt >> 3);
+            if (r.ran_out() || pos > n_in || len > n_in - pos) return kInfTruncated;
             if (len > (uint32_t)(out_end - op)) return kInfOutputOverrun;
             const uint8_t *p = in + pos;
             uint32_t i = 0;
             for (; i + 8 <= len; i += 8) store_le64(op + i, load_le64(p + i));
             for (; i < len; ++i) op[i] = p[i];
             op += len;
-            bitbuf = 0, bitcnt = 0, wpos = pos + len, wr = 0, rd = 0;  // the next block starts behind them
+            // the next block starts behind them (seek() refills at once what the loop's head would refill: the same positions and
+            // the same run-out answers; behind a FINAL stored block it is one ring fill that goes unused)
+            r.seek((uint64_t)(pos + len) * 8);
             if (final_block) break;
             continue;
         }
         if (type == 3) return kInfBadBlockType;
         if (type == 1) {
-            // the fixed code of RFC 1951 3.2.6: lengths 7 (256..279), 8 (0..143, 280..287), 9 (144..255); 32 distance codewords of
-            // 5 bits (symbols 30 and 31 complete the code and are refused when met)
-            uint64_t ca = 0, cb = 0, cc = 0;
-            p15_add(ca, cb, cc, 7, 24), p15_add(ca, cb, cc, 8, 152), p15_add(ca, cb, cc, 9, 112);
-            (void)tables_from_counts(ca, cb, cc, 288, ll_limit, ll_base, true);
-            // rank k -> symbol: 256..279, then 0..143, then 280..287, then 144..255
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma nounroll
-#endif
-            for (uint32_t k = 0; k < 288; ++k) ll_sorted[k] = (uint16_t)(k < 24 ? 256 + k : k < 168 ? k - 24 : k < 176 ? k + 112 : k - 32);
-            ca = cb = cc = 0;
-            p15_add(ca, cb, cc, 5, 32);
-            (void)tables_from_counts(ca, cb, cc, 32, d_limit, d_base, true);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma nounroll
-#endif
-            for (uint32_t k = 0; k < 32; ++k) d_sorted[k] = (uint16_t)k;
+            fixed_tables(t);
         } else {
-            const uint32_t hlit = ((uint32_t)bitbuf & 31u) + 257, hdist = ((uint32_t)(bitbuf >> 5) & 31u) + 1,
-                           hclen = ((uint32_t)(bitbuf >> 10) & 15u) + 4;
-            MKZ_TAKE(14);
-            if (hlit > 286 || hdist > 30) return kInfBadLengths;
-            // the code-length code: 19 lengths of 3 bits, sent in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-            uint64_t cl = 0;
-            {
-                const uint64_t order_lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 |
-                                          5ull << 45 | 11ull << 50 | 4ull << 55;
-                const uint64_t order_hi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
-                for (uint32_t i = 0; i < hclen; ++i) {
-                    MKZ_NEED32();
-                    const uint32_t sym = (uint32_t)((i < 12 ? order_lo >> (5 * i) : order_hi >> (5 * (i - 12))) & 31u);
-                    cl |= (uint64_t)((uint32_t)bitbuf & 7u) << (3 * sym);
-                    MKZ_TAKE(3);
-                }
-            }
-            ClCode clc;
-            if (cl_build(cl, clc)) return kInfBadLengths;
-            // where the code lengths begin, in bits of the stream: pass 2 starts here again
-            const uint64_t lens_at = (uint64_t)MKZ_TAKEN() * 8 - bitcnt;
-            uint64_t la = 0, lb = 0, lc = 0, da = 0, db = 0, dc = 0;  // (Pack15 each) pass 1: codewords per length; pass 2: the next free rank of every length
-            uint32_t ll_used = 0, d_used = 0;
-            bool has_eob = false;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma nounroll
-#endif
-            for (int pass = 0; pass < 2; ++pass) {
-                if (pass == 1) {
-                    if (!has_eob) return kInfBadLengths;  // no end-of-block codeword
-                    if (tables_from_counts(la, lb, lc, ll_used, ll_limit, ll_base, true)) return kInfBadLengths;
-                    if (tables_from_counts(da, db, dc, d_used, d_limit, d_base, true)) return kInfBadLengths;
-                    // back to the first code length
-                    const uint32_t byte = (uint32_t)(lens_at >> 3);
-                    bitbuf = 0, bitcnt = 0, wpos = byte, wr = 0, rd = 0;
-                    MKZ_NEED32();
-                    MKZ_TAKE((uint32_t)lens_at & 7u);
-                }
-                uint32_t i = 0, prev = 0;
-                while (i < hlit + hdist) {
-                    MKZ_NEED32();
-                    if (MKZ_RAN_OUT()) return kInfTruncated;
-                    const uint32_t e = cl_decode((uint32_t)bitbuf, clc);
-                    if (e == 0) return kInfBadLengths;
-                    MKZ_TAKE(e & 15u);
-                    const uint32_t sym = e >> 4;
-                    uint32_t rep = 1, val = sym;
-                    if (sym == 16) {
-                        if (i == 0) return kInfBadLengths;
-                        val = prev;
-                        rep = 3 + ((uint32_t)bitbuf & 3u);
-                        MKZ_TAKE(2);
-                    } else if (sym == 17) {
-                        val = 0;
-                        rep = 3 + ((uint32_t)bitbuf & 7u);
-                        MKZ_TAKE(3);
-                    } else if (sym == 18) {
-                        val = 0;
-                        rep = 11 + ((uint32_t)bitbuf & 127u);
-                        MKZ_TAKE(7);
-                    }
-                    if (i + rep > hlit + hdist) return kInfBadLengths;
-                    if (val) {  // (rep <= 6 here: runs of a non-zero length come from symbol 16 or are single)
-                        for (uint32_t j = i; j < i + rep; ++j) {
-                            const bool lit = j < hlit;
-                            const uint32_t symbol = lit ? j : j - hlit;
-                            if (pass == 0) {
-                                if (lit) ++ll_used, has_eob = has_eob || symbol == 256;
-                                else ++d_used;
-                            } else if (lit) {
-                                ll_sorted[p15_get(la, lb, lc, val)] = (uint16_t)symbol;
-                            } else {
-                                d_sorted[p15_get(da, db, dc, val)] = (uint16_t)symbol;
-                            }
-                            if (lit) p15_add(la, lb, lc, val, 1);  // (pass 1 counts, pass 2 moves on to the next rank: the same step)
-                            else p15_add(da, db, dc, val, 1);
-                        }
-                    }
-                    prev = val, i += rep;
-                }
-            }
+            const int rc = dynamic_header(r, t);
+            if (rc) return rc;
         }
         // Symbols of this block.  One token per turn of the loop, and a turn never waits for memory it has just asked
         // for (the 64 lanes of a wave turn together: whatever one of them waits for, all wait for):
@@ -372,14 +414,14 @@ MKZ_HD int inflate_stream(const uint8_t *in, uint32_t n_in, uint8_t *out, uint32
         uint64_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;
         int status = 1;  // 1 = in the block, 0 = end of block, < 0 = error
         while (status == 1) {
-            if ((turn++ & 7u) == 0) MKZ_TOPUP();
+            if ((turn++ & 7u) == 0) r.topup();
             bool literal = false;
             if (pend == 0) {
-                MKZ_NEED32();
-                const uint32_t e = decode_codeword((uint32_t)bitbuf, ll_sorted, ll_limit, ll_base);
-                MKZ_TAKE(e & 15u);
+                r.need32();
+                const uint32_t e = decode_codeword((uint32_t)r.bitbuf, ll_sorted, ll_limit, ll_base);
+                r.take(e & 15u);
                 const uint32_t sym = e >> 4;
-                if (e == 0 || MKZ_RAN_OUT()) {
+                if (e == 0 || r.ran_out()) {
                     status = e == 0 ? kInfBadSymbol : kInfTruncated;
                 } else if (sym < 256) {
                     if (op == out_end) status = kInfOutputOverrun;
@@ -391,15 +433,15 @@ MKZ_HD int inflate_stream(const uint8_t *in, uint32_t n_in, uint8_t *out, uint32
                 } else {
                     const uint32_t idx = sym - 257;
                     const uint32_t leb = length_extra_bits(idx);
-                    const uint32_t len = length_base(idx) + ((uint32_t)bitbuf & ((1u << leb) - 1));
-                    MKZ_TAKE(leb);
-                    MKZ_NEED32();
-                    const uint32_t d = decode_codeword((uint32_t)bitbuf, d_sorted, d_limit, d_base);
-                    MKZ_TAKE(d & 15u);
+                    const uint32_t len = length_base(idx) + ((uint32_t)r.bitbuf & ((1u << leb) - 1));
+                    r.take(leb);
+                    r.need32();
+                    const uint32_t d = decode_codeword((uint32_t)r.bitbuf, d_sorted, d_limit, d_base);
+                    r.take(d & 15u);
                     const uint32_t dsym = d >> 4;
                     const uint32_t deb = dsym < 30 ? distance_extra_bits(dsym) : 0;
-                    const uint32_t dist = dsym < 30 ? distance_base(dsym) + ((uint32_t)bitbuf & ((1u << deb) - 1)) : 0;
-                    MKZ_TAKE(deb);
+                    const uint32_t dist = dsym < 30 ? distance_base(dsym) + ((uint32_t)r.bitbuf & ((1u << deb) - 1)) : 0;
+                    r.take(deb);
                     if (d == 0 || dsym > 29) status = kInfBadSymbol;
                     else if (dist > (uint32_t)(op - out)) status = kInfBadDistance;
                     else if (len > (uint32_t)(out_end - op)) status = kInfOutputOverrun;
@@ -445,16 +487,11 @@ MKZ_HD int inflate_stream(const uint8_t *in, uint32_t n_in, uint8_t *out, uint32
             }
         }
         if (status < 0) return status;
-        if (MKZ_RAN_OUT()) return kInfTruncated;
+        if (r.ran_out()) return kInfTruncated;
         if (final_block) break;
     }
     // bits consumed must lie inside the stream
-    if (MKZ_RAN_OUT() || (uint64_t)MKZ_TAKEN() - (bitcnt >> 3) > (uint64_t)n_in) return kInfTruncated;
-#undef MKZ_TOPUP
-#undef MKZ_NEED32
-#undef MKZ_TAKEN
-#undef MKZ_RAN_OUT
-#undef MKZ_TAKE
+    if (r.ran_out() || (uint64_t)r.taken() - (r.bitcnt >> 3) > (uint64_t)n_in) return kInfTruncated;
     return op == out_end ? 0 : kInfOutputShort;
 }
 

@@ -1,6 +1,14 @@
 // inflate_wave_common.hpp -- what the wave-uniform DEFLATE decoders share (bgzf_inflate_wave.hip: a wave per BGZF member;
 // gzip_segments_wave.hip: a wave per piece of a gzip stream): canonical tables built by all lanes, the direct tables whose entries
-// carry everything a token turn needs.  RFC 1951.
+// carry everything a token turn needs, and the struct that holds them (WaveTables).  RFC 1951.
+// The bit reader and the set-up of a block (code lengths -> tables) are NOT here: each decoder carries its own copy, as macros over
+// locals.  One reader struct and one wave_block_tables() for both were built and measured against these copies
+// (profiles/inflate_header_refactor.txt, series 1, with the patch beside it): same LDS, same waves per SIMD, but 4-6 more VGPRs and
+// two more spilled SGPRs in kernels that the scalar unit bounds -- the BGZF kernels 2-4 % slower on zlib level-6 members (256 MB
+// with the 2 KiB ring 8.92 -> 9.20 ms), the gunzip's pieces 43.1 -> 45.7 ms on gzip -1 FASTQ (gzip -6: 31.3 -> 32.9, inside the
+// parent's spread).  These kernels answer to any change of their text: the order constants alone, read through cl_order_at() in
+// the BGZF kernel, cost its 8 KiB ring 3-4 % at equal register counts (series 2), so that file keeps them inline.  The lane
+// decoders do share their header reader (dynamic_header(), inflate_serial.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,6 +100,18 @@ __device__ void wave_fill_fast_d(uint32_t *fast, const uint16_t *sorted, const u
     }
 }
 
+// everything a wave decoder keeps per block, in LDS
+struct WaveTables {
+    // direct tables for codewords of <= 10 / 9 bits (else 0), everything a token turn needs in ONE read (r05: the decoders are bound by
+    // their scalar instructions -- 107 per token, 1 M per member, one scalar unit per CU --, so what can be looked up is not computed):
+    // ll_fast: a literal or end-of-block = symbol << 4 | codeword length (< 0x8000); a length symbol = 0x8000 | (base - 3) << 7 |
+    // extra bits << 4 | codeword length.  d_fast: distance base << 8 | extra bits << 4 | codeword length.
+    uint16_t ll_fast[1 << kFastLl];
+    uint32_t d_fast[1 << kFastD];
+    uint16_t ll_limit[16], ll_base[16], d_limit[16], d_base[16];
+    uint16_t ll_sorted[288], d_sorted[32];
+    uint8_t lens[320];  // code lengths of the block being set up: literal / length [0, 288), distance [288, 320)
+};
 
 }  // namespace
 }  // namespace mkz

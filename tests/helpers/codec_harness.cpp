@@ -2,6 +2,9 @@
 // (merkurio_amd/csrc/codec/*.hpp), driven by tests/test_codec_cpu.py against zlib:
 //   inflate <container> <out>   container = records {u32 n_in, u32 n_out, n_in bytes of raw DEFLATE}; writes the
 //                               inflated bytes of every record back to back, prints one status per record
+//   both <container>            every record through inflate_stream and, as one piece from bit 0 to the final block, through
+//                               inflate_segment (gzip_segments.hpp); prints "status status same" per record, same = both are 0 and
+//                               the piece's symbols are the stream's bytes
 //   deflate <in> <block> <out>  cuts <in> into blocks, encodes each as ONE dynamic DEFLATE block with the shared code
 //                               builder / header writer over a plain greedy parse; container {u32 n, bytes} out
 //   crc <in> <pieces>           CRC-32 folded from <pieces> pieces, as the kernels fold the lanes' pieces
@@ -13,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "codec/gzip_segments.hpp"
 #include "codec/inflate_serial.hpp"
 
 static std::vector<uint8_t> slurp(const char *path) {
@@ -46,6 +50,34 @@ static int do_inflate(const char *in_path, const char *out_path) {
         fwrite(out.data(), 1, n_out, o);
     }
     fclose(o);
+    return 0;
+}
+
+// the two lane decoders side by side: one block-header reader (inflate_serial.hpp) over two bit readers
+static int do_both(const char *in_path) {
+    std::vector<uint8_t> c = slurp(in_path);
+    size_t at = 0;
+    std::vector<uint32_t> lane(mkz::kLaneTableU16 / 2);
+    const uint64_t cap = 131072;
+    std::vector<uint16_t> sym(mkz::kSegPrefix + cap + mkz::kSegSlack);
+    while (at + 8 <= c.size()) {
+        uint32_t n_in, n_out;
+        memcpy(&n_in, &c[at], 4), memcpy(&n_out, &c[at + 4], 4);
+        at += 8;
+        std::vector<uint8_t> in(c.begin() + at, c.begin() + at + n_in);
+        in.resize(n_in + mkz::kStreamPad, 0);
+        at += n_in;
+        std::vector<uint8_t> out(n_out + 8, 0xee);
+        uint16_t *const t = reinterpret_cast<uint16_t *>(lane.data());
+        const int rc = mkz::inflate_stream(in.data(), n_in, out.data(), n_out, t);
+        for (uint32_t k = 0; k < mkz::kSegPrefix; ++k) sym[k] = (uint16_t)(mkz::kSegUnknown | k);
+        uint64_t n_sym = 0, stop = 0;
+        bool fin = false;
+        const int rs = mkz::inflate_segment(in.data(), n_in, 0, ~0ull, 0, sym.data() + mkz::kSegPrefix, cap, t, &n_sym, &stop, &fin);
+        bool same = rc == 0 && rs == 0 && n_sym == n_out;
+        for (uint64_t i = 0; same && i < n_sym; ++i) same = sym[mkz::kSegPrefix + i] == out[i];  // (all below 256, then)
+        printf("%d %d %d\n", rc, rs, (int)same);
+    }
     return 0;
 }
 
@@ -150,8 +182,9 @@ static int do_crc(const char *in_path, size_t pieces) {
 
 int main(int argc, char **argv) {
     if (argc >= 4 && !strcmp(argv[1], "inflate")) return do_inflate(argv[2], argv[3]);
+    if (argc >= 3 && !strcmp(argv[1], "both")) return do_both(argv[2]);
     if (argc >= 5 && !strcmp(argv[1], "deflate")) return do_deflate(argv[2], (size_t)atol(argv[3]), argv[4]);
     if (argc >= 4 && !strcmp(argv[1], "crc")) return do_crc(argv[2], (size_t)atol(argv[3]));
-    fprintf(stderr, "usage: codec_harness inflate|deflate|crc ...\n");
+    fprintf(stderr, "usage: codec_harness inflate|both|deflate|crc ...\n");
     return 2;
 }

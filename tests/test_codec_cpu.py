@@ -201,6 +201,57 @@ def test_inflate_hand_made_streams_match_zlib(harness, tmp_path):
         at += n_out
 
 
+def _catalogue_records():
+    """(name, stream, n_out) as test_inflate_hand_made_streams_match_zlib asks for them"""
+    import deflate_craft as craft
+    recs = []
+    for name, raw, lenient in craft.CATALOGUE:
+        if name.startswith("ok-"):
+            recs.append((name, raw, len(craft.verdict(raw)[0])))
+        else:
+            for n_out in sorted({len(craft.WRITTEN[name]), len(lenient) if lenient is not None else 1 << 16, 1 << 16}):
+                recs.append((name, raw, n_out))
+    return recs
+
+
+def test_inflate_hand_made_streams_refusal_codes(harness, tmp_path):
+    """WHY the lane decoder refuses each stream of the catalogue: the status per (stream, length asked for) is the one recorded in
+    tests/golden/inflate_lane_status.json before the block-header reader became one function over two bit readers"""
+    import json
+    with open(os.path.join(ROOT, "tests/golden/inflate_lane_status.json")) as f:
+        golden = json.load(f)
+    recs = _catalogue_records()
+    status, _ = run_inflate(harness, tmp_path, [(raw, n_out) for _, raw, n_out in recs])
+    got = {}
+    for (name, _, n_out), s in zip(recs, status):
+        got.setdefault(name, {})[str(n_out)] = s
+    assert got == golden
+
+
+def test_lane_decoders_agree_on_hand_made_streams(harness, tmp_path):
+    """inflate_stream (the LDS-ring reader) and inflate_segment (SegReader; one piece from bit 0, the place-holder prefix in front,
+    131 072 symbols of room) share dynamic_header() / fixed_tables(): every `ok-` stream gives the same text through both, its symbols
+    all bytes; a `bad-` stream refused for its block type, a stored block's LEN, its code lengths or a symbol is refused with the same
+    code by both.  Truncation and distance codes are exempt: the two readers bound the stream differently on purpose, and a match in
+    front of the stream is a place-holder to the piece decoder."""
+    recs = _catalogue_records()
+    cont = tmp_path / "in.bin"
+    with open(cont, "wb") as f:
+        for _, z, n_out in recs:
+            f.write(struct.pack("<II", len(z), n_out) + z)
+    r = subprocess.run([harness, "both", str(cont)], capture_output=True, text=True, check=True)
+    rows = [tuple(int(x) for x in line.split()) for line in r.stdout.splitlines()]
+    assert len(rows) == len(recs)
+    same_code = {-2, -3, -4, -5}  # kInfBadBlockType, kInfBadStored, kInfBadLengths, kInfBadSymbol
+    for (name, _, n_out), (lane, seg, same) in zip(recs, rows):
+        if name.startswith("ok-"):
+            assert (lane, seg, same) == (0, 0, 1), (name, lane, seg, same)
+        else:
+            assert lane != 0, (name, n_out)
+            if lane in same_code:
+                assert seg == lane, (name, n_out, lane, seg)
+
+
 @pytest.fixture(scope="module")
 def gzip_harness(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("gzip") / "gzip_harness")
