@@ -123,7 +123,7 @@ def fl(x):
 # floats inside the rule: ties, both ends, zeros, one digit, six digits, values that round up to the next power of ten
 IN_RULE = [fl(131072.5), fl(131073.5), fl(0.0001), fl(999999.4375), fl(0.0), fl(-0.0), fl(1.0), fl(-1.5), fl(0.1), fl(3.14159274), fl(100000.0), fl(99999.95),
            fl(9.9999995), fl(0.00012345), fl(-524292.0), fl(0.5), fl(2.5), fl(1234.5), fl(0.001), fl(65504.0), struct.pack("<I", 0x38D1B714)]
-SEQ_LENS = (0, 1, 2, 15, 16, 17, 31, 32, 33, 150, 2500)
+SEQ_LENS = (0, 1, 2, 15, 16, 17, 31, 32, 33, 127, 128, 129, 150, 255, 256, 257, 271, 272, 273, 2500)
 
 
 def rand_float(rnd):
