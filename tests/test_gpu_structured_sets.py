@@ -7,7 +7,9 @@ flags under contention, where probe_chain walks beyond its second round, where p
 lane and bucket and drains the hit ring in the middle of a round, where the context kernels see entries of one key with
 different masks, and where order_hits / sets / the tag kernels get a hundred tuples per record.  Every test asserts with
 keys_per_entry(), at the geometry the matcher reports, that its set does stress the table, and from kernel_name that the
-kernel variant it meant to run is the one that ran.  Run on the GPU box with `-m gpu`.
+kernel variant it meant to run is the one that ran.  The cases here name kernel FAMILIES (a part of kernel_name) and between
+them launch well under half of the compiled variants; every variant, by its exact name and on a batch with an occurrence at
+every residue of the stride and a near-miss at every base, is test_gpu_scan_variants.py.  Run on the GPU box with `-m gpu`.
 """
 import functools
 import gzip
