@@ -704,6 +704,32 @@ int mk_bzip2_inflate_device(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t
 int mk_bzip2_info(const mk_codec *c, uint32_t *blocks, float ms[5]);
 int mk_codec_set_bzip2_pass_blocks(mk_codec *c, uint64_t blocks);
 
+/* (an addition to v7; `merkurio extract --device-zstd`) A .zst file decoded on the device, one wave per block (merkurio_amd/csrc/codec/zstd_inflate.hip, zstd_serial.hpp,
+ * zstd_plan.hpp) -- what `merkurio extract` reads through needletail's zstd reader (src/cmd_extract.rs:281).  zs[0, n) is the whole
+ * file: Zstandard frames (RFC 8878) and skippable frames back to back.  The host walks the frame headers and every block header, and
+ * of a compressed block the literals and sequences headers; it names, for every table a block repeats, the bytes that describe it.
+ * Then, a wave per block: the Huffman and FSE tables built in LDS and the literals and sequences decoded; two scans on the host (text
+ * offsets, the three repeat offsets in front of every block, composed from each block's symbolic effect on them); the text written,
+ * a match that reaches in front of its block leaving the text position it copies from; rounds of pointer doubling over those
+ * positions, at most log2(blocks) + 2; and per frame that carries one the content checksum, XXH64 on the host over the text as it
+ * is downloaded.
+ * *taken = 1 only when frames, skippable ones included, cover zs[0, n) with nothing left over, every size agrees and every checksum
+ * agrees: the text of all frames then lies back to back where mk_gzip_inflate_device leaves its text (mk_gzip_text_read / _device /
+ * _release, mk_window_source::device_text), *n_blocks says how many blocks it came from (an empty frame: 0 blocks, 0 bytes).
+ * *taken = 0 (MK_OK, nothing else touched) means the caller runs libzstd, which also words the error: a legacy or unknown magic, a
+ * reserved bit in the frame header descriptor, a dictionary id other than 0, a window above 2^27 bytes, a block above min(window,
+ * 128 KiB), a compressed block under 3 bytes or of 128 KiB and more, the Reserved block type, Huffman weights that do not sum to a power of two or need more than 11 bits, an FSE description
+ * whose probabilities do not add up or whose accuracy log is out of range, Repeat or treeless with nothing to repeat, a bitstream
+ * that does not end exactly at its first bit, more literals asked for than there are, an offset of zero, in front of the frame's first
+ * byte or beyond the window, a block that regenerates more than 128 KiB, a content size or checksum that disagrees, trailing bytes that
+ * start no frame, data that ends early, 4 GiB of text and more, more rounds than the cap, text plus scratch (8 bytes per text byte)
+ * beyond half of the free device memory, any device error.  With a gzip or bzip2 stream open on the handle: MK_E_INVALID_ARG.
+ * Everything here is sized by the file.
+ * mk_zstd_info: blocks, frames and resolution rounds of the last call and its phases in milliseconds: upload, tables + entropy
+ * decode, scans, execution, cross-block rounds, checksum. */
+int mk_zstd_inflate_device(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
+int mk_zstd_info(const mk_codec *c, uint32_t *blocks, uint32_t *frames, uint32_t *rounds, float ms[6]);
+
 /* (v7) A .bz2 file of ANY size, decoded on the device window by window: nothing on the device is sized by the file.  The contract is
  * mk_gzip_stream_*'s (below).  mk_bzip2_stream_begin: bz[0, n) = the whole file (the caller's -- the mapped file -- until _end);
  * window_bytes = compressed bytes per window (0 = 256 MiB, an unmeasured choice: profiles/e2e_bunzip2_windows.txt).  *taken = 0: no

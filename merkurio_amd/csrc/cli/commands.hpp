@@ -39,6 +39,7 @@ struct CommonArgs {
 constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
 
 constexpr uint64_t kGzipWindow = 256ull << 20;  // (an unmeasured choice: README, "Gunzip window by window")
+constexpr uint64_t kZstdWindow = 256ull << 20;   // (an unmeasured choice, like its siblings: profiles/e2e_unzstd.txt)
 constexpr uint64_t kBzip2Window = 256ull << 20;  // (an unmeasured choice: README, "Bunzip2 window by window"; profiles/e2e_bunzip2_windows.txt)
 
 struct ExtractArgs : CommonArgs {
@@ -54,6 +55,10 @@ struct ExtractArgs : CommonArgs {
     uint64_t gzip_window = kGzipWindow;
     // --bzip2-window: likewise for a .bz2 input (mk_bzip2_stream_*; a smaller one: mk_bzip2_inflate_device)
     uint64_t bzip2_window = kBzip2Window;
+    // --device-zstd: a .zst input of at most --zstd-window compressed bytes is decoded on the device in one call
+    // (mk_zstd_inflate_device); a larger one, and every .zst input without the flag, is libzstd's.  Opt-in: the path has not been timed
+    bool device_zstd = false;
+    uint64_t zstd_window = kZstdWindow;
 };
 
 struct TagArgs : CommonArgs {

@@ -204,6 +204,34 @@ void inflate_zstd(const std::string &path, const unsigned char *d, size_t n, std
 
 }  // namespace
 
+bool zstd_first_bytes(const unsigned char *d, size_t n, std::vector<char> &out, size_t want) {
+    out.clear();
+    void *h = open_any({"libzstd.so.1", "libzstd.so"});
+    if (!h) return false;
+    auto create = (void *(*)())dlsym(h, "ZSTD_createDStream");
+    auto free_ = (size_t (*)(void *))dlsym(h, "ZSTD_freeDStream");
+    auto run = (size_t (*)(void *, ZSTD_outBuffer *, ZSTD_inBuffer *))dlsym(h, "ZSTD_decompressStream");
+    auto is_err = (unsigned (*)(size_t))dlsym(h, "ZSTD_isError");
+    if (!create || !free_ || !run || !is_err) return false;
+    void *z = create();
+    if (!z) return false;
+    out.resize(want);
+    ZSTD_inBuffer in{d, n, 0};
+    ZSTD_outBuffer ob{out.data(), want, 0};
+    bool ok = true;
+    while (ob.pos < ob.size && in.pos < in.size) {  // (frames may be empty or skippable: on to the next)
+        const size_t before_in = in.pos, before_out = ob.pos;
+        if (is_err(run(z, &ob, &in))) {
+            ok = false;
+            break;
+        }
+        if (in.pos == before_in && ob.pos == before_out) break;
+    }
+    free_(z);
+    out.resize(ob.pos);
+    return ok;
+}
+
 bool inflate_by_magic(const std::string &path, const unsigned char *d, size_t n, std::vector<char> &out) {
     if (n >= 3 && !memcmp(d, "BZh", 3)) {
         inflate_bz2(path, d, n, out);

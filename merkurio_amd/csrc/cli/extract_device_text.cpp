@@ -1,5 +1,5 @@
 // extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
-// inflated in one piece or member by member, or of a bzip2 file (windows are ranges of it), and a gzip or bzip2 file decoded window by
+// inflated in one piece or member by member, or of a bzip2 or (--device-zstd) zstd file (windows are ranges of it), and a gzip or bzip2 file decoded window by
 // window (mk_gzip_stream_*, mk_bzip2_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
 // "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
 #include <hip/hip_runtime_api.h>
@@ -165,8 +165,8 @@ struct DeviceStream : DeviceText {
 }  // namespace
 
 std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t stream_window, Gate &g) {
-    const bool bz = f.s.raw_is_bzip2();
-    if (!bz && !f.s.raw_is_gzip()) return nullptr;
+    const bool bz = f.s.raw_is_bzip2(), zs = f.s.raw_is_zstd();
+    if (!bz && !zs && !f.s.raw_is_gzip()) return nullptr;
     const uint8_t *z = f.s.source().file_bytes();
     const uint64_t n = f.s.source().file_size();
     double t0 = PhaseTimer::now();
@@ -174,7 +174,24 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (bz && n > stream_window) {
+    if (zs) {
+        // --device-zstd: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- anything it
+        // refuses, a damaged file, no room -- and a file of more compressed bytes than --zstd-window, libzstd reads whole, as
+        // without the flag, and words the error
+        uint64_t blocks = 0;
+        if (n <= stream_window && mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        if (codec && mk_zstd_inflate_device(codec, z, n, &text_bytes, &taken, &blocks) != MK_OK) taken = 0;
+        if (g.timing && taken) {
+            float ms6[6] = {0, 0, 0, 0, 0, 0};
+            uint32_t frames = 0, rounds = 0;
+            (void)mk_zstd_info(codec, nullptr, &frames, &rounds, ms6);
+            fprintf(stderr, "[timing]   zstd on the device: %llu blocks, %u frames, %u rounds, upload %.1f, tables + entropy decode %.1f, scans %.1f, execution %.1f, cross-block rounds %.1f, checksum %.1f ms (input %d: %llu text bytes, %.3f s)\n",
+                    (unsigned long long)blocks, frames, rounds, ms6[0], ms6[1], ms6[2], ms6[3], ms6[4], ms6[5], i, (unsigned long long)text_bytes, PhaseTimer::now() - t0);
+        } else if (g.timing) {
+            fprintf(stderr, "[timing]   zstd input %d: NOT taken by the device after %.3f s (%s; libzstd reads it)\n", i, PhaseTimer::now() - t0,
+                    n > stream_window ? "more compressed bytes than --zstd-window" : "handed back");
+        }
+    } else if (bz && n > stream_window) {
         // more than one bzip2 window: decoded window by window as the text windows reach it, device memory bounded by the window; what
         // the stream does not take, from whichever window on, is libbz2's
         if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;

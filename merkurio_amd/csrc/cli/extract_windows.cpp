@@ -197,13 +197,13 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     int kind[2] = {-1, -1};
     for (int i = 0; i < J.n_in; ++i) {
         xw::InputFile &I = J.in[i];
-        I.s.open(I.path, !a.host_codec);
-        if (I.s.raw_is_bzip2()) {
+        I.s.open(I.path, !a.host_codec, !a.host_codec && a.device_zstd);
+        if (I.s.raw_is_deferred()) {
             // not inflated here: run() hands the file to the device once the HIP runtime is up.  What its records are is read from
-            // the start of the first block's text (libbz2); where that does not say (an empty first stream, a damaged file), libbz2
-            // reads the whole file now, as under --host-codec, and words what is wrong with it
+            // the start of the first block's text (libbz2; libzstd for a .zst input under --device-zstd); where that does not say (an
+            // empty first stream, a damaged file), the library reads the whole file now, as under --host-codec, and words what is wrong with it
             std::vector<char> first;
-            if (bz2_first_bytes(I.s.source().file_bytes(), I.s.source().file_size(), first, 1u << 16))
+            if ((I.s.raw_is_zstd() ? zstd_first_bytes : bz2_first_bytes)(I.s.source().file_bytes(), I.s.source().file_size(), first, 1u << 16))
                 for (char ch : first)
                     if (ch != '\n' && ch != '\r') {
                         kind[i] = (unsigned char)ch;
@@ -213,7 +213,7 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
         }
         if (J.members_input(i)) {
             kind[i] = first_text_byte_of_bgzf(I.s.source(), I.path);
-        } else if (!I.s.raw_is_bzip2()) {
+        } else if (!I.s.raw_is_deferred()) {
             I.have_first = I.s.raw_fill(std::min(J.plain_target, kFirstWindow), &I.first_text, &I.first_n, &I.first_resume);
             if (I.have_first) kind[i] = I.s.raw_fastq() ? '@' : '>';
         }
@@ -225,7 +225,7 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     if (J.n_in == 2 && kind[0] != kind[1]) return false;
     J.fastq = kind[0] == '@';
     // (a plain gzip input may become device text once the HIP runtime is up, run(): its windows then end anywhere too)
-    J.chained = J.n_in == 2 || J.members_input(0) || (!a.host_codec && J.in[0].s.raw_is_gzip()) || J.in[0].s.raw_is_bzip2();
+    J.chained = J.n_in == 2 || J.members_input(0) || (!a.host_codec && J.in[0].s.raw_is_gzip()) || J.in[0].s.raw_is_deferred();
     return true;
 }
 
@@ -265,10 +265,11 @@ void WindowExtract::Impl::take_inputs_on_device() {
     // The two bzip2 files of a pair that go up WHOLE go ONE AFTER THE OTHER: a one-shot call sizes its passes and accepts its text by the
     // memory that is free when it runs, so the second must find the first's text there already, not a sibling that is about to take the
     // same half.  A file the device does not take is libbz2's, whole, and the job goes on with host text
+    // the same holds for the .zst files of a pair under --device-zstd (a larger one than --zstd-window is libzstd's, until zstd streams)
     for (int i = 0; i < n_in; ++i) {
         xw::InputFile &I = in[i];
-        if (!I.s.raw_is_bzip2() || bzip2_streamed(i)) continue;
-        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], a.bzip2_window, gate)) {  // (at or below the window: in one call)
+        if (!I.s.raw_is_deferred() || bzip2_streamed(i)) continue;
+        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], I.s.raw_is_zstd() ? a.zstd_window : a.bzip2_window, gate)) {  // (at or below the window: in one call)
             src[i] = std::move(dev);
             continue;
         }

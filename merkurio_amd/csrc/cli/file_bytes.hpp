@@ -33,5 +33,7 @@ bool inflate_by_magic(const std::string &path, const unsigned char *data, size_t
 // the first bytes of a bzip2 file's text, at most `want` of them, by libbz2 (the first block is decoded, no more): false if the library is
 // missing or the file is damaged before that many bytes have come out (the whole-file call then words the error)
 bool bz2_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
+// likewise for a zstd file, by libzstd
+bool zstd_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
 
 }  // namespace cli

@@ -18,8 +18,10 @@ struct WindowSource {
     // defer_bzip2: a bzip2 file is mapped as stored and NOT inflated (is_bzip2()): the caller may decode file_bytes() elsewhere
     // (extract's mk_bzip2_inflate_device path); settle() -- which every read of the text through FastxStream begins with -- inflates it
     // with libbz2 after all, and from then on it is plain text like any other inflated bzip2 input
-    void open(const std::string &path, bool defer_bzip2 = false);
+    // defer_zstd: likewise for a zstd file (is_zstd(); extract's mk_zstd_inflate_device path under --device-zstd); settle(): libzstd
+    void open(const std::string &path, bool defer_bzip2 = false, bool defer_zstd = false);
     bool is_bzip2() const { return kind == BZIP2; }
+    bool is_zstd() const { return kind == ZSTD; }
     void settle();
     bool mapped() const { return kind == PLAIN; }  // text()/text_size() is the complete text
     bool is_file_mapping() const { return kind == PLAIN && src.map != nullptr; }  // (not an inflated bzip2 / xz / zstd copy)
@@ -51,7 +53,7 @@ struct WindowSource {
     WindowSource &operator=(const WindowSource &) = delete;
 
    private:
-    enum Kind { PLAIN, GZIP, BGZF, BZIP2 } kind = PLAIN;
+    enum Kind { PLAIN, GZIP, BGZF, BZIP2, ZSTD } kind = PLAIN;
     std::string path;
     FileBytes src;  // the file as stored (PLAIN: the text itself, or inflated bzip2 / xz / zstd)
     bool src_eof = false;

@@ -106,6 +106,23 @@ int download(mk_codec *c, uint8_t *dst, const void *d_src, uint64_t n) {
     }
     return MK_OK;
 }
+int download_each(mk_codec *c, const void *d_src, uint64_t n, const std::function<void(const uint8_t *, uint64_t)> &each) {
+    int rc = stage_buffers(c);
+    if (rc) return rc;
+    const uint64_t pieces = (n + kStageBytes - 1) / kStageBytes;
+    for (uint64_t j = 0; j <= pieces; ++j) {
+        if (j < pieces) {
+            const uint64_t at = j * kStageBytes, m = std::min<uint64_t>(kStageBytes, n - at);
+            MKC_HIP(hipMemcpyAsync(c->h_stage[j & 1], (const uint8_t *)d_src + at, m, hipMemcpyDeviceToHost, c->stream), "download");
+            MKC_HIP(hipEventRecord(c->ev_stage[j & 1], c->stream), "hipEventRecord");
+        }
+        if (j > 0) {
+            MKC_HIP(hipEventSynchronize(c->ev_stage[(j - 1) & 1]), "hipEventSynchronize");
+            each((const uint8_t *)c->h_stage[(j - 1) & 1], std::min<uint64_t>(kStageBytes, n - (j - 1) * kStageBytes));
+        }
+    }
+    return MK_OK;
+}
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

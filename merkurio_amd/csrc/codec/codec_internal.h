@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -83,6 +84,10 @@ struct mk_codec {
     float bz_ms[5] = {0, 0, 0, 0, 0};  // upload, marker search, block decode, text, CRC
     uint64_t bz_pass_blocks = 0;       // mk_codec_set_bzip2_pass_blocks; 0 = by the free memory
     uint64_t bz_text_cap = 0;          // mk_codec_set_bzip2_text_cap: bytes per text window of a bzip2 stream; 0 = by the free memory
+    // mk_zstd_inflate_device (its text is gz_text too; compressed file, literals + sequences, tables and the two source arrays borrow
+    // d_gz_in / d_gz_sym / d_gz_tab / d_gz_ctx)
+    uint32_t zs_blocks = 0, zs_frames = 0, zs_rounds = 0;
+    float zs_ms[6] = {0, 0, 0, 0, 0, 0};  // upload, tables + entropy decode, scans, execution, cross-block rounds, checksum
     int inflate_kernel = 0;  // mk_codec_set_inflate_kernel: 0 = chosen per call, 1 = a lane per member, 2 = a wave per member
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size
@@ -99,6 +104,8 @@ void parallel_copy(uint8_t *dst, const uint8_t *src, uint64_t n);
 int upload(mk_codec *c, void *d_dst, const uint8_t *src, uint64_t n);
 // d_src[0, n) -> dst; waits for the stream (everything enqueued before it included)
 int download(mk_codec *c, uint8_t *dst, const void *d_src, uint64_t n);
+// d_src[0, n) handed to `each` piece by piece, in order, out of the staging buffers: piece k + 1 travels while `each` works on piece k
+int download_each(mk_codec *c, const void *d_src, uint64_t n, const std::function<void(const uint8_t *, uint64_t)> &each);
 double now_ms();
 inline float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0;
