@@ -775,6 +775,53 @@ int mk_bzip2_stream_info(const mk_codec *c, mk_bzip2_stream_stats *out);
 int mk_bzip2_stream_end(mk_codec *c);
 int mk_codec_set_bzip2_text_cap(mk_codec *c, uint64_t text_bytes);
 
+/* (an addition to v7; `merkurio extract --zstd-stream`) A .zst file of ANY size, decoded on the device window by window: nothing on
+ * the device is sized by the file, and a frame may hold 4 GiB of text or more.  The contract is mk_bzip2_stream_*'s.
+ * mk_zstd_stream_begin: zs[0, n) = the whole file (the caller's -- the mapped file -- until _end); window_bytes = compressed bytes per
+ * window (0 = 256 MiB, an unmeasured choice: profiles/e2e_unzstd_windows.txt).  *taken = 0: no frame or skippable-frame magic at byte
+ * 0, no stream is open.  Every block header states its block's compressed size, so mk_zstd_stream_next walks on from where the window
+ * before stopped (merkurio_amd/csrc/codec/zstd_chain.hpp, zstd_plan.hpp) and stops behind the first block at which the compressed
+ * bytes taken reach window_bytes, or at which another block of 128 KiB beside the carried history would exceed the text cap, or the
+ * file ends -- one block at the least; no start is guessed and no window grows.  A frame's 4 checksum bytes go with its last block.
+ * The text cap is chosen from the free device memory, below 4 GiB minus the largest history (an unmeasured choice);
+ * mk_codec_set_zstd_text_cap sets it (test hook; 0 = default; results do not depend on it).  Carried from window to window: whether a
+ * frame is open, its window, content size, checksum flag and text so far (64 bits), the running XXH64 state, the three repeat
+ * offsets behind the last block, a copy of the bytes that describe the tree and the three sequence tables in force (128 bytes each at
+ * the most, laid in front of the next window's compressed bytes so that a block which repeats one builds it as it builds its own),
+ * and the history: the last H = min(frame window, frame text so far) bytes of text, copied on the device to the front of the next
+ * window's text buffer.  The execute step reads a match source inside the history as a byte; only sources inside the window wait
+ * for the rounds of resolution, at most log2(blocks of the window) + 2.  The content checksum is XXH64 on the host over each
+ * window's new text as it is downloaded, compared when the frame's last block has been decoded; a content size likewise, in 64 bits.
+ * *state = 0: a window of text was produced, *text_bytes long (its NEW text, without the history; 0 for a window of empty frames):
+ *             it is what mk_gzip_text_device / mk_gzip_text_read refer to, in one of two text buffers -- window w stays valid until
+ *             the call that produces w + 2;
+ *          1: end of file: every frame's size and checksum agree; no text in this call;
+ *          2: handed back (MK_OK): no text in this call and the stream produces nothing more -- whatever mk_zstd_inflate_device
+ *             lists, met in this window, a carried description above 128 bytes, no room, any device error.  The windows delivered
+ *             before it are a prefix of what libzstd writes before it refuses: the caller's libzstd reads the file from the front
+ *             and skips stats.text_bytes.
+ * mk_zstd_stream_end closes the stream and frees what it held (the two text buffers included).  mk_zstd_stream_info takes the codec's
+ * lock; without an open stream: the last stream's figures.  While a zstd stream is open the one-shot gzip, bzip2 and zstd calls and
+ * mk_gzip_stream_begin / mk_bzip2_stream_begin return MK_E_INVALID_ARG -- and mk_zstd_stream_begin does while another stream is --,
+ * and mk_gzip_text_release ends the stream as mk_zstd_stream_end does. */
+typedef struct mk_zstd_stream_stats {
+    uint64_t windows;           /* windows of text produced */
+    uint64_t frames;            /* frames closed: content size and checksum agree */
+    uint64_t blocks;            /* blocks delivered */
+    uint64_t consumed_bytes;    /* compressed bytes in front of the next window */
+    uint64_t text_bytes;        /* text bytes delivered so far */
+    uint64_t rounds;            /* cross-block resolution rounds, summed over the windows */
+    uint64_t max_history;       /* the largest history carried into a window, bytes */
+    uint64_t peak_device_bytes; /* most device memory the stream has held */
+    float ms[6];                /* summed over the windows, mk_zstd_info's phases: upload, tables + entropy decode, scans, execution
+                                   (the history's copy included), cross-block rounds, checksum */
+} mk_zstd_stream_stats;
+int mk_zstd_stream_begin(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t window_bytes, uint32_t *taken);
+int mk_zstd_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state);
+int mk_zstd_stream_info(const mk_codec *c, mk_zstd_stream_stats *out);
+int mk_zstd_stream_end(mk_codec *c);
+int mk_codec_set_zstd_text_cap(mk_codec *c, uint64_t text_bytes);
+
 /* (v7) A gzip file of SEVERAL members -- `cat a.gz b.gz`, a member per tile or per block without BGZF's BC field.  A member carries no
  * compressed size: where it ends is known once it is decoded.  So the starts are guessed on the host and proved on the device.
  * mk_gzip_member_guesses (host code, no device needed) reports every offset at which an RFC 1952 header parses inside gz[0, n): ID1

@@ -58,6 +58,9 @@ struct ExtractArgs : CommonArgs {
     // --device-zstd: a .zst input of at most --zstd-window compressed bytes is decoded on the device in one call
     // (mk_zstd_inflate_device); a larger one, and every .zst input without the flag, is libzstd's.  Opt-in: the path has not been timed
     bool device_zstd = false;
+    // --zstd-stream (implies --device-zstd): a larger .zst input is decoded window by window (mk_zstd_stream_*), each window of
+    // about --zstd-window compressed bytes.  Opt-in like its sibling: not timed
+    bool zstd_stream = false;
     uint64_t zstd_window = kZstdWindow;
 };
 

@@ -1,6 +1,6 @@
 // extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
-// inflated in one piece or member by member, or of a bzip2 or (--device-zstd) zstd file (windows are ranges of it), and a gzip or bzip2 file decoded window by
-// window (mk_gzip_stream_*, mk_bzip2_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
+// inflated in one piece or member by member, or of a bzip2 or (--device-zstd) zstd file (windows are ranges of it), and a gzip, bzip2 or (--zstd-stream) zstd file decoded window by
+// window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
 // "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
 #include <hip/hip_runtime_api.h>
 
@@ -49,6 +49,9 @@ struct StreamCalls {
     int (*end)(mk_codec *);
     // the stream's own figures: compressed bytes consumed, what it counted, its phases and its peak
     void (*figures)(mk_codec *, uint64_t *consumed, std::string *counts, std::string *phases);
+    // (may be null) the phases summed so far, for a window's row to show what each cost in that window
+    void (*phase_ms)(mk_codec *, float ms[6]);
+    const char *phase_names[6];
 };
 
 template <class... A>
@@ -67,7 +70,7 @@ const StreamCalls kGzipCalls = {"gzip", "zlib", mk_gzip_stream_next, mk_gzip_str
                                                   (unsigned long long)st.windows_grown, (unsigned long long)st.rounds_repeated);
                                     *phases = fmt("upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
                                                   st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
-                                }};
+                                }, nullptr, {}};
 const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_next, mk_bzip2_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
                                      mk_bzip2_stream_stats st;
                                      memset(&st, 0, sizeof(st));
@@ -77,7 +80,22 @@ const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_next, mk_bzi
                                                    (unsigned long long)st.blocks, (unsigned long long)st.windows_grown);
                                      *phases = fmt("upload %.1f, marker search %.1f, block decode %.1f, text %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
                                                    st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
-                                 }};
+                                 }, nullptr, {}};
+const StreamCalls kZstdCalls = {"zstd", "libzstd", mk_zstd_stream_next, mk_zstd_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+                                    mk_zstd_stream_stats st;
+                                    memset(&st, 0, sizeof(st));
+                                    (void)mk_zstd_stream_info(c, &st);
+                                    *consumed = st.consumed_bytes;
+                                    *counts = fmt("%llu windows, %llu frames closed, %llu blocks, %llu rounds, largest history %llu bytes", (unsigned long long)st.windows,
+                                                  (unsigned long long)st.frames, (unsigned long long)st.blocks, (unsigned long long)st.rounds, (unsigned long long)st.max_history);
+                                    *phases = fmt("upload %.1f, tables + entropy decode %.1f, walk + scans %.1f, execution %.1f, cross-block rounds %.1f, checksum %.1f ms; peak %llu device bytes",
+                                                  st.ms[0], st.ms[1], st.ms[2], st.ms[3], st.ms[4], st.ms[5], (unsigned long long)st.peak_device_bytes);
+                                }, [](mk_codec *c, float ms[6]) {
+                                    mk_zstd_stream_stats st;
+                                    memset(&st, 0, sizeof(st));
+                                    (void)mk_zstd_stream_info(c, &st);
+                                    for (int k = 0; k < 6; ++k) ms[k] = st.ms[k];
+                                }, {"upload", "tables + entropy decode", "walk + scans", "execution", "cross-block rounds", "checksum"}};
 
 // A file the device decodes window by window (mk_gzip_stream_*, mk_bzip2_stream_*).  Window w of the stream lies in text buffer w & 1
 struct DeviceStream : DeviceText {
@@ -88,6 +106,7 @@ struct DeviceStream : DeviceText {
     uint64_t windows = 0;                 // windows the stream has produced
     uint64_t last_k[2] = {~0ull, ~0ull};  // the last text window whose body lies in either buffer
     uint64_t delivered = 0;               // text bytes of all its windows
+    float seen_ms[6] = {0, 0, 0, 0, 0, 0};  // the stream's phases up to the window before (calls.phase_ms)
     enum { RUNNING, ENDED, HANDED_BACK } state = RUNNING;  // HANDED_BACK (the stream's state 2): the host library takes the file from the chain's tail on
     const double t0;
     DeviceStream(const StreamCalls &calls_, mk_codec *c, InputFile &f_, int i_, Gate &g_, double t0_) : DeviceText(c), calls(calls_), f(f_), i(i_), g(g_), t0(t0_) {}
@@ -110,11 +129,18 @@ struct DeviceStream : DeviceText {
             if (calls.next(codec, &text_bytes, &st_now) != MK_OK) st_now = 2;
             std::string counts, phases;
             calls.figures(codec, &consumed, &counts, &phases);
+            std::string window_phases;
+            if (calls.phase_ms) {
+                float ms[6];
+                calls.phase_ms(codec, ms);
+                for (int p = 0; p < 6; ++p) window_phases += fmt("%s%s %.1f", p ? ", " : "; ", calls.phase_names[p], ms[p] - seen_ms[p]), seen_ms[p] = ms[p];
+                window_phases += " ms";
+            }
             if (st_now == 0) {
                 if (g.timing)
-                    fprintf(stderr, "[timing]   %s input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu)\n",
+                    fprintf(stderr, "[timing]   %s input %d on the device: window %llu taken, %llu text bytes, %llu compressed bytes consumed, %.1f ms (in front of text window %llu%s)\n",
                             calls.format, i, (unsigned long long)windows, (unsigned long long)text_bytes, (unsigned long long)consumed, (PhaseTimer::now() - t_win) * 1e3,
-                            (unsigned long long)k);
+                            (unsigned long long)k, window_phases.c_str());
                 ++windows;
                 delivered += text_bytes;
                 text = (const uint8_t *)mk_gzip_text_device(codec, &bytes);
@@ -174,7 +200,15 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (zs) {
+    if (zs && f.zstd_stream) {
+        // --zstd-stream, more than one zstd window: decoded window by window as the text windows reach it, device memory bounded by
+        // the window; what the stream does not take, from whichever window on, is libzstd's
+        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        t0 = PhaseTimer::now();
+        if (codec && mk_zstd_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new DeviceStream(kZstdCalls, codec, f, i, g, t0));
+        if (g.timing) fprintf(stderr, "[timing]   zstd input %d on the device, window by window: NOT taken (libzstd reads it)\n", i);
+    } else if (zs) {
         // --device-zstd: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- anything it
         // refuses, a damaged file, no room -- and a file of more compressed bytes than --zstd-window, libzstd reads whole, as
         // without the flag, and words the error

@@ -265,10 +265,18 @@ void WindowExtract::Impl::take_inputs_on_device() {
     // The two bzip2 files of a pair that go up WHOLE go ONE AFTER THE OTHER: a one-shot call sizes its passes and accepts its text by the
     // memory that is free when it runs, so the second must find the first's text there already, not a sibling that is about to take the
     // same half.  A file the device does not take is libbz2's, whole, and the job goes on with host text
-    // the same holds for the .zst files of a pair under --device-zstd (a larger one than --zstd-window is libzstd's, until zstd streams)
+    // the same holds for the .zst files of a pair under --device-zstd (a larger one than --zstd-window is libzstd's, unless --zstd-stream)
+    // A streamed zstd file holds, per window, its compressed bytes, its literals and 12 bytes per sequence, two text buffers and 8
+    // bytes of sources per text byte: at 5 bytes of text per compressed byte about 60 times the window.  An estimate, not measured;
+    // the library bounds a window's text by its own cap whatever this factor is.  Same rule
+    uint64_t zstd_window = a.zstd_window, n_zs_streamed = 0;
+    for (int i = 0; i < n_in; ++i)
+        if (zstd_streamed(i)) ++n_zs_streamed;
+    if (const uint64_t free_b = n_zs_streamed ? xw::device_free_bytes(devs[0]) : 0)
+        while (zstd_window > (1u << 20) && n_zs_streamed * 2 * 60 * zstd_window > free_b / 2) zstd_window /= 2;
     for (int i = 0; i < n_in; ++i) {
         xw::InputFile &I = in[i];
-        if (!I.s.raw_is_deferred() || bzip2_streamed(i)) continue;
+        if (!I.s.raw_is_deferred() || bzip2_streamed(i) || zstd_streamed(i)) continue;
         if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], I.s.raw_is_zstd() ? a.zstd_window : a.bzip2_window, gate)) {  // (at or below the window: in one call)
             src[i] = std::move(dev);
             continue;
@@ -278,6 +286,13 @@ void WindowExtract::Impl::take_inputs_on_device() {
     run_threads((size_t)n_in, [&](size_t i) {  // (the two streamed files of a pair side by side: a handle and a stream each, sized by their windows)
         if (bzip2_streamed((int)i)) {
             if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], bzip2_window, gate)) src[i] = std::move(dev);
+            else settle_bzip2(in[i]);
+            return;
+        }
+        if (zstd_streamed((int)i)) {
+            // (the stream is asked for by the file's size against --zstd-window as given; its windows may be smaller)
+            in[i].zstd_stream = true;
+            if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], zstd_window, gate)) src[i] = std::move(dev);
             else settle_bzip2(in[i]);
             return;
         }

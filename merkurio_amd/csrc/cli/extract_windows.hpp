@@ -54,6 +54,8 @@ struct WindowExtract::Impl {
     void take_inputs_on_device();
     // a .bz2 input of more compressed bytes than --bzip2-window: decoded window by window (under --host-codec no input is_bzip2)
     bool bzip2_streamed(int i) const { return in[i].s.raw_is_bzip2() && in[i].s.source().file_size() > a.bzip2_window; }
+    // a .zst input of more compressed bytes than --zstd-window under --zstd-stream: likewise (without the flag it is libzstd's)
+    bool zstd_streamed(int i) const { return a.zstd_stream && in[i].s.raw_is_zstd() && in[i].s.source().file_size() > a.zstd_window; }
     void settle_bzip2(xw::InputFile &I);
     void reader_loop();
     void device_loop(size_t d);

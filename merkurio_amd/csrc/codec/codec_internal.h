@@ -11,6 +11,7 @@
 #include "../host_common.h"
 #include "bzip2_chain.hpp"
 #include "gzip_chain.hpp"
+#include "zstd_chain.hpp"
 
 namespace mk {
 int hip_fail(hipError_t e, const char *what);
@@ -53,6 +54,19 @@ struct mk_bzip2_stream {
     size_t n_tab = 0;   // blocks the device tables of the decoded window are laid out for
 };
 
+// mk_zstd_stream_*: a .zst file in windows of its compressed bytes (zstd_host.cpp).  What is decided about a window is mkz::ZsStream's
+// (zstd_chain.hpp); here what the stream owns on the device: two text buffers, each a window's history and its new text behind it
+// (the handle's d_gz_text points at the latest window's NEW text).  Prelude + compressed bytes, literals + sequences, tables and the
+// two source arrays are the handle's d_gz_in / d_gz_sym / d_gz_tab / d_gz_ctx, sized by the window.
+struct mk_zstd_stream {
+    bool active = false;
+    mkz::ZsStream s;
+    int text_cur = 0;
+    void *d_text[2] = {nullptr, nullptr};
+    size_t text_cap[2] = {0, 0};
+    uint64_t text_total = 0;  // history + new text of the latest window, in d_text[text_cur]
+};
+
 struct mk_codec {
     int device = 0, num_cus = 256;
     hipStream_t stream = nullptr;
@@ -88,13 +102,15 @@ struct mk_codec {
     // d_gz_in / d_gz_sym / d_gz_tab / d_gz_ctx)
     uint32_t zs_blocks = 0, zs_frames = 0, zs_rounds = 0;
     float zs_ms[6] = {0, 0, 0, 0, 0, 0};  // upload, tables + entropy decode, scans, execution, cross-block rounds, checksum
+    uint64_t zs_text_cap = 0;             // mk_codec_set_zstd_text_cap: bytes of text per window of a zstd stream; 0 = by the free memory
     int inflate_kernel = 0;  // mk_codec_set_inflate_kernel: 0 = chosen per call, 1 = a lane per member, 2 = a wave per member
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size
     uint64_t deflate_pass_blocks = 0, inflate_pass_text = 0;  // mk_codec_set_pass_limits; 0 = the defaults below
     mk_gzip_stream gzs;
     mk_bzip2_stream bzs;
-    bool stream_open() const { return gzs.active || bzs.active; }  // one stream per handle, and no one-shot call beside it
+    mk_zstd_stream zss;
+    bool stream_open() const { return gzs.active || bzs.active || zss.active; }  // one stream per handle, and no one-shot call beside it
 };
 
 namespace mkz {
@@ -119,6 +135,8 @@ void gz_keep_text(mk_codec *c);
 void gzip_stream_close(mk_codec *c);
 // ---- bzip2_host.cpp: an open bzip2 stream ends likewise
 void bzip2_stream_close(mk_codec *c);
+// ---- zstd_host.cpp: an open zstd stream ends likewise
+void zstd_stream_close(mk_codec *c);
 // ---- bgzf_host.cpp
 // One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
 // output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on

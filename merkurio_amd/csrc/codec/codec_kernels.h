@@ -115,10 +115,10 @@ void launch_bz2_crc(const uint8_t *text, const unsigned long long *text_off, con
 void launch_zs_decode(const uint8_t *in, uint64_t n, uint64_t n_words, const void *blocks, uint32_t n_blocks, uint8_t *lit, uint32_t *ll, uint32_t *ml, uint32_t *of,
                       void *rep, hipStream_t s);
 // the same blocks executed from start[b] (ZsStart): text, and per text byte kZsResolved or the position it copies from; status[b],
-// *open_total += the bytes left as positions
+// *open_total += the bytes left as positions.  text[0, settled) is final (a stream's history; the one-shot call: 0): read as bytes
 void launch_zs_execute(const uint8_t *in, const void *blocks, const void *start, const void *rep, uint32_t n_blocks, uint8_t *lit, uint32_t *ll, uint32_t *ml,
-                       uint32_t *of, uint8_t *text, uint32_t *src, int32_t *status, unsigned long long *open_total, hipStream_t s);
-// one round of pointer doubling over text[0, total): sources a -> b; *open_total += the bytes still open
-void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t total, unsigned long long *open_total, int num_cus, hipStream_t s);
+                       uint32_t *of, uint8_t *text, uint32_t *src, uint64_t settled, int32_t *status, unsigned long long *open_total, hipStream_t s);
+// one round of pointer doubling over text[first, total): sources a -> b; *open_total += the bytes still open
+void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t first, uint64_t total, unsigned long long *open_total, int num_cus, hipStream_t s);
 
 }  // namespace mkz

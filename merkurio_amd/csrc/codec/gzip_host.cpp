@@ -349,6 +349,7 @@ int mk_gzip_text_release(mk_codec *c) {
     (void)hipSetDevice(c->device);
     mkz::gzip_stream_close(c);  // (an open stream's text is the text: the stream ends with it)
     mkz::bzip2_stream_close(c);
+    mkz::zstd_stream_close(c);
     mkz::gz_release(c);
     return MK_OK;
 }

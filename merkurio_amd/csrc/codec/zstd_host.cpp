@@ -1,9 +1,10 @@
-// zstd_host.cpp -- host side of mk_zstd_inflate_device (include/merkurio_hip.h): a .zst file decoded on the device, a wave per block,
-// the whole file in one call.  The walk over the frames and block headers is mkz::zs_plan, the two scans mkz::zs_scan (zstd_plan.hpp,
-// no HIP in it: the CPU harness of the tests runs both); kernels: zstd_inflate.hip.  Here: upload, tables + entropy decode, scans,
-// execution, the rounds of cross-block resolution, and the content checksum, which the host computes per frame over the text as it
-// comes down through the staging buffers (XXH64 is four serial chains: nothing for a wave to fold).  The buffers are the gzip path's
-// (codec_internal.h).
+// zstd_host.cpp -- host side of mk_zstd_inflate_device and mk_zstd_stream_* (include/merkurio_hip.h): a .zst file decoded on the
+// device, a wave per block -- the whole file in one call, or a file of any size window by window.  The walk over the frames and block
+// headers is mkz::zs_walk, the two scans mkz::zs_scan (zstd_plan.hpp), everything that is decided about a window zstd_chain.hpp's;
+// none of them has HIP in it and the CPU harnesses of the tests run them; kernels: zstd_inflate.hip.  Here: the three device steps
+// both entry points share -- upload + tables + entropy decode; execution + the rounds of cross-block resolution; the content checksum,
+// which the host computes over the text as it comes down through the staging buffers (XXH64 is four serial chains: nothing for a
+// wave to fold) -- and the calls around them.  The buffers are the gzip path's (codec_internal.h).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -46,6 +47,120 @@ bool zs_ensure(void **p, size_t *cap, size_t need) {
 }
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
+// the device tables of B blocks behind each other: blocks | reports | starts | status | two counters
+struct ZsTab {
+    uint64_t o_rep, o_start, o_status, o_count, bytes;
+    explicit ZsTab(size_t B) {
+        o_rep = up16(B * sizeof(mkz::ZsBlock)), o_start = o_rep + up16(B * sizeof(mkz::ZsReport)), o_status = o_start + up16(B * sizeof(mkz::ZsStart));
+        o_count = o_status + up16(B * 4), bytes = o_count + 64;
+    }
+};
+// literals | LL | ML | OF of a plan inside d_gz_sym
+struct ZsSym {
+    uint64_t lit_bytes, seq_bytes;
+    explicit ZsSym(const mkz::ZsPlan &P) : lit_bytes(up16(P.lit_bytes + 16)), seq_bytes(up16((P.n_seq + 4) * 4)) {}
+    uint64_t bytes() const { return lit_bytes + 3 * seq_bytes; }
+};
+
+// ---- step 1: the device's input is pre[0, n_pre) | zs[0, n) (zeros behind it up to the reader's pad), which the positions of P's
+// blocks count in; tables + entropy decode of all of them -> rep.  false: no room, a device error.  ms[0], ms[1]
+bool zs_decode(mk_codec *c, const uint8_t *pre, uint64_t n_pre, const uint8_t *zs, uint64_t n, const mkz::ZsPlan &P, std::vector<mkz::ZsReport> &rep, float *ms) {
+    const size_t B = P.blocks.size();
+    double t0 = now_ms();
+    const uint64_t n_in = n_pre + n, n_words = (n_in + mkz::kZsStreamPad + 3) / 4;
+    const ZsSym sym(P);
+    const ZsTab t(B);
+    if (!zs_room(n_words * 4 + sym.bytes() + t.bytes, c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap) || !zs_ensure(&c->d_gz_in, &c->gz_in_cap, n_words * 4) ||
+        !zs_ensure(&c->d_gz_sym, &c->gz_sym_cap, sym.bytes()) || !zs_ensure(&c->d_gz_tab, &c->gz_tab_cap, t.bytes))
+        return false;
+    if (n_pre) MKZS_HIP(hipMemcpyAsync(c->d_gz_in, pre, n_pre, hipMemcpyHostToDevice, c->stream));
+    if (mkz::upload(c, (uint8_t *)c->d_gz_in + n_pre, zs, n)) return false;
+    MKZS_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n_in, 0, n_words * 4 - n_in, c->stream));
+    uint8_t *tab = (uint8_t *)c->d_gz_tab;
+    MKZS_HIP(hipMemcpyAsync(tab, P.blocks.data(), B * sizeof(mkz::ZsBlock), hipMemcpyHostToDevice, c->stream));
+    MKZS_HIP(hipStreamSynchronize(c->stream));
+    ms[0] += (float)(now_ms() - t0);
+    uint8_t *lit = (uint8_t *)c->d_gz_sym;
+    uint32_t *ll = (uint32_t *)(lit + sym.lit_bytes), *ml = (uint32_t *)(lit + sym.lit_bytes + sym.seq_bytes), *of = (uint32_t *)(lit + sym.lit_bytes + 2 * sym.seq_bytes);
+    MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
+    mkz::launch_zs_decode((const uint8_t *)c->d_gz_in, n_in, n_words, tab, (uint32_t)B, lit, ll, ml, of, tab + t.o_rep, c->stream);
+    MKZS_HIP(hipGetLastError());
+    MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
+    rep.resize(B);
+    MKZS_HIP(hipMemcpyAsync(rep.data(), tab + t.o_rep, B * sizeof(mkz::ZsReport), hipMemcpyDeviceToHost, c->stream));
+    MKZS_HIP(hipStreamSynchronize(c->stream));
+    ms[1] += elapsed(c->ev[0], c->ev[1]);
+    return true;
+}
+
+// ---- step 2: the decoded blocks executed from start[] into d_text[0, total) (128 bytes of room behind it), and one source per byte
+// in two arrays (a round reads one and writes the other); d_text[0, settled) is final: d_hist[0, settled) copied there first (a
+// stream's history; the one-shot call: none), and the rounds of pointer doubling visit [settled, total) until one leaves nothing
+// open -> *rounds.  false: a block's status, more rounds than the cap, no room, a device error.  ms[3], ms[4]
+bool zs_text(mk_codec *c, const mkz::ZsPlan &P, const std::vector<mkz::ZsStart> &start, uint8_t *d_text, const uint8_t *d_hist, uint64_t settled, uint64_t total,
+             uint32_t *rounds, float *ms) {
+    const size_t B = P.blocks.size();
+    *rounds = 0;
+    if (settled) MKZS_HIP(hipMemcpyAsync(d_text, d_hist, settled, hipMemcpyDeviceToDevice, c->stream));
+    if (!B) {
+        MKZS_HIP(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    const ZsSym sym(P);
+    const ZsTab t(B);
+    const uint64_t src_bytes = up16(total * 4 + 16);
+    if (!zs_room(2 * src_bytes, c->gz_ctx_cap) || !zs_ensure(&c->d_gz_ctx, &c->gz_ctx_cap, 2 * src_bytes)) return false;
+    uint8_t *tab = (uint8_t *)c->d_gz_tab, *lit = (uint8_t *)c->d_gz_sym;
+    uint32_t *ll = (uint32_t *)(lit + sym.lit_bytes), *ml = (uint32_t *)(lit + sym.lit_bytes + sym.seq_bytes), *of = (uint32_t *)(lit + sym.lit_bytes + 2 * sym.seq_bytes);
+    uint32_t *src[2] = {(uint32_t *)c->d_gz_ctx, (uint32_t *)((uint8_t *)c->d_gz_ctx + src_bytes)};
+    unsigned long long *d_open = (unsigned long long *)(tab + t.o_count);
+    MKZS_HIP(hipMemcpyAsync(tab + t.o_start, start.data(), B * sizeof(mkz::ZsStart), hipMemcpyHostToDevice, c->stream));
+    MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
+    MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
+    if (settled) {  // (kZsResolved is all ones)
+        MKZS_HIP(hipMemsetAsync(src[0], 0xff, settled * 4, c->stream));
+        MKZS_HIP(hipMemsetAsync(src[1], 0xff, settled * 4, c->stream));
+    }
+    mkz::launch_zs_execute((const uint8_t *)c->d_gz_in, tab, tab + t.o_start, tab + t.o_rep, (uint32_t)B, lit, ll, ml, of, d_text, src[0], settled,
+                           (int32_t *)(tab + t.o_status), d_open, c->stream);
+    MKZS_HIP(hipGetLastError());
+    MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
+    std::vector<int32_t> status(B);
+    unsigned long long open = 0;
+    MKZS_HIP(hipMemcpyAsync(status.data(), tab + t.o_status, B * 4, hipMemcpyDeviceToHost, c->stream));
+    MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
+    MKZS_HIP(hipStreamSynchronize(c->stream));
+    ms[3] += elapsed(c->ev[0], c->ev[1]);
+    for (int32_t st : status)
+        if (st != 0) return false;
+    // ---- cross-block resolution: rounds of pointer doubling until one leaves nothing open
+    const double t0 = now_ms();
+    const uint32_t cap = mkz::zs_round_cap(B);
+    int cur = 0;
+    while (open) {
+        if (*rounds == cap) return false;
+        MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
+        mkz::launch_zs_resolve(src[cur], src[cur ^ 1], d_text, settled, total, d_open, c->num_cus, c->stream);
+        MKZS_HIP(hipGetLastError());
+        MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
+        MKZS_HIP(hipStreamSynchronize(c->stream));
+        cur ^= 1, ++*rounds;
+    }
+    ms[4] += (float)(now_ms() - t0);
+    return true;
+}
+
+// ---- step 3: d_text[0, len) comes down through h.  ms[5]
+bool zs_hash(mk_codec *c, const uint8_t *d_text, uint64_t len, mkz::Xxh64 &h, float *ms) {
+    const double t0 = now_ms();
+    if (len && mkz::download_each(c, d_text, len, [&](const uint8_t *p, uint64_t m) { h.update(p, m); })) {
+        (void)hipGetLastError();
+        return false;
+    }
+    ms[5] += (float)(now_ms() - t0);
+    return true;
+}
+
 // the whole file in one call; false: not taken
 bool zstd_inflate(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_bytes, uint64_t *n_blocks) {
     mkz::ZsPlan P;
@@ -56,89 +171,25 @@ bool zstd_inflate(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_byt
     if (B) {
         if (B >= (1u << 30)) return false;
         MKZS_HIP(hipSetDevice(c->device));
-        // ---- upload: the file (zeros behind it up to the reader's pad) and the walk's table
-        double t0 = now_ms();
-        const uint64_t n_words = (n + mkz::kZsStreamPad + 3) / 4;
-        const uint64_t lit_bytes = up16(P.lit_bytes + 16), seq_bytes = up16((P.n_seq + 4) * 4);
-        // tables: blocks | reports | starts | status | two counters
-        const uint64_t o_rep = up16(B * sizeof(mkz::ZsBlock)), o_start = o_rep + up16(B * sizeof(mkz::ZsReport)), o_status = o_start + up16(B * sizeof(mkz::ZsStart)),
-                       o_count = o_status + up16(B * 4), tab_bytes = o_count + 64;
-        if (!zs_room(n_words * 4 + lit_bytes + 3 * seq_bytes + tab_bytes, c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap) ||
-            !zs_ensure(&c->d_gz_in, &c->gz_in_cap, n_words * 4) || !zs_ensure(&c->d_gz_sym, &c->gz_sym_cap, lit_bytes + 3 * seq_bytes) ||
-            !zs_ensure(&c->d_gz_tab, &c->gz_tab_cap, tab_bytes))
-            return false;
-        if (mkz::upload(c, c->d_gz_in, zs, n)) return false;
-        MKZS_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n, 0, n_words * 4 - n, c->stream));
-        uint8_t *tab = (uint8_t *)c->d_gz_tab;
-        MKZS_HIP(hipMemcpyAsync(tab, P.blocks.data(), B * sizeof(mkz::ZsBlock), hipMemcpyHostToDevice, c->stream));
-        MKZS_HIP(hipStreamSynchronize(c->stream));
-        c->zs_ms[0] = (float)(now_ms() - t0);
-        uint8_t *lit = (uint8_t *)c->d_gz_sym;
-        uint32_t *ll = (uint32_t *)(lit + lit_bytes), *ml = (uint32_t *)(lit + lit_bytes + seq_bytes), *of = (uint32_t *)(lit + lit_bytes + 2 * seq_bytes);
-        unsigned long long *d_open = (unsigned long long *)(tab + o_count);
-        // ---- tables + entropy decode
-        MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
-        mkz::launch_zs_decode((const uint8_t *)c->d_gz_in, n, n_words, tab, (uint32_t)B, lit, ll, ml, of, tab + o_rep, c->stream);
-        MKZS_HIP(hipGetLastError());
-        MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
-        std::vector<mkz::ZsReport> rep(B);
-        MKZS_HIP(hipMemcpyAsync(rep.data(), tab + o_rep, B * sizeof(mkz::ZsReport), hipMemcpyDeviceToHost, c->stream));
-        MKZS_HIP(hipStreamSynchronize(c->stream));
-        c->zs_ms[1] = elapsed(c->ev[0], c->ev[1]);
+        std::vector<mkz::ZsReport> rep;
+        if (!zs_decode(c, nullptr, 0, zs, n, P, rep, c->zs_ms)) return false;
         for (const mkz::ZsReport &r : rep)
             if (r.status != 0) return false;
         // ---- the two scans: where every block's text starts, the repeat offsets in front of it
-        t0 = now_ms();
+        const double t0 = now_ms();
         std::vector<mkz::ZsStart> start;
         if (!mkz::zs_scan(P, rep, start, &total)) return false;
         c->zs_ms[2] = (float)(now_ms() - t0);
-        // ---- execution: the text, and one source per byte in two arrays (a round reads one and writes the other)
-        const uint64_t src_bytes = up16(total * 4 + 16);
-        if (!zs_room(total + 128 + 2 * src_bytes, c->gz_text_cap + c->gz_ctx_cap) || !zs_ensure(&c->d_gz_text, &c->gz_text_cap, total + 128) ||
-            !zs_ensure(&c->d_gz_ctx, &c->gz_ctx_cap, 2 * src_bytes))
-            return false;
-        uint32_t *src[2] = {(uint32_t *)c->d_gz_ctx, (uint32_t *)((uint8_t *)c->d_gz_ctx + src_bytes)};
-        MKZS_HIP(hipMemcpyAsync(tab + o_start, start.data(), B * sizeof(mkz::ZsStart), hipMemcpyHostToDevice, c->stream));
-        MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
-        MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
-        mkz::launch_zs_execute((const uint8_t *)c->d_gz_in, tab, tab + o_start, tab + o_rep, (uint32_t)B, lit, ll, ml, of, (uint8_t *)c->d_gz_text, src[0],
-                               (int32_t *)(tab + o_status), d_open, c->stream);
-        MKZS_HIP(hipGetLastError());
-        MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
-        std::vector<int32_t> status(B);
-        unsigned long long open = 0;
-        MKZS_HIP(hipMemcpyAsync(status.data(), tab + o_status, B * 4, hipMemcpyDeviceToHost, c->stream));
-        MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
-        MKZS_HIP(hipStreamSynchronize(c->stream));
-        c->zs_ms[3] = elapsed(c->ev[0], c->ev[1]);
-        for (int32_t st : status)
-            if (st != 0) return false;
-        // ---- cross-block resolution: rounds of pointer doubling until one leaves nothing open
-        t0 = now_ms();
-        const uint32_t cap = mkz::zs_round_cap(B);
-        int cur = 0;
-        while (open) {
-            if (rounds == cap) return false;
-            MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
-            mkz::launch_zs_resolve(src[cur], src[cur ^ 1], (uint8_t *)c->d_gz_text, total, d_open, c->num_cus, c->stream);
-            MKZS_HIP(hipGetLastError());
-            MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
-            MKZS_HIP(hipStreamSynchronize(c->stream));
-            cur ^= 1, ++rounds;
-        }
-        c->zs_ms[4] = (float)(now_ms() - t0);
+        // ---- execution and rounds: the text, 8 bytes of sources per byte beside it
+        if (!zs_room(total + 128 + 2 * up16(total * 4 + 16), c->gz_text_cap + c->gz_ctx_cap) || !zs_ensure(&c->d_gz_text, &c->gz_text_cap, total + 128)) return false;
+        if (!zs_text(c, P, start, (uint8_t *)c->d_gz_text, nullptr, 0, total, &rounds, c->zs_ms)) return false;
         // ---- content checksums: the low 32 bits of XXH64 of every frame's text that carries one
-        t0 = now_ms();
         for (const mkz::ZsFrame &F : P.frames) {
             if (!F.has_checksum) continue;
             mkz::Xxh64 h;
-            if (F.text_len && mkz::download_each(c, (const uint8_t *)c->d_gz_text + F.text_off, F.text_len, [&](const uint8_t *p, uint64_t m) { h.update(p, m); })) {
-                (void)hipGetLastError();
-                return false;
-            }
+            if (!zs_hash(c, (const uint8_t *)c->d_gz_text + F.text_off, F.text_len, h, c->zs_ms)) return false;
             if ((uint32_t)h.digest() != F.checksum) return false;
         }
-        c->zs_ms[5] = (float)(now_ms() - t0);
     } else {
         for (const mkz::ZsFrame &F : P.frames) {  // frames without text: their sizes and checksums are checked all the same
             if (F.content_size != ~0ull && F.content_size != 0) return false;
@@ -150,7 +201,60 @@ bool zstd_inflate(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_byt
     return true;
 }
 
+// ---- the device behind a stream (zstd_chain.hpp: Dev)
+struct ZsStreamDev {
+    mk_codec *c;
+    mk_zstd_stream &D;
+    uint64_t text_room() { return default_text_cap(c); }
+    // per text byte of a window: the byte in each of the two text buffers and two 4-byte sources -- a tenth of half of the free
+    // memory, an unmeasured choice (profiles/e2e_unzstd_windows.txt)
+    static uint64_t default_text_cap(const mk_codec *c) {
+        if (c->zs_text_cap) return c->zs_text_cap;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return mkz::kZsBlockMax;
+        return std::min<uint64_t>(free_b / 2 / 10, mkz::kZsTextCapMax);
+    }
+    bool decode(const mkz::ZsWindow &W, std::vector<mkz::ZsReport> &rep) {
+        return zs_decode(c, W.prelude, mkz::kZsPrelude, D.s.zs + W.from, W.to - W.from, W.P, rep, D.s.stats.ms);
+    }
+    bool execute(const mkz::ZsWindow &W, const std::vector<mkz::ZsStart> &start, uint64_t history, uint64_t total, uint32_t *rounds) {
+        const int buf = D.text_cur ^ 1;
+        if (history > D.text_total) return false;
+        if (!zs_room(total + 128 + 2 * up16(total * 4 + 16), D.text_cap[buf] + c->gz_ctx_cap) || !zs_ensure(&D.d_text[buf], &D.text_cap[buf], total + 128)) return false;
+        const uint8_t *hist = history ? (const uint8_t *)D.d_text[D.text_cur] + (D.text_total - history) : nullptr;
+        return zs_text(c, W.P, start, (uint8_t *)D.d_text[buf], hist, history, total, rounds, D.s.stats.ms);
+    }
+    bool hash(uint64_t off, uint64_t len, mkz::Xxh64 &h) { return zs_hash(c, (const uint8_t *)D.d_text[D.text_cur ^ 1] + off, len, h, D.s.stats.ms); }
+    void commit(uint64_t history, uint64_t total) {
+        D.text_cur ^= 1, D.text_total = total;
+        c->d_gz_text = D.d_text[D.text_cur] ? (uint8_t *)D.d_text[D.text_cur] + history : nullptr;
+        c->gz_text_cap = D.d_text[D.text_cur] ? D.text_cap[D.text_cur] - history : 0;
+    }
+};
+
+uint64_t stream_held(const mk_codec *c) { return c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap + c->gz_ctx_cap + c->zss.text_cap[0] + c->zss.text_cap[1]; }
+
 }  // namespace
+
+namespace mkz {
+
+void zstd_stream_close(mk_codec *c) {
+    mk_zstd_stream &D = c->zss;
+    if (!D.active) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (void *&p : D.d_text) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    c->d_gz_text = nullptr, c->gz_text_cap = 0;  // (it pointed into one of the stream's two)
+    gz_release(c);
+    const mk_zstd_stream_stats last = D.s.stats;  // (mk_zstd_stream_info without an open stream: what the last one left)
+    D = mk_zstd_stream();
+    D.s.stats = last;
+}
+
+}  // namespace mkz
 
 extern "C" {
 
@@ -159,7 +263,7 @@ int mk_zstd_inflate_device(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t 
     if (!c || !text_bytes || !taken || !n_blocks || (n && !zs)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_blocks = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_inflate_device: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end)");
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_inflate_device: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
     c->gz_text_bytes = 0, c->zs_blocks = c->zs_frames = c->zs_rounds = 0;
     for (float &x : c->zs_ms) x = 0;
     // (whatever keeps the file from being taken -- anything the walk, a block or a checksum refuses, no room, a device error -- is MK_OK
@@ -181,6 +285,71 @@ int mk_zstd_info(const mk_codec *c, uint32_t *blocks, uint32_t *frames, uint32_t
     if (ms)
         for (int k = 0; k < 6; ++k) ms[k] = c->zs_ms[k];
     return MK_OK;
+}
+
+// ---- a .zst file of any size, window by window
+
+int mk_zstd_stream_begin(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t window_bytes, uint32_t *taken) {
+    MK_ABI_BEGIN
+    if (!c || !taken || (n && !zs)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_begin: NULL argument");
+    *taken = 0;
+    if (window_bytes > (1ull << 40)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_begin: a window of 1 TiB at most");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_begin: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+    mkz::ZsStream s;
+    if (!mkz::zs_stream_open(s, zs, n, window_bytes)) return MK_OK;  // (not a zstd file)
+    MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
+    mkz::gz_release(c);  // the one-shot text of an earlier call goes: d_gz_text is the stream's from here on
+    c->zs_blocks = c->zs_frames = c->zs_rounds = 0;
+    c->zss = mk_zstd_stream();
+    c->zss.s = s, c->zss.active = true;
+    c->zss.s.text_cap = ZsStreamDev::default_text_cap(c);  // (once: a stream's windows do not move with the free memory)
+    *taken = 1;
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_zstd_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
+    MK_ABI_BEGIN
+    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_next: NULL argument");
+    *text_bytes = 0, *state = 2;
+    std::lock_guard<std::mutex> lock(c->mu);
+    mk_zstd_stream &D = c->zss;
+    if (!D.active) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_next: no open stream (mk_zstd_stream_begin)");
+    c->gz_text_bytes = 0;
+    if (hipSetDevice(c->device) != hipSuccess) {
+        (void)hipGetLastError();
+        D.s.dead = true;
+        return MK_OK;
+    }
+    ZsStreamDev dev{c, D};
+    const double t0 = now_ms();
+    const float in_steps = D.s.stats.ms[0] + D.s.stats.ms[1] + D.s.stats.ms[3] + D.s.stats.ms[4] + D.s.stats.ms[5];
+    mkz::zs_stream_next(D.s, dev, text_bytes, state);
+    // (scans: what the window's call spent on the host outside the device steps -- the walk and the two scans)
+    D.s.stats.ms[2] += std::max(0.f, (float)(now_ms() - t0) - (D.s.stats.ms[0] + D.s.stats.ms[1] + D.s.stats.ms[3] + D.s.stats.ms[4] + D.s.stats.ms[5] - in_steps));
+    if (*state == 0) c->gz_text_bytes = *text_bytes;
+    D.s.stats.peak_device_bytes = std::max<uint64_t>(D.s.stats.peak_device_bytes, stream_held(c));
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_zstd_stream_info(const mk_codec *c, mk_zstd_stream_stats *out) {
+    MK_ABI_BEGIN
+    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_info: NULL argument");
+    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_zstd_stream_next writes them under it: a call beside it waits for the window)
+    *out = c->zss.s.stats;  // (no stream open: what the last one left, zeros if there was none)
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_zstd_stream_end(mk_codec *c) {
+    MK_ABI_BEGIN
+    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_end: NULL handle");
+    std::lock_guard<std::mutex> lock(c->mu);
+    mkz::zstd_stream_close(c);
+    return MK_OK;
+    MK_ABI_END
 }
 
 }  // extern "C"

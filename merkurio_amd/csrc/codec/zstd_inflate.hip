@@ -22,8 +22,12 @@
 //                          its source's source.  A round reads the round before it only (two source arrays); the host launches
 //                          rounds until one leaves nothing open, at most log2(blocks) + 2 of them.
 //
-// LDS: ZsTables, 9.8 KB per wave in the decode kernel (58 VGPRs; LDS admits 16 waves per CU), none elsewhere (14 and 12 VGPRs).  No
-// private memory anywhere.
+// A stream (mk_zstd_stream_*, zstd_chain.hpp) launches the same three kernels per window: text below `settled` -- the history the
+// window before left, copied to the front of the text buffer -- is final, the execute step reads a match source there as a byte,
+// and the rounds start behind it.  The one-shot call passes 0 for both.
+//
+// LDS: ZsTables, 9.8 KB per wave in the decode kernel (58 VGPRs; LDS admits 16 waves per CU), none elsewhere (14 and 14 VGPRs).  No
+// private memory anywhere (profiles/isa_resources.txt).
 #include <hip/hip_runtime.h>
 
 #include "codec_kernels.h"
@@ -53,7 +57,9 @@ struct ZsWaveOut {
     uint8_t *text;
     uint32_t *src;
     uint32_t lane;
-    uint64_t synced;  // every store of this wave to text below this position has been waited for
+    uint64_t synced;   // every store of this wave to text below this position has been waited for
+    uint64_t settled;  // text below this position is final: a stream's history, copied there by an earlier operation of the launch's
+                       // HIP stream (the one-shot call: 0)
     __device__ __forceinline__ bool leader() const { return lane == 0; }
     __device__ __forceinline__ uint32_t first() const { return lane; }
     __device__ __forceinline__ uint32_t step() const { return 64; }
@@ -93,7 +99,10 @@ struct ZsWaveOut {
             bool is_open = false;
             if (k < len) {
                 const uint64_t from = to - off + (off >= len ? k : k % off);
-                if (from < block_pos) {
+                if (from < settled) {
+                    // (a per-lane choice, no cross-lane step inside it.  A plain load: this launch does not write below `settled`)
+                    text[to + k] = text[from], src[to + k] = kZsResolved;
+                } else if (from < block_pos) {
                     src[to + k] = (uint32_t)from, is_open = true;
                 } else {
                     // (past the CU's L1: a line may have been cached before its last bytes were stored)
@@ -114,17 +123,17 @@ __global__ __launch_bounds__(64) void mk_zs_decode_kernel(const uint8_t *in, uin
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
     ZsIn<ZsWaveWords> bits;
     bits.w = ZsWaveWords{reinterpret_cast<const uint32_t *>(in), n_words, ~0ull, 0u, lane};
-    ZsWaveOut out{in, lit, ll, ml, of, nullptr, nullptr, lane, 0};
+    ZsWaveOut out{in, lit, ll, ml, of, nullptr, nullptr, lane, 0, 0};
     ZsReport r;
     zs_decode_block(bits, n, blocks[b], T, out, r);
     if (lane == 0) rep[b] = r;
 }
 
 __global__ __launch_bounds__(64) void mk_zs_execute_kernel(const uint8_t *in, const ZsBlock *blocks, const ZsStart *start, const ZsReport *rep, uint8_t *lit,
-                                                          uint32_t *ll, uint32_t *ml, uint32_t *of, uint8_t *text, uint32_t *src, int32_t *status,
-                                                          unsigned long long *open_total) {
+                                                          uint32_t *ll, uint32_t *ml, uint32_t *of, uint8_t *text, uint32_t *src, uint64_t settled,
+                                                          int32_t *status, unsigned long long *open_total) {
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
-    ZsWaveOut out{in, lit, ll, ml, of, text, src, lane, 0};
+    ZsWaveOut out{in, lit, ll, ml, of, text, src, lane, 0, settled};
     uint32_t open = 0;
     const int st = zs_execute(blocks[b], start[b], rep[b].regen, ll, ml, of, out, &open);
     if (lane == 0) {
@@ -133,9 +142,13 @@ __global__ __launch_bounds__(64) void mk_zs_execute_kernel(const uint8_t *in, co
     }
 }
 
-__global__ __launch_bounds__(256) void mk_zs_resolve_kernel(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t total, unsigned long long *open_total) {
+// positions [first, total): what lies below `first` (a stream's settled history) is final and is never a source's source -- every
+// source of a visited byte is either settled, and was then copied by the execute step, or lies in an earlier block of the same
+// window --, so zs_round_cap(blocks of the window) bounds the rounds as it bounds them for a whole file
+__global__ __launch_bounds__(256) void mk_zs_resolve_kernel(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t first, uint64_t total,
+                                                            unsigned long long *open_total) {
     const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = (uint64_t)blockIdx.x * 256; base < total; base += (uint64_t)gridDim.x * 256) {
+    for (uint64_t base = first + (uint64_t)blockIdx.x * 256; base < total; base += (uint64_t)gridDim.x * 256) {
         const uint64_t i = base + threadIdx.x;
         const uint32_t open = i < total ? zs_resolve_byte(i, a, b, text) : 0u;
         const unsigned long long m = __ballot(open != 0);
@@ -151,14 +164,14 @@ void launch_zs_decode(const uint8_t *in, uint64_t n, uint64_t n_words, const voi
                        reinterpret_cast<ZsReport *>(rep));
 }
 void launch_zs_execute(const uint8_t *in, const void *blocks, const void *start, const void *rep, uint32_t n_blocks, uint8_t *lit, uint32_t *ll, uint32_t *ml,
-                       uint32_t *of, uint8_t *text, uint32_t *src, int32_t *status, unsigned long long *open_total, hipStream_t s) {
+                       uint32_t *of, uint8_t *text, uint32_t *src, uint64_t settled, int32_t *status, unsigned long long *open_total, hipStream_t s) {
     hipLaunchKernelGGL(mk_zs_execute_kernel, dim3(n_blocks), dim3(64), 0, s, in, reinterpret_cast<const ZsBlock *>(blocks), reinterpret_cast<const ZsStart *>(start),
-                       reinterpret_cast<const ZsReport *>(rep), lit, ll, ml, of, text, src, status, open_total);
+                       reinterpret_cast<const ZsReport *>(rep), lit, ll, ml, of, text, src, settled, status, open_total);
 }
-void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t total, unsigned long long *open_total, int num_cus, hipStream_t s) {
-    const uint64_t want = (total + 255) / 256;
+void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t first, uint64_t total, unsigned long long *open_total, int num_cus, hipStream_t s) {
+    const uint64_t want = (total - first + 255) / 256;
     const uint32_t grid = (uint32_t)(want < (uint64_t)num_cus * 16 ? want : (uint64_t)num_cus * 16);
-    hipLaunchKernelGGL(mk_zs_resolve_kernel, dim3(grid ? grid : 1), dim3(256), 0, s, a, b, text, total, open_total);
+    hipLaunchKernelGGL(mk_zs_resolve_kernel, dim3(grid ? grid : 1), dim3(256), 0, s, a, b, text, first, total, open_total);
 }
 
 }  // namespace mkz

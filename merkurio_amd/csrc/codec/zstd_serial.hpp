@@ -152,6 +152,8 @@ struct ZsSerialOut {
     uint32_t *ll, *ml, *of;
     uint8_t *text;
     uint32_t *src;
+    uint64_t settled = 0;       // text below this position is final (a stream's carried history): a match reads it as bytes
+    uint64_t settled_hits = 0;  // (the tests' census: bytes copied out of it)
     MKZS_HD bool leader() const { return true; }
     MKZS_HD uint32_t first() const { return 0; }
     MKZS_HD uint32_t step() const { return 1; }
@@ -175,13 +177,15 @@ struct ZsSerialOut {
     MKZS_HD void text_fill(uint64_t to, uint32_t n, uint32_t b) {
         for (uint32_t k = 0; k < n; ++k) text[to + k] = (uint8_t)b, src[to + k] = kZsResolved;
     }
-    // byte k of the match = byte k mod off of the off bytes in front of it.  A source in front of the block is left as a position; a
-    // source inside the block that is itself a position hands that position on.  -> bytes left as positions
+    // byte k of the match = byte k mod off of the off bytes in front of it.  A source in front of the block is left as a position --
+    // unless it lies below `settled`, where the text is final: that byte is copied --; a source inside the block that is itself a
+    // position hands that position on.  -> bytes left as positions
     MKZS_HD uint32_t text_match(uint64_t to, uint64_t off, uint32_t len, uint64_t block_pos) {
         uint32_t open = 0;
         for (uint32_t k = 0; k < len; ++k) {
             const uint64_t from = to - off + (off >= len ? k : k % off);
-            if (from < block_pos) src[to + k] = (uint32_t)from, ++open;
+            if (from < settled) text[to + k] = text[from], src[to + k] = kZsResolved, ++settled_hits;
+            else if (from < block_pos) src[to + k] = (uint32_t)from, ++open;
             else if (src[from] == kZsResolved) text[to + k] = text[from], src[to + k] = kZsResolved;
             else src[to + k] = src[from], ++open;
         }
@@ -549,7 +553,8 @@ MKZS_HD int zs_execute(const ZsBlock &B, const ZsStart &S, uint32_t regen, const
 }
 
 // ---- cross-block resolution: one step of pointer doubling for text byte i, from the sources `a` of the round before to `b` --------------
-// Every source lies in an earlier block, so a chain is at most as long as the file has blocks.  -> 1: the byte is still a position
+// Every source lies in an earlier block -- of the same launch: what lies below a stream's settled history never becomes a position --,
+// so a chain is at most as long as the launch has blocks.  -> 1: the byte is still a position
 MKZS_HD uint32_t zs_resolve_byte(uint64_t i, const uint32_t *a, uint32_t *b, uint8_t *text) {
     const uint32_t s = a[i];
     if (s == kZsResolved) {

@@ -11,6 +11,10 @@ in alternation.
          way: the control row, which must not move.  Every run is a process of its own under a time limit; a run that fails ends the
          script there.
 
+  sweep  the large files under --zstd-stream at every --windows value (compressed bytes per window, mk_zstd_stream_*) against the
+         parent's binary, in alternation, medians of --runs; per window size the stream's summary row (windows, rounds, the six
+         phases summed, peak device bytes) as medians.  Prints the table of profiles/e2e_unzstd_windows.txt.
+
 Prints the table of profiles/e2e_unzstd.txt.  The device path becomes `extract`'s default for .zst only if its median is below the
 parent's on both large-file rows by more than the two ranges overlap.  Example:
   tools/e2e_unzstd.py make --dir /tmp/zs
@@ -133,6 +137,40 @@ def run(a):
             print(f"{inp}: " + ", ".join(f"{n} {statistics.median(c):.1f}" for n, c in zip(names, cols)) + " (ms, medians)")
 
 
+STREAM = re.compile(r"zstd input 0 on the device, window by window: (\d+) windows, (\d+) frames closed, (\d+) blocks, (\d+) rounds, largest history (\d+) bytes, "
+                    r"handed back at -, [\d.]+ s \(upload ([\d.]+), tables \+ entropy decode ([\d.]+), walk \+ scans ([\d.]+), execution ([\d.]+), "
+                    r"cross-block rounds ([\d.]+), checksum ([\d.]+) ms; peak (\d+) device bytes")
+
+
+def sweep(a):
+    patterns = os.path.join(a.dir, "patterns.txt")
+    out = os.path.join(a.dir, "out.fastq")
+    inputs = ["big.l3.fastq.zst", "big.l19.fastq.zst"]
+    windows = [int(w) for w in a.windows.split(",")]
+    times = {(inp, w): [] for inp in inputs for w in windows + ["parent"]}
+    rows = {(inp, w): [] for inp in inputs for w in windows}
+    for r in range(a.runs):
+        for inp in inputs:
+            path = os.path.join(a.dir, inp)
+            for w in windows:  # (this build at one window size, then the parent: in alternation)
+                dt, err = run_once(BIN, path, patterns, out, ["--zstd-stream", "--zstd-window", str(w)])
+                m = STREAM.search(err)
+                if not m:
+                    raise SystemExit(f"{inp} at window {w}: the stream did not reach the file's end\n{err[-2000:]}")
+                times[(inp, w)].append(dt)
+                rows[(inp, w)].append([float(x) for x in m.groups()])
+                times[(inp, "parent")].append(run_once(a.parent_bin, path, patterns, out, [])[0])
+            print(f"# round {r}: {inp} done", flush=True)
+    print(f"extract --zstd-stream, seconds per run, median [min .. max] of {a.runs}, alternating with the parent's binary")
+    names = ("windows", "frames", "blocks", "rounds", "largest history", "upload", "tables + entropy decode", "walk + scans", "execution", "cross-block rounds",
+             "checksum", "peak device bytes")
+    for inp in inputs:
+        print(f"{inp:24s} parent (libzstd, one thread) {med(times[(inp, 'parent')])}")
+        for w in windows:
+            print(f"{inp:24s} --zstd-window {w:<12d} {med(times[(inp, w)])}")
+            print("    " + ", ".join(f"{n} {statistics.median(c):.1f}" for n, c in zip(names, zip(*rows[(inp, w)]))) + " (ms summed over the windows, medians)")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -144,5 +182,10 @@ if __name__ == "__main__":
     r.add_argument("--dir", required=True)
     r.add_argument("--parent-bin", required=True)
     r.add_argument("--runs", type=int, default=5)
+    s = sub.add_parser("sweep")
+    s.add_argument("--dir", required=True)
+    s.add_argument("--parent-bin", required=True)
+    s.add_argument("--runs", type=int, default=5)
+    s.add_argument("--windows", default="16777216,67108864,268435456", help="compressed bytes per window, comma-separated")
     a = ap.parse_args()
-    make(a) if a.cmd == "make" else run(a)
+    {"make": make, "run": run, "sweep": sweep}[a.cmd](a)
