@@ -730,6 +730,32 @@ int mk_codec_set_bzip2_pass_blocks(mk_codec *c, uint64_t blocks);
 int mk_zstd_inflate_device(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
 int mk_zstd_info(const mk_codec *c, uint32_t *blocks, uint32_t *frames, uint32_t *rounds, float ms[6]);
 
+/* (v7) The kept records of `extract` as a .zst file, compressed on the device (zstd_deflate.hip, a wave per frame): what
+ * mk_bgzf_deflate_records is for BGZF.  The text is cut by the rule of mk_bgzf_record_cuts with two other constants: a cut is looked for at
+ * every multiple of MK_ZSTD_CUT_GRID among the record ends of the next MK_ZSTD_FRAME_TEXT_MAX - MK_ZSTD_CUT_GRID bytes, so only a longer
+ * record is cut inside.  Every piece becomes one frame that decodes on its own: magic, descriptor 0xA4 (Single_Segment,
+ * Content_Checksum, 4-byte Frame_Content_Size), ONE block with Last_Block set, the low 32 bits of XXH64 (seed 0) of its text -- 16 bytes
+ * plus the block.  The block is RLE where all bytes are equal, Raw where the compressed form is not smaller than the text, Compressed
+ * otherwise.  Fixed choices of the writer: no match reaches in front of its block and there is no dictionary; offsets are always coded
+ * as offset + 3 (no repeat-offset codes); literals are RLE for one distinct byte, Huffman-coded under a tree of direct 4-bit weights
+ * (code lengths <= 11; one stream below 1024 literals, four from there on), and Raw where that does not shrink them or a byte above 128
+ * occurs (FSE-coded weights are not written); each sequence table is RLE where one code occurs, else the cheaper of Predefined and
+ * FSE_Compressed by an estimate from its histogram.  Any conforming decoder reads the frames; no ratio is promised.
+ * mk_zstd_record_cuts (host code, no device): the rule -> cut[0, *n_cuts); the contract of mk_bgzf_record_cuts.
+ * mk_zstd_deflate_bound: the bytes the frames of n bytes of text take at most.
+ * mk_zstd_deflate_records: the contract of mk_bgzf_deflate_records -- rec_end[n_rec - 1] == n and non-decreasing ends, else
+ * MK_E_INVALID_ARG; MK_E_CAPACITY with the exact need in *out_len; n == 0 writes nothing (0 frames); passes of
+ * mk_codec_set_pass_limits' deflate_blocks frames; MK_E_INVALID_ARG while a stream is open on the handle.
+ * mk_zstd_deflate_info: of the last such call, the frames, how many blocks were Raw / RLE / Compressed, and milliseconds of upload,
+ * cut + deflate + pack, download. */
+#define MK_ZSTD_CUT_GRID 114688u
+#define MK_ZSTD_FRAME_TEXT_MAX 131072u
+int mk_zstd_record_cuts(const uint64_t *rec_end, uint64_t n_rec, uint64_t *cut, uint64_t cap, uint64_t *n_cuts);
+uint64_t mk_zstd_deflate_bound(uint64_t n);   /* n + 16 * (n / MK_ZSTD_CUT_GRID + 2) */
+int mk_zstd_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const uint64_t *rec_end, uint64_t n_rec,
+                            uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *n_frames);
+int mk_zstd_deflate_info(const mk_codec *c, uint64_t *n_frames, uint32_t kinds[3] /* raw, rle, compressed blocks */, float ms[3]);
+
 /* (v7) A .bz2 file of ANY size, decoded on the device window by window: nothing on the device is sized by the file.  The contract is
  * mk_gzip_stream_*'s (below).  mk_bzip2_stream_begin: bz[0, n) = the whole file (the caller's -- the mapped file -- until _end);
  * window_bytes = compressed bytes per window (0 = 256 MiB, an unmeasured choice: profiles/e2e_bunzip2_windows.txt).  *taken = 0: no

@@ -63,6 +63,7 @@ def _units():
     units.append(("codec_gzip_segments_wave.o", "codec/gzip_segments_wave.hip", []))
     units.append(("codec_bzip2_inflate.o", "codec/bzip2_inflate.hip", []))
     units.append(("codec_zstd_inflate.o", "codec/zstd_inflate.hip", []))
+    units.append(("codec_zstd_deflate.o", "codec/zstd_deflate.hip", []))
     units.append(("codec_host.o", "codec/codec_host.cpp", []))
     units.append(("codec_bgzf_host.o", "codec/bgzf_host.cpp", []))
     units.append(("codec_gzip_host.o", "codec/gzip_host.cpp", []))

@@ -47,6 +47,7 @@ struct ExtractArgs : CommonArgs {
     std::optional<std::string> in_fastq_2;  // -2
     std::optional<std::string> out_fastx;   // -o
     bool bgzf_output = false;               // -z: the kept records are written as BGZF members that end at record ends (output name + ".gz")
+    bool zstd_output = false;               // --zstd-output: the kept records are written as zstd frames that end at record ends (output name + ".zst")
     // --z-members-from: with -z on the window path, a window whose written kept records take this many bytes or more is cut and deflated
     // where it lies and comes down as members (mk_extract_window_members); a smaller one comes down as text and gathers with its neighbours
     uint64_t z_members_from = kZMembersFrom;

@@ -7,6 +7,7 @@
 
 #include <cstring>
 
+#include "bgzf_out.hpp"
 #include "io.hpp"
 
 namespace cli {
@@ -203,6 +204,28 @@ void inflate_zstd(const std::string &path, const unsigned char *d, size_t n, std
 }
 
 }  // namespace
+
+// (declared in bgzf_out.hpp) `extract --zstd-output --host-codec`: one frame per call, a context per call (the callers are threads)
+void zstd_compress_frame(const uint8_t *src, size_t n, int level, std::vector<uint8_t> &out) {
+    static void *h = open_any({"libzstd.so.1", "libzstd.so"});
+    if (!h) bail("zstd output with --host-codec needs libzstd.so.1, which is not installed");
+    static auto create = (void *(*)())dlsym(h, "ZSTD_createCCtx");
+    static auto free_ = (size_t (*)(void *))dlsym(h, "ZSTD_freeCCtx");
+    static auto set = (size_t (*)(void *, int, int))dlsym(h, "ZSTD_CCtx_setParameter");
+    static auto run = (size_t (*)(void *, void *, size_t, const void *, size_t))dlsym(h, "ZSTD_compress2");
+    static auto bound = (size_t (*)(size_t))dlsym(h, "ZSTD_compressBound");
+    static auto is_err = (unsigned (*)(size_t))dlsym(h, "ZSTD_isError");
+    if (!create || !free_ || !set || !run || !bound || !is_err) bail("libzstd lacks the ZSTD_compress2 API");
+    void *z = create();
+    if (!z) bail("Error compressing the output");
+    out.resize(bound(n));
+    // (ZSTD_c_compressionLevel = 100, ZSTD_c_checksumFlag = 201)
+    const bool bad = is_err(set(z, 100, level)) || is_err(set(z, 201, 1));
+    const size_t k = bad ? 0 : run(z, out.data(), out.size(), src, n);
+    free_(z);
+    if (bad || is_err(k)) bail("Error compressing the output");
+    out.resize(k);
+}
 
 bool zstd_first_bytes(const unsigned char *d, size_t n, std::vector<char> &out, size_t want) {
     out.clear();

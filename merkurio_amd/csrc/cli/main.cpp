@@ -23,7 +23,7 @@ const Spec kCommon[] = {{'s', "kmer-seq", 2},      {'f', "kmer-file", 1},    {'r
                         {'I', "case-insensitive", 0}, {'L', "lowercase", 0}, {'U', "uppercase", 0},          {'q', "q-size", 1},
                         {'a', "aho-corasick", 0},  {0, "device", 1},         {0, "batch-mb", 1},           {0, "gpus", 1},                 {0, "window-mb", 1},
                         {0, "host-ingest", 0},     {0, "host-codec", 0},     {0, "device-codec-always", 0}};
-const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}, {'z', "bgzf-output", 0}, {0, "z-members-from", 1}, {0, "gzip-window", 1}, {0, "bzip2-window", 1}, {0, "zstd-window", 1}, {0, "device-zstd", 0}, {0, "zstd-stream", 0}};
+const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}, {'z', "bgzf-output", 0}, {0, "z-members-from", 1}, {0, "gzip-window", 1}, {0, "bzip2-window", 1}, {0, "zstd-window", 1}, {0, "device-zstd", 0}, {0, "zstd-stream", 0}, {0, "zstd-output", 0}};
 const Spec kTag[] = {{'i', "in-file", 1}, {'o', "out-file", 1}, {'t', "tag", 1}, {'p', "threads", 1}, {'m', "filter-matching", 0}};
 
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -46,6 +46,7 @@ void print_help(const char *sub) {
              "      --z-members-from <BYTES> with -z: a window whose kept records take this many bytes or more leaves the GPU as BGZF members [8388608]\n"
              "      --gzip-window <BYTES>    a .gz input larger than this is inflated on the GPU a window of this many compressed bytes at a time [268435456]\n"
              "      --bzip2-window <BYTES>   a .bz2 input larger than this is decoded on the GPU a window of this many compressed bytes at a time [268435456]\n"
+             "      --zstd-output            write the records as zstd frames ending at record ends (output name + .zst; compressed on the GPU, --host-codec: libzstd level 3; not timed)\n"
              "      --device-zstd            decode a .zst input on the GPU (default: libzstd on the host; the GPU path has not been timed)\n"
              "      --zstd-window <BYTES>    with --device-zstd: a .zst input of at most this many compressed bytes goes to the GPU in one call [268435456]\n"
              "      --zstd-stream            implies --device-zstd: a larger .zst input is decoded on the GPU window by window (not timed either)\n"
@@ -257,6 +258,9 @@ int main(int argc, char **argv) {
             if (auto v = p.get("zstd-window")) a.zstd_window = std::max<uint64_t>(1, to_num((*v)[0], "--zstd-window <BYTES>"));
             a.zstd_stream = p.get("zstd-stream") != nullptr;
             a.device_zstd = a.zstd_stream || p.get("device-zstd") != nullptr;
+            a.zstd_output = p.get("zstd-output") != nullptr;
+            if (a.zstd_output && a.bgzf_output) usage_error("the argument '--bgzf-output' cannot be used with '--zstd-output'");
+            if (a.zstd_output && p.get("suppress-output")) usage_error("the argument '--suppress-output' cannot be used with '--zstd-output'");
             if (a.bgzf_output && p.get("suppress-output")) usage_error("the argument '--suppress-output' cannot be used with '--bgzf-output'");
             fill_common(p, a, (bool)a.out_fastx);
             g_process_is_ending = true;

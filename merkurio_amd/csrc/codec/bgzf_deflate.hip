@@ -371,34 +371,14 @@ __global__ __launch_bounds__(64, 4) void mk_bgzf_deflate_ranges_kernel(const uin
     deflate_members(L, in, RangeTable{off, len}, n_blocks, crc, tokens, slots, slot_len, next_block);
 }
 
-// ---- members that end at record ends: the cut rule of include/merkurio_hip.h (mk_bgzf_record_cuts is the same rule on the host) ----
-// rec_end[0, n_rec): the ends of the records of a text of T bytes, non-decreasing (a record that is not kept repeats the end in front
-// of it), rec_end[n_rec - 1] = T.  Grid point k (x = k * kCutGrid, k = 1 .. K - 1, K = ceil(T / kCutGrid)) snaps to the first record
-// end e >= x if e < x + kCutReach, and stays at x otherwise.  One lane per grid point, one binary search for its own cut and one for
-// the cut behind it: snap(x) lies in [x, x + kCutReach) and kCutReach <= kCutGrid, so the cuts of two grid points never meet -- the
-// only cut that can coincide with another is the last one with T, which is what lane K - 1 looks at.  Member k = [cut k, cut k + 1):
-// off[k], len[k]; *n_members = K, or K - 1 when the last grid point snapped to T.
+// ---- members that end at record ends: the cut rule of include/merkurio_hip.h (mk_bgzf_record_cuts is the same rule on the host; both
+// are bgzf_cuts.hpp's, instantiated with kCutGrid and kCutReach).  Member k = [cut k, cut k + 1): off[k], len[k]; *n_members = K, or K - 1
+// when the last grid point snapped to T.
 static_assert(kCutReach <= kCutGrid && kCutGrid + kCutReach == kMaxBlockBytes, "the cuts of two grid points cannot coincide; a member holds kMaxBlockBytes at most");
-__device__ __forceinline__ uint64_t snap_cut(const unsigned long long *__restrict__ rec_end, uint64_t n_rec, uint64_t x) {
-    uint64_t lo = 0, hi = n_rec;  // the first record end >= x: there is one, x < T = rec_end[n_rec - 1]
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (rec_end[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    const uint64_t e = lo < n_rec ? rec_end[lo] : x;
-    return e - x < kCutReach ? e : x;
-}
 __global__ __launch_bounds__(128) void mk_bgzf_cuts_kernel(const unsigned long long *__restrict__ rec_end, uint64_t n_rec, uint64_t T,
                                                            uint32_t n_grid, unsigned long long *__restrict__ off, uint32_t *__restrict__ len,
                                                            uint32_t *__restrict__ n_members) {
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n_grid; k += gridDim.x * blockDim.x) {
-        const uint64_t a = k ? snap_cut(rec_end, n_rec, (uint64_t)k * kCutGrid) : 0;
-        const uint64_t b = k + 1 < n_grid ? snap_cut(rec_end, n_rec, (uint64_t)(k + 1) * kCutGrid) : T;
-        off[k] = a;
-        len[k] = (uint32_t)(b - a);
-        if (k + 1 == n_grid) *n_members = b > a ? n_grid : n_grid - 1;
-    }
+    cut_ranges<kCutGrid, kCutReach>(rec_end, n_rec, T, n_grid, off, len, n_members);
 }
 
 // ---- CRC-32 of each block: a piece per lane (slice-by-4), folded by the wave ------------------------------------

@@ -103,6 +103,11 @@ struct mk_codec {
     uint32_t zs_blocks = 0, zs_frames = 0, zs_rounds = 0;
     float zs_ms[6] = {0, 0, 0, 0, 0, 0};  // upload, tables + entropy decode, scans, execution, cross-block rounds, checksum
     uint64_t zs_text_cap = 0;             // mk_codec_set_zstd_text_cap: bytes of text per window of a zstd stream; 0 = by the free memory
+    // mk_zstd_deflate_records (zstd_host.cpp; text, record ends, range table, slots and packed frames are the deflate side's buffers above,
+    // the waves' literal / sequence scratch is d_tokens)
+    uint64_t zd_frames = 0;
+    uint32_t zd_kinds[3] = {0, 0, 0};  // Raw, RLE, Compressed blocks of the last call
+    float zd_ms[3] = {0, 0, 0};        // upload, cut + deflate + pack, download
     int inflate_kernel = 0;  // mk_codec_set_inflate_kernel: 0 = chosen per call, 1 = a lane per member, 2 = a wave per member
     float ms[3] = {0, 0, 0};
     uint64_t gzip_chunk = 0;  // mk_codec_set_gzip_chunk; 0 = by the stream's size

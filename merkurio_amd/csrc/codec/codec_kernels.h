@@ -121,4 +121,19 @@ void launch_zs_execute(const uint8_t *in, const void *blocks, const void *start,
 // one round of pointer doubling over text[first, total): sources a -> b; *open_total += the bytes still open
 void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t first, uint64_t total, unsigned long long *open_total, int num_cus, hipStream_t s);
 
+// ---- zstd frames written on the device, a wave per frame (zstd_deflate.hip, zstd_enc_serial.hpp) ----
+constexpr uint32_t kZsDeflateSlotBytes = 131328;       // a frame never exceeds 16 bytes + 128 KiB of text (a Raw block)
+constexpr uint32_t kZsDeflateLitBytes = 131136;        // literal scratch of one resident wave
+constexpr uint32_t kZsDeflateSeqCap = 43712;           // sequences a block holds at most (128 KiB / the minimum match of 3), rounded up
+constexpr uint64_t kZsDeflateWaveScratch = 1005376;    // literals + five u32 per sequence
+uint32_t zstd_deflate_grid(uint32_t n_frames, int num_cus);
+// the range table of the frames of a text (launch_cuts with kZsCutGrid / kZsCutReach)
+void launch_zstd_cuts(const unsigned long long *rec_end, uint64_t n_rec, uint64_t n_text, uint32_t n_grid, unsigned long long *off, uint32_t *len,
+                      uint32_t *n_frames, hipStream_t s);
+// frame b = in[off[b], off[b] + len[b]) (len[b] <= 128 KiB) -> slots[b * kZsDeflateSlotBytes ...], slot_len[b]; kinds[0 .. 2] += Raw / RLE /
+// Compressed blocks.  scratch: kZsDeflateWaveScratch bytes per launched wave; `in` readable up to kPad bytes behind the last range
+void launch_zstd_deflate(const uint8_t *in, const unsigned long long *off, const uint32_t *len, uint32_t n_frames, uint8_t *scratch, uint8_t *slots,
+                         uint32_t *slot_len, uint32_t *next_frame, uint32_t *kinds, uint32_t grid, hipStream_t s);
+void launch_zstd_pack(const uint8_t *slots, const uint32_t *slot_len, uint64_t *slot_off, uint64_t *total, uint32_t n_frames, uint8_t *packed, hipStream_t s);
+
 }  // namespace mkz

@@ -352,4 +352,110 @@ int mk_zstd_stream_end(mk_codec *c) {
     MK_ABI_END
 }
 
+// ---- zstd frames written on the device (zstd_deflate.hip): the kept records of `extract` as a .zst file, one frame per cut
+
+int mk_zstd_record_cuts(const uint64_t *rec_end, uint64_t n_rec, uint64_t *cut, uint64_t cap, uint64_t *n_cuts) {
+    if (!n_cuts || (n_rec && !rec_end) || (cap && !cut)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_record_cuts: NULL argument");
+    *n_cuts = 0;
+    for (uint64_t r = 1; r < n_rec; ++r)
+        if (rec_end[r] < rec_end[r - 1]) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_record_cuts: record end %llu lies in front of the one before it", (unsigned long long)r);
+    const uint64_t k = mkz::zstd_record_cuts(rec_end, n_rec, cut, cap);
+    *n_cuts = k;
+    if (k > cap) return mk::fail(MK_E_CAPACITY, "mk_zstd_record_cuts: %llu cuts, room for %llu", (unsigned long long)k, (unsigned long long)cap);
+    return MK_OK;
+}
+
+uint64_t mk_zstd_deflate_bound(uint64_t n) { return n + 16 * (n / mkz::kZsCutGrid + 2); }  // a frame of a Raw block: 16 bytes + its text
+
+int mk_zstd_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const uint64_t *rec_end, uint64_t n_rec, uint8_t *out, uint64_t out_cap,
+                            uint64_t *out_len, uint64_t *n_frames) {
+    MK_ABI_BEGIN
+    if (!c || !out_len || !n_frames || (n && (!text || !rec_end)) || (out_cap && !out)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: NULL argument");
+    *out_len = 0, *n_frames = 0;
+    if ((n_rec ? rec_end[n_rec - 1] : 0) != n) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: the last record does not end where the text does");
+    for (uint64_t r = 1; r < n_rec; ++r)
+        if (rec_end[r] < rec_end[r - 1]) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: record end %llu lies in front of the one before it", (unsigned long long)r);
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+    MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
+    c->zd_frames = 0;
+    for (int k = 0; k < 3; ++k) c->zd_kinds[k] = 0, c->zd_ms[k] = 0;
+    if (!n) return MK_OK;
+    const uint64_t grid64 = (n + mkz::kZsCutGrid - 1) / mkz::kZsCutGrid;
+    if (grid64 >= 0x7FFFFFFFull) return mk::fail(MK_E_UNSUPPORTED, "%llu output frames", (unsigned long long)grid64);
+    const uint32_t n_grid = (uint32_t)grid64;
+    int rc;
+    // the range table: count | kinds[3] | off[n_grid] | len[n_grid]
+    if ((rc = mk::ensure_device(&c->d_in, &c->in_cap, n + mkz::kPad)) || (rc = mk::ensure_device(&c->d_ends, &c->ends_cap, n_rec * 8ull)) ||
+        (rc = mk::ensure_device(&c->d_cut, &c->cut_cap, 16 + n_grid * 12ull)))
+        return rc;
+    uint32_t *d_count = (uint32_t *)c->d_cut, *d_kinds = d_count + 1;
+    unsigned long long *d_off = (unsigned long long *)((uint8_t *)c->d_cut + 16);
+    uint32_t *d_len = (uint32_t *)(d_off + n_grid);
+    double t0 = mkz::now_ms();
+    if ((rc = mkz::upload(c, c->d_in, text, n)) || (rc = mkz::upload(c, c->d_ends, (const uint8_t *)rec_end, n_rec * 8ull))) return rc;
+    MKC_HIP(hipMemsetAsync((uint8_t *)c->d_in + n, 0, mkz::kPad, c->stream), "hipMemsetAsync");
+    MKC_HIP(hipMemsetAsync(c->d_cut, 0, 16, c->stream), "hipMemsetAsync");
+    MKC_HIP(hipStreamSynchronize(c->stream), "upload of the text");
+    c->zd_ms[0] = (float)(mkz::now_ms() - t0);
+    t0 = mkz::now_ms();
+    mkz::launch_zstd_cuts((const unsigned long long *)c->d_ends, n_rec, n, n_grid, d_off, d_len, d_count, c->stream);
+    uint32_t frames = 0;
+    MKC_HIP(hipGetLastError(), "the cut kernel");
+    MKC_HIP(hipMemcpyAsync(&frames, d_count, 4, hipMemcpyDeviceToHost, c->stream), "download of the frame count");
+    MKC_HIP(hipStreamSynchronize(c->stream), "the cut kernel");
+    if (frames > n_grid || frames + 1 < n_grid) return mk::fail(MK_E_HIP, "the cut kernel reports %u frames of %u grid points", frames, n_grid);
+    c->zd_ms[1] = (float)(mkz::now_ms() - t0);
+    // passes of frames; a pass is downloaded as long as everything so far has fitted.  4 096 frames by default: 0.54 GB of slots (131 328 B
+    // each) beside the resident waves' scratch (8 per CU x 1 005 376 B: 2.06 GB on 256 CUs once a pass has that many frames)
+    const uint64_t pass = std::min<uint64_t>(c->deflate_pass_blocks ? c->deflate_pass_blocks : 4096, 0x7FFFFFFFu);
+    uint64_t written = 0;
+    bool fits = true;
+    for (uint64_t f0 = 0; f0 < frames; f0 += pass) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(pass, frames - f0);
+        const uint32_t grid = mkz::zstd_deflate_grid(cnt, c->num_cus);
+        const uint64_t bound = std::min<uint64_t>((uint64_t)cnt * mkz::kZsBlockMax, n) + cnt * 16ull;
+        if ((rc = mk::ensure_device(&c->d_tokens, &c->tokens_cap, (uint64_t)grid * mkz::kZsDeflateWaveScratch)) ||
+            (rc = mk::ensure_device(&c->d_slots, &c->slots_cap, (uint64_t)cnt * mkz::kZsDeflateSlotBytes)) ||
+            (rc = mk::ensure_device(&c->d_len, &c->len_cap, (cnt + 1) * 4ull)) || (rc = mk::ensure_device(&c->d_off, &c->off_cap, (cnt + 2) * 8ull)) ||
+            (rc = mk::ensure_device(&c->d_out, &c->out_cap, bound)))
+            return rc;
+        uint64_t *d_total = (uint64_t *)c->d_off + cnt;
+        t0 = mkz::now_ms();
+        mkz::launch_zstd_deflate((const uint8_t *)c->d_in, d_off + f0, d_len + f0, cnt, (uint8_t *)c->d_tokens, (uint8_t *)c->d_slots, (uint32_t *)c->d_len,
+                                 (uint32_t *)(d_total + 1), d_kinds, grid, c->stream);
+        mkz::launch_zstd_pack((const uint8_t *)c->d_slots, (const uint32_t *)c->d_len, (uint64_t *)c->d_off, d_total, cnt, (uint8_t *)c->d_out, c->stream);
+        uint64_t total = 0;
+        MKC_HIP(hipGetLastError(), "zstd deflate kernels");
+        MKC_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream), "download of the size");
+        MKC_HIP(hipStreamSynchronize(c->stream), "zstd deflate on the device");
+        c->zd_ms[1] += (float)(mkz::now_ms() - t0);
+        if (total > bound) return mk::fail(MK_E_HIP, "mk_zstd_deflate_records: frames exceed their bound (internal error)");
+        fits = fits && written + total <= out_cap;
+        if (fits && total) {
+            t0 = mkz::now_ms();
+            if ((rc = mkz::download(c, out + written, c->d_out, total))) return rc;
+            c->zd_ms[2] += (float)(mkz::now_ms() - t0);
+        }
+        written += total;
+    }
+    MKC_HIP(hipMemcpyAsync(c->zd_kinds, d_kinds, 12, hipMemcpyDeviceToHost, c->stream), "download of the block kinds");
+    MKC_HIP(hipStreamSynchronize(c->stream), "download of the block kinds");
+    c->zd_frames = frames;
+    *out_len = written, *n_frames = frames;
+    if (written > out_cap) return mk::fail(MK_E_CAPACITY, "mk_zstd_deflate_records: the frames take %llu bytes, room for %llu", (unsigned long long)written, (unsigned long long)out_cap);
+    return MK_OK;
+    MK_ABI_END
+}
+
+int mk_zstd_deflate_info(const mk_codec *c, uint64_t *n_frames, uint32_t kinds[3], float ms[3]) {
+    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_info: NULL handle");
+    if (n_frames) *n_frames = c->zd_frames;
+    for (int k = 0; k < 3; ++k) {
+        if (kinds) kinds[k] = c->zd_kinds[k];
+        if (ms) ms[k] = c->zd_ms[k];
+    }
+    return MK_OK;
+}
+
 }  // extern "C"

@@ -54,7 +54,7 @@ EXPORTS = [
     "mk_synth_reads_host", "mk_synth_reads_device_range", "mk_reduce_counters", "mk_reduce_prepare", "mk_comm_available", "mk_comm_unique_id", "mk_comm_init",
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
-    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_zstd_inflate_device", "mk_zstd_info", "mk_codec_set_bzip2_pass_blocks",
+    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_zstd_inflate_device", "mk_zstd_info", "mk_zstd_record_cuts", "mk_zstd_deflate_bound", "mk_zstd_deflate_records", "mk_zstd_deflate_info", "mk_codec_set_bzip2_pass_blocks",
     "mk_bzip2_stream_begin", "mk_bzip2_stream_next", "mk_bzip2_stream_info", "mk_bzip2_stream_end", "mk_codec_set_bzip2_text_cap",
     "mk_zstd_stream_begin", "mk_zstd_stream_next", "mk_zstd_stream_info", "mk_zstd_stream_end", "mk_codec_set_zstd_text_cap",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
@@ -334,6 +334,12 @@ def load(build_if_missing=True):
     L.mk_bzip2_stream_info.argtypes = [C.c_void_p, C.POINTER(Bzip2StreamStats)]
     L.mk_bzip2_stream_end.argtypes = [C.c_void_p]
     L.mk_codec_set_bzip2_text_cap.argtypes = [C.c_void_p, C.c_uint64]
+    L.mk_zstd_record_cuts.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mk_zstd_deflate_bound.argtypes = [C.c_uint64]
+    L.mk_zstd_deflate_bound.restype = C.c_uint64
+    L.mk_zstd_deflate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]
+    L.mk_zstd_deflate_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
     L.mk_zstd_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
     L.mk_zstd_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.mk_zstd_stream_info.argtypes = [C.c_void_p, C.POINTER(ZstdStreamStats)]
@@ -1146,6 +1152,21 @@ def bgzf_eof():
     return bytes(load().mk_bgzf_eof().contents)
 
 
+ZSTD_CUT_GRID, ZSTD_FRAME_TEXT_MAX = 114688, 131072
+
+
+def zstd_record_cuts(rec_end):
+    """mk_zstd_record_cuts (host code): where the zstd frames of a text end whose records end at rec_end -- the rule of
+    bgzf_record_cuts with MK_ZSTD_CUT_GRID and MK_ZSTD_FRAME_TEXT_MAX -> the cuts, from 0 to the text's end"""
+    L = load()
+    ends = np.ascontiguousarray(rec_end, dtype=np.uint64)
+    total = int(ends[-1]) if ends.size else 0
+    cut = np.empty(total // ZSTD_CUT_GRID + 3, dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(L.mk_zstd_record_cuts(ends.ctypes.data if ends.size else None, ends.size, cut.ctypes.data, cut.size, C.byref(n)))
+    return cut[:n.value].copy()
+
+
 def bgzf_record_cuts(rec_end):
     """mk_bgzf_record_cuts (host code): where the members of a text end whose records end at rec_end -- the cut rule of
     include/merkurio_hip.h -> uint64 array, first 0, last rec_end[-1] (no records: [0])"""
@@ -1215,6 +1236,30 @@ class Codec:
         self.last_need, self.last_members = n.value, members.value
         _check(rc)
         return out[:n.value].tobytes()
+
+    def zstd_records(self, text, rec_end, out_cap=None):
+        """mk_zstd_deflate_records: zstd frames of `text` that end at record ends (rec_end[-1] == len(text)), cut and compressed on the
+        device, one frame per cut.  out_cap (tests): the output buffer's size; too small raises MK_E_CAPACITY with self.last_need = the
+        exact need.  self.last_frames = how many frames there are"""
+        src = np.frombuffer(text, dtype=np.uint8)
+        ends = np.ascontiguousarray(rec_end, dtype=np.uint64)
+        if out_cap is None:
+            out_cap = self._L.mk_zstd_deflate_bound(src.size)
+        out = np.empty(out_cap, dtype=np.uint8)
+        n, frames = C.c_uint64(0), C.c_uint64(0)
+        rc = self._L.mk_zstd_deflate_records(self._h, src.ctypes.data if src.size else None, src.size, ends.ctypes.data if ends.size else None, ends.size,
+                                             out.ctypes.data if out.size else None, out.size, C.byref(n), C.byref(frames))
+        self.last_need, self.last_frames = n.value, frames.value
+        _check(rc)
+        return out[:n.value].tobytes()
+
+    zstd_record_cuts = staticmethod(lambda rec_end: zstd_record_cuts(rec_end))
+
+    def zstd_records_info(self):
+        """mk_zstd_deflate_info: (frames, (raw, rle, compressed) blocks, ms of upload / cut + deflate + pack / download) of the last zstd_records"""
+        n, kinds, ms = C.c_uint64(0), (C.c_uint32 * 3)(), (C.c_float * 3)()
+        _check(self._L.mk_zstd_deflate_info(self._h, C.byref(n), kinds, ms))
+        return n.value, tuple(kinds), tuple(ms)
 
     def cut_times(self):
         """members and ms (cut kernel, CRC-32 + deflate + pack, download) of the last deflate_records call"""
