@@ -730,6 +730,34 @@ int mk_codec_set_bzip2_pass_blocks(mk_codec *c, uint64_t blocks);
 int mk_zstd_inflate_device(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
 int mk_zstd_info(const mk_codec *c, uint32_t *blocks, uint32_t *frames, uint32_t *rounds, float ms[6]);
 
+/* (an addition to v7; `merkurio extract --device-xz`) An .xz file decoded on the device, one wave per block (merkurio_amd/csrc/codec/xz_inflate.hip,
+ * lzma_serial.hpp, xz_plan.hpp) -- what `merkurio extract` reads through needletail's xz reader (src/cmd_extract.rs:279-281).  xz[0, n)
+ * is the whole file: streams (xz file format 1.0.4) and Stream Padding back to back.  The host walks it from its end: every stream's
+ * footer, Index and header, then every Block Header; the Index states each block's stored size and text size, so every block's place
+ * in the file and in the text is known before a bit is decoded.  Then, a wave per block: its LZMA2 chunks decoded to the block's
+ * place in the text, the probabilities in LDS; and a wave per block for the stream's check, CRC-32 or CRC-64 (None costs nothing).
+ * *taken = 1 only when streams and padding cover xz[0, n), every header, Index and footer is well-formed with its CRC-32 right, every
+ * block's 0x00 control byte sits exactly at its stored end, its text has exactly the Index's length and its check matches: the text
+ * of all blocks then lies back to back where mk_gzip_inflate_device leaves its text (mk_gzip_text_read / _device / _release,
+ * mk_window_source::device_text), *n_blocks says how many blocks it came from (an empty stream: 0 blocks, 0 bytes).
+ * *taken = 0 (MK_OK, nothing else touched) means the caller runs liblzma, which also words the error; mk_xz_info's status names why
+ * (negative, as uint32_t; the codes are xz_plan.hpp's and lzma_serial.hpp's): every malformation of the container (magic, a CRC-32,
+ * a non-minimal multi-byte integer, non-zero padding, sizes in a Block Header or the Backward Size that disagree with the Index,
+ * trailing bytes, data that ends early) and of a block (a control byte 0x03-0x7F, a first chunk without dictionary reset, an LZMA
+ * chunk without properties, lc + lp > 4, a first range-coder byte other than 0, a chunk whose stored bytes are not consumed exactly
+ * or whose final code is not 0, text past a chunk's or the block's size, a distance in front of the block's first byte or beyond
+ * the dictionary size, the end-of-payload marker, a check that does not match); and what is valid but not this path's: the SHA-256
+ * check and reserved check ids, any filter chain other than one LZMA2 (BCJ, delta), a dictionary above 1.5 GiB, more than 2^20
+ * blocks, text beyond half of the free device memory, any device error -- and a file whose LARGEST BLOCK's text times the spread K
+ * exceeds its whole text: a block is one wave's serial decode, so a file of one huge block is liblzma's.  K defaults to 107
+ * (ceil(2 x liblzma's rate on one host thread / one wave's rate), measured: profiles/e2e_unxz.txt); mk_codec_set_xz_spread sets it (0 = the default, 1 = every file is tried).  With a gzip, bzip2
+ * or zstd stream open on the handle: MK_E_INVALID_ARG.  Opt-in everywhere: nothing is claimed about speed.
+ * mk_xz_info: blocks, streams and status of the last call, the text bytes of the file's largest block, and the phases in
+ * milliseconds: upload, decode, check, the whole call. */
+int mk_xz_inflate_device(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
+int mk_xz_info(const mk_codec *c, uint32_t *blocks, uint32_t *streams, uint32_t *status, uint64_t *largest_block_text, float ms[4]);
+int mk_codec_set_xz_spread(mk_codec *c, uint32_t spread);
+
 /* (v7) The kept records of `extract` as a .zst file, compressed on the device (zstd_deflate.hip, a wave per frame): what
  * mk_bgzf_deflate_records is for BGZF.  The text is cut by the rule of mk_bgzf_record_cuts with two other constants: a cut is looked for at
  * every multiple of MK_ZSTD_CUT_GRID among the record ends of the next MK_ZSTD_FRAME_TEXT_MAX - MK_ZSTD_CUT_GRID bytes, so only a longer

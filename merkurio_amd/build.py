@@ -63,12 +63,14 @@ def _units():
     units.append(("codec_gzip_segments_wave.o", "codec/gzip_segments_wave.hip", []))
     units.append(("codec_bzip2_inflate.o", "codec/bzip2_inflate.hip", []))
     units.append(("codec_zstd_inflate.o", "codec/zstd_inflate.hip", []))
+    units.append(("codec_xz_inflate.o", "codec/xz_inflate.hip", []))
     units.append(("codec_zstd_deflate.o", "codec/zstd_deflate.hip", []))
     units.append(("codec_host.o", "codec/codec_host.cpp", []))
     units.append(("codec_bgzf_host.o", "codec/bgzf_host.cpp", []))
     units.append(("codec_gzip_host.o", "codec/gzip_host.cpp", []))
     units.append(("codec_bzip2_host.o", "codec/bzip2_host.cpp", []))
     units.append(("codec_zstd_host.o", "codec/zstd_host.cpp", []))
+    units.append(("codec_xz_host.o", "codec/xz_host.cpp", []))
     units += [(s.replace(".cpp", ".o"), s, []) for s in HOST_SOURCES if os.path.exists(os.path.join(CSRC, s))]
     return units
 

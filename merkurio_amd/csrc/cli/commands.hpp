@@ -39,6 +39,7 @@ struct CommonArgs {
 constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
 
 constexpr uint64_t kGzipWindow = 256ull << 20;  // (an unmeasured choice: README, "Gunzip window by window")
+constexpr uint64_t kXzWindow = 256ull << 20;     // (an unmeasured choice, the zstd and bzip2 value: profiles/e2e_unxz.txt)
 constexpr uint64_t kZstdWindow = 256ull << 20;   // (an unmeasured choice, like its siblings: profiles/e2e_unzstd.txt)
 constexpr uint64_t kBzip2Window = 256ull << 20;  // (an unmeasured choice: README, "Bunzip2 window by window"; profiles/e2e_bunzip2_windows.txt)
 
@@ -63,6 +64,12 @@ struct ExtractArgs : CommonArgs {
     // about --zstd-window compressed bytes.  Opt-in like its sibling: not timed
     bool zstd_stream = false;
     uint64_t zstd_window = kZstdWindow;
+    // --device-xz: an .xz input of at most --xz-window compressed bytes is decoded on the device in one call (mk_xz_inflate_device),
+    // when its largest block's text x --xz-spread <= its whole text (0 = the library's default, 107: profiles/e2e_unxz.txt); a larger one, one
+    // the rule or the call hands back, and every .xz input without the flag, is liblzma's.  Opt-in: the path has not been timed
+    bool device_xz = false;
+    uint64_t xz_window = kXzWindow;
+    uint32_t xz_spread = 0;
 };
 
 struct TagArgs : CommonArgs {

@@ -227,6 +227,27 @@ void zstd_compress_frame(const uint8_t *src, size_t n, int level, std::vector<ui
     out.resize(k);
 }
 
+bool xz_first_bytes(const unsigned char *d, size_t n, std::vector<char> &out, size_t want) {
+    out.clear();
+    void *h = open_any({"liblzma.so.5", "liblzma.so"});
+    if (!h) return false;
+    auto dec = (int (*)(lzma_stream *, uint64_t, uint32_t))dlsym(h, "lzma_stream_decoder");
+    auto code = (int (*)(lzma_stream *, int))dlsym(h, "lzma_code");
+    auto end = (void (*)(lzma_stream *))dlsym(h, "lzma_end");
+    if (!dec || !code || !end) return false;
+    lzma_stream s;
+    memset(&s, 0, sizeof(s));  // LZMA_STREAM_INIT
+    if (dec(&s, UINT64_MAX, LZMA_CONCATENATED) != LZMA_OK) return false;
+    out.resize(want);
+    s.next_in = d, s.avail_in = n;
+    s.next_out = (uint8_t *)out.data(), s.avail_out = want;
+    int r = LZMA_OK;
+    while (r == LZMA_OK && s.avail_out != 0) r = code(&s, s.avail_in ? LZMA_RUN : LZMA_FINISH);
+    end(&s);
+    out.resize(want - s.avail_out);
+    return r == LZMA_OK || r == LZMA_STREAM_END;
+}
+
 bool zstd_first_bytes(const unsigned char *d, size_t n, std::vector<char> &out, size_t want) {
     out.clear();
     void *h = open_any({"libzstd.so.1", "libzstd.so"});

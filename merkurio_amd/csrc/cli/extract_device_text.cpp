@@ -1,5 +1,5 @@
 // extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
-// inflated in one piece or member by member, or of a bzip2 or (--device-zstd) zstd file (windows are ranges of it), and a gzip, bzip2 or (--zstd-stream) zstd file decoded window by
+// inflated in one piece or member by member, or of a bzip2, (--device-zstd) zstd or (--device-xz) xz file (windows are ranges of it), and a gzip, bzip2 or (--zstd-stream) zstd file decoded window by
 // window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
 // "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
 #include <hip/hip_runtime_api.h>
@@ -191,8 +191,8 @@ struct DeviceStream : DeviceText {
 }  // namespace
 
 std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t stream_window, Gate &g) {
-    const bool bz = f.s.raw_is_bzip2(), zs = f.s.raw_is_zstd();
-    if (!bz && !zs && !f.s.raw_is_gzip()) return nullptr;
+    const bool bz = f.s.raw_is_bzip2(), zs = f.s.raw_is_zstd(), xz = f.s.raw_is_xz();
+    if (!bz && !zs && !xz && !f.s.raw_is_gzip()) return nullptr;
     const uint8_t *z = f.s.source().file_bytes();
     const uint64_t n = f.s.source().file_size();
     double t0 = PhaseTimer::now();
@@ -200,7 +200,28 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (zs && f.zstd_stream) {
+    if (xz) {
+        // --device-xz: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- a file of one huge
+        // block (the spread rule), anything else it refuses, a damaged file, no room -- and a file of more compressed bytes than
+        // --xz-window, liblzma reads whole, as without the flag, and words the error
+        uint64_t blocks = 0;
+        if (n <= stream_window && mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        if (codec && f.xz_spread) (void)mk_codec_set_xz_spread(codec, f.xz_spread);
+        if (codec && mk_xz_inflate_device(codec, z, n, &text_bytes, &taken, &blocks) != MK_OK) taken = 0;
+        float ms4[4] = {0, 0, 0, 0};
+        uint32_t streams = 0, status = 0;
+        uint64_t largest = 0;
+        if (codec) (void)mk_xz_info(codec, nullptr, &streams, &status, &largest, ms4);
+        if (g.timing && taken) {
+            fprintf(stderr, "[timing]   xz on the device: %llu blocks, %u streams, largest block %llu text bytes, upload %.1f, decode %.1f, check %.1f, total %.1f ms (input %d: %llu text bytes, %.3f s)\n",
+                    (unsigned long long)blocks, streams, (unsigned long long)largest, ms4[0], ms4[1], ms4[2], ms4[3], i, (unsigned long long)text_bytes, PhaseTimer::now() - t0);
+        } else if (g.timing) {
+            char why[96];
+            snprintf(why, sizeof why, "handed back, status %d, largest block %llu text bytes", (int)status, (unsigned long long)largest);
+            fprintf(stderr, "[timing]   xz input %d: NOT taken by the device after %.3f s (%s; liblzma reads it)\n", i, PhaseTimer::now() - t0,
+                    n > stream_window ? "more compressed bytes than --xz-window" : why);
+        }
+    } else if (zs && f.zstd_stream) {
         // --zstd-stream, more than one zstd window: decoded window by window as the text windows reach it, device memory bounded by
         // the window; what the stream does not take, from whichever window on, is libzstd's
         if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;

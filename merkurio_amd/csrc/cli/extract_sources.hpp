@@ -43,6 +43,7 @@ struct InputFile {  // one input file as prepare() opened it
     const char *first_text = nullptr;  // the first raw window (prepare())
     uint64_t first_n = 0, first_resume = 0;
     bool have_first = false;
+    uint32_t xz_spread = 0;    // --xz-spread for an .xz input under --device-xz (0 = the library's default)
     bool zstd_stream = false;  // --zstd-stream and more compressed bytes than --zstd-window: take_on_device opens a stream
 };
 

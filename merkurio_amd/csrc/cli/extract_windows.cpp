@@ -197,13 +197,14 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     int kind[2] = {-1, -1};
     for (int i = 0; i < J.n_in; ++i) {
         xw::InputFile &I = J.in[i];
-        I.s.open(I.path, !a.host_codec, !a.host_codec && a.device_zstd);
+        I.s.open(I.path, !a.host_codec, !a.host_codec && a.device_zstd, !a.host_codec && a.device_xz);
+        I.xz_spread = a.xz_spread;
         if (I.s.raw_is_deferred()) {
             // not inflated here: run() hands the file to the device once the HIP runtime is up.  What its records are is read from
-            // the start of the first block's text (libbz2; libzstd for a .zst input under --device-zstd); where that does not say (an
+            // the start of the first block's text (libbz2; libzstd for a .zst input under --device-zstd, liblzma for an .xz input under --device-xz); where that does not say (an
             // empty first stream, a damaged file), the library reads the whole file now, as under --host-codec, and words what is wrong with it
             std::vector<char> first;
-            if ((I.s.raw_is_zstd() ? zstd_first_bytes : bz2_first_bytes)(I.s.source().file_bytes(), I.s.source().file_size(), first, 1u << 16))
+            if ((I.s.raw_is_xz() ? xz_first_bytes : I.s.raw_is_zstd() ? zstd_first_bytes : bz2_first_bytes)(I.s.source().file_bytes(), I.s.source().file_size(), first, 1u << 16))
                 for (char ch : first)
                     if (ch != '\n' && ch != '\r') {
                         kind[i] = (unsigned char)ch;
@@ -266,6 +267,7 @@ void WindowExtract::Impl::take_inputs_on_device() {
     // memory that is free when it runs, so the second must find the first's text there already, not a sibling that is about to take the
     // same half.  A file the device does not take is libbz2's, whole, and the job goes on with host text
     // the same holds for the .zst files of a pair under --device-zstd (a larger one than --zstd-window is libzstd's, unless --zstd-stream)
+    // and for the .xz files of a pair under --device-xz (a larger one than --xz-window is liblzma's)
     // A streamed zstd file holds, per window, its compressed bytes, its literals and 12 bytes per sequence, two text buffers and 8
     // bytes of sources per text byte: at 5 bytes of text per compressed byte about 60 times the window.  An estimate, not measured;
     // the library bounds a window's text by its own cap whatever this factor is.  Same rule
@@ -277,7 +279,7 @@ void WindowExtract::Impl::take_inputs_on_device() {
     for (int i = 0; i < n_in; ++i) {
         xw::InputFile &I = in[i];
         if (!I.s.raw_is_deferred() || bzip2_streamed(i) || zstd_streamed(i)) continue;
-        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], I.s.raw_is_zstd() ? a.zstd_window : a.bzip2_window, gate)) {  // (at or below the window: in one call)
+        if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], I.s.raw_is_xz() ? a.xz_window : I.s.raw_is_zstd() ? a.zstd_window : a.bzip2_window, gate)) {  // (at or below the window: in one call)
             src[i] = std::move(dev);
             continue;
         }

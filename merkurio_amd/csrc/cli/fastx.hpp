@@ -41,7 +41,7 @@ struct FastxFile {
 //                    ...records [0, n) of s.view...; join; more = s.fill(W); }
 struct FastxStream {
     FastxFile view;  // the current window: view.data / view.recs / view.fastq; all FastxFile accessors work on it
-    void open(const std::string &path, bool defer_bzip2 = false, bool defer_zstd = false) { src.open(path, defer_bzip2, defer_zstd); }
+    void open(const std::string &path, bool defer_bzip2 = false, bool defer_zstd = false, bool defer_xz = false) { src.open(path, defer_bzip2, defer_zstd, defer_xz); }
     // Makes the next window current: every complete record among the unconsumed bytes plus up to
     // `window_bytes` new ones (parsed here unless prefetch() already did).  false: no record is left.
     bool fill(uint64_t window_bytes);
@@ -74,10 +74,12 @@ struct FastxStream {
     bool raw_is_gzip() const { return src.is_gzip(); }
     // a bzip2 input opened with defer_bzip2 that nothing has read yet: source().file_bytes() is the file as stored
     bool raw_is_bzip2() const { return src.is_bzip2(); }
-    // likewise a zstd input opened with defer_zstd; raw_is_deferred: either of the two
+    // likewise a zstd input opened with defer_zstd; raw_is_deferred: any of the three
     bool raw_is_zstd() const { return src.is_zstd(); }
-    bool raw_is_deferred() const { return src.is_bzip2() || src.is_zstd(); }
-    void raw_settle() { src.settle(); }  // libbz2 / libzstd inflates it now
+    // and an xz input opened with defer_xz
+    bool raw_is_xz() const { return src.is_xz(); }
+    bool raw_is_deferred() const { return src.is_bzip2() || src.is_zstd() || src.is_xz(); }
+    void raw_settle() { src.settle(); }  // libbz2 / libzstd / liblzma inflates it now
     const WindowSource &source() const { return src; }
 
    private:

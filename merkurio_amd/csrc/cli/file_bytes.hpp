@@ -35,5 +35,7 @@ bool inflate_by_magic(const std::string &path, const unsigned char *data, size_t
 bool bz2_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
 // likewise for a zstd file, by libzstd
 bool zstd_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
+// and for an xz file, by liblzma
+bool xz_first_bytes(const unsigned char *data, size_t n, std::vector<char> &out, size_t want);
 
 }  // namespace cli

@@ -15,14 +15,14 @@ WindowSource::~WindowSource() {
 }
 
 void WindowSource::settle() {
-    if (kind != BZIP2 && kind != ZSTD) return;
+    if (kind != BZIP2 && kind != ZSTD && kind != XZ) return;
     std::vector<char> out;
     (void)inflate_by_magic(path, (const unsigned char *)src.p, (size_t)src.n, out);  // (raises on a damaged file)
     src.adopt(std::move(out));
     kind = PLAIN;
 }
 
-void WindowSource::open(const std::string &p, bool defer_bzip2, bool defer_zstd) {
+void WindowSource::open(const std::string &p, bool defer_bzip2, bool defer_zstd, bool defer_xz) {
     path = p;
     kind = PLAIN;
     if (!src.map_file(p)) {  // not a regular file with bytes in it: gzopen reads it whole (plain or gzip)
@@ -34,6 +34,8 @@ void WindowSource::open(const std::string &p, bool defer_bzip2, bool defer_zstd)
         kind = BZIP2;
     } else if (defer_zstd && src.n >= 4 && d[0] == 0x28 && d[1] == 0xB5 && d[2] == 0x2F && d[3] == 0xFD) {
         kind = ZSTD;
+    } else if (defer_xz && src.n >= 6 && !memcmp(d, "\xfd" "7zXZ\0", 6)) {
+        kind = XZ;
     } else if (src.n >= 2 && d[0] == 0x1f && d[1] == 0x8b) {
         if (bgzf_walk(d, (size_t)src.n, members)) {
             kind = BGZF;

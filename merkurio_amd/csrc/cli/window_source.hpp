@@ -19,9 +19,11 @@ struct WindowSource {
     // (extract's mk_bzip2_inflate_device path); settle() -- which every read of the text through FastxStream begins with -- inflates it
     // with libbz2 after all, and from then on it is plain text like any other inflated bzip2 input
     // defer_zstd: likewise for a zstd file (is_zstd(); extract's mk_zstd_inflate_device path under --device-zstd); settle(): libzstd
-    void open(const std::string &path, bool defer_bzip2 = false, bool defer_zstd = false);
+    // defer_xz: likewise for an xz file (is_xz(); extract's mk_xz_inflate_device path under --device-xz); settle(): liblzma
+    void open(const std::string &path, bool defer_bzip2 = false, bool defer_zstd = false, bool defer_xz = false);
     bool is_bzip2() const { return kind == BZIP2; }
     bool is_zstd() const { return kind == ZSTD; }
+    bool is_xz() const { return kind == XZ; }
     void settle();
     bool mapped() const { return kind == PLAIN; }  // text()/text_size() is the complete text
     bool is_file_mapping() const { return kind == PLAIN && src.map != nullptr; }  // (not an inflated bzip2 / xz / zstd copy)
@@ -53,7 +55,7 @@ struct WindowSource {
     WindowSource &operator=(const WindowSource &) = delete;
 
    private:
-    enum Kind { PLAIN, GZIP, BGZF, BZIP2, ZSTD } kind = PLAIN;
+    enum Kind { PLAIN, GZIP, BGZF, BZIP2, ZSTD, XZ } kind = PLAIN;
     std::string path;
     FileBytes src;  // the file as stored (PLAIN: the text itself, or inflated bzip2 / xz / zstd)
     bool src_eof = false;

@@ -1,5 +1,5 @@
 // codec_internal.h -- the opaque mk_codec handle and what the codec's host files share: codec_host.cpp (the handle, the staging
-// copies), bgzf_host.cpp, gzip_host.cpp, bzip2_host.cpp (a format each).  window_ingest.cpp borrows the handle's device buffers for
+// copies), bgzf_host.cpp, gzip_host.cpp, bzip2_host.cpp, zstd_host.cpp, xz_host.cpp (a format each).  window_ingest.cpp borrows the handle's device buffers for
 // mk_extract_fastq_bgzf, which inflates a window of members straight into the matcher's text buffer.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -103,6 +103,12 @@ struct mk_codec {
     uint32_t zs_blocks = 0, zs_frames = 0, zs_rounds = 0;
     float zs_ms[6] = {0, 0, 0, 0, 0, 0};  // upload, tables + entropy decode, scans, execution, cross-block rounds, checksum
     uint64_t zs_text_cap = 0;             // mk_codec_set_zstd_text_cap: bytes of text per window of a zstd stream; 0 = by the free memory
+    // mk_xz_inflate_device (xz_host.cpp; its text is gz_text too; the file and the block table borrow d_gz_in / d_gz_tab)
+    uint32_t xz_blocks = 0, xz_streams = 0;
+    int xz_status = 0;        // 0 = taken, else why the last call handed the file back (xz_plan.hpp, lzma_serial.hpp)
+    uint64_t xz_largest = 0;  // text bytes of the file's largest block
+    float xz_ms[4] = {0, 0, 0, 0};  // upload, decode, check, the whole call
+    uint32_t xz_spread = 0;         // mk_codec_set_xz_spread; 0 = kXzSpreadDefault
     // mk_zstd_deflate_records (zstd_host.cpp; text, record ends, range table, slots and packed frames are the deflate side's buffers above,
     // the waves' literal / sequence scratch is d_tokens)
     uint64_t zd_frames = 0;

@@ -54,7 +54,7 @@ EXPORTS = [
     "mk_synth_reads_host", "mk_synth_reads_device_range", "mk_reduce_counters", "mk_reduce_prepare", "mk_comm_available", "mk_comm_unique_id", "mk_comm_init",
     "mk_comm_reduce_counters", "mk_comm_size", "mk_comm_destroy",
     "mk_codec_create", "mk_codec_destroy", "mk_bgzf_deflate_bound", "mk_bgzf_deflate", "mk_bgzf_deflate_pieces", "mk_bgzf_inflate", "mk_bgzf_members", "mk_bgzf_eof",
-    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_zstd_inflate_device", "mk_zstd_info", "mk_zstd_record_cuts", "mk_zstd_deflate_bound", "mk_zstd_deflate_records", "mk_zstd_deflate_info", "mk_codec_set_bzip2_pass_blocks",
+    "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_zstd_inflate_device", "mk_zstd_info", "mk_xz_inflate_device", "mk_xz_info", "mk_codec_set_xz_spread", "mk_zstd_record_cuts", "mk_zstd_deflate_bound", "mk_zstd_deflate_records", "mk_zstd_deflate_info", "mk_codec_set_bzip2_pass_blocks",
     "mk_bzip2_stream_begin", "mk_bzip2_stream_next", "mk_bzip2_stream_info", "mk_bzip2_stream_end", "mk_codec_set_bzip2_text_cap",
     "mk_zstd_stream_begin", "mk_zstd_stream_next", "mk_zstd_stream_info", "mk_zstd_stream_end", "mk_codec_set_zstd_text_cap",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
@@ -328,6 +328,9 @@ def load(build_if_missing=True):
     L.mk_bzip2_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
     L.mk_zstd_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.mk_zstd_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.mk_xz_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.mk_xz_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+    L.mk_codec_set_xz_spread.argtypes = [C.c_void_p, C.c_uint32]
     L.mk_codec_set_bzip2_pass_blocks.argtypes = [C.c_void_p, C.c_uint64]
     L.mk_bzip2_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
     L.mk_bzip2_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
@@ -1341,6 +1344,32 @@ class Codec:
         blocks, frames, rounds, ms = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), (C.c_float * 6)()
         _check(self._L.mk_zstd_info(self._h, C.byref(blocks), C.byref(frames), C.byref(rounds), ms))
         return blocks.value, frames.value, rounds.value, tuple(round(x, 3) for x in ms)
+
+    def unxz(self, data):
+        """mk_xz_inflate_device + mk_gzip_text_read: an .xz file of one or more streams decoded on the device, a wave per block ->
+        (taken, text, n_blocks); taken = False (text None): the device handed the file back (unxz_info()[2] says why) and the
+        caller's liblzma decodes it"""
+        src = np.frombuffer(data, dtype=np.uint8)
+        n, taken, blocks = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        t0 = time.perf_counter()
+        _check(self._L.mk_xz_inflate_device(self._h, src.ctypes.data if src.size else None, src.size, C.byref(n), C.byref(taken), C.byref(blocks)))
+        self.last_call_s = time.perf_counter() - t0
+        if not taken.value:
+            return False, None, 0
+        out = np.empty(n.value, dtype=np.uint8)
+        _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
+        return True, out.tobytes(), blocks.value
+
+    def unxz_info(self):
+        """mk_xz_info: (blocks, streams, status, text bytes of the largest block of the last unxz, ms of upload / decode / check /
+        the whole call); status 0 = taken, else the refusal's code (xz_plan.hpp, lzma_serial.hpp)"""
+        blocks, streams, status, largest, ms = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), (C.c_float * 4)()
+        _check(self._L.mk_xz_info(self._h, C.byref(blocks), C.byref(streams), C.byref(status), C.byref(largest), ms))
+        return blocks.value, streams.value, C.c_int32(status.value).value, largest.value, tuple(round(x, 3) for x in ms)
+
+    def set_xz_spread(self, spread):
+        """mk_codec_set_xz_spread: an .xz file is taken only when its largest block's text x spread <= its whole text; 0 = the default"""
+        _check(self._L.mk_codec_set_xz_spread(self._h, spread))
 
     def set_bzip2_pass_blocks(self, blocks):
         """blocks per device pass of bunzip2 (mk_codec_set_bzip2_pass_blocks); 0 = by the free memory"""
