@@ -750,13 +750,66 @@ int mk_zstd_info(const mk_codec *c, uint32_t *blocks, uint32_t *frames, uint32_t
  * check and reserved check ids, any filter chain other than one LZMA2 (BCJ, delta), a dictionary above 1.5 GiB, more than 2^20
  * blocks, text beyond half of the free device memory, any device error -- and a file whose LARGEST BLOCK's text times the spread K
  * exceeds its whole text: a block is one wave's serial decode, so a file of one huge block is liblzma's.  K defaults to 107
- * (ceil(2 x liblzma's rate on one host thread / one wave's rate), measured: profiles/e2e_unxz.txt); mk_codec_set_xz_spread sets it (0 = the default, 1 = every file is tried).  With a gzip, bzip2
- * or zstd stream open on the handle: MK_E_INVALID_ARG.  Opt-in everywhere: nothing is claimed about speed.
+ * (ceil(2 x liblzma's rate on one host thread / one wave's rate), measured: profiles/e2e_unxz.txt); mk_codec_set_xz_spread sets it (0 = the default, 1 = every file is tried).  With a gzip, bzip2,
+ * zstd or xz stream open on the handle: MK_E_INVALID_ARG.  Opt-in everywhere: nothing is claimed about speed.
  * mk_xz_info: blocks, streams and status of the last call, the text bytes of the file's largest block, and the phases in
  * milliseconds: upload, decode, check, the whole call. */
 int mk_xz_inflate_device(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t *text_bytes, uint32_t *taken, uint64_t *n_blocks);
 int mk_xz_info(const mk_codec *c, uint32_t *blocks, uint32_t *streams, uint32_t *status, uint64_t *largest_block_text, float ms[4]);
 int mk_codec_set_xz_spread(mk_codec *c, uint32_t spread);
+
+/* (an addition to v7; `merkurio extract --xz-stream`) An .xz file of ANY size, decoded on the device window by window: nothing on the
+ * device is sized by the file.  The contract is mk_zstd_stream_*'s.
+ * mk_xz_stream_begin: xz[0, n) = the whole file (the caller's -- the mapped file -- until _end).  The container walk of
+ * mk_xz_inflate_device runs once over it (footers, Indexes, stream headers, Block Headers: one header per block, no compressed
+ * payload is read), and because the Index states every block's stored size and text size, ALL windows are planned here, before a bit
+ * is decoded (merkurio_amd/csrc/codec/xz_chain.hpp).  The plan is greedy and deterministic: a window is the longest run of consecutive
+ * blocks from the cursor whose text is at most the text cap T and whose compressed span -- from the first block's Block Header to
+ * the end of the last block's check -- is at most window_bytes (0 = no bound on the span: bounded by the text cap only); one block at
+ * the least, also where that block alone exceeds window_bytes.  A window may run across stream boundaries, Stream Padding and streams
+ * of other check kinds; a stream without blocks makes no window and counts as closed with the blocks in front of it.  Blocks need
+ * nothing from each other: no history and no table crosses a seam.
+ * *taken = 0 (MK_OK, no stream is open; mk_xz_stream_info's status names why): everything mk_xz_inflate_device's walk refuses, under
+ * the same codes; a block whose text alone exceeds T (kXzBlockOverCap, -33); the spread rule, generalised: K x the sum over the
+ * windows of (that window's largest block's text) must not exceed the whole text (kXzSpread) -- a window costs as long as its
+ * slowest block, so many small windows cost more than one large one, and with one window this is mk_xz_inflate_device's rule; K is
+ * mk_codec_set_xz_spread's.  The rule ignores that a window may hold more blocks than the device has resident waves (a known
+ * approximation, as in the one-shot call).  With 24 MiB blocks and K = 107 a window must hold about 2.5 GiB of text, which is why
+ * window_bytes = 0 sets no bound of its own.  T is chosen from the free device memory: a sixth of it, so that two text buffers of T
+ * and the largest window's upload and tables fit in half of what is free (checked against the plan: kXzTooLarge otherwise).  That
+ * default is an UNMEASURED choice (profiles/e2e_unxz_windows.txt).  mk_codec_set_xz_text_cap sets T (test hook; 0 = default; results
+ * do not depend on it).
+ * mk_xz_stream_next uploads only the window's compressed span, walks the chunk headers of the window's blocks (the launch's LDS is
+ * sized by this window's lc + lp), and launches the two kernels of mk_xz_inflate_device over the window's blocks, largest text first.
+ * *state = 0: a window of text was produced, *text_bytes long (0 is possible: blocks without text): it is what mk_gzip_text_device /
+ *             mk_gzip_text_read refer to, in one of two text buffers -- window w stays valid until the call that produces w + 2;
+ *          1: end of file: every block of every window was proved as in the one-shot call -- the control byte 0x00 at the stored
+ *             end, the Index's text length, the check; no text in this call;
+ *          2: handed back (MK_OK): stats.status names the first block of this window that failed, or kXzTooLarge (no room), or
+ *             kXzDevice (any device error).  No text comes from this window and nothing after it.  The windows delivered before it
+ *             are a prefix of liblzma's text, in whole blocks: the caller's liblzma reads from the front and skips stats.text_bytes.
+ * mk_xz_stream_end closes the stream and frees what it held (the two text buffers included).  mk_xz_stream_info takes the codec's
+ * lock; without an open stream: the last stream's figures, a refusal at _begin included.  While an xz stream is open every one-shot
+ * call and every other *_stream_begin return MK_E_INVALID_ARG -- and mk_xz_stream_begin does while another stream is --, and
+ * mk_gzip_text_release ends the stream as mk_xz_stream_end does.  Opt-in everywhere: nothing is claimed about speed. */
+typedef struct mk_xz_stream_stats {
+    uint64_t windows;            /* windows of text produced */
+    uint64_t streams;            /* streams whose blocks have all been delivered (all of them at state 1) */
+    uint64_t blocks;             /* blocks delivered */
+    uint64_t consumed_bytes;     /* compressed bytes in front of the next window (the file's size behind the last) */
+    uint64_t text_bytes;         /* text bytes delivered so far */
+    uint64_t planned_windows;    /* windows of the plan made at _begin */
+    uint64_t largest_block_text; /* text bytes of the file's largest block */
+    uint64_t peak_device_bytes;  /* most device memory the stream has held */
+    int32_t status;              /* 0, or why _begin refused / a window was handed back (xz_plan.hpp, lzma_serial.hpp, xz_chain.hpp) */
+    uint32_t reserved;
+    float ms[4];                 /* summed over the windows: upload, decode, check, the whole of the calls */
+} mk_xz_stream_stats;
+int mk_xz_stream_begin(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t window_bytes, uint32_t *taken);
+int mk_xz_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state);
+int mk_xz_stream_info(const mk_codec *c, mk_xz_stream_stats *out);
+int mk_xz_stream_end(mk_codec *c);
+int mk_codec_set_xz_text_cap(mk_codec *c, uint64_t text_bytes);
 
 /* (v7) The kept records of `extract` as a .zst file, compressed on the device (zstd_deflate.hip, a wave per frame): what
  * mk_bgzf_deflate_records is for BGZF.  The text is cut by the rule of mk_bgzf_record_cuts with two other constants: a cut is looked for at

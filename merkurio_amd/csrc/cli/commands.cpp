@@ -306,6 +306,9 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
     Loggers lg;
     open_loggers(a, lg);
     if (lg.active) write_log_header(lg.text, "extract", argv, nullptr, pats.list.size(), a.invert_match);
+    // (what the logs hold before any input is read -- the text log's header, the JSON log's opening: Sink::rollback cuts them back to this)
+    if (lg.text.out) lg.text.out->mark();
+    if (lg.has_json) lg.json.out->mark();
     PhaseTimer tm;
     bool use_ac = false;
     // HIP initialisation + pattern-set compilation (0.1-0.3 s) runs beside the input parsing

@@ -70,6 +70,10 @@ struct ExtractArgs : CommonArgs {
     bool device_xz = false;
     uint64_t xz_window = kXzWindow;
     uint32_t xz_spread = 0;
+    // --xz-stream (implies --device-xz): a larger .xz input is decoded window by window (mk_xz_stream_*), windows of whole blocks
+    // bounded by --xz-text-cap bytes of text (0 = the library's default, by the free device memory).  Opt-in like its sibling: not timed
+    bool xz_stream = false;
+    uint64_t xz_text_cap = 0;
 };
 
 struct TagArgs : CommonArgs {

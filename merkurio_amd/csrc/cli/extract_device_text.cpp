@@ -1,6 +1,6 @@
 // extract_device_text.cpp -- the sources of the extract window driver whose text the device makes and keeps: the text of a gzip file
-// inflated in one piece or member by member, or of a bzip2, (--device-zstd) zstd or (--device-xz) xz file (windows are ranges of it), and a gzip, bzip2 or (--zstd-stream) zstd file decoded window by
-// window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 mid-way.  Owns the step that tries the device for an input and the
+// inflated in one piece or member by member, or of a bzip2, (--device-zstd) zstd or (--device-xz) xz file (windows are ranges of it), and a gzip, bzip2, (--zstd-stream) zstd or (--xz-stream) xz file decoded window by
+// window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*, mk_xz_stream_*: one class over a table of calls), which may hand the file back to zlib / libbz2 / libzstd / liblzma mid-way.  Owns the step that tries the device for an input and the
 // "free bytes on this device" helper.  Every HIP runtime call of the extract driver is in this file.
 #include <hip/hip_runtime_api.h>
 
@@ -52,6 +52,7 @@ struct StreamCalls {
     // (may be null) the phases summed so far, for a window's row to show what each cost in that window
     void (*phase_ms)(mk_codec *, float ms[6]);
     const char *phase_names[6];
+    bool discard_kept_on_error = false;  // the host library's error behind a hand-back leaves no kept records' file (Gate::discard_kept)
 };
 
 template <class... A>
@@ -97,7 +98,18 @@ const StreamCalls kZstdCalls = {"zstd", "libzstd", mk_zstd_stream_next, mk_zstd_
                                     for (int k = 0; k < 6; ++k) ms[k] = st.ms[k];
                                 }, {"upload", "tables + entropy decode", "walk + scans", "execution", "cross-block rounds", "checksum"}};
 
-// A file the device decodes window by window (mk_gzip_stream_*, mk_bzip2_stream_*).  Window w of the stream lies in text buffer w & 1
+const StreamCalls kXzCalls = {"xz", "liblzma", mk_xz_stream_next, mk_xz_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+                                  mk_xz_stream_stats st;
+                                  memset(&st, 0, sizeof(st));
+                                  (void)mk_xz_stream_info(c, &st);
+                                  *consumed = st.consumed_bytes;
+                                  *counts = fmt("%llu planned windows, %llu windows, %llu blocks, %llu streams closed, largest block %llu text bytes, status %d", (unsigned long long)st.planned_windows,
+                                                (unsigned long long)st.windows, (unsigned long long)st.blocks, (unsigned long long)st.streams, (unsigned long long)st.largest_block_text, (int)st.status);
+                                  *phases = fmt("upload %.1f, decode %.1f, check %.1f, calls %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2], st.ms[3],
+                                                (unsigned long long)st.peak_device_bytes);
+                              }, nullptr, {}, true};
+
+// A file the device decodes window by window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*, mk_xz_stream_*).  Window w of the stream lies in text buffer w & 1
 struct DeviceStream : DeviceText {
     const StreamCalls &calls;
     InputFile &f;
@@ -179,11 +191,13 @@ struct DeviceStream : DeviceText {
         const uint64_t used = delivered - std::min<uint64_t>(delivered, S.head.size());
         S.head.clear();
         (void)calls.end(codec);
+        g.discard_kept = calls.discard_kept_on_error;  // (until the host library has read what the windows used)
         f.s.raw_settle();
         if (used) {
             f.have_first = false;
             if (!f.s.raw_skip(used)) bail("Error while decompressing " + f.path);
         }
+        g.discard_kept = false;
         return host_text_source(f, i, g);
     }
 };
@@ -200,7 +214,24 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (xz) {
+    if (xz && f.xz_stream) {
+        // --xz-stream, more compressed bytes than --xz-window: decoded window by window as the text windows reach it, windows of whole
+        // blocks planned when the stream begins (stream_window = 0: bounded by the text cap only); what the stream does not take -- at
+        // its begin or from whichever window on -- is liblzma's, which also words the error
+        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+        t0 = PhaseTimer::now();
+        if (codec && f.xz_spread) (void)mk_codec_set_xz_spread(codec, f.xz_spread);
+        if (codec && f.xz_text_cap) (void)mk_codec_set_xz_text_cap(codec, f.xz_text_cap);
+        if (codec && mk_xz_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new DeviceStream(kXzCalls, codec, f, i, g, t0));
+        if (g.timing) {
+            mk_xz_stream_stats st;
+            memset(&st, 0, sizeof(st));
+            if (codec) (void)mk_xz_stream_info(codec, &st);
+            fprintf(stderr, "[timing]   xz input %d on the device, window by window: NOT taken (status %d, largest block %llu text bytes; liblzma reads it)\n", i, (int)st.status,
+                    (unsigned long long)st.largest_block_text);
+        }
+    } else if (xz) {
         // --device-xz: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- a file of one huge
         // block (the spread rule), anything else it refuses, a damaged file, no room -- and a file of more compressed bytes than
         // --xz-window, liblzma reads whole, as without the flag, and words the error

@@ -27,6 +27,10 @@ struct Gate {
     bool failed = false;
     std::string failure;
     uint64_t n_done = 0;  // windows the device loops are through with (chained inputs: in order)
+    // an xz stream handed its file back and liblzma then refused it: --host-codec would have met that error at load, before it opened
+    // the kept records' files or wrote a log row, so the driver removes the former and cuts the logs back before it reports the
+    // failure (Sink::discard, Sink::rollback)
+    bool discard_kept = false;
     const bool timing = getenv("MERKURIO_TIMING") != nullptr;
     void fail_all(const std::string &msg) {
         std::lock_guard<std::mutex> lk(mu);
@@ -45,6 +49,8 @@ struct InputFile {  // one input file as prepare() opened it
     bool have_first = false;
     uint32_t xz_spread = 0;    // --xz-spread for an .xz input under --device-xz (0 = the library's default)
     bool zstd_stream = false;  // --zstd-stream and more compressed bytes than --zstd-window: take_on_device opens a stream
+    bool xz_stream = false;    // --xz-stream and more compressed bytes than --xz-window: likewise
+    uint64_t xz_text_cap = 0;  // --xz-text-cap for that stream (0 = the library's default)
 };
 
 struct Source;

@@ -198,7 +198,7 @@ bool WindowExtract::prepare(const ExtractArgs &a, const std::vector<int> &devs) 
     for (int i = 0; i < J.n_in; ++i) {
         xw::InputFile &I = J.in[i];
         I.s.open(I.path, !a.host_codec, !a.host_codec && a.device_zstd, !a.host_codec && a.device_xz);
-        I.xz_spread = a.xz_spread;
+        I.xz_spread = a.xz_spread, I.xz_text_cap = a.xz_text_cap;
         if (I.s.raw_is_deferred()) {
             // not inflated here: run() hands the file to the device once the HIP runtime is up.  What its records are is read from
             // the start of the first block's text (libbz2; libzstd for a .zst input under --device-zstd, liblzma for an .xz input under --device-xz); where that does not say (an
@@ -267,7 +267,8 @@ void WindowExtract::Impl::take_inputs_on_device() {
     // memory that is free when it runs, so the second must find the first's text there already, not a sibling that is about to take the
     // same half.  A file the device does not take is libbz2's, whole, and the job goes on with host text
     // the same holds for the .zst files of a pair under --device-zstd (a larger one than --zstd-window is libzstd's, unless --zstd-stream)
-    // and for the .xz files of a pair under --device-xz (a larger one than --xz-window is liblzma's)
+    // and for the .xz files of a pair under --device-xz (a larger one than --xz-window is liblzma's, unless --xz-stream: then it is
+    // streamed with window_bytes = 0 -- its windows are bounded by the library's text cap, which the spread rule wants large)
     // A streamed zstd file holds, per window, its compressed bytes, its literals and 12 bytes per sequence, two text buffers and 8
     // bytes of sources per text byte: at 5 bytes of text per compressed byte about 60 times the window.  An estimate, not measured;
     // the library bounds a window's text by its own cap whatever this factor is.  Same rule
@@ -276,9 +277,18 @@ void WindowExtract::Impl::take_inputs_on_device() {
         if (zstd_streamed(i)) ++n_zs_streamed;
     if (const uint64_t free_b = n_zs_streamed ? xw::device_free_bytes(devs[0]) : 0)
         while (zstd_window > (1u << 20) && n_zs_streamed * 2 * 60 * zstd_window > free_b / 2) zstd_window /= 2;
+    // The library's default text cap -- a sixth of the free memory, two text buffers and an upload in half of what is free -- is
+    // chosen per codec: the two streamed .xz files of a pair begin side by side and would each see the same free memory, so the CLI
+    // gives each its share of that default.  A cap the user set stands as given
+    uint64_t n_xz_streamed = 0;
+    for (int i = 0; i < n_in; ++i)
+        if (xz_streamed(i)) ++n_xz_streamed;
+    if (const uint64_t free_b = n_xz_streamed > 1 && !a.xz_text_cap ? xw::device_free_bytes(devs[0]) : 0)
+        for (int i = 0; i < n_in; ++i)
+            if (xz_streamed(i)) in[i].xz_text_cap = std::max<uint64_t>(free_b / 6 / n_xz_streamed, 1u << 20);
     for (int i = 0; i < n_in; ++i) {
         xw::InputFile &I = in[i];
-        if (!I.s.raw_is_deferred() || bzip2_streamed(i) || zstd_streamed(i)) continue;
+        if (!I.s.raw_is_deferred() || bzip2_streamed(i) || zstd_streamed(i) || xz_streamed(i)) continue;
         if (std::unique_ptr<xw::Source> dev = xw::take_on_device(I, i, devs[0], I.s.raw_is_xz() ? a.xz_window : I.s.raw_is_zstd() ? a.zstd_window : a.bzip2_window, gate)) {  // (at or below the window: in one call)
             src[i] = std::move(dev);
             continue;
@@ -295,6 +305,12 @@ void WindowExtract::Impl::take_inputs_on_device() {
             // (the stream is asked for by the file's size against --zstd-window as given; its windows may be smaller)
             in[i].zstd_stream = true;
             if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], zstd_window, gate)) src[i] = std::move(dev);
+            else settle_bzip2(in[i]);
+            return;
+        }
+        if (xz_streamed((int)i)) {
+            in[i].xz_stream = true;
+            if (std::unique_ptr<xw::Source> dev = xw::take_on_device(in[i], (int)i, devs[0], 0, gate)) src[i] = std::move(dev);
             else settle_bzip2(in[i]);
             return;
         }
@@ -381,6 +397,11 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     }
     for (auto &t : th) t.join();
     for (auto &t : pin_threads) t.join();
+    if (G.failed && G.discard_kept) {  // (the logs likewise: back to what they held before the first window)
+        w1.discard(), w2.discard();
+        if (lg.text.out) lg.text.out->rollback();
+        if (lg.has_json) lg.json.out->rollback();
+    }
     if (!writer_error.empty()) bail(writer_error);
     if (G.failed) bail(G.failure);
     if (G.timing && a.bgzf_output) {

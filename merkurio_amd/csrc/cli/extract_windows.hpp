@@ -56,6 +56,8 @@ struct WindowExtract::Impl {
     bool bzip2_streamed(int i) const { return in[i].s.raw_is_bzip2() && in[i].s.source().file_size() > a.bzip2_window; }
     // a .zst input of more compressed bytes than --zstd-window under --zstd-stream: likewise (without the flag it is libzstd's)
     bool zstd_streamed(int i) const { return a.zstd_stream && in[i].s.raw_is_zstd() && in[i].s.source().file_size() > a.zstd_window; }
+    // an .xz input of more compressed bytes than --xz-window under --xz-stream: likewise (without the flag it is liblzma's)
+    bool xz_streamed(int i) const { return a.xz_stream && in[i].s.raw_is_xz() && in[i].s.source().file_size() > a.xz_window; }
     void settle_bzip2(xw::InputFile &I);
     void reader_loop();
     void device_loop(size_t d);

@@ -1,6 +1,7 @@
 #include "util.hpp"
 
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <cstring>
 #include <ctime>
@@ -176,7 +177,27 @@ Sink::~Sink() {
     flush();
     if (f && owned) fclose(f);
 }
-void Sink::open(const std::string &path) {
+void Sink::discard() {
+    buf.clear();
+    if (z_text) z_text->clear();
+    if (z_ends) z_ends->clear();
+    if (f && owned) {
+        fclose(f);
+        remove(path.c_str());
+    }
+    if (owned) f = nullptr;
+}
+void Sink::mark() { mark_at = f && owned ? ftell(f) + (long)buf.size() : -1; }
+void Sink::rollback() {
+    if (!f || !owned || mark_at < 0) {  // (STDOUT: what is still buffered is all that can be dropped)
+        buf.clear();
+        return;
+    }
+    flush();
+    if (ftruncate(fileno(f), mark_at) == 0) fseek(f, mark_at, SEEK_SET);
+}
+void Sink::open(const std::string &p) {
+    path = p;
     if (path == "STDOUT") {
         f = stdout;
         owned = false;

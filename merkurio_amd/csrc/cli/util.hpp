@@ -60,9 +60,17 @@ std::string json_pretty(const Json &v, int indent = 0);
 struct Sink {
     FILE *f = nullptr;
     bool owned = false;
-    std::string buf;
+    std::string buf, path;
+    long mark_at = -1;  // mark(): the file's length then
     ~Sink();
     void open(const std::string &path);  // "STDOUT" or a path
+    // Taking back what a failed run wrote (extract --xz-stream: liblzma refuses a file the device had handed back; --host-codec meets
+    // that error at load).  discard(): a file is closed and removed.  mark() / rollback(): a file is cut back to what it held at the
+    // mark.  LIMITS: open() has truncated a file that existed at the path before the run, so discard() removes a file that the same
+    // error under --host-codec would have left untouched; and nothing that has been flushed to STDOUT can be taken back by either
+    void discard();
+    void mark();
+    void rollback();
     void write(const std::string &s) { write(s.data(), s.size()); }
     void write(const char *p, size_t n);
     void flush();

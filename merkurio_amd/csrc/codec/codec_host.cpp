@@ -169,6 +169,7 @@ void mk_codec_destroy(mk_codec *c) {
     mkz::gzip_stream_close(c);  // (its text buffers are what d_gz_text points at)
     mkz::bzip2_stream_close(c);
     mkz::zstd_stream_close(c);
+    mkz::xz_stream_close(c);
     for (void *p : {c->d_in, c->d_crc, c->d_tokens, c->d_slots, c->d_len, c->d_off, c->d_out, c->d_aux, c->d_ends, c->d_cut, c->d_gz_in, c->d_gz_sym, c->d_gz_tab, c->d_gz_ctx, c->d_gz_text})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)
@@ -227,6 +228,13 @@ int mk_codec_set_zstd_text_cap(mk_codec *c, uint64_t text_bytes) {
     if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_codec_set_zstd_text_cap: NULL handle");
     std::lock_guard<std::mutex> lock(c->mu);
     c->zs_text_cap = text_bytes;
+    return MK_OK;
+}
+
+int mk_codec_set_xz_text_cap(mk_codec *c, uint64_t text_bytes) {
+    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_codec_set_xz_text_cap: NULL handle");
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->xz_text_cap = text_bytes;
     return MK_OK;
 }
 

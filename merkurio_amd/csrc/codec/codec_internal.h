@@ -11,6 +11,7 @@
 #include "../host_common.h"
 #include "bzip2_chain.hpp"
 #include "gzip_chain.hpp"
+#include "xz_chain.hpp"
 #include "zstd_chain.hpp"
 
 namespace mk {
@@ -67,6 +68,17 @@ struct mk_zstd_stream {
     uint64_t text_total = 0;  // history + new text of the latest window, in d_text[text_cur]
 };
 
+// mk_xz_stream_*: an .xz file in windows of whole blocks (xz_host.cpp).  What is decided about a window is mkz::XzStream's (xz_chain.hpp:
+// all windows are planned at _begin); here what the stream owns on the device: two text buffers (the handle's d_gz_text points at
+// the latest window's).  The window's compressed span and its tables are the handle's d_gz_in / d_gz_tab, sized by the window.
+struct mk_xz_stream {
+    bool active = false;
+    mkz::XzStream s;
+    int text_cur = 0;
+    void *d_text[2] = {nullptr, nullptr};
+    size_t text_cap[2] = {0, 0};
+};
+
 struct mk_codec {
     int device = 0, num_cus = 256;
     hipStream_t stream = nullptr;
@@ -109,6 +121,7 @@ struct mk_codec {
     uint64_t xz_largest = 0;  // text bytes of the file's largest block
     float xz_ms[4] = {0, 0, 0, 0};  // upload, decode, check, the whole call
     uint32_t xz_spread = 0;         // mk_codec_set_xz_spread; 0 = kXzSpreadDefault
+    uint64_t xz_text_cap = 0;       // mk_codec_set_xz_text_cap: bytes of text per window of an xz stream; 0 = by the free memory
     // mk_zstd_deflate_records (zstd_host.cpp; text, record ends, range table, slots and packed frames are the deflate side's buffers above,
     // the waves' literal / sequence scratch is d_tokens)
     uint64_t zd_frames = 0;
@@ -121,7 +134,8 @@ struct mk_codec {
     mk_gzip_stream gzs;
     mk_bzip2_stream bzs;
     mk_zstd_stream zss;
-    bool stream_open() const { return gzs.active || bzs.active || zss.active; }  // one stream per handle, and no one-shot call beside it
+    mk_xz_stream xzs;
+    bool stream_open() const { return gzs.active || bzs.active || zss.active || xzs.active; }  // one stream per handle, and no one-shot call beside it
 };
 
 namespace mkz {
@@ -148,6 +162,8 @@ void gzip_stream_close(mk_codec *c);
 void bzip2_stream_close(mk_codec *c);
 // ---- zstd_host.cpp: an open zstd stream ends likewise
 void zstd_stream_close(mk_codec *c);
+// ---- xz_host.cpp: an open xz stream ends likewise
+void xz_stream_close(mk_codec *c);
 // ---- bgzf_host.cpp
 // One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
 // output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on

@@ -123,11 +123,14 @@ void launch_zs_resolve(const uint32_t *a, uint32_t *b, uint8_t *text, uint64_t f
 
 // ---- an .xz file, a wave per block (xz_inflate.hip, lzma_serial.hpp, xz_plan.hpp) ----
 // blocks[0, n_blocks) (XzBlock, device memory) of the file in `in` (zeros up to n_words dwords behind it): block b's text to
-// text + its text_off, status[b] = 0 or the refusal.  lclp_room: the largest lc + lp the launch's LDS has room for
+// text + its text_off, status[b] = 0 or the refusal.  lclp_room: the largest lc + lp the launch's LDS has room for.  order (device
+// memory, may be null): workgroup i handles block order[i] (a stream's window: largest text first); null: block i
 size_t xz_decode_lds_bytes(uint32_t lclp_room);
-void launch_xz_decode(const uint8_t *in, uint64_t n_words, const void *blocks, uint32_t n_blocks, uint8_t *text, uint32_t lclp_room, int32_t *status, hipStream_t s);
+void launch_xz_decode(const uint8_t *in, uint64_t n_words, const void *blocks, const uint32_t *order, uint32_t n_blocks, uint8_t *text, uint32_t lclp_room,
+                      int32_t *status, hipStream_t s);
 // every decoded block's CRC-32 / CRC-64 against its stored check: check[b] = 0 or kLzCheck
-void launch_xz_check(const uint8_t *in, const void *blocks, uint32_t n_blocks, const uint8_t *text, const int32_t *status, int32_t *check, hipStream_t s);
+void launch_xz_check(const uint8_t *in, const void *blocks, const uint32_t *order, uint32_t n_blocks, const uint8_t *text, const int32_t *status, int32_t *check,
+                     hipStream_t s);
 
 // ---- zstd frames written on the device, a wave per frame (zstd_deflate.hip, zstd_enc_serial.hpp) ----
 constexpr uint32_t kZsDeflateSlotBytes = 131328;       // a frame never exceeds 16 bytes + 128 KiB of text (a Raw block)

@@ -350,6 +350,7 @@ int mk_gzip_text_release(mk_codec *c) {
     mkz::gzip_stream_close(c);  // (an open stream's text is the text: the stream ends with it)
     mkz::bzip2_stream_close(c);
     mkz::zstd_stream_close(c);
+    mkz::xz_stream_close(c);
     mkz::gz_release(c);
     return MK_OK;
 }

@@ -1,4 +1,4 @@
-// xz_inflate.hip -- an .xz file decoded on the device, a wave per block (mk_xz_inflate_device, xz_host.cpp).
+// xz_inflate.hip -- an .xz file decoded on the device, a wave per block (mk_xz_inflate_device, and window by window mk_xz_stream_*: xz_host.cpp).
 //
 // The Index of an .xz file says where every block's bytes lie and how long its text is (xz_plan.hpp), so nothing is searched for or
 // guessed here: block b's wave decodes its LZMA2 chunks to text + text_off[b].  LZMA inside a block is serial, one adaptive bit at
@@ -29,7 +29,7 @@
 //     workgroup-scope fence: it waits for the wave's own stores, and within one compute unit loads behind it see them.
 //
 // LDS per wave: 2 x (1846 + (768 << lclp)) + kXzRing bytes = 19.7 KB at lc + lp = 3 (xz's presets), 31.7 KB at 4: of 160 KiB that
-// admits 8 and 5 waves per CU.  No private memory (scratch 0); 106 SGPRs, 38 VGPRs, and 491 SGPR spills: the decoder's values are
+// admits 8 and 5 waves per CU.  No private memory (scratch 0); 106 SGPRs, 38 VGPRs, and 493 SGPR spills (491 before the order table): the decoder's values are
 // scalar, but the compiler keeps part of them in VGPR lanes (v_writelane / v_readlane) inside the bit loop.
 #include <hip/hip_runtime.h>
 
@@ -124,12 +124,14 @@ struct XzWaveOut {
     __device__ void finish(uint64_t pos) { flush(pos); }
 };
 
-// blocks[b]: XzBlock; the file in in32 (n_words dwords, zeros behind its bytes); text: of the whole file.  status[b] = 0 or the refusal.
-// Dynamic LDS: 2 x lzma_probs(lclp_room) rounded up to 16, then kXzRing
-__global__ __launch_bounds__(64) void mk_xz_decode_kernel(const uint32_t *in32, uint64_t n_words, const XzBlock *blocks, uint8_t *text, uint32_t lclp_room,
-                                                         int32_t *status) {
+// blocks[b]: XzBlock; the file (a stream: the window's span of it) in in32 (n_words dwords, zeros behind its bytes: the j < n_words
+// guard of XzWaveIn keeps the last block's read-ahead inside the upload); text: of the whole file (the window).  status[b] = 0 or the
+// refusal.  order (may be null): workgroup i handles block order[i] -- a window passes its blocks largest text first; that workgroups
+// start in index order is an assumption, nothing here depends on it.  Dynamic LDS: 2 x lzma_probs(lclp_room) rounded up to 16, then kXzRing
+__global__ __launch_bounds__(64) void mk_xz_decode_kernel(const uint32_t *in32, uint64_t n_words, const XzBlock *blocks, const uint32_t *order, uint8_t *text,
+                                                         uint32_t lclp_room, int32_t *status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t lane = threadIdx.x, b = blockIdx.x;
+    const uint32_t lane = threadIdx.x, b = order ? order[blockIdx.x] : blockIdx.x;
     const XzBlock B = blocks[b];
     XzWaveIn in{in32, n_words, B.in_off, ~0ull, ~0ull, 0u, 0u, lane};
     XzWaveProbs pr{reinterpret_cast<uint16_t *>(lds), lane};
@@ -174,9 +176,10 @@ __device__ int xz_check_block(const uint8_t *t, uint64_t len, const uint8_t *sto
     return r == want ? 0 : kLzCheck;
 }
 
-__global__ __launch_bounds__(64) void mk_xz_check_kernel(const uint8_t *in8, const XzBlock *blocks, const uint8_t *text, const int32_t *status, int32_t *check) {
+__global__ __launch_bounds__(64) void mk_xz_check_kernel(const uint8_t *in8, const XzBlock *blocks, const uint32_t *order, const uint8_t *text, const int32_t *status,
+                                                        int32_t *check) {
     __shared__ uint64_t table[256];
-    const uint32_t lane = threadIdx.x, b = blockIdx.x;
+    const uint32_t lane = threadIdx.x, b = order ? order[blockIdx.x] : blockIdx.x;
     const XzBlock B = blocks[b];
     int st = 0;
     if (status[b] != 0 || B.check_kind == kXzCheckNone) {
@@ -193,12 +196,14 @@ __global__ __launch_bounds__(64) void mk_xz_check_kernel(const uint8_t *in8, con
 
 size_t xz_decode_lds_bytes(uint32_t lclp_room) { return ((2 * lzma_probs(lclp_room) + 15u) & ~15u) + kXzRing; }
 
-void launch_xz_decode(const uint8_t *in, uint64_t n_words, const void *blocks, uint32_t n_blocks, uint8_t *text, uint32_t lclp_room, int32_t *status, hipStream_t s) {
+void launch_xz_decode(const uint8_t *in, uint64_t n_words, const void *blocks, const uint32_t *order, uint32_t n_blocks, uint8_t *text, uint32_t lclp_room,
+                      int32_t *status, hipStream_t s) {
     hipLaunchKernelGGL(mk_xz_decode_kernel, dim3(n_blocks), dim3(64), xz_decode_lds_bytes(lclp_room), s, reinterpret_cast<const uint32_t *>(in), n_words,
-                       reinterpret_cast<const XzBlock *>(blocks), text, lclp_room, status);
+                       reinterpret_cast<const XzBlock *>(blocks), order, text, lclp_room, status);
 }
-void launch_xz_check(const uint8_t *in, const void *blocks, uint32_t n_blocks, const uint8_t *text, const int32_t *status, int32_t *check, hipStream_t s) {
-    hipLaunchKernelGGL(mk_xz_check_kernel, dim3(n_blocks), dim3(64), 0, s, in, reinterpret_cast<const XzBlock *>(blocks), text, status, check);
+void launch_xz_check(const uint8_t *in, const void *blocks, const uint32_t *order, uint32_t n_blocks, const uint8_t *text, const int32_t *status, int32_t *check,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(mk_xz_check_kernel, dim3(n_blocks), dim3(64), 0, s, in, reinterpret_cast<const XzBlock *>(blocks), order, text, status, check);
 }
 
 }  // namespace mkz

@@ -2,7 +2,7 @@
 // stream -- footer, Index, header -- then every Block Header of every stream.  The Index states each block's stored size and text
 // size, so the walk ends with a table that says where every block's LZMA2 bytes lie and where its text goes, before a bit is decoded.
 // What does not add up is refused with a name (liblzma then words the error); what is valid but not this path's -- SHA-256, filters
-// other than one LZMA2, a file of one huge block -- is refused with a name of its own.  Used by xz_host.cpp and tests/helpers/xz_harness.cpp.
+// other than one LZMA2, a file of one huge block -- is refused with a name of its own.  Used by xz_host.cpp, xz_chain.hpp and the tests' harnesses.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -31,8 +31,12 @@ struct XzBlock {
 };
 struct XzPlan {
     std::vector<XzBlock> blocks;
-    uint32_t streams = 0, lclp_max = 0;
+    uint32_t streams = 0, lclp_max = 0;  // lclp_max: xz_plan's; xz_walk leaves it 0
     uint64_t text_total = 0, largest_block_text = 0;
+    // beside the table, for a stream's windows (xz_chain.hpp): where each block's Block Header stands in the file, and per stream in
+    // file order the blocks in front of its end (a stream without blocks repeats the figure before it)
+    std::vector<uint64_t> head_off;
+    std::vector<uint32_t> stream_end;
 };
 
 inline uint32_t xz_check_bytes(uint32_t kind) { return kind == 0 ? 0u : kind < 4 ? 4u : kind < 7 ? 8u : kind < 10 ? 16u : kind < 13 ? 32u : 64u; }
@@ -118,8 +122,17 @@ inline int xz_block_header(const uint8_t *xz, uint64_t at, uint64_t unpadded, ui
     return 0;
 }
 
-// xz[0, n) -> P, or the refusal.  A file of no bytes is no xz file (kXzTruncated)
-inline int xz_plan(const uint8_t *xz, uint64_t n, XzPlan &P) {
+// the largest lc + lp among the chunks of blocks[0, count), whose in_off counts from xz
+inline uint32_t xz_blocks_lclp(const uint8_t *xz, const XzBlock *blocks, size_t count) {
+    uint32_t most = 0;
+    for (size_t k = 0; k < count; ++k) most = std::max(most, xz_block_lclp(xz + blocks[k].in_off, blocks[k].in_bytes));
+    return most;
+}
+
+// The container walk: xz[0, n) -> P without lclp_max, or the refusal.  It reads footers, Indexes, stream headers, Block Headers and
+// block padding, never a block's LZMA2 bytes: a stream (xz_chain.hpp) runs it once over the mapped file and walks the chunk headers
+// window by window.  A file of no bytes is no xz file (kXzTruncated)
+inline int xz_walk(const uint8_t *xz, uint64_t n, XzPlan &P) {
     static const uint8_t kMagic[6] = {0xFD, '7', 'z', 'X', 'Z', 0x00};
     P = XzPlan{};
     if (n < 32) return kXzTruncated;
@@ -128,6 +141,7 @@ inline int xz_plan(const uint8_t *xz, uint64_t n, XzPlan &P) {
         uint64_t unpadded, text;
     };
     std::vector<std::vector<XzBlock>> per_stream;  // last stream first
+    std::vector<std::vector<uint64_t>> per_stream_head;
     uint64_t end = n, n_blocks = 0;
     while (end > 0) {
         // ---- Stream Padding: zero bytes in multiples of four
@@ -173,24 +187,37 @@ inline int xz_plan(const uint8_t *xz, uint64_t n, XzPlan &P) {
         if (kind != kXzCheckNone && kind != kXzCheckCrc32 && kind != kXzCheckCrc64) return kXzCheckKind;
         // ---- the Block Headers
         std::vector<XzBlock> blocks((size_t)count);
+        std::vector<uint64_t> heads((size_t)count);
         uint64_t at = s0 + 12;
         for (size_t k = 0; k < recs.size(); ++k) {
+            heads[k] = at;
             const int st = xz_block_header(xz, at, recs[k].unpadded, recs[k].text, kind, blocks[k]);
             if (st) return st;
             at += (recs[k].unpadded + 3) & ~3ull;
         }
         per_stream.push_back(std::move(blocks));
+        per_stream_head.push_back(std::move(heads));
         ++P.streams;
         end = s0;
     }
-    for (size_t s = per_stream.size(); s-- > 0;)
+    for (size_t s = per_stream.size(); s-- > 0;) {
         for (XzBlock &B : per_stream[s]) {
             B.text_off = P.text_total;
             if (B.text_bytes > (1ull << 62) || (P.text_total += B.text_bytes) > (1ull << 62)) return kXzTooLarge;
             P.largest_block_text = std::max(P.largest_block_text, B.text_bytes);
-            P.lclp_max = std::max(P.lclp_max, xz_block_lclp(xz + B.in_off, B.in_bytes));
             P.blocks.push_back(B);
         }
+        P.head_off.insert(P.head_off.end(), per_stream_head[s].begin(), per_stream_head[s].end());
+        P.stream_end.push_back((uint32_t)P.blocks.size());
+    }
+    return 0;
+}
+
+// xz[0, n) -> P with lclp_max (the one-shot call sizes its launch by it), or the refusal
+inline int xz_plan(const uint8_t *xz, uint64_t n, XzPlan &P) {
+    const int st = xz_walk(xz, n, P);
+    if (st) return st;
+    P.lclp_max = xz_blocks_lclp(xz, P.blocks.data(), P.blocks.size());
     return 0;
 }
 

@@ -57,6 +57,7 @@ EXPORTS = [
     "mk_codec_times", "mk_codec_set_pass_limits", "mk_codec_set_inflate_kernel", "mk_codec_set_gzip_chunk", "mk_gzip_inflate_device", "mk_gzip_member_guesses", "mk_gzip_members_inflate_device", "mk_gzip_text_read", "mk_gzip_text_device", "mk_gzip_text_release", "mk_gzip_info", "mk_bzip2_inflate_device", "mk_bzip2_info", "mk_zstd_inflate_device", "mk_zstd_info", "mk_xz_inflate_device", "mk_xz_info", "mk_codec_set_xz_spread", "mk_zstd_record_cuts", "mk_zstd_deflate_bound", "mk_zstd_deflate_records", "mk_zstd_deflate_info", "mk_codec_set_bzip2_pass_blocks",
     "mk_bzip2_stream_begin", "mk_bzip2_stream_next", "mk_bzip2_stream_info", "mk_bzip2_stream_end", "mk_codec_set_bzip2_text_cap",
     "mk_zstd_stream_begin", "mk_zstd_stream_next", "mk_zstd_stream_info", "mk_zstd_stream_end", "mk_codec_set_zstd_text_cap",
+    "mk_xz_stream_begin", "mk_xz_stream_next", "mk_xz_stream_info", "mk_xz_stream_end", "mk_codec_set_xz_text_cap",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
     "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
@@ -96,6 +97,13 @@ class ZstdStreamStats(C.Structure):
     """mk_zstd_stream_stats"""
     _fields_ = [("windows", C.c_uint64), ("frames", C.c_uint64), ("blocks", C.c_uint64), ("consumed_bytes", C.c_uint64), ("text_bytes", C.c_uint64),
                 ("rounds", C.c_uint64), ("max_history", C.c_uint64), ("peak_device_bytes", C.c_uint64), ("ms", C.c_float * 6)]
+
+
+class XzStreamStats(C.Structure):
+    """mk_xz_stream_stats"""
+    _fields_ = [("windows", C.c_uint64), ("streams", C.c_uint64), ("blocks", C.c_uint64), ("consumed_bytes", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("planned_windows", C.c_uint64), ("largest_block_text", C.c_uint64), ("peak_device_bytes", C.c_uint64), ("status", C.c_int32),
+                ("reserved", C.c_uint32), ("ms", C.c_float * 4)]
 
 
 class MatcherOptions(C.Structure):
@@ -348,6 +356,11 @@ def load(build_if_missing=True):
     L.mk_zstd_stream_info.argtypes = [C.c_void_p, C.POINTER(ZstdStreamStats)]
     L.mk_zstd_stream_end.argtypes = [C.c_void_p]
     L.mk_codec_set_zstd_text_cap.argtypes = [C.c_void_p, C.c_uint64]
+    L.mk_xz_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
+    L.mk_xz_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.mk_xz_stream_info.argtypes = [C.c_void_p, C.POINTER(XzStreamStats)]
+    L.mk_xz_stream_end.argtypes = [C.c_void_p]
+    L.mk_codec_set_xz_text_cap.argtypes = [C.c_void_p, C.c_uint64]
     L.mk_gzip_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
     L.mk_gzip_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.mk_gzip_stream_info.argtypes = [C.c_void_p, C.POINTER(GzipStreamStats)]
@@ -1446,6 +1459,47 @@ class Codec:
                 yield out.tobytes()
         finally:
             _check(self._L.mk_zstd_stream_end(self._h))
+
+    def unxz_stream_info(self):
+        """mk_xz_stream_info as a dict: of the open stream, or what the last one left (a refusal at _begin included: its status)"""
+        st = XzStreamStats()
+        _check(self._L.mk_xz_stream_info(self._h, C.byref(st)))
+        out = {k: getattr(st, k) for k, _ in XzStreamStats._fields_ if k not in ("ms", "reserved")}
+        out["ms"] = tuple(round(x, 2) for x in st.ms)
+        return out
+
+    def unxz_stream(self, blob, window_bytes=0, text_cap=0):
+        """mk_xz_stream_begin / _next / _end: an .xz file of any size decoded window by window (`window_bytes`: a bound on a window's
+        compressed span, 0 = none; text_cap: mk_codec_set_xz_text_cap for this stream, 0 = by the free memory) -> a generator of the
+        windows' texts.  self.stream_state = 1 when it ends at the file's end (every block proved), 2 when the device handed the file
+        back (what was yielded before is a prefix of liblzma's text in whole blocks; nothing was, for a file refused at _begin);
+        self.stream_stats = unxz_stream_info() of the stream as it ended (its status names a refusal),
+        self.stream_windows = that dict behind every call of _next (a list)"""
+        src = np.frombuffer(blob, dtype=np.uint8)
+        taken = C.c_uint32(0)
+        self.stream_state, self.stream_stats, self.stream_windows = 2, None, []
+        _check(self._L.mk_codec_set_xz_text_cap(self._h, text_cap))
+        try:
+            _check(self._L.mk_xz_stream_begin(self._h, src.ctypes.data if src.size else None, src.size, window_bytes, C.byref(taken)))
+        finally:
+            _check(self._L.mk_codec_set_xz_text_cap(self._h, 0))  # (the stream took it when it began)
+        self.stream_stats = self.unxz_stream_info()
+        if not taken.value:
+            return
+        try:
+            n, state = C.c_uint64(0), C.c_uint32(0)
+            while True:
+                _check(self._L.mk_xz_stream_next(self._h, C.byref(n), C.byref(state)))
+                self.stream_stats = self.unxz_stream_info()
+                self.stream_windows.append(self.stream_stats)
+                self.stream_state = state.value
+                if state.value != 0:
+                    return
+                out = np.empty(n.value, dtype=np.uint8)
+                _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
+                yield out.tobytes()
+        finally:
+            _check(self._L.mk_xz_stream_end(self._h))
 
     def gunzip_members(self, gz):
         """mk_gzip_members_inflate_device + mk_gzip_text_read: a gzip file of one or more members, all of them inflated in one batch of

@@ -15,6 +15,12 @@
          thread at load), in alternation, medians of --runs with ranges; the [timing] row says which path ran: the single-block files
          show the rule handing them back.  The plain big.fastq goes through both binaries as the control row.
 
+  sweep  the big multi-block files under --xz-stream at every --caps value (text bytes per window, --xz-text-cap; 0 = the default)
+         against the parent's binary with liblzma, in alternation, medians of --runs; per cap the stream's summary row (planned
+         windows, windows, blocks, phases, peak device bytes).  --spread is passed as --xz-spread (0 = the default K, under which a
+         file of 24 MiB blocks passes the rule only in windows of about 2.5 GiB of text).  Prints the table of
+         profiles/e2e_unxz_windows.txt
+
 Prints the table of profiles/e2e_unxz.txt.  Example:
   timeout -k 10 300 tools/e2e_unxz.py rates
   tools/e2e_unxz.py make --dir /tmp/xz && tools/e2e_unxz.py run --dir /tmp/xz --parent-bin /path/to/parent/merkurio --runs 5
@@ -135,6 +141,32 @@ def run(a):
         print(f"{inp}: {path_ran[inp]}")
 
 
+def sweep(a):
+    patterns, out = os.path.join(a.dir, "patterns.txt"), os.path.join(a.dir, "out.fastq")
+    inputs = ["big.t4.fastq.xz", "big.1m.fastq.xz"]
+    caps = [int(c) for c in a.caps.split(",")]
+    times = {(inp, c): [] for inp in inputs for c in caps + ["parent"]}
+    summary = {}
+    for r in range(a.runs):
+        for inp in inputs:
+            path = os.path.join(a.dir, inp)
+            for c in caps:
+                extra = ["--xz-stream", "--xz-window", "1", "--xz-text-cap", str(c)] + (["--xz-spread", str(a.spread)] if a.spread else [])
+                dt, err = run_once(BIN, path, patterns, out, extra)
+                times[(inp, c)].append(dt)
+                rows = [ln.strip() for ln in err.split("\n") if "window by window" in ln]
+                summary[(inp, c)] = rows[-1] if rows else "(no stream row)"
+                dt, _ = run_once(a.parent_bin, path, patterns, out, [])
+                times[(inp, "parent")].append(dt)
+            print(f"# round {r}: {inp} done", flush=True)
+    print(f"extract --xz-stream, seconds per run, median [min .. max] of {a.runs}, alternating with the parent's binary")
+    for inp in inputs:
+        print(f"{inp:24s} parent (liblzma, one thread) {med(times[(inp, 'parent')])}")
+        for c in caps:
+            print(f"{inp:24s} --xz-text-cap {c:<12d} {med(times[(inp, c)])}")
+            print(f"    {summary[(inp, c)]}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -150,5 +182,11 @@ if __name__ == "__main__":
     r.add_argument("--parent-bin", required=True)
     r.add_argument("--runs", type=int, default=5)
     r.add_argument("--spread", type=int, default=0, help="--xz-spread for this build's runs; 0 = the default")
+    w = sub.add_parser("sweep")
+    w.add_argument("--dir", required=True)
+    w.add_argument("--parent-bin", required=True)
+    w.add_argument("--runs", type=int, default=5)
+    w.add_argument("--caps", default="0,268435456,1073741824", help="--xz-text-cap values, comma separated; 0 = the default")
+    w.add_argument("--spread", type=int, default=0, help="--xz-spread for this build's runs; 0 = the default")
     a = ap.parse_args()
-    {"rates": rates, "make": make, "run": run}[a.cmd](a)
+    {"rates": rates, "make": make, "run": run, "sweep": sweep}[a.cmd](a)
