@@ -655,6 +655,33 @@ int mk_extract_window_members(mk_matcher *m, mk_codec *codec, uint32_t format, u
                               uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status);
 
 /* -------------------------------------------------------------------------------------
+ * A window's kept records as zstd frames (v7 addition) -- the output side of `extract --zstd-output`: mk_extract_window_members with the
+ * other codec.  Same arguments and outputs, the same mk_window_members per source (paired: each source has frames of its own), the same
+ * body: only the step that turns the packed written text into compressed bytes differs.  In the struct, `members` holds the FRAMES back
+ * to back, n_member_bytes their bytes and n_members how many there are.
+ *
+ * The frames are those of mk_zstd_deflate_records (below) applied to the window's written text (THE WRITTEN FORM, above) with the
+ * written record ends: cut by the rule of mk_zstd_record_cuts -- grid MK_ZSTD_CUT_GRID = 114688, at most MK_ZSTD_FRAME_TEXT_MAX = 131072
+ * bytes of text per frame, so every frame starts at a record start unless a record is longer than 16384 bytes --, each a
+ * self-contained frame of one block with a content checksum, byte for byte what that call makes of the same text and ends.  Cuts start
+ * again with every window and every source.  Nothing kept: 0 frames, 0 bytes (the empty frame that makes an empty job's output a
+ * valid .zst is the caller's business).
+ *
+ * text_below, ids / ids_cap / id_end, n_written, n_kept, as_text and written_ms: as for members.  *status = 2 for a kept FASTA record
+ * that the written form does not describe: every mk_window_members reports 0 bytes, as for members.  members_cap too small:
+ * MK_E_CAPACITY with n_member_bytes = the exact need; ids_cap too small: MK_E_CAPACITY with n_id_bytes = the need; both stand where they
+ * stand for members in the order of "the first thing that does not fit".
+ * MK_E_INVALID_ARG: no codec; a codec on another device than the matcher's; a source with a `kept` buffer; logging with invert; a
+ * codec handle with an open stream (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*, mk_xz_stream_*), as for
+ * mk_zstd_deflate_records.
+ * mk_zstd_deflate_info reports, for the codec handle's last such call, the frames, the block kinds and the milliseconds SUMMED over the
+ * sources (ms[0], upload, is 0: nothing goes up) -- what mk_codec_cut_times is for members.
+ * --------------------------------------------------------------------------------------- */
+int mk_extract_window_frames(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *sources,
+                             mk_window_members *frames, int logging, int invert, uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep, mk_row *rows,
+                             uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status);
+
+/* -------------------------------------------------------------------------------------
  * A gzip file inflated in parallel on the device (v6: one member; v7: a chain of members) -- a .fastq.gz / .fasta.gz as plain gzip (or pigz, or zlib) writes it: ONE
  * DEFLATE stream of thousands of blocks, which zlib can only walk from the front.  Replaces needletail's gzip reader under
  * `merkurio extract` (src/cmd_extract.rs:281-282) for such files.  The stream is cut where block starts can be FOUND (a dynamic
@@ -827,8 +854,8 @@ int mk_codec_set_xz_text_cap(mk_codec *c, uint64_t text_bytes);
  * mk_zstd_deflate_records: the contract of mk_bgzf_deflate_records -- rec_end[n_rec - 1] == n and non-decreasing ends, else
  * MK_E_INVALID_ARG; MK_E_CAPACITY with the exact need in *out_len; n == 0 writes nothing (0 frames); passes of
  * mk_codec_set_pass_limits' deflate_blocks frames; MK_E_INVALID_ARG while a stream is open on the handle.
- * mk_zstd_deflate_info: of the last such call, the frames, how many blocks were Raw / RLE / Compressed, and milliseconds of upload,
- * cut + deflate + pack, download. */
+ * mk_zstd_deflate_info: of the last such call (or the last mk_extract_window_frames with this handle: summed over its sources), the
+ * frames, how many blocks were Raw / RLE / Compressed, and milliseconds of upload, cut + deflate + pack, download. */
 #define MK_ZSTD_CUT_GRID 114688u
 #define MK_ZSTD_FRAME_TEXT_MAX 131072u
 int mk_zstd_record_cuts(const uint64_t *rec_end, uint64_t n_rec, uint64_t *cut, uint64_t cap, uint64_t *n_cuts);

@@ -57,7 +57,8 @@ void RecordGzip::window_done(bool force) {
     text_.clear(), ends_.clear();
 }
 
-// --zstd-output: what has gathered -> frames
+// --zstd-output: what has gathered -> frames (on the one device codec of this output, whatever --gpus says: the windows that are worth
+// a launch of their own have left as frames from their own devices, put_members)
 void RecordGzip::zstd_window() {
     FILE *f = sink_->f;
     const auto t0 = std::chrono::steady_clock::now();
@@ -96,7 +97,19 @@ void RecordGzip::put_members(const uint8_t *p, uint64_t n, uint64_t count) {
     if (!sink_) return;
     window_done(true);
     if (sink_->f && n && fwrite(p, 1, n, sink_->f) != n) bail("Error writing the compressed output");
-    members += count;
+    members += count, window_members += count;
+    if (!zstd_) return;
+    // the kind of every frame's one block, from its header (include/merkurio_hip.h: 4 bytes of magic, the descriptor, 4 bytes of
+    // content size, the 3-byte block header -- type in bits 1-2, size above --, the block, 4 bytes of checksum)
+    uint64_t at = 0, seen = 0;
+    for (; n - at >= 16; ++seen) {
+        const uint32_t bh = p[at + 9] | (uint32_t)p[at + 10] << 8 | (uint32_t)p[at + 11] << 16, type = bh >> 1 & 3;
+        if (type > 2) break;
+        const uint64_t size = 16 + (type == 1 ? 1 : bh >> 3);
+        if (size > n - at) break;
+        kinds[type] += 1, at += size;
+    }
+    if (at != n || seen != count) bail("Error writing the compressed output: the frames of a window do not add up to its bytes");
 }
 
 void RecordGzip::finish() {

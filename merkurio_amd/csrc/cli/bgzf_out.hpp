@@ -12,14 +12,17 @@ namespace cli {
 // / MK_ZSTD_FRAME_TEXT_MAX): cut and compressed on the device (mk_zstd_deflate_records), or, with --host-codec, cut by
 // mk_zstd_record_cuts and compressed by libzstd at level 3 on the host threads, every range a frame of its own with a checksum (the
 // checker).  No end marker; a job that kept nothing writes one empty frame, so that the file is a valid .zst.
+// On the window path a window whose kept records take --z-members-from bytes or more does not gather: it arrives as members / frames
+// made on its own device (mk_extract_window_members / mk_extract_window_frames) and is passed through (put_members).
 struct RecordGzip {
     void attach(Sink &sink, int device, bool zstd = false);  // device < 0: zlib / libzstd on the host threads
     void window_done(bool force = false);
-    // members made on the device (mk_extract_window_members): whatever text has gathered is forced out first, so that record order
-    // holds, then the members are written through
+    // members / frames made on the device (mk_extract_window_members / mk_extract_window_frames): whatever text has gathered is forced out
+    // first, so that record order holds, then they are written through (frames: their block kinds are counted from their headers)
     void put_members(const uint8_t *p, uint64_t n, uint64_t count);
     void finish();
     uint64_t members = 0;          // BGZF members, or zstd frames
+    uint64_t window_members = 0;   // ... of them through put_members: made on the windows' devices (the rest: from gathered text)
     uint64_t kinds[3] = {0, 0, 0};  // zstd frames of the device codec: Raw, RLE, Compressed blocks
     double upload_ms = 0;           // zstd frames of the device codec (cut_ms stays 0: the library times the cut kernel with the deflate)
     double cut_ms = 0, deflate_ms = 0, download_ms = 0;  // device codec: summed over the calls; host codec: deflate_ms alone

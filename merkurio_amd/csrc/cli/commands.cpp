@@ -367,7 +367,7 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
     }
     // -z: what the sinks are given leaves as BGZF members that end at record ends
     RecordGzip z1, z2;
-    if (a.bgzf_output || a.zstd_output) {  // (--zstd-output: as zstd frames, on the first device)
+    if (a.bgzf_output || a.zstd_output) {  // (--zstd-output: as zstd frames; what gathers here is compressed on the first device)
         z1.attach(w1, a.host_codec ? -1 : devs[0], a.zstd_output);
         if (paired) z2.attach(w2, a.host_codec ? -1 : devs[0], a.zstd_output);
     }
@@ -557,10 +557,11 @@ int run_extract(const ExtractArgs &a, const std::vector<std::string> &argv) {
         fprintf(stderr, "[timing] BGZF output (%s): %llu members written, cut %.1f ms, deflate %.1f ms, download %.1f ms\n", a.host_codec ? "zlib, host" : "device codec",
                 (unsigned long long)(z1.members + z2.members), z1.cut_ms + z2.cut_ms, z1.deflate_ms + z2.deflate_ms, z1.download_ms + z2.download_ms);
     if (tm.on && a.zstd_output)
-        fprintf(stderr, "[timing] zstd output (%s): %llu frames written, blocks raw %llu rle %llu compressed %llu, upload %.1f ms, cut + deflate %.1f ms, download %.1f ms\n",
+        fprintf(stderr, "[timing] zstd output (%s): %llu frames written, blocks raw %llu rle %llu compressed %llu, upload %.1f ms, cut + deflate %.1f ms, download %.1f ms (of the gathering path); %llu frames from the window path, %llu from the gathering path\n",
                 a.host_codec ? "libzstd, host" : "device codec", (unsigned long long)(z1.members + z2.members), (unsigned long long)(z1.kinds[0] + z2.kinds[0]),
                 (unsigned long long)(z1.kinds[1] + z2.kinds[1]), (unsigned long long)(z1.kinds[2] + z2.kinds[2]), z1.upload_ms + z2.upload_ms,
-                z1.deflate_ms + z2.deflate_ms, z1.download_ms + z2.download_ms);
+                z1.deflate_ms + z2.deflate_ms, z1.download_ms + z2.download_ms, (unsigned long long)(z1.window_members + z2.window_members),
+                (unsigned long long)(z1.members + z2.members - z1.window_members - z2.window_members));
     if (tm.on && (call_ms[0] + call_ms[1] + call_ms[2] + call_ms[3]) > 0)
         fprintf(stderr, "[timing] inside the batch calls: upload %.3f s, device %.3f s, download %.3f s, host loop %.3f s\n", call_ms[0] * 1e-3,
                 call_ms[1] * 1e-3, call_ms[2] * 1e-3, call_ms[3] * 1e-3);

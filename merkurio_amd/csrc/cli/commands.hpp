@@ -36,7 +36,9 @@ struct CommonArgs {
                                // (BAM records indexed and tagged on the host threads) where BAM -> BAM would keep them on the device
 };
 
-constexpr uint64_t kZMembersFrom = 8ull << 20;  // (the sweep of DESIGN.md §5.9: inside the parent build's range at 1 % kept, ahead of it from 20 %)
+// (the sweep of DESIGN.md §5.9, for -z: inside the parent build's range at 1 % kept, ahead of it from 20 %.  For --zstd-output the same
+// value is an UNMEASURED choice: 64-73 frames per launch, on a kernel that keeps 8 waves per CU)
+constexpr uint64_t kZMembersFrom = 8ull << 20;
 
 constexpr uint64_t kGzipWindow = 256ull << 20;  // (an unmeasured choice: README, "Gunzip window by window")
 constexpr uint64_t kXzWindow = 256ull << 20;     // (an unmeasured choice, the zstd and bzip2 value: profiles/e2e_unxz.txt)
@@ -49,8 +51,9 @@ struct ExtractArgs : CommonArgs {
     std::optional<std::string> out_fastx;   // -o
     bool bgzf_output = false;               // -z: the kept records are written as BGZF members that end at record ends (output name + ".gz")
     bool zstd_output = false;               // --zstd-output: the kept records are written as zstd frames that end at record ends (output name + ".zst")
-    // --z-members-from: with -z on the window path, a window whose written kept records take this many bytes or more is cut and deflated
-    // where it lies and comes down as members (mk_extract_window_members); a smaller one comes down as text and gathers with its neighbours
+    // --z-members-from: with -z or --zstd-output on the window path, a window whose written kept records take this many bytes or more is
+    // cut and compressed where it lies and comes down as members (mk_extract_window_members) or frames (mk_extract_window_frames); a
+    // smaller one comes down as text and gathers with its neighbours
     uint64_t z_members_from = kZMembersFrom;
     // --gzip-window: a plain gzip input of more compressed bytes than this is inflated on the device window by window (mk_gzip_stream_*),
     // a smaller one in one piece (mk_gzip_inflate_device / mk_gzip_members_inflate_device)

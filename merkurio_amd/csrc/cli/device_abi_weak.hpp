@@ -15,4 +15,10 @@ __attribute__((weak)) int mk_bgzf_inflate(mk_codec *c, const uint8_t *in, uint64
 __attribute__((weak)) const char *mk_last_error(void);
 __attribute__((weak)) int mk_host_alloc(size_t bytes, void **out);
 __attribute__((weak)) void mk_host_free(void *p);
+// (extract_window_call.cpp: reached by `extract --zstd-output` on the window path only, which needs a codec handle)
+__attribute__((weak)) int mk_extract_window_frames(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *sources,
+                                                   mk_window_members *frames, int logging, int invert, uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep,
+                                                   mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters, uint32_t *pattern_hit_counts,
+                                                   uint32_t *status);
+__attribute__((weak)) int mk_zstd_deflate_info(const mk_codec *c, uint64_t *n_frames, uint32_t kinds[3], float ms[3]);
 }

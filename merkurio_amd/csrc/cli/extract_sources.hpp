@@ -81,7 +81,8 @@ struct Side {  // one input's part of a window
         std::vector<uint64_t> rec_start;
         uint64_t n_window = 0, n_used = 0;
         std::vector<char> tail;  // the text behind the processed records: the next window's head
-        // MEMBERS / WRITTEN (-z, mk_extract_window_members): the kept records came down as BGZF members of their written form / as that
+        // MEMBERS / WRITTEN (-z, mk_extract_window_members; --zstd-output, mk_extract_window_frames): the kept records came down as BGZF
+        // members (zstd frames) of their written form / as that
         // text (a window below --z-members-from), the ids of the kept records beside them -- the writer needs no stored text
         enum Layout { HEAD_BODY, PACKED_KEPT, WHOLE, MEMBERS, WRITTEN } layout = HEAD_BODY;
         std::vector<char> text;  // what the writer reads from unless HEAD_BODY: the kept records, the whole window, the host parser's text
@@ -104,7 +105,7 @@ struct Win {
     mk_counters cb;
     std::vector<uint32_t> cnt;
     bool by_host = false;
-    float z_ms[4] = {0, 0, 0, 0};  // -z on the device: written form (select, scan, gather), cut, deflate, download
+    float z_ms[4] = {0, 0, 0, 0};  // -z on the device: written form (select, scan, gather), cut, deflate, download (--zstd-output: cut is in deflate)
     void index_kept() {
         kept.clear();
         for (uint64_t r = 0; r < n_rec; ++r)

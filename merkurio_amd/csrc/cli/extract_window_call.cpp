@@ -1,6 +1,7 @@
 // extract_window_call.cpp -- one window of the extract window driver through the matcher: the device call (mk_extract_window /
-// mk_extract_window_members: its output buffers, the first guesses of their sizes, the capacity-and-repeat protocol, what comes back)
+// mk_extract_window_members / mk_extract_window_frames: its output buffers, the first guesses of their sizes, the capacity-and-repeat protocol, what comes back)
 // and the host parser's path for a window the device refuses; both end with Win::kept and the text the writer needs (pack_host_text).
+#include "device_abi_weak.hpp"
 #include "extract_windows.hpp"
 
 namespace cli {
@@ -140,13 +141,14 @@ uint64_t WindowExtract::Impl::bind_outputs(Win &W, Call &c) {
 
 // the members' and the ids' buffers are guessed, and a wrong guess is dear: their needs are known only after the scan, the gather and
 // the deflate, so MK_E_CAPACITY means the whole window is processed once more.  Under -v nearly everything is kept: the written
-// text's bound (a record grows by three line-end bytes at most), every member stored.  Otherwise the share of its window's text that
+// text's bound (a record grows by three line-end bytes at most), every member stored (every frame's block raw).  Otherwise the share of its window's text that
 // the last window needed, an eighth added -- the first window is small, the ones behind it 16 times its size --, and never less than
 // the text a window may come back as (anything below --z-members-from, or the bound)
 void WindowExtract::Impl::guess_member_buffers(Win &W, Call &c) {
     const uint64_t bound = c.cap_text + 3 * c.rec_cap + 64;
     const uint64_t share = members_share_seen.load(), share_ids = ids_share_seen.load();
-    uint64_t guess = a.invert_match ? bound + 31 * (bound / MK_BGZF_CUT_GRID + 1) : ((c.cap_text >> 10) + 1) * (share + (share >> 3));
+    const uint64_t stored = a.zstd_output ? bound + 16 * (bound / MK_ZSTD_CUT_GRID + 2) : bound + 31 * (bound / MK_BGZF_CUT_GRID + 1);
+    uint64_t guess = a.invert_match ? stored : ((c.cap_text >> 10) + 1) * (share + (share >> 3));
     guess = std::max<uint64_t>(guess, std::min<uint64_t>(a.z_members_from, bound));
     for (int i = 0; i < n_in; ++i) {
         W.side[i].out.text.resize(std::max<uint64_t>(1u << 20, guess));
@@ -183,9 +185,10 @@ bool WindowExtract::Impl::grow_named(Win &W, Call &c) {
 // the results of a call that took the window: sizes, tails, the kept-record index, and the text the writer will need
 void WindowExtract::Impl::collect(Win &W, Call &c, mk_codec *codec) {
     if (c.use_members) {
-        if (codec) {
+        if (codec) {  // (frames: no upload, and the cut kernel is timed with the deflate -- z_ms[1] stays 0)
             float ms3[3] = {0, 0, 0};
-            (void)mk_codec_cut_times(codec, nullptr, ms3);
+            if (a.zstd_output) (void)mk_zstd_deflate_info(codec, nullptr, nullptr, ms3), ms3[0] = 0;
+            else (void)mk_codec_cut_times(codec, nullptr, ms3);
             for (int k = 0; k < 3; ++k) W.z_ms[k + 1] = ms3[k];
         }
         uint64_t most = 0, most_ids = 0;
@@ -229,7 +232,8 @@ void WindowExtract::Impl::collect(Win &W, Call &c, mk_codec *codec) {
 }
 
 void WindowExtract::Impl::device_window(Win &W, mk_matcher *m, mk_codec *codec) {
-    // (-z: a window whose written form the device refuses, *status = 2, is called once more for its kept records as stored text)
+    // (-z / --zstd-output: a window whose written form the device refuses, *status = 2, is called once more for its kept records as
+    // stored text)
     for (bool use_members = z_members;; use_members = false) {
         Call c;
         c.use_members = use_members;
@@ -255,8 +259,9 @@ void WindowExtract::Impl::device_window(Win &W, mk_matcher *m, mk_codec *codec) 
             memset(&W.cb, 0, sizeof(W.cb));
             std::fill(W.cnt.begin(), W.cnt.end(), 0);
             const uint32_t format = fastq ? MK_TEXT_FASTQ : MK_TEXT_FASTA;
-            const int rc = use_members ? mk_extract_window_members(m, codec, format, (uint32_t)n_in, c.src, c.mem, lg->active, a.invert_match, c.rec_cap,
-                                                                   &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status)
+            const auto packed = a.zstd_output ? mk_extract_window_frames : mk_extract_window_members;
+            const int rc = use_members ? packed(m, codec, format, (uint32_t)n_in, c.src, c.mem, lg->active, a.invert_match, c.rec_cap,
+                                                &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status)
                                        : mk_extract_window(m, c.any_bgzf ? codec : nullptr, format, (uint32_t)n_in, c.src, lg->active, a.invert_match, c.rec_cap,
                                                            &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status);
             if (rc == MK_E_CAPACITY && attempt < 8 && grow_named(W, c)) continue;  // once more with what was too small grown

@@ -331,8 +331,8 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     bool any_bgzf = false;
     for (int i = 0; i < J.n_in; ++i) any_bgzf = any_bgzf || J.members_input(i);
     const bool logs = a.out_log || a.json_log;
-    J.z_members = a.bgzf_output && !a.host_codec && !a.host_ingest && !a.suppress_output && !(logs && a.invert_match);
-    if (any_bgzf || J.z_members) {  // (a codec per device: BGZF input is inflated, -z output deflated where its window is)
+    J.z_members = (a.bgzf_output || a.zstd_output) && !a.host_codec && !a.host_ingest && !a.suppress_output && !(logs && a.invert_match);
+    if (any_bgzf || J.z_members) {  // (a codec per device: BGZF input is inflated, -z / --zstd-output compressed where its window is)
         for (size_t d = 0; d < N; ++d) {
             mk_codec *c = nullptr;
             mk_check(mk_codec_create(devs[d], &c), "Error setting up the BGZF codec");
@@ -411,6 +411,10 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             fprintf(stderr, "[timing] extract -z on the windows' devices: written form %.1f ms, cut %.1f ms, deflate %.1f ms, download %.1f ms; %llu calls repeated for a larger buffer\n",
                     J.z_ms[0], J.z_ms[1], J.z_ms[2], J.z_ms[3], (unsigned long long)J.z_repeats.load());
     }
+    // (--zstd-output: the library times the cut kernel with the deflate; the frames themselves are counted in the "zstd output" row)
+    if (G.timing && a.zstd_output && J.z_member_windows + J.z_text_windows)
+        fprintf(stderr, "[timing] extract --zstd-output on the windows' devices: %llu windows as frames, %llu as text; written form %.1f ms, cut + deflate %.1f ms, download %.1f ms; %llu calls repeated for a larger buffer\n",
+                (unsigned long long)J.z_member_windows, (unsigned long long)J.z_text_windows, J.z_ms[0], J.z_ms[2], J.z_ms[3], (unsigned long long)J.z_repeats.load());
 }
 
 }  // namespace cli

@@ -38,8 +38,8 @@ struct WindowExtract::Impl {
     uint64_t n_windows = 0;  // (valid once reader_done)
     uint64_t last_head[2] = {0, 0};  // (the reader's)
     std::atomic<uint64_t> rec_cap_seen{0};
-    // -z: the kept records leave the device as BGZF members (mk_extract_window_members) -- not with --host-codec, and not with logs under
-    // -v, whose rows name records that are not kept
+    // -z / --zstd-output: the kept records leave the device as BGZF members (mk_extract_window_members) / zstd frames
+    // (mk_extract_window_frames) -- not with --host-codec, and not with logs under -v, whose rows name records that are not kept
     bool z_members = false;
     // the last window's needs, carried forward as rec_cap_seen is: bytes of members (or of text, for a window that came back as text)
     // and of ids per KiB of window text

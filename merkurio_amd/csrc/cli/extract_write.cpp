@@ -119,7 +119,7 @@ void WindowExtract::Impl::write_window(Win &W, Sink &w1, Sink &w2, const std::st
     tm.mark("window: records out");
 }
 
-// a window of the -z member path: log rows from the packed ids, then per output the members as they are, or -- a window below
+// a window of the -z member path (--zstd-output: frames): log rows from the packed ids, then per output the members as they are, or -- a window below
 // --z-members-from -- the written text, which gathers with its neighbours' as the host writer's would (its record ends are found
 // again: every fourth line end of FASTQ, every header line of FASTA)
 void WindowExtract::Impl::write_members_window(Win &W, Sink **w, const std::string **names, PhaseTimer &tm) {

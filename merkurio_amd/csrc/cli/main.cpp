@@ -43,10 +43,12 @@ void print_help(const char *sub) {
              "  -s, --kmer-seq <SEQ>...      query sequences\n  -f, --kmer-file <PATH>       file with one k-mer per line\n"
              "  -o, --out-fastx <PATH>       output path (extension derived from the input)\n  -r, --reverse-complement     also search reverse complements\n"
              "  -z, --bgzf-output            write the records bgzip'ed, members ending at record ends (output name + .gz; deflated on the GPU, --host-codec: zlib)\n"
-             "      --z-members-from <BYTES> with -z: a window whose kept records take this many bytes or more leaves the GPU as BGZF members [8388608]\n"
+             "      --z-members-from <BYTES> with -z or --zstd-output: a window whose kept records take this many bytes or more leaves the GPU as BGZF members / zstd frames\n"
+             "                               [8388608: measured for -z; for --zstd-output an unmeasured choice, 64-73 frames per launch]\n"
              "      --gzip-window <BYTES>    a .gz input larger than this is inflated on the GPU a window of this many compressed bytes at a time [268435456]\n"
              "      --bzip2-window <BYTES>   a .bz2 input larger than this is decoded on the GPU a window of this many compressed bytes at a time [268435456]\n"
-             "      --zstd-output            write the records as zstd frames ending at record ends (output name + .zst; compressed on the GPU, --host-codec: libzstd level 3; not timed)\n"
+             "      --zstd-output            write the records as zstd frames ending at record ends (output name + .zst; compressed on the GPU where the window lies,\n"
+             "                               --host-codec: libzstd level 3; not timed)\n"
              "      --device-zstd            decode a .zst input on the GPU (default: libzstd on the host; the GPU path has not been timed)\n"
              "      --zstd-window <BYTES>    with --device-zstd: a .zst input of at most this many compressed bytes goes to the GPU in one call [268435456]\n"
              "      --device-xz              decode an .xz input on the GPU, a wave per block (default: liblzma on the host; the GPU path has not been timed)\n"

@@ -162,6 +162,14 @@ void gzip_stream_close(mk_codec *c);
 void bzip2_stream_close(mk_codec *c);
 // ---- zstd_host.cpp: an open zstd stream ends likewise
 void zstd_stream_close(mk_codec *c);
+// zd_frames, zd_kinds and zd_ms back to 0: what mk_zstd_deflate_info reports starts again
+void zstd_deflate_reset(mk_codec *c);
+// d_text[0, n_text) (kPad ZERO bytes behind it) whose records end at d_ends[0, n_ends) (device memory, non-decreasing, the last one =
+// n_text) -> the zstd frames of the cut rule (include/merkurio_hip.h), cut, compressed and packed on stream st in passes, downloaded to
+// out as long as they fit out_cap: *need = the bytes of all of them (> out_cap: the caller reports MK_E_CAPACITY), *frames how many.
+// ADDS to zd_frames, zd_kinds, zd_ms[1] and zd_ms[2].  The caller holds c->mu, with c->device current
+int zstd_deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, uint8_t *out,
+                        uint64_t out_cap, uint64_t *need, uint64_t *frames);
 // ---- xz_host.cpp: an open xz stream ends likewise
 void xz_stream_close(mk_codec *c);
 // ---- bgzf_host.cpp

@@ -254,6 +254,83 @@ void zstd_stream_close(mk_codec *c) {
     D.s.stats = last;
 }
 
+void zstd_deflate_reset(mk_codec *c) {
+    c->zd_frames = 0;
+    for (int k = 0; k < 3; ++k) c->zd_kinds[k] = 0, c->zd_ms[k] = 0;
+}
+
+// d_text[0, n_text) (kPad ZERO bytes behind it: the deflate kernel reads 16 at a time) whose records end at d_ends[0, n_ends) (device
+// memory, non-decreasing, the last one = n_text) -> the frames of the cut rule (include/merkurio_hip.h, mk_zstd_record_cuts), cut,
+// compressed and packed on stream st in passes of frames.  *need = the bytes of all frames, *frames how many.  A pass's frames are
+// downloaded to out as long as everything so far has fitted out_cap: *need > out_cap means out holds only the passes in front of the
+// one that did not fit (the caller reports MK_E_CAPACITY).  ADDS to c->zd_frames, c->zd_kinds and c->zd_ms[1], [2] (cut + deflate +
+// pack, download): a caller with several texts per call (the two sources of a paired window) resets them once (zstd_deflate_reset).
+// The caller holds c->mu and has made c->device current.  (Shared with mk_extract_window_frames, extract_window.cpp: the ends are then
+// the offsets scan of a window's written lengths, where a record that is not kept repeats the end in front of it.)
+int zstd_deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, uint8_t *out,
+                        uint64_t out_cap, uint64_t *need, uint64_t *frames_out) {
+    *need = 0, *frames_out = 0;
+    if (!n_text) return MK_OK;
+    const uint64_t grid64 = (n_text + kZsCutGrid - 1) / kZsCutGrid;
+    if (grid64 >= 0x7FFFFFFFull) return mk::fail(MK_E_UNSUPPORTED, "%llu output frames", (unsigned long long)grid64);
+    const uint32_t n_grid = (uint32_t)grid64;
+    int rc;
+    // the range table: count | kinds[3] | off[n_grid] | len[n_grid]
+    if ((rc = mk::ensure_device(&c->d_cut, &c->cut_cap, 16 + n_grid * 12ull))) return rc;
+    uint32_t *d_count = (uint32_t *)c->d_cut, *d_kinds = d_count + 1;
+    unsigned long long *d_off = (unsigned long long *)((uint8_t *)c->d_cut + 16);
+    uint32_t *d_len = (uint32_t *)(d_off + n_grid);
+    double t0 = now_ms();
+    MKC_HIP(hipMemsetAsync(c->d_cut, 0, 16, st), "hipMemsetAsync");
+    launch_zstd_cuts(d_ends, n_ends, n_text, n_grid, d_off, d_len, d_count, st);
+    uint32_t frames = 0;
+    MKC_HIP(hipGetLastError(), "the cut kernel");
+    MKC_HIP(hipMemcpyAsync(&frames, d_count, 4, hipMemcpyDeviceToHost, st), "download of the frame count");
+    MKC_HIP(hipStreamSynchronize(st), "the cut kernel");
+    if (frames > n_grid || frames + 1 < n_grid) return mk::fail(MK_E_HIP, "the cut kernel reports %u frames of %u grid points", frames, n_grid);
+    c->zd_ms[1] += (float)(now_ms() - t0);
+    // passes of frames; a pass is downloaded as long as everything so far has fitted.  4 096 frames by default: 0.54 GB of slots (131 328 B
+    // each) beside the resident waves' scratch (8 per CU x 1 005 376 B: 2.06 GB on 256 CUs once a pass has that many frames)
+    const uint64_t pass = std::min<uint64_t>(c->deflate_pass_blocks ? c->deflate_pass_blocks : 4096, 0x7FFFFFFFu);
+    uint64_t written = 0;
+    bool fits = true;
+    for (uint64_t f0 = 0; f0 < frames; f0 += pass) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(pass, frames - f0);
+        const uint32_t grid = zstd_deflate_grid(cnt, c->num_cus);
+        const uint64_t bound = std::min<uint64_t>((uint64_t)cnt * kZsBlockMax, n_text) + cnt * 16ull;
+        if ((rc = mk::ensure_device(&c->d_tokens, &c->tokens_cap, (uint64_t)grid * kZsDeflateWaveScratch)) ||
+            (rc = mk::ensure_device(&c->d_slots, &c->slots_cap, (uint64_t)cnt * kZsDeflateSlotBytes)) ||
+            (rc = mk::ensure_device(&c->d_len, &c->len_cap, (cnt + 1) * 4ull)) || (rc = mk::ensure_device(&c->d_off, &c->off_cap, (cnt + 2) * 8ull)) ||
+            (rc = mk::ensure_device(&c->d_out, &c->out_cap, bound)))
+            return rc;
+        uint64_t *d_total = (uint64_t *)c->d_off + cnt;
+        t0 = now_ms();
+        launch_zstd_deflate(d_text, d_off + f0, d_len + f0, cnt, (uint8_t *)c->d_tokens, (uint8_t *)c->d_slots, (uint32_t *)c->d_len, (uint32_t *)(d_total + 1),
+                            d_kinds, grid, st);
+        launch_zstd_pack((const uint8_t *)c->d_slots, (const uint32_t *)c->d_len, (uint64_t *)c->d_off, d_total, cnt, (uint8_t *)c->d_out, st);
+        uint64_t total = 0;
+        MKC_HIP(hipGetLastError(), "zstd deflate kernels");
+        MKC_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st), "download of the size");
+        MKC_HIP(hipStreamSynchronize(st), "zstd deflate on the device");
+        c->zd_ms[1] += (float)(now_ms() - t0);
+        if (total > bound) return mk::fail(MK_E_HIP, "zstd frames exceed their bound (internal error)");
+        fits = fits && written + total <= out_cap;
+        if (fits && total) {  // (st has been waited for: the packed frames are final, whichever stream carries them down)
+            t0 = now_ms();
+            if ((rc = download(c, out + written, c->d_out, total))) return rc;
+            c->zd_ms[2] += (float)(now_ms() - t0);
+        }
+        written += total;
+    }
+    uint32_t kinds[3] = {0, 0, 0};
+    MKC_HIP(hipMemcpyAsync(kinds, d_kinds, 12, hipMemcpyDeviceToHost, st), "download of the block kinds");
+    MKC_HIP(hipStreamSynchronize(st), "download of the block kinds");
+    for (int k = 0; k < 3; ++k) c->zd_kinds[k] += kinds[k];
+    c->zd_frames += frames;
+    *need = written, *frames_out = frames;
+    return MK_OK;
+}
+
 }  // namespace mkz
 
 extern "C" {
@@ -378,72 +455,19 @@ int mk_zstd_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const 
     std::lock_guard<std::mutex> lock(c->mu);
     if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
-    c->zd_frames = 0;
-    for (int k = 0; k < 3; ++k) c->zd_kinds[k] = 0, c->zd_ms[k] = 0;
+    mkz::zstd_deflate_reset(c);
     if (!n) return MK_OK;
-    const uint64_t grid64 = (n + mkz::kZsCutGrid - 1) / mkz::kZsCutGrid;
-    if (grid64 >= 0x7FFFFFFFull) return mk::fail(MK_E_UNSUPPORTED, "%llu output frames", (unsigned long long)grid64);
-    const uint32_t n_grid = (uint32_t)grid64;
     int rc;
-    // the range table: count | kinds[3] | off[n_grid] | len[n_grid]
-    if ((rc = mk::ensure_device(&c->d_in, &c->in_cap, n + mkz::kPad)) || (rc = mk::ensure_device(&c->d_ends, &c->ends_cap, n_rec * 8ull)) ||
-        (rc = mk::ensure_device(&c->d_cut, &c->cut_cap, 16 + n_grid * 12ull)))
-        return rc;
-    uint32_t *d_count = (uint32_t *)c->d_cut, *d_kinds = d_count + 1;
-    unsigned long long *d_off = (unsigned long long *)((uint8_t *)c->d_cut + 16);
-    uint32_t *d_len = (uint32_t *)(d_off + n_grid);
-    double t0 = mkz::now_ms();
+    if ((rc = mk::ensure_device(&c->d_in, &c->in_cap, n + mkz::kPad)) || (rc = mk::ensure_device(&c->d_ends, &c->ends_cap, n_rec * 8ull))) return rc;
+    const double t0 = mkz::now_ms();
     if ((rc = mkz::upload(c, c->d_in, text, n)) || (rc = mkz::upload(c, c->d_ends, (const uint8_t *)rec_end, n_rec * 8ull))) return rc;
     MKC_HIP(hipMemsetAsync((uint8_t *)c->d_in + n, 0, mkz::kPad, c->stream), "hipMemsetAsync");
-    MKC_HIP(hipMemsetAsync(c->d_cut, 0, 16, c->stream), "hipMemsetAsync");
     MKC_HIP(hipStreamSynchronize(c->stream), "upload of the text");
     c->zd_ms[0] = (float)(mkz::now_ms() - t0);
-    t0 = mkz::now_ms();
-    mkz::launch_zstd_cuts((const unsigned long long *)c->d_ends, n_rec, n, n_grid, d_off, d_len, d_count, c->stream);
-    uint32_t frames = 0;
-    MKC_HIP(hipGetLastError(), "the cut kernel");
-    MKC_HIP(hipMemcpyAsync(&frames, d_count, 4, hipMemcpyDeviceToHost, c->stream), "download of the frame count");
-    MKC_HIP(hipStreamSynchronize(c->stream), "the cut kernel");
-    if (frames > n_grid || frames + 1 < n_grid) return mk::fail(MK_E_HIP, "the cut kernel reports %u frames of %u grid points", frames, n_grid);
-    c->zd_ms[1] = (float)(mkz::now_ms() - t0);
-    // passes of frames; a pass is downloaded as long as everything so far has fitted.  4 096 frames by default: 0.54 GB of slots (131 328 B
-    // each) beside the resident waves' scratch (8 per CU x 1 005 376 B: 2.06 GB on 256 CUs once a pass has that many frames)
-    const uint64_t pass = std::min<uint64_t>(c->deflate_pass_blocks ? c->deflate_pass_blocks : 4096, 0x7FFFFFFFu);
-    uint64_t written = 0;
-    bool fits = true;
-    for (uint64_t f0 = 0; f0 < frames; f0 += pass) {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(pass, frames - f0);
-        const uint32_t grid = mkz::zstd_deflate_grid(cnt, c->num_cus);
-        const uint64_t bound = std::min<uint64_t>((uint64_t)cnt * mkz::kZsBlockMax, n) + cnt * 16ull;
-        if ((rc = mk::ensure_device(&c->d_tokens, &c->tokens_cap, (uint64_t)grid * mkz::kZsDeflateWaveScratch)) ||
-            (rc = mk::ensure_device(&c->d_slots, &c->slots_cap, (uint64_t)cnt * mkz::kZsDeflateSlotBytes)) ||
-            (rc = mk::ensure_device(&c->d_len, &c->len_cap, (cnt + 1) * 4ull)) || (rc = mk::ensure_device(&c->d_off, &c->off_cap, (cnt + 2) * 8ull)) ||
-            (rc = mk::ensure_device(&c->d_out, &c->out_cap, bound)))
-            return rc;
-        uint64_t *d_total = (uint64_t *)c->d_off + cnt;
-        t0 = mkz::now_ms();
-        mkz::launch_zstd_deflate((const uint8_t *)c->d_in, d_off + f0, d_len + f0, cnt, (uint8_t *)c->d_tokens, (uint8_t *)c->d_slots, (uint32_t *)c->d_len,
-                                 (uint32_t *)(d_total + 1), d_kinds, grid, c->stream);
-        mkz::launch_zstd_pack((const uint8_t *)c->d_slots, (const uint32_t *)c->d_len, (uint64_t *)c->d_off, d_total, cnt, (uint8_t *)c->d_out, c->stream);
-        uint64_t total = 0;
-        MKC_HIP(hipGetLastError(), "zstd deflate kernels");
-        MKC_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream), "download of the size");
-        MKC_HIP(hipStreamSynchronize(c->stream), "zstd deflate on the device");
-        c->zd_ms[1] += (float)(mkz::now_ms() - t0);
-        if (total > bound) return mk::fail(MK_E_HIP, "mk_zstd_deflate_records: frames exceed their bound (internal error)");
-        fits = fits && written + total <= out_cap;
-        if (fits && total) {
-            t0 = mkz::now_ms();
-            if ((rc = mkz::download(c, out + written, c->d_out, total))) return rc;
-            c->zd_ms[2] += (float)(mkz::now_ms() - t0);
-        }
-        written += total;
-    }
-    MKC_HIP(hipMemcpyAsync(c->zd_kinds, d_kinds, 12, hipMemcpyDeviceToHost, c->stream), "download of the block kinds");
-    MKC_HIP(hipStreamSynchronize(c->stream), "download of the block kinds");
-    c->zd_frames = frames;
-    *out_len = written, *n_frames = frames;
-    if (written > out_cap) return mk::fail(MK_E_CAPACITY, "mk_zstd_deflate_records: the frames take %llu bytes, room for %llu", (unsigned long long)written, (unsigned long long)out_cap);
+    uint64_t need = 0;
+    if ((rc = mkz::zstd_deflate_ranges(c, c->stream, (const uint8_t *)c->d_in, n, (const unsigned long long *)c->d_ends, n_rec, out, out_cap, &need, n_frames))) return rc;
+    *out_len = need;
+    if (need > out_cap) return mk::fail(MK_E_CAPACITY, "mk_zstd_deflate_records: the frames take %llu bytes, room for %llu", (unsigned long long)need, (unsigned long long)out_cap);
     return MK_OK;
     MK_ABI_END
 }

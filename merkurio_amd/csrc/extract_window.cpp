@@ -1,6 +1,6 @@
 // extract_window.cpp -- `extract` on text windows that stay on the device: the window steps of window_ingest.cpp, then the extract loop
 // as in mk_extract_single / mk_extract_paired, then the kept records' way back -- their stored text (window_kept) or BGZF members of
-// their written form (window_members)
+// their written form, or zstd frames of it (window_members)
 #include <mutex>
 
 #include "device_loop.hpp"
@@ -10,6 +10,10 @@
 using namespace mk;
 
 namespace {
+
+// what the written text of a window's kept records leaves the device as
+enum class Packed { kMembers, kFrames };  // BGZF members (mk_extract_window_members), zstd frames (mk_extract_window_frames)
+const char *entry_name(Packed kind) { return kind == Packed::kFrames ? "mk_extract_window_frames" : "mk_extract_window_members"; }
 
 // scratch of a kept-records step in m->d_aux: `arrays` u32 arrays of n + 2 entries from *d_len on | a spare word | the tile sums of
 // the offsets scan; room for the offsets themselves in m->d_off
@@ -67,11 +71,11 @@ int window_kept(mk_matcher *m, WindowSide &W, uint64_t n, const uint8_t *d_keep,
     return pack_download(m, S.kept, total, st, "copy of the kept records failed");
 }
 
-// the kept records of side W in their written form (include/merkurio_hip.h), packed on the device, then cut and deflated there:
-// only the members come down -- or, below S.text_below bytes, the text.  With logging the ids of the kept records follow, packed by
-// the sequences' gather kernel.  *status = 2: a FASTA record the device does not write (nothing has been written to S's buffers).
-// The time of the codec's steps is ADDED to cut_ms / *cut_members (a paired window has two sides).
-int window_members(mk_matcher *m, mk_codec *codec, uint32_t format, WindowSide &W, uint64_t n, const uint8_t *d_keep, const std::vector<uint32_t> &rs,
+// the kept records of side W in their written form (include/merkurio_hip.h), packed on the device, then cut and compressed there --
+// BGZF members or zstd frames by `kind`, the one place the two differ: only they come down -- or, below S.text_below bytes, the text.
+// With logging the ids of the kept records follow, packed by the sequences' gather kernel.  *status = 2: a FASTA record the device does not write (nothing has been written to S's buffers).
+// The time of the codec's steps is ADDED to cut_ms / *cut_members (a paired window has two sides); frames: to the handle's zd_* fields.
+int window_members(mk_matcher *m, mk_codec *codec, Packed kind, uint32_t format, WindowSide &W, uint64_t n, const uint8_t *d_keep, const std::vector<uint32_t> &rs,
                    const uint8_t *keep_host, int logging, mk_window_members &S, DeviceLoop &dl, float cut_ms[3], uint64_t *cut_members, uint32_t *status) {
     hipStream_t st = dl.st;
     if (!n) return MK_OK;
@@ -150,11 +154,16 @@ int window_members(mk_matcher *m, mk_codec *codec, uint32_t format, WindowSide &
             if (hipStreamSynchronize(st) != hipSuccess) return fail(MK_E_HIP, "gather of the written records failed");
             // the offsets scan is the record-end table: off[r + 1] = where record r's written form ends (a record that is not kept
             // repeats the end in front of it)
-            if ((rc = mkz::deflate_ranges(codec, st, m->d_seq, total, d_off + 1, n, nullptr, 0, S.members, S.members_cap, &need, &members))) return rc;
-            for (int k = 0; k < 3; ++k) cut_ms[k] += codec->cut_ms[k];
-            *cut_members += members;
+            if (kind == Packed::kFrames) {
+                if ((rc = mkz::zstd_deflate_ranges(codec, st, m->d_seq, total, d_off + 1, n, S.members, S.members_cap, &need, &members))) return rc;
+            } else {
+                if ((rc = mkz::deflate_ranges(codec, st, m->d_seq, total, d_off + 1, n, nullptr, 0, S.members, S.members_cap, &need, &members))) return rc;
+                for (int k = 0; k < 3; ++k) cut_ms[k] += codec->cut_ms[k];
+                *cut_members += members;
+            }
             S.n_member_bytes = need, S.n_members = members;
-            if (need > S.members_cap) cap_rc = fail(MK_E_CAPACITY, "the members of the kept records take %llu bytes", (unsigned long long)need);
+            if (need > S.members_cap)
+                cap_rc = fail(MK_E_CAPACITY, "the %s of the kept records take %llu bytes", kind == Packed::kFrames ? "frames" : "members", (unsigned long long)need);
         }
     }
     kernel_ms();
@@ -173,8 +182,9 @@ int window_members(mk_matcher *m, mk_codec *codec, uint32_t format, WindowSide &
     return cap_rc;
 }
 
-// the body of mk_extract_window (mem == nullptr) and mk_extract_window_members (one mk_window_members per source)
-int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem, int logging,
+// the body of mk_extract_window (mem == nullptr) and of mk_extract_window_members / mk_extract_window_frames (one mk_window_members per
+// source; kind: which of the two)
+int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem, Packed kind, int logging,
                         int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
                         uint32_t *counts, uint32_t *status) {
     if (!m || !src || !n_rec_out || !status || !c || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
@@ -194,13 +204,20 @@ int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_
         mk_window_members &M = mem[k];
         M.n_member_bytes = M.n_members = M.n_written = M.n_kept = M.n_id_bytes = 0, M.as_text = 0, M.written_ms = 0;
         if ((M.members_cap && !M.members) || (M.ids_cap && !M.ids) || (logging && !M.id_end))
-            return fail(MK_E_INVALID_ARG, "mk_extract_window_members: a size without its buffer in source %u", k);
-        if (S.kept || S.kept_cap) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the kept records leave as members, not as source %u's kept text", k);
+            return fail(MK_E_INVALID_ARG, "%s: a size without its buffer in source %u", entry_name(kind), k);
+        if (S.kept || S.kept_cap)
+            return fail(MK_E_INVALID_ARG, "%s: the kept records leave as members or frames, not as source %u's kept text", entry_name(kind), k);
     }
     if (mem) {
-        if (!codec) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the members need a codec handle");
-        if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: the codec and the matcher are on different devices");
-        if (logging && invert) return fail(MK_E_INVALID_ARG, "mk_extract_window_members: with logging and invert the rows name records that are not kept");
+        if (!codec) return fail(MK_E_INVALID_ARG, "%s: the members or frames need a codec handle", entry_name(kind));
+        if (logging && invert) return fail(MK_E_INVALID_ARG, "%s: with logging and invert the rows name records that are not kept", entry_name(kind));
+        if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "%s: the codec and the matcher are on different devices", entry_name(kind));
+        if (kind == Packed::kFrames) {  // (the frame writer's rule, as mk_zstd_deflate_records has it; what it reports starts again)
+            std::lock_guard<std::mutex> lock(codec->mu);
+            if (codec->stream_open())
+                return fail(MK_E_INVALID_ARG, "mk_extract_window_frames: the codec handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+            mkz::zstd_deflate_reset(codec);
+        }
     }
     MK_ABI_BEGIN
     if (hipSetDevice(m->device) != hipSuccess) return fail(MK_E_HIP, "hipSetDevice failed");
@@ -305,13 +322,13 @@ int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_
         float cut_ms[3] = {0, 0, 0};
         uint64_t cut_members = 0;
         for (uint32_t k = 0; k < n_sources && !*status; ++k) {
-            if (mem) rc = window_members(m, codec, format, W[k], n, m->d_flags2, rs[k], keep, logging, mem[k], dl, cut_ms, &cut_members, status);
+            if (mem) rc = window_members(m, codec, kind, format, W[k], n, m->d_flags2, rs[k], keep, logging, mem[k], dl, cut_ms, &cut_members, status);
             else if (src[k].kept || src[k].kept_cap) rc = window_kept(m, W[k], n, m->d_flags2, rs[k], keep, src[k], dl);
             else continue;
             if (rc == MK_E_CAPACITY) cap_rc = rc;  // (every source reports its needs before the call returns)
             else if (rc) return rc;
         }
-        if (mem) {
+        if (mem && kind == Packed::kMembers) {
             std::lock_guard<std::mutex> lock(codec->mu);
             for (int k = 0; k < 3; ++k) codec->cut_ms[k] = cut_ms[k];
             codec->cut_members = cut_members;
@@ -335,14 +352,21 @@ extern "C" {
 int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, int logging, int invert,
                       uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
                       uint32_t *counts, uint32_t *status) {
-    return extract_window_body(m, codec, format, n_sources, src, nullptr, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+    return extract_window_body(m, codec, format, n_sources, src, nullptr, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 int mk_extract_window_members(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem,
                               int logging, int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap,
                               uint64_t *n_rows, mk_counters *c, uint32_t *counts, uint32_t *status) {
     if (!mem) return fail(MK_E_INVALID_ARG, "null argument");
-    return extract_window_body(m, codec, format, n_sources, src, mem, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+    return extract_window_body(m, codec, format, n_sources, src, mem, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+}
+
+int mk_extract_window_frames(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem,
+                             int logging, int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap,
+                             uint64_t *n_rows, mk_counters *c, uint32_t *counts, uint32_t *status) {
+    if (!mem) return fail(MK_E_INVALID_ARG, "null argument");
+    return extract_window_body(m, codec, format, n_sources, src, mem, Packed::kFrames, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 // (v4 / v5 entry points, kept: one FASTQ source whose window ends at a record end / one bgzip'ed FASTQ source with a head)

@@ -59,7 +59,7 @@ EXPORTS = [
     "mk_zstd_stream_begin", "mk_zstd_stream_next", "mk_zstd_stream_info", "mk_zstd_stream_end", "mk_codec_set_zstd_text_cap",
     "mk_xz_stream_begin", "mk_xz_stream_next", "mk_xz_stream_info", "mk_xz_stream_end", "mk_codec_set_xz_text_cap",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
-    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members",
+    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members", "mk_extract_window_frames",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
@@ -376,6 +376,7 @@ def load(build_if_missing=True):
     L.mk_extract_window_members.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64,
                                             C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Counters),
                                             C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mk_extract_window_frames.argtypes = L.mk_extract_window_members.argtypes  # (the same arguments: zstd frames where members are)
     L.mk_bgzf_deflate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]
     L.mk_codec_cut_times.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
@@ -852,7 +853,15 @@ class Matcher:
         -> extract_window's dict (sources: n_window, n_used, n_rec_seen, rec_start, tail) plus per source
            members (bytes: the members, or the text when as_text), n_members, n_written, n_kept, as_text, ids (bytes), id_end (list),
            written_ms"""
-        L = load()
+        return self._extract_window_packed(load().mk_extract_window_members, sources, codec, fmt, logging, invert, text_below, caps)
+
+    def extract_window_frames(self, sources, codec, fmt=MK_TEXT_FASTQ, logging=False, invert=False, text_below=0, caps=None):
+        """mk_extract_window_frames: the same call with zstd frames where the members are (the frames of Codec.zstd_records on the
+        written text and its record ends).  Arguments and the dictionary as extract_window_members: `members` holds the frames back to
+        back, n_members is how many there are; Codec.zstd_records_info reports the call's frames, block kinds and milliseconds."""
+        return self._extract_window_packed(load().mk_extract_window_frames, sources, codec, fmt, logging, invert, text_below, caps)
+
+    def _extract_window_packed(self, entry, sources, codec, fmt, logging, invert, text_below, caps):
         n_src = len(sources)
         arr, hold, bound = self._window_sources(sources)
         cap = max(1, bound // (2 if fmt == MK_TEXT_FASTA else 8) + 2)
@@ -874,8 +883,8 @@ class Matcher:
         rows = np.zeros(4096, dtype=ROW_DTYPE)
         for _ in range(8):
             c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = L.mk_extract_window_members(self._h, codec._h if codec else None, fmt, n_src, arr, mem, int(logging), int(invert), cap, C.byref(n_rec),
-                                             keep.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows), C.byref(c2), k2.ctypes.data, C.byref(status))
+            rc = entry(self._h, codec._h if codec else None, fmt, n_src, arr, mem, int(logging), int(invert), cap, C.byref(n_rec),
+                       keep.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows), C.byref(c2), k2.ctypes.data, C.byref(status))
             if rc == MK_E_CAPACITY and caps is None:
                 grown = False
                 if n_rows.value > len(rows):
