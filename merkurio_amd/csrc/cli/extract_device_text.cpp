@@ -42,9 +42,10 @@ struct DeviceText : Source {
     }
 };
 
-// What differs between the two formats the device decodes window by window: the library calls, and the wording of the [timing] rows
+// What differs between the formats the device decodes window by window: the library calls, and the wording of the [timing] rows
 struct StreamCalls {
     const char *format, *host_library;  // "gzip" / "zlib"
+    int (*begin)(mk_codec *, const uint8_t *file, uint64_t n, uint64_t window_bytes, uint32_t *taken);
     int (*next)(mk_codec *, uint64_t *text_bytes, uint32_t *state);
     int (*end)(mk_codec *);
     // the stream's own figures: compressed bytes consumed, what it counted, its phases and its peak
@@ -53,6 +54,9 @@ struct StreamCalls {
     void (*phase_ms)(mk_codec *, float ms[6]);
     const char *phase_names[6];
     bool discard_kept_on_error = false;  // the host library's error behind a hand-back leaves no kept records' file (Gate::discard_kept)
+    void (*knobs)(mk_codec *, const InputFile &) = nullptr;  // the input's options that the stream takes when it begins
+    std::string (*why_not)(mk_codec *) = nullptr;           // what the NOT taken row says of a refusal at _begin (the codec may be null)
+    bool needs_codec = false;  // no codec handle is the run's error, not the host library's file
 };
 
 template <class... A>
@@ -62,7 +66,7 @@ std::string fmt(const char *f, A... a) {
     return buf;
 }
 
-const StreamCalls kGzipCalls = {"gzip", "zlib", mk_gzip_stream_next, mk_gzip_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+const StreamCalls kGzipCalls = {"gzip", "zlib", mk_gzip_stream_begin, mk_gzip_stream_next, mk_gzip_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
                                     mk_gzip_stream_stats st;
                                     memset(&st, 0, sizeof(st));
                                     (void)mk_gzip_stream_info(c, &st);
@@ -71,8 +75,8 @@ const StreamCalls kGzipCalls = {"gzip", "zlib", mk_gzip_stream_next, mk_gzip_str
                                                   (unsigned long long)st.windows_grown, (unsigned long long)st.rounds_repeated);
                                     *phases = fmt("upload %.1f, block search %.1f, pieces %.1f, resolution %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
                                                   st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
-                                }, nullptr, {}};
-const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_next, mk_bzip2_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+                                }, nullptr, {}, false, nullptr, nullptr, true};
+const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_begin, mk_bzip2_stream_next, mk_bzip2_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
                                      mk_bzip2_stream_stats st;
                                      memset(&st, 0, sizeof(st));
                                      (void)mk_bzip2_stream_info(c, &st);
@@ -82,7 +86,7 @@ const StreamCalls kBzip2Calls = {"bzip2", "libbz2", mk_bzip2_stream_next, mk_bzi
                                      *phases = fmt("upload %.1f, marker search %.1f, block decode %.1f, text %.1f, CRC %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2],
                                                    st.ms[3], st.ms[4], (unsigned long long)st.peak_device_bytes);
                                  }, nullptr, {}};
-const StreamCalls kZstdCalls = {"zstd", "libzstd", mk_zstd_stream_next, mk_zstd_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+const StreamCalls kZstdCalls = {"zstd", "libzstd", mk_zstd_stream_begin, mk_zstd_stream_next, mk_zstd_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
                                     mk_zstd_stream_stats st;
                                     memset(&st, 0, sizeof(st));
                                     (void)mk_zstd_stream_info(c, &st);
@@ -98,7 +102,7 @@ const StreamCalls kZstdCalls = {"zstd", "libzstd", mk_zstd_stream_next, mk_zstd_
                                     for (int k = 0; k < 6; ++k) ms[k] = st.ms[k];
                                 }, {"upload", "tables + entropy decode", "walk + scans", "execution", "cross-block rounds", "checksum"}};
 
-const StreamCalls kXzCalls = {"xz", "liblzma", mk_xz_stream_next, mk_xz_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
+const StreamCalls kXzCalls = {"xz", "liblzma", mk_xz_stream_begin, mk_xz_stream_next, mk_xz_stream_end, [](mk_codec *c, uint64_t *consumed, std::string *counts, std::string *phases) {
                                   mk_xz_stream_stats st;
                                   memset(&st, 0, sizeof(st));
                                   (void)mk_xz_stream_info(c, &st);
@@ -107,7 +111,15 @@ const StreamCalls kXzCalls = {"xz", "liblzma", mk_xz_stream_next, mk_xz_stream_e
                                                 (unsigned long long)st.windows, (unsigned long long)st.blocks, (unsigned long long)st.streams, (unsigned long long)st.largest_block_text, (int)st.status);
                                   *phases = fmt("upload %.1f, decode %.1f, check %.1f, calls %.1f ms; peak %llu device bytes", st.ms[0], st.ms[1], st.ms[2], st.ms[3],
                                                 (unsigned long long)st.peak_device_bytes);
-                              }, nullptr, {}, true};
+                              }, nullptr, {}, true, [](mk_codec *c, const InputFile &f) {
+                                  if (f.xz_spread) (void)mk_codec_set_xz_spread(c, f.xz_spread);
+                                  if (f.xz_text_cap) (void)mk_codec_set_xz_text_cap(c, f.xz_text_cap);
+                              }, [](mk_codec *c) {
+                                  mk_xz_stream_stats st;
+                                  memset(&st, 0, sizeof(st));
+                                  if (c) (void)mk_xz_stream_info(c, &st);
+                                  return fmt("status %d, largest block %llu text bytes; ", (int)st.status, (unsigned long long)st.largest_block_text);
+                              }};
 
 // A file the device decodes window by window (mk_gzip_stream_*, mk_bzip2_stream_*, mk_zstd_stream_*, mk_xz_stream_*).  Window w of the stream lies in text buffer w & 1
 struct DeviceStream : DeviceText {
@@ -214,23 +226,22 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
     uint64_t text_bytes = 0;
     uint32_t taken = 0;
     // (the codec rule: whatever a call reports other than "taken" -- an error of the device included -- the file is the host library's)
-    if (xz && f.xz_stream) {
-        // --xz-stream, more compressed bytes than --xz-window: decoded window by window as the text windows reach it, windows of whole
-        // blocks planned when the stream begins (stream_window = 0: bounded by the text cap only); what the stream does not take -- at
-        // its begin or from whichever window on -- is liblzma's, which also words the error
-        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
+    // A stream: --xz-stream / --zstd-stream, or a gzip or bzip2 file of more compressed bytes than one window.  It is decoded window by
+    // window as the text windows reach it, device memory bounded by the window (xz: windows of whole blocks planned when the stream
+    // begins; stream_window = 0: bounded by the text cap only).  What the stream does not take -- at its begin or from whichever window
+    // on -- is the host library's, which also words the error
+    const StreamCalls *sc = xz ? (f.xz_stream ? &kXzCalls : nullptr) : zs ? (f.zstd_stream ? &kZstdCalls : nullptr) : n <= stream_window ? nullptr : bz ? &kBzip2Calls : &kGzipCalls;
+    if (sc) {
+        const int made = mk_codec_create(device, &codec);
+        if (sc->needs_codec) mk_check(made, "Error setting up the gzip codec");
+        if (made != MK_OK) codec = nullptr;
         t0 = PhaseTimer::now();
-        if (codec && f.xz_spread) (void)mk_codec_set_xz_spread(codec, f.xz_spread);
-        if (codec && f.xz_text_cap) (void)mk_codec_set_xz_text_cap(codec, f.xz_text_cap);
-        if (codec && mk_xz_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
-        if (taken) return std::unique_ptr<Source>(new DeviceStream(kXzCalls, codec, f, i, g, t0));
-        if (g.timing) {
-            mk_xz_stream_stats st;
-            memset(&st, 0, sizeof(st));
-            if (codec) (void)mk_xz_stream_info(codec, &st);
-            fprintf(stderr, "[timing]   xz input %d on the device, window by window: NOT taken (status %d, largest block %llu text bytes; liblzma reads it)\n", i, (int)st.status,
-                    (unsigned long long)st.largest_block_text);
-        }
+        if (codec && sc->knobs) sc->knobs(codec, f);
+        if (codec && sc->begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
+        if (taken) return std::unique_ptr<Source>(new DeviceStream(*sc, codec, f, i, g, t0));
+        if (g.timing)
+            fprintf(stderr, "[timing]   %s input %d on the device, window by window: NOT taken (%s%s reads it)\n", sc->format, i, sc->why_not ? sc->why_not(codec).c_str() : "",
+                    sc->host_library);
     } else if (xz) {
         // --device-xz: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- a file of one huge
         // block (the spread rule), anything else it refuses, a damaged file, no room -- and a file of more compressed bytes than
@@ -252,14 +263,6 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
             fprintf(stderr, "[timing]   xz input %d: NOT taken by the device after %.3f s (%s; liblzma reads it)\n", i, PhaseTimer::now() - t0,
                     n > stream_window ? "more compressed bytes than --xz-window" : why);
         }
-    } else if (zs && f.zstd_stream) {
-        // --zstd-stream, more than one zstd window: decoded window by window as the text windows reach it, device memory bounded by
-        // the window; what the stream does not take, from whichever window on, is libzstd's
-        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
-        t0 = PhaseTimer::now();
-        if (codec && mk_zstd_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
-        if (taken) return std::unique_ptr<Source>(new DeviceStream(kZstdCalls, codec, f, i, g, t0));
-        if (g.timing) fprintf(stderr, "[timing]   zstd input %d on the device, window by window: NOT taken (libzstd reads it)\n", i);
     } else if (zs) {
         // --device-zstd: its blocks are decoded on the device, a wave each, in one call.  What the call does not take -- anything it
         // refuses, a damaged file, no room -- and a file of more compressed bytes than --zstd-window, libzstd reads whole, as
@@ -277,14 +280,6 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
             fprintf(stderr, "[timing]   zstd input %d: NOT taken by the device after %.3f s (%s; libzstd reads it)\n", i, PhaseTimer::now() - t0,
                     n > stream_window ? "more compressed bytes than --zstd-window" : "handed back");
         }
-    } else if (bz && n > stream_window) {
-        // more than one bzip2 window: decoded window by window as the text windows reach it, device memory bounded by the window; what
-        // the stream does not take, from whichever window on, is libbz2's
-        if (mk_codec_create(device, &codec) != MK_OK) codec = nullptr;
-        t0 = PhaseTimer::now();
-        if (codec && mk_bzip2_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
-        if (taken) return std::unique_ptr<Source>(new DeviceStream(kBzip2Calls, codec, f, i, g, t0));
-        if (g.timing) fprintf(stderr, "[timing]   bzip2 input %d on the device, window by window: NOT taken (libbz2 reads it)\n", i);
     } else if (bz) {
         // its blocks are decoded on the device, a wave each.  What the call does not take -- anything it refuses, a damaged file, no room
         // -- libbz2 reads whole, as under --host-codec, and words the error
@@ -299,14 +294,6 @@ std::unique_ptr<Source> take_on_device(InputFile &f, int i, int device, uint64_t
         } else if (g.timing) {
             fprintf(stderr, "[timing]   bzip2 input %d: NOT taken by the device after %.3f s (libbz2 reads it)\n", i, PhaseTimer::now() - t0);
         }
-    } else if (n > stream_window) {
-        // more than one gzip window: inflated window by window as the text windows reach it; what the stream does not take, from
-        // whichever window on, is zlib's
-        mk_check(mk_codec_create(device, &codec), "Error setting up the gzip codec");
-        t0 = PhaseTimer::now();
-        if (mk_gzip_stream_begin(codec, z, n, stream_window, &taken) != MK_OK) taken = 0;
-        if (taken) return std::unique_ptr<Source>(new DeviceStream(kGzipCalls, codec, f, i, g, t0));
-        if (g.timing) fprintf(stderr, "[timing]   gzip input %d on the device, window by window: NOT taken (zlib reads it)\n", i);
     } else {
         // ONE DEFLATE stream, which zlib walks from the front at 0.5 GB/s -- the device inflates it in parallel pieces and keeps the
         // text; a file of several members (`cat a.gz b.gz`) goes to mk_gzip_members_inflate_device, which cuts all of them into pieces

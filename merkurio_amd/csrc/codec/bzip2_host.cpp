@@ -13,8 +13,8 @@
 
 #include "../host_common.h"
 #include "bzip2_chain.hpp"
-#include "codec_internal.h"
 #include "codec_kernels.h"
+#include "codec_stream.hpp"
 
 using mkz::elapsed;
 using mkz::now_ms;
@@ -24,30 +24,6 @@ namespace {
 
 constexpr uint32_t kBzMaxMarkers = 1u << 20;  // candidates of one file; more = not taken (900 kB blocks: 1 Mi of them are ~1 TB of text)
 constexpr uint64_t kBzMaxPassBlocks = 4096;
-
-// a device error on this path hands the file back (*taken stays 0, a stream's state 2), it is not the caller's error.  NOTE: the
-// macro RETURNS false from the function that uses it.  Kernels of the pass may still be in flight then; nothing is waited for here,
-// because the buffers they use are freed with hipFree, which waits for the device first (the one-shot call's wrapper, right after;
-// a stream when it closes, behind a wait for the handle's stream)
-#define MKB_HIP(call)                      \
-    do {                                   \
-        if ((call) != hipSuccess) {        \
-            (void)hipGetLastError();       \
-            return false;                  \
-        }                                  \
-    } while (0)
-
-// `need` bytes in buffers of which the handle holds `held` already: what has to be added fits into half of the free memory
-bool bz_room(uint64_t need, uint64_t held) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    return need <= held || need - held <= free_b / 2;
-}
-bool bz_ensure(void **p, size_t *cap, size_t need) {
-    if (mk::ensure_device(p, cap, need) == MK_OK) return true;
-    (void)hipGetLastError();
-    return false;
-}
 
 // the device tables of B blocks behind each other: bit | pre_off | text_off | text_len (u64) | reports | level | crc (u32)
 struct BzTab {
@@ -73,26 +49,26 @@ uint64_t bz_slot_bytes(uint32_t level) { return mkz::kBzSelBytes + 4 * ((level *
 bool bz_upload_and_search(mk_codec *c, const uint8_t *up, uint64_t n, uint32_t cap, std::vector<mkz::BzMarker> &markers, float *ms) {
     double t0 = now_ms();
     const uint64_t n_words = (n + mkz::kBzStreamPad + 3) / 4;
-    if (!bz_room(n_words * 4 + cap * 8ull + 64, c->gz_in_cap + c->gz_tab_cap) || !bz_ensure(&c->d_gz_in, &c->gz_in_cap, n_words * 4) ||
-        !bz_ensure(&c->d_gz_tab, &c->gz_tab_cap, cap * 8ull + 64))
+    if (!mkz::room(n_words * 4 + cap * 8ull + 64, c->gz_in_cap + c->gz_tab_cap) || !mkz::ensure_quiet(&c->d_gz_in, &c->gz_in_cap, n_words * 4) ||
+        !mkz::ensure_quiet(&c->d_gz_tab, &c->gz_tab_cap, cap * 8ull + 64))
         return false;
     if (upload(c, c->d_gz_in, up, n)) return false;
-    MKB_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n, 0, n_words * 4 - n, c->stream));
-    MKB_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n, 0, n_words * 4 - n, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     ms[0] += (float)(now_ms() - t0);
     t0 = now_ms();
     unsigned long long *d_markers = (unsigned long long *)c->d_gz_tab;
     uint32_t *d_count = (uint32_t *)(d_markers + cap);
-    MKB_HIP(hipMemsetAsync(d_count, 0, 4, c->stream));
+    MKZ_HIP(hipMemsetAsync(d_count, 0, 4, c->stream), false);
     mkz::launch_bz2_markers((const uint8_t *)c->d_gz_in, n, n_words, d_markers, cap, d_count, c->num_cus, c->stream);
-    MKB_HIP(hipGetLastError());
+    MKZ_HIP(hipGetLastError(), false);
     uint32_t count = 0;
-    MKB_HIP(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, c->stream));
-    MKB_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     if (count > cap) return false;
     std::vector<unsigned long long> raw(count);
-    if (count) MKB_HIP(hipMemcpyAsync(raw.data(), d_markers, count * 8ull, hipMemcpyDeviceToHost, c->stream));
-    MKB_HIP(hipStreamSynchronize(c->stream));
+    if (count) MKZ_HIP(hipMemcpyAsync(raw.data(), d_markers, count * 8ull, hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     std::sort(raw.begin(), raw.end());
     markers.resize(count);
     for (uint32_t k = 0; k < count; ++k) markers[k] = mkz::BzMarker{raw[k] >> 1, (uint32_t)(raw[k] & 1u)};
@@ -111,7 +87,7 @@ bool bz_decode(mk_codec *c, uint64_t n, size_t B, const unsigned long long *bit,
     *done = 0, *n_tab = 0;
     const uint64_t n_words = (n + mkz::kBzStreamPad + 3) / 4;
     size_t free_b = 0, total_b = 0;
-    MKB_HIP(hipMemGetInfo(&free_b, &total_b));
+    MKZ_HIP(hipMemGetInfo(&free_b, &total_b), false);
     const uint64_t budget = free_b / 2 + c->gz_sym_cap + c->gz_ctx_cap;  // (what the handle holds of them already is not asked for again)
     std::vector<unsigned long long> pre_off(B);
     uint64_t pre_total = 0, slot_bytes = 0;
@@ -125,27 +101,27 @@ bool bz_decode(mk_codec *c, uint64_t n, size_t B, const unsigned long long *bit,
     B = fit, *n_tab = fit;
     uint64_t pass = c->bz_pass_blocks ? c->bz_pass_blocks : std::max<uint64_t>(1, (budget - pre_total) / 2 / slot_bytes);
     pass = std::min<uint64_t>(std::min<uint64_t>(pass, B), kBzMaxPassBlocks);
-    if (!bz_ensure(&c->d_gz_tab, &c->gz_tab_cap, BzTab::bytes(B)) || !bz_ensure(&c->d_gz_sym, &c->gz_sym_cap, pre_total + 64) ||
-        !bz_ensure(&c->d_gz_ctx, &c->gz_ctx_cap, pass * slot_bytes))
+    if (!mkz::ensure_quiet(&c->d_gz_tab, &c->gz_tab_cap, BzTab::bytes(B)) || !mkz::ensure_quiet(&c->d_gz_sym, &c->gz_sym_cap, pre_total + 64) ||
+        !mkz::ensure_quiet(&c->d_gz_ctx, &c->gz_ctx_cap, pass * slot_bytes))
         return false;
     const BzTab t(c->d_gz_tab, B);
-    MKB_HIP(hipMemcpyAsync(t.bit, bit, B * 8, hipMemcpyHostToDevice, c->stream));
-    MKB_HIP(hipMemcpyAsync(t.pre, pre_off.data(), B * 8, hipMemcpyHostToDevice, c->stream));
-    MKB_HIP(hipMemcpyAsync(t.level, level, B * 4, hipMemcpyHostToDevice, c->stream));
+    MKZ_HIP(hipMemcpyAsync(t.bit, bit, B * 8, hipMemcpyHostToDevice, c->stream), false);
+    MKZ_HIP(hipMemcpyAsync(t.pre, pre_off.data(), B * 8, hipMemcpyHostToDevice, c->stream), false);
+    MKZ_HIP(hipMemcpyAsync(t.level, level, B * 4, hipMemcpyHostToDevice, c->stream), false);
     rep.assign(B, mkz::Bz2Block{}), text_len.assign(B, 0);
     for (size_t b0 = 0; b0 < B; b0 += pass) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(pass, B - b0);
-        MKB_HIP(hipEventRecord(c->ev[0], c->stream));
+        MKZ_HIP(hipEventRecord(c->ev[0], c->stream), false);
         mkz::launch_bz2_decode((const uint8_t *)c->d_gz_in, n, n_words, t.bit, t.level, t.pre, (uint8_t *)c->d_gz_sym, (uint8_t *)c->d_gz_ctx, slot_bytes, (uint32_t)b0, cnt,
                                t.rep, c->stream);
-        MKB_HIP(hipGetLastError());
-        MKB_HIP(hipEventRecord(c->ev[1], c->stream));
+        MKZ_HIP(hipGetLastError(), false);
+        MKZ_HIP(hipEventRecord(c->ev[1], c->stream), false);
         mkz::launch_bz2_walk(t.pre, t.level, (uint8_t *)c->d_gz_sym, (const uint8_t *)c->d_gz_ctx, slot_bytes, (uint32_t)b0, cnt, t.rep, t.tlen, c->stream);
-        MKB_HIP(hipGetLastError());
-        MKB_HIP(hipEventRecord(c->ev[2], c->stream));
-        MKB_HIP(hipMemcpyAsync(rep.data() + b0, t.rep + b0, cnt * sizeof(mkz::Bz2Block), hipMemcpyDeviceToHost, c->stream));
-        MKB_HIP(hipMemcpyAsync(text_len.data() + b0, t.tlen + b0, cnt * 8ull, hipMemcpyDeviceToHost, c->stream));
-        MKB_HIP(hipStreamSynchronize(c->stream));
+        MKZ_HIP(hipGetLastError(), false);
+        MKZ_HIP(hipEventRecord(c->ev[2], c->stream), false);
+        MKZ_HIP(hipMemcpyAsync(rep.data() + b0, t.rep + b0, cnt * sizeof(mkz::Bz2Block), hipMemcpyDeviceToHost, c->stream), false);
+        MKZ_HIP(hipMemcpyAsync(text_len.data() + b0, t.tlen + b0, cnt * 8ull, hipMemcpyDeviceToHost, c->stream), false);
+        MKZ_HIP(hipStreamSynchronize(c->stream), false);
         ms[2] += elapsed(c->ev[0], c->ev[1]), ms[3] += elapsed(c->ev[1], c->ev[2]);
         *done = b0 + cnt;
         // (the stream has been waited for above, so nothing of this pass is in flight here)
@@ -161,16 +137,16 @@ bool bz_decode(mk_codec *c, uint64_t n, size_t B, const unsigned long long *bit,
 bool bz_text(mk_codec *c, size_t B, size_t b0, size_t b1, const unsigned long long *text_off, uint8_t *d_text, uint32_t *crc, float *ms) {
     const BzTab t(c->d_gz_tab, B);
     const uint32_t cnt = (uint32_t)(b1 - b0);
-    MKB_HIP(hipMemcpyAsync(t.toff + b0, text_off, cnt * 8ull, hipMemcpyHostToDevice, c->stream));
-    MKB_HIP(hipEventRecord(c->ev[0], c->stream));
+    MKZ_HIP(hipMemcpyAsync(t.toff + b0, text_off, cnt * 8ull, hipMemcpyHostToDevice, c->stream), false);
+    MKZ_HIP(hipEventRecord(c->ev[0], c->stream), false);
     mkz::launch_bz2_expand(t.pre + b0, t.level + b0, (const uint8_t *)c->d_gz_sym, t.rep + b0, t.toff + b0, d_text, cnt, c->stream);
-    MKB_HIP(hipGetLastError());
-    MKB_HIP(hipEventRecord(c->ev[1], c->stream));
+    MKZ_HIP(hipGetLastError(), false);
+    MKZ_HIP(hipEventRecord(c->ev[1], c->stream), false);
     mkz::launch_bz2_crc(d_text, t.toff + b0, t.tlen + b0, t.crc + b0, cnt, c->stream);
-    MKB_HIP(hipGetLastError());
-    MKB_HIP(hipEventRecord(c->ev[2], c->stream));
-    MKB_HIP(hipMemcpyAsync(crc, t.crc + b0, cnt * 4ull, hipMemcpyDeviceToHost, c->stream));
-    MKB_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipGetLastError(), false);
+    MKZ_HIP(hipEventRecord(c->ev[2], c->stream), false);
+    MKZ_HIP(hipMemcpyAsync(crc, t.crc + b0, cnt * 4ull, hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     ms[3] += elapsed(c->ev[0], c->ev[1]), ms[4] += elapsed(c->ev[1], c->ev[2]);
     return true;
 }
@@ -178,7 +154,7 @@ bool bz_text(mk_codec *c, size_t B, size_t b0, size_t b1, const unsigned long lo
 // the whole file in one call; false: not taken
 bool bzip2_inflate(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t *text_bytes, uint64_t *n_blocks) {
     if (n < 14 || bz[0] != 'B' || bz[1] != 'Z' || bz[2] != 'h' || bz[3] < '1' || bz[3] > '9') return false;
-    MKB_HIP(hipSetDevice(c->device));
+    MKZ_HIP(hipSetDevice(c->device), false);
     std::vector<mkz::BzMarker> markers;
     if (!bz_upload_and_search(c, bz, n, kBzMaxMarkers, markers, c->bz_ms)) return false;
     // ---- the table walked into streams and blocks (guesses: every block has yet to end on the magic behind it)
@@ -199,7 +175,7 @@ bool bzip2_inflate(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t *text_by
             if (rep[k].status != 0 || rep[k].end_bit != end_bit[k]) return false;
         for (size_t k = 0; k < B; ++k) text_off[k] = total, total += text_len[k];
         // ---- the text at every block's offset, and its CRC
-        if (!bz_room(total + 128, c->gz_text_cap) || !bz_ensure(&c->d_gz_text, &c->gz_text_cap, total + 128)) return false;
+        if (!mkz::room(total + 128, c->gz_text_cap) || !mkz::ensure_quiet(&c->d_gz_text, &c->gz_text_cap, total + 128)) return false;
         if (!bz_text(c, B, 0, B, text_off.data(), (uint8_t *)c->d_gz_text, crcs.data(), c->bz_ms)) return false;
         for (size_t k = 0; k < B; ++k)
             if (crcs[k] != rep[k].crc) return false;
@@ -236,42 +212,18 @@ struct BzStreamDev {
         if (c->bz_text_cap) return c->bz_text_cap;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
-        const uint64_t room = free_b / 2 + D.text_cap[D.text_cur ^ 1];
+        const uint64_t room = free_b / 2 + D.text.cap[D.text.other()];
         return room > 128 ? room - 128 : 0;  // (expand asks for the text and 128 bytes behind it within the same bound)
     }
     bool expand(uint32_t b0, uint32_t b1, const unsigned long long *text_off, uint64_t total, uint32_t *crc) {
-        const int buf = D.text_cur ^ 1;
-        if (!bz_room(total + 128, D.text_cap[buf]) || !bz_ensure(&D.d_text[buf], &D.text_cap[buf], total + 128)) return false;
-        if (!bz_text(c, D.n_tab, b0, b1, text_off, (uint8_t *)D.d_text[buf], crc, D.s.stats.ms)) return false;
-        D.text_cur = buf;
-        c->d_gz_text = D.d_text[buf], c->gz_text_cap = D.text_cap[buf];
+        if (!mkz::room(total + 128, D.text.cap[D.text.other()]) || !D.text.ensure_other(total + 128)) return false;
+        if (!bz_text(c, D.n_tab, b0, b1, text_off, D.text.other_text(), crc, D.s.stats.ms)) return false;
+        D.text.flip(c);
         return true;
     }
 };
 
-uint64_t stream_held(const mk_codec *c) { return c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap + c->gz_ctx_cap + c->bzs.text_cap[0] + c->bzs.text_cap[1]; }
-
 }  // namespace
-
-namespace mkz {
-
-void bzip2_stream_close(mk_codec *c) {
-    mk_bzip2_stream &D = c->bzs;
-    if (!D.active) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *&p : D.d_text) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    c->d_gz_text = nullptr, c->gz_text_cap = 0;  // (it was one of the stream's two)
-    gz_release(c);
-    const mk_bzip2_stream_stats last = D.s.stats;  // (mk_bzip2_stream_info without an open stream: what the last one left)
-    D = mk_bzip2_stream{};
-    D.s.stats = last;
-}
-
-}  // namespace mkz
 
 extern "C" {
 
@@ -280,7 +232,7 @@ int mk_bzip2_inflate_device(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t
     if (!c || !text_bytes || !taken || !n_blocks || (n && !bz)) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_blocks = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_inflate_device: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_bzip2_inflate_device");
     c->gz_text_bytes = 0, c->bz_blocks = 0;
     for (float &x : c->bz_ms) x = 0;
     // (whatever keeps the file from being taken -- anything the walk or the proof refuses, no room, a device error -- is MK_OK with
@@ -309,7 +261,7 @@ int mk_bzip2_stream_begin(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t w
     *taken = 0;
     if (window_bytes > (1ull << 40)) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_begin: a window of 1 TiB at most");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_begin: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_bzip2_stream_begin");
     mkz::BzStream s;
     if (!mkz::bz2_stream_open(s, bz, n, window_bytes)) return MK_OK;  // (not a bzip2 file)
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
@@ -323,42 +275,14 @@ int mk_bzip2_stream_begin(mk_codec *c, const uint8_t *bz, uint64_t n, uint64_t w
 }
 
 int mk_bzip2_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
-    MK_ABI_BEGIN
-    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_next: NULL argument");
-    *text_bytes = 0, *state = 2;
-    std::lock_guard<std::mutex> lock(c->mu);
-    mk_bzip2_stream &D = c->bzs;
-    if (!D.active) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_next: no open stream (mk_bzip2_stream_begin)");
-    c->gz_text_bytes = 0;
-    if (hipSetDevice(c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        D.s.dead = true;
-        return MK_OK;
-    }
-    BzStreamDev dev{c, D};
-    mkz::bz2_stream_next(D.s, dev, text_bytes, state);
-    if (*state == 0) c->gz_text_bytes = *text_bytes;
-    D.s.stats.peak_device_bytes = std::max<uint64_t>(D.s.stats.peak_device_bytes, stream_held(c));
-    return MK_OK;
-    MK_ABI_END
+    return mkz::chain_stream_next(c, &mk_codec::bzs, text_bytes, state, [&](mk_bzip2_stream &D) {
+        BzStreamDev dev{c, D};
+        mkz::bz2_stream_next(D.s, dev, text_bytes, state);
+    });
 }
 
-int mk_bzip2_stream_info(const mk_codec *c, mk_bzip2_stream_stats *out) {
-    MK_ABI_BEGIN
-    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_info: NULL argument");
-    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_bzip2_stream_next writes them under it: a call beside it waits for the window)
-    *out = c->bzs.s.stats;  // (no stream open: what the last one left, zeros if there was none)
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_bzip2_stream_info(const mk_codec *c, mk_bzip2_stream_stats *out) { return mkz::stream_info(c, &mk_codec::bzs, out); }
 
-int mk_bzip2_stream_end(mk_codec *c) {
-    MK_ABI_BEGIN
-    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_bzip2_stream_end: NULL handle");
-    std::lock_guard<std::mutex> lock(c->mu);
-    mkz::bzip2_stream_close(c);
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_bzip2_stream_end(mk_codec *c) { return mkz::stream_end(c, &mk_codec::bzs); }
 
 }  // extern "C"

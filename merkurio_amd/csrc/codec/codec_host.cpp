@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "../host_common.h"
-#include "codec_internal.h"
+#include "codec_stream.hpp"
 
 namespace {
 
@@ -126,6 +126,13 @@ int download_each(mk_codec *c, const void *d_src, uint64_t n, const std::functio
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+// (the one place that names the streams a handle may hold, beside mk_codec::stream_open)
+void streams_close(mk_codec *c) {
+    stream_close(c, c->gzs);
+    stream_close(c, c->bzs);
+    stream_close(c, c->zss);
+    stream_close(c, c->xzs);
+}
 
 }  // namespace mkz
 
@@ -166,10 +173,7 @@ void mk_codec_destroy(mk_codec *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    mkz::gzip_stream_close(c);  // (its text buffers are what d_gz_text points at)
-    mkz::bzip2_stream_close(c);
-    mkz::zstd_stream_close(c);
-    mkz::xz_stream_close(c);
+    mkz::streams_close(c);  // (an open stream's text buffers are what d_gz_text points at)
     for (void *p : {c->d_in, c->d_crc, c->d_tokens, c->d_slots, c->d_len, c->d_off, c->d_out, c->d_aux, c->d_ends, c->d_cut, c->d_gz_in, c->d_gz_sym, c->d_gz_tab, c->d_gz_ctx, c->d_gz_text})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev)

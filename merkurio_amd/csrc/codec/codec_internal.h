@@ -1,6 +1,7 @@
 // codec_internal.h -- the opaque mk_codec handle and what the codec's host files share: codec_host.cpp (the handle, the staging
-// copies), bgzf_host.cpp, gzip_host.cpp, bzip2_host.cpp, zstd_host.cpp, xz_host.cpp (a format each).  window_ingest.cpp borrows the handle's device buffers for
-// mk_extract_fastq_bgzf, which inflates a window of members straight into the matcher's text buffer.
+// copies), bgzf_host.cpp, gzip_host.cpp, bzip2_host.cpp, zstd_host.cpp, xz_host.cpp (a format each); codec_stream.hpp has the frame of the
+// four streams' entry points.  window_ingest.cpp borrows the handle's device buffers for mk_extract_fastq_bgzf, which inflates a
+// window of members straight into the matcher's text buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,58 +26,107 @@ int ensure_device(void **p, size_t *cap, size_t need);
         if (e_ != hipSuccess) return mk::hip_fail(e_, what);  \
     } while (0)
 
-// mk_gzip_stream_*: a gzip file in windows of its compressed bytes (gzip_host.cpp).  The stream owns two text buffers (the handle's
-// d_gz_text points at the latest window's) and two carry buffers of 32 KiB; symbols, tables and contexts are the handle's, sized by
-// the window.
+// A device error on a decode path hands the file back (*taken stays 0, a stream's state 2), it is not the caller's error.  NOTE: the
+// macro RETURNS `ret` from the function that uses it (whose handle is `c`), behind a wait for the stream: a copy may still be on its
+// way into a vector of that function or of its caller
+#define MKZ_HIP(call, ret)                          \
+    do {                                            \
+        if ((call) != hipSuccess) {                 \
+            (void)hipGetLastError();                \
+            (void)hipStreamSynchronize(c->stream);  \
+            (void)hipGetLastError();                \
+            return ret;                             \
+        }                                           \
+    } while (0)
+
+struct mk_codec;
+
+namespace mkz {
+// `need` bytes in buffers of which the handle holds `held` already: what has to be added fits into half of the free memory
+inline bool room(uint64_t need, uint64_t held, uint64_t free_b) { return need <= held || need - held <= free_b / 2; }
+inline bool room(uint64_t need, uint64_t held) {
+    size_t free_b = 0, total_b = 0;
+    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && room(need, held, free_b);
+}
+// mk::ensure_device on a path where no room is "not taken": the error is swallowed
+inline bool ensure_quiet(void **p, size_t *cap, size_t need) {
+    if (mk::ensure_device(p, cap, need) == MK_OK) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// The two text buffers every stream owns.  The latest window's text lies in d[cur], and the handle's d_gz_text / gz_text_cap point at
+// it; the next window is made in the other one, so window w's text stays valid until the call that produces window w + 2.
+struct TextWindows {
+    void *d[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    int cur = 0;
+    int other() const { return cur ^ 1; }  // the buffer the latest window does not lie in
+    uint8_t *other_text() const { return (uint8_t *)d[cur ^ 1]; }
+    bool ensure_other(size_t need) { return ensure_quiet(&d[cur ^ 1], &cap[cur ^ 1], need); }
+    // the other buffer holds the latest window now: the handle's text is what lies `history` bytes into it (zstd: the new text behind
+    // the window's history)
+    inline void flip(mk_codec *c, uint64_t history = 0);
+    uint64_t held() const { return cap[0] + cap[1]; }
+    void free_all() {
+        for (int k = 0; k < 2; ++k) {
+            if (d[k]) (void)hipFree(d[k]);
+            d[k] = nullptr, cap[k] = 0;
+        }
+    }
+};
+}  // namespace mkz
+
+// The four streams (codec_stream.hpp has what their entry points share): `format` words their messages, info() is what mk_*_stream_info
+// reports and what outlives the stream, text the two windows.  Symbols, tables, contexts and compressed bytes are the handle's d_gz_*.
+
+// mk_gzip_stream_*: a gzip file in windows of its compressed bytes (gzip_host.cpp).  Beside the text, two carry buffers of 32 KiB
 struct mk_gzip_stream {
+    static constexpr const char *format = "gzip";
     bool active = false, dead = false;  // dead: handed back (state 2), nothing more is produced
     const uint8_t *gz = nullptr;
     uint64_t n = 0, window = 0;
     std::vector<mk_gzip_guess> guesses;  // of the whole file, once
     mkz::GzStreamPos at;                 // where the next window starts, and what the open member has so far (gzip_chain.hpp)
     uint32_t grow = 0;
-    int carry_cur = 0, text_cur = 0;
-    void *d_carry[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
-    size_t text_cap[2] = {0, 0};
+    int carry_cur = 0;
+    void *d_carry[2] = {nullptr, nullptr};
+    mkz::TextWindows text;
     mk_gzip_stream_stats stats{};
+    mk_gzip_stream_stats &info() { return stats; }
 };
 
 // mk_bzip2_stream_*: a .bz2 file in windows of its compressed bytes (bzip2_host.cpp).  What is decided about a window is mkz::BzStream's
-// (bzip2_chain.hpp); here what the stream owns on the device: two text buffers (the handle's d_gz_text points at the latest text
-// window's).  Compressed bytes, the bytes in front of the run-length step, tables and pass scratch are the handle's d_gz_in /
-// d_gz_sym / d_gz_tab / d_gz_ctx, sized by the window's blocks.
+// (bzip2_chain.hpp)
 struct mk_bzip2_stream {
+    static constexpr const char *format = "bzip2";
     bool active = false;
     mkz::BzStream s;
-    int text_cur = 0;
-    void *d_text[2] = {nullptr, nullptr};
-    size_t text_cap[2] = {0, 0};
+    mkz::TextWindows text;
     uint64_t n_up = 0;  // bytes of the latest upload
     size_t n_tab = 0;   // blocks the device tables of the decoded window are laid out for
+    mk_bzip2_stream_stats &info() { return s.stats; }
 };
 
 // mk_zstd_stream_*: a .zst file in windows of its compressed bytes (zstd_host.cpp).  What is decided about a window is mkz::ZsStream's
-// (zstd_chain.hpp); here what the stream owns on the device: two text buffers, each a window's history and its new text behind it
-// (the handle's d_gz_text points at the latest window's NEW text).  Prelude + compressed bytes, literals + sequences, tables and the
-// two source arrays are the handle's d_gz_in / d_gz_sym / d_gz_tab / d_gz_ctx, sized by the window.
+// (zstd_chain.hpp).  A text buffer holds a window's history and its new text behind it
 struct mk_zstd_stream {
+    static constexpr const char *format = "zstd";
     bool active = false;
     mkz::ZsStream s;
-    int text_cur = 0;
-    void *d_text[2] = {nullptr, nullptr};
-    size_t text_cap[2] = {0, 0};
-    uint64_t text_total = 0;  // history + new text of the latest window, in d_text[text_cur]
+    mkz::TextWindows text;
+    uint64_t text_total = 0;  // history + new text of the latest window, in text.d[text.cur]
+    mk_zstd_stream_stats &info() { return s.stats; }
 };
 
 // mk_xz_stream_*: an .xz file in windows of whole blocks (xz_host.cpp).  What is decided about a window is mkz::XzStream's (xz_chain.hpp:
-// all windows are planned at _begin); here what the stream owns on the device: two text buffers (the handle's d_gz_text points at
-// the latest window's).  The window's compressed span and its tables are the handle's d_gz_in / d_gz_tab, sized by the window.
+// all windows are planned at _begin)
 struct mk_xz_stream {
+    static constexpr const char *format = "xz";
     bool active = false;
     mkz::XzStream s;
-    int text_cur = 0;
-    void *d_text[2] = {nullptr, nullptr};
-    size_t text_cap[2] = {0, 0};
+    mkz::TextWindows text;
+    mk_xz_stream_stats &info() { return s.stats; }
 };
 
 struct mk_codec {
@@ -138,7 +188,18 @@ struct mk_codec {
     bool stream_open() const { return gzs.active || bzs.active || zss.active || xzs.active; }  // one stream per handle, and no one-shot call beside it
 };
 
+inline void mkz::TextWindows::flip(mk_codec *c, uint64_t history) {
+    cur ^= 1;
+    c->d_gz_text = d[cur] ? (uint8_t *)d[cur] + history : nullptr;
+    c->gz_text_cap = d[cur] ? cap[cur] - history : 0;
+}
+
 namespace mkz {
+// What every call that may not run beside a stream says (the one-shot calls, the four _begin, the frame writers)
+constexpr const char *kOpenStream = "the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end, mk_xz_stream_end)";
+inline int refuse_open_stream(const char *entry) { return mk::fail(MK_E_INVALID_ARG, "%s: %s", entry, kOpenStream); }
+// whichever stream is open ends, with its text buffers (which are what d_gz_text points at) and the handle's scratch (codec_host.cpp)
+void streams_close(mk_codec *c);
 // ---- codec_host.cpp: host buffers <-> device through the handle's two page-locked staging buffers
 void parallel_copy(uint8_t *dst, const uint8_t *src, uint64_t n);
 // src[0, n) -> d_dst, enqueued on the handle's stream; the host side of it is done when this returns
@@ -154,14 +215,9 @@ inline float elapsed(hipEvent_t a, hipEvent_t b) {
 }
 // ---- gzip_host.cpp: the buffers of the gzip / bzip2 paths.  gz_release: all five and their caps (the text included: gz_text_bytes = 0).
 // gz_keep_text: what is left to keep is the text -- the compressed bytes, the symbols and the contexts go back to the device.
-// gzip_stream_close: an open stream ends, with its text buffers (which are what d_gz_text points at) and the handle's scratch
 void gz_release(mk_codec *c);
 void gz_keep_text(mk_codec *c);
-void gzip_stream_close(mk_codec *c);
-// ---- bzip2_host.cpp: an open bzip2 stream ends likewise
-void bzip2_stream_close(mk_codec *c);
-// ---- zstd_host.cpp: an open zstd stream ends likewise
-void zstd_stream_close(mk_codec *c);
+// ---- zstd_host.cpp
 // zd_frames, zd_kinds and zd_ms back to 0: what mk_zstd_deflate_info reports starts again
 void zstd_deflate_reset(mk_codec *c);
 // d_text[0, n_text) (kPad ZERO bytes behind it) whose records end at d_ends[0, n_ends) (device memory, non-decreasing, the last one =
@@ -170,8 +226,6 @@ void zstd_deflate_reset(mk_codec *c);
 // ADDS to zd_frames, zd_kinds, zd_ms[1] and zd_ms[2].  The caller holds c->mu, with c->device current
 int zstd_deflate_ranges(mk_codec *c, hipStream_t st, const uint8_t *d_text, uint64_t n_text, const unsigned long long *d_ends, uint64_t n_ends, uint8_t *out,
                         uint64_t out_cap, uint64_t *need, uint64_t *frames);
-// ---- xz_host.cpp: an open xz stream ends likewise
-void xz_stream_close(mk_codec *c);
 // ---- bgzf_host.cpp
 // One device pass of the deflate side, shared by everything that writes members from text that lies on the device (the tag windows'
 // output side, mk_bgzf_deflate_records): CRC-32, deflate and pack of `blocks` members of d_text on

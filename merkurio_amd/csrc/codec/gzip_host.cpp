@@ -12,8 +12,8 @@
 #include <vector>
 
 #include "../host_common.h"
-#include "codec_internal.h"
 #include "codec_kernels.h"
+#include "codec_stream.hpp"
 #include "gzip_chain.hpp"
 
 namespace {
@@ -29,9 +29,7 @@ void free_all(std::initializer_list<void **> ps) {
     }
 }
 
-uint64_t stream_held(const mk_codec *c) {
-    return c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap + c->gz_ctx_cap + c->gzs.text_cap[0] + c->gzs.text_cap[1] + (c->gzs.d_carry[0] ? 2ull * mkz::kSegPrefix : 0);
-}
+uint64_t stream_held(const mk_codec *c) { return mkz::stream_held(c, c->gzs.text) + (c->gzs.d_carry[0] ? 2ull * mkz::kSegPrefix : 0); }
 
 // What the callers of the driver do differently.  Each of these is meant.
 struct GzRun {
@@ -83,7 +81,7 @@ int decode_pieces(mk_codec *c, const mkz::GzPieces &P, const DevTab &t, uint64_t
     const uint32_t J = P.J;
     const uint64_t sym_need = std::max<uint64_t>(P.elems, sym_floor) * 2 + 64;
     size_t free_b = 0, total_b = 0;
-    *room = !(hipMemGetInfo(&free_b, &total_b) == hipSuccess && sym_need > c->gz_sym_cap && sym_need - c->gz_sym_cap > free_b / 2);
+    *room = hipMemGetInfo(&free_b, &total_b) != hipSuccess || mkz::room(sym_need, c->gz_sym_cap, free_b);  // (no answer: the allocation decides)
     if (!*room) return MK_OK;
     int rc;
     if ((rc = mk::ensure_device(&c->d_gz_sym, &c->gz_sym_cap, sym_need))) return rc;
@@ -169,17 +167,18 @@ int gzip_run(mk_codec *c, const GzRun &o, std::vector<mkz::GzCandidate> mem, uin
     if (!gzip_text_offsets(mem, P, n_out, o.up, o.whole, continues ? S->at.open_len : 0, T)) return MK_OK;
     // ---- contexts, text
     t0 = now_ms();
-    void **d_text = S ? &S->d_text[S->text_cur ^ 1] : &c->d_gz_text;
-    size_t *text_cap = S ? &S->text_cap[S->text_cur ^ 1] : &c->gz_text_cap;
     // (the contexts, and behind them two sets of J - 1 maps of 32 768 16-bit elements: codec_kernels.h)
     if ((rc = mk::ensure_device(&c->d_gz_ctx, &c->gz_ctx_cap, std::max<size_t>(J, seg_room) * kSegPrefix * 5 + 16))) return rc;
-    if ((rc = mk::ensure_device(d_text, text_cap, std::max<uint64_t>(T.total, R.ratio * o.nominal) + 64))) return rc;
+    // (a stream: the buffer its latest window does not lie in; no room for it is "not taken", rc being MK_OK here)
+    const size_t text_need = std::max<uint64_t>(T.total, R.ratio * o.nominal) + 64;
+    if (S ? !S->text.ensure_other(text_need) : (rc = mk::ensure_device(&c->d_gz_text, &c->gz_text_cap, text_need)) != MK_OK) return rc;
+    const uint8_t *const d_text = S ? S->text.other_text() : (const uint8_t *)c->d_gz_text;
     uint32_t bad = 0;
     if (J) {
         MKC_HIP(hipMemcpyAsync(t.toff, T.off.data(), J * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the text offsets");
         MKC_HIP(hipMemcpyAsync(t.first, P.seg_first.data(), (J + 1) * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the member table");
         MKC_HIP(hipMemsetAsync(t.bad, 0, 4, c->stream), "hipMemsetAsync");
-        launch_gzip_resolve((const uint16_t *)c->d_gz_sym, t.off, t.nout, t.toff, t.first, J, T.max_member_segs, (uint8_t *)c->d_gz_ctx, (uint8_t *)*d_text, t.bad, c->stream,
+        launch_gzip_resolve((const uint16_t *)c->d_gz_sym, t.off, t.nout, t.toff, t.first, J, T.max_member_segs, (uint8_t *)c->d_gz_ctx, (uint8_t *)d_text, t.bad, c->stream,
                             continues ? (const uint8_t *)S->d_carry[S->carry_cur] : nullptr, continues ? S->at.carry_len : 0);
         MKC_HIP(hipGetLastError(), "gzip resolution");
         MKC_HIP(hipMemcpyAsync(&bad, t.bad, 4, hipMemcpyDeviceToHost, c->stream), "download");
@@ -201,7 +200,7 @@ int gzip_run(mk_codec *c, const GzRun &o, std::vector<mkz::GzCandidate> mem, uin
     if (blocks) {
         MKC_HIP(hipMemcpyAsync(c->d_off, blk_off.data(), blocks * 8ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
         MKC_HIP(hipMemcpyAsync(c->d_len, blk_len.data(), blocks * 4ull, hipMemcpyHostToDevice, c->stream), "upload of the CRC blocks");
-        launch_crc_ranges((const uint8_t *)*d_text, (const unsigned long long *)c->d_off, (const uint32_t *)c->d_len, (uint32_t)blocks, (uint32_t *)c->d_crc, c->stream);
+        launch_crc_ranges(d_text, (const unsigned long long *)c->d_off, (const uint32_t *)c->d_len, (uint32_t)blocks, (uint32_t *)c->d_crc, c->stream);
         MKC_HIP(hipGetLastError(), "CRC kernel");
         MKC_HIP(hipMemcpyAsync(crcs.data(), c->d_crc, blocks * 4ull, hipMemcpyDeviceToHost, c->stream), "download of the CRCs");
     }
@@ -212,15 +211,14 @@ int gzip_run(mk_codec *c, const GzRun &o, std::vector<mkz::GzCandidate> mem, uin
     if (S) {
         if (next_in_member) {  // the last 32 KiB of the open member's text so far: what the next window's first pieces reach back into
             const uint8_t *prev = gzip_window_continues(S->at, M, next_in_member) ? (const uint8_t *)S->d_carry[S->carry_cur] : nullptr;
-            launch_gzip_carry((const uint8_t *)*d_text + T.last_member_off(P), T.mem_text[M - 1], prev, (uint8_t *)S->d_carry[S->carry_cur ^ 1], c->stream);
+            launch_gzip_carry(d_text + T.last_member_off(P), T.mem_text[M - 1], prev, (uint8_t *)S->d_carry[S->carry_cur ^ 1], c->stream);
             MKC_HIP(hipGetLastError(), "gzip carry");
             MKC_HIP(hipStreamSynchronize(c->stream), "gzip carry");
             S->carry_cur ^= 1;
         }
         gzip_window_stands(S->at, M, T.mem_text[M - 1], mem_crc[M - 1], next_bit, next_in_member);
         for (size_t m = 0; m < M; ++m) S->stats.members += mem[m].closed;
-        S->text_cur ^= 1;
-        c->d_gz_text = *d_text, c->gz_text_cap = *text_cap;
+        S->text.flip(c);
         S->stats.windows += 1, S->stats.text_bytes += T.total, S->stats.consumed_bytes = S->at.pos_bit >> 3;
     }
     c->gz_text_bytes = T.total;
@@ -267,17 +265,6 @@ void gz_keep_text(mk_codec *c) {
     c->gz_sym_cap = c->gz_ctx_cap = c->gz_in_cap = 0;
 }
 
-void gzip_stream_close(mk_codec *c) {
-    mk_gzip_stream &S = c->gzs;
-    if (!S.active) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_all({&S.d_carry[0], &S.d_carry[1], &S.d_text[0], &S.d_text[1]});
-    c->d_gz_text = nullptr;  // (it was one of the stream's two)
-    gz_release(c);
-    S = mk_gzip_stream{};
-}
-
 }  // namespace mkz
 
 extern "C" {
@@ -295,7 +282,7 @@ int mk_gzip_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t 
     if (!c || !text_bytes || !taken || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_gzip_inflate_device");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // RFC 1952: the member's header, then the DEFLATE stream up to the 8 trailer bytes.  One member is what is taken here: the stream
@@ -312,7 +299,7 @@ int mk_gzip_members_inflate_device(mk_codec *c, const uint8_t *gz, uint64_t n, u
     if (!c || !text_bytes || !taken || !n_members || (n && !gz)) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_members = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_members_inflate_device: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_gzip_members_inflate_device");
     c->gz_text_bytes = 0, c->gz_segments = 0;
     for (float &x : c->gz_ms) x = 0;
     // the member starts as the host can guess them: every place where a header parses.  The file goes up whole; which guesses are
@@ -347,10 +334,7 @@ int mk_gzip_text_release(mk_codec *c) {
     if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_text_release: NULL handle");
     std::lock_guard<std::mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
-    mkz::gzip_stream_close(c);  // (an open stream's text is the text: the stream ends with it)
-    mkz::bzip2_stream_close(c);
-    mkz::zstd_stream_close(c);
-    mkz::xz_stream_close(c);
+    mkz::streams_close(c);  // (an open stream's text is the text: the stream ends with it)
     mkz::gz_release(c);
     return MK_OK;
 }
@@ -371,7 +355,7 @@ int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t wi
     *taken = 0;
     if (window_bytes && (window_bytes < 4096 || window_bytes > (1ull << 40))) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: a window of 4 KiB at least");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_begin: the handle has an open stream (mk_gzip_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_gzip_stream_begin");
     const uint64_t n_guesses = mkz::gzip_member_guesses(gz, n, nullptr, 0);
     if (!n_guesses) return MK_OK;  // (not a gzip file)
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
@@ -385,7 +369,7 @@ int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t wi
         if (hipMalloc(&S.d_carry[k], mkz::kSegPrefix) != hipSuccess || hipMemsetAsync(S.d_carry[k], 0, mkz::kSegPrefix, c->stream) != hipSuccess) {
             (void)hipGetLastError();
             S.active = true;
-            mkz::gzip_stream_close(c);
+            mkz::stream_close(c, S);
             return MK_OK;  // (the codec rule: the device's trouble is "not taken")
         }
     }
@@ -396,53 +380,38 @@ int mk_gzip_stream_begin(mk_codec *c, const uint8_t *gz, uint64_t n, uint64_t wi
 }
 
 int mk_gzip_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
-    MK_ABI_BEGIN
-    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_next: NULL argument");
-    *text_bytes = 0, *state = 2;
-    std::lock_guard<std::mutex> lock(c->mu);
-    mk_gzip_stream &S = c->gzs;
-    if (!S.active) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_next: no open stream (mk_gzip_stream_begin)");
-    if (S.dead) return MK_OK;
-    if (!S.at.in_member && (S.at.pos_bit >> 3) == S.n) {
-        *state = 1;
-        return MK_OK;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) {
-        S.dead = true;
-        return MK_OK;
-    }
-    S.grow = 0;
-    for (;;) {
-        uint32_t st = 2;
-        const int rc = gzip_stream_window(c, &st);
-        if (rc != MK_OK) st = 2, (void)hipGetLastError();  // (a device error hands the stream back)
-        if (st == 3) {  // no proved start inside the window: twice the window, as long as the file and the device have the room
-            if (!mkz::gzip_window_may_grow(S.at.pos_bit, S.window, S.grow, S.n)) st = 2;
-            else {
-                ++S.grow, ++S.stats.windows_grown;
-                continue;
-            }
+    return mkz::stream_next(c, &mk_codec::gzs, text_bytes, state, [&](mk_gzip_stream &S) {
+        if (S.dead) return;
+        if (!S.at.in_member && (S.at.pos_bit >> 3) == S.n) {
+            *state = 1;
+            return;
         }
-        if (st == 0) *text_bytes = c->gz_text_bytes;
-        else S.dead = true, c->gz_text_bytes = 0;
-        *state = st;
-        return MK_OK;
-    }
-    MK_ABI_END
+        if (hipSetDevice(c->device) != hipSuccess) {
+            S.dead = true;
+            return;
+        }
+        S.grow = 0;
+        for (;;) {
+            uint32_t st = 2;
+            const int rc = gzip_stream_window(c, &st);
+            if (rc != MK_OK) st = 2, (void)hipGetLastError();  // (a device error hands the stream back)
+            if (st == 3) {  // no proved start inside the window: twice the window, as long as the file and the device have the room
+                if (!mkz::gzip_window_may_grow(S.at.pos_bit, S.window, S.grow, S.n)) st = 2;
+                else {
+                    ++S.grow, ++S.stats.windows_grown;
+                    continue;
+                }
+            }
+            if (st == 0) *text_bytes = c->gz_text_bytes;
+            else S.dead = true, c->gz_text_bytes = 0;
+            *state = st;
+            return;
+        }
+    });
 }
 
-int mk_gzip_stream_info(const mk_codec *c, mk_gzip_stream_stats *out) {
-    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_info: NULL argument");
-    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_gzip_stream_next writes them under it: a call beside it waits for the window)
-    *out = c->gzs.stats;  // (no stream open: what the last one left, zeros if there was none)
-    return MK_OK;
-}
+int mk_gzip_stream_info(const mk_codec *c, mk_gzip_stream_stats *out) { return mkz::stream_info(c, &mk_codec::gzs, out); }
 
-int mk_gzip_stream_end(mk_codec *c) {
-    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_gzip_stream_end: NULL handle");
-    std::lock_guard<std::mutex> lock(c->mu);
-    mkz::gzip_stream_close(c);
-    return MK_OK;
-}
+int mk_gzip_stream_end(mk_codec *c) { return mkz::stream_end(c, &mk_codec::gzs); }
 
 }  // extern "C"

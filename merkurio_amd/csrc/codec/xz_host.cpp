@@ -12,8 +12,8 @@
 #include <vector>
 
 #include "../host_common.h"
-#include "codec_internal.h"
 #include "codec_kernels.h"
+#include "codec_stream.hpp"
 #include "lzma_serial.hpp"
 #include "xz_chain.hpp"
 #include "xz_plan.hpp"
@@ -23,23 +23,6 @@ using mkz::now_ms;
 
 namespace {
 
-// a device error on this path hands the file back (*taken stays 0), it is not the caller's error.  NOTE: the macro RETURNS from the
-// function that uses it, behind a wait for the stream: a copy may still be on its way into a vector of that function
-#define MKXZ_HIP(call)                              \
-    do {                                            \
-        if ((call) != hipSuccess) {                 \
-            (void)hipGetLastError();                \
-            (void)hipStreamSynchronize(c->stream);  \
-            (void)hipGetLastError();                \
-            return mkz::kXzDevice;                  \
-        }                                           \
-    } while (0)
-
-bool xz_ensure(void **p, size_t *cap, size_t need) {
-    if (mk::ensure_device(p, cap, need) == MK_OK) return true;
-    (void)hipGetLastError();
-    return false;
-}
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 // ---- the one body: src[0, n) goes up (zeros behind it up to the reader's pad; n_words is THIS upload's, and the kernel's j < n_words
@@ -52,30 +35,30 @@ int xz_run(mk_codec *c, const uint8_t *src, uint64_t n, const mkz::XzBlock *bloc
     const uint64_t n_words = (n + mkz::kXzStreamPad + 3) / 4;
     const uint64_t o_status = up16(B * sizeof(mkz::XzBlock)), o_check = o_status + up16(B * 4), o_order = o_check + up16(B * 4);
     const uint64_t tab_bytes = o_order + (order ? up16(B * 4) : 0);
-    if (!xz_ensure(&c->d_gz_in, &c->gz_in_cap, n_words * 4) || !xz_ensure(&c->d_gz_tab, &c->gz_tab_cap, tab_bytes)) return mkz::kXzTooLarge;
+    if (!mkz::ensure_quiet(&c->d_gz_in, &c->gz_in_cap, n_words * 4) || !mkz::ensure_quiet(&c->d_gz_tab, &c->gz_tab_cap, tab_bytes)) return mkz::kXzTooLarge;
     if (mkz::upload(c, c->d_gz_in, src, n)) {
         (void)hipGetLastError();
         return mkz::kXzDevice;
     }
-    MKXZ_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n, 0, n_words * 4 - n, c->stream));
+    MKZ_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n, 0, n_words * 4 - n, c->stream), mkz::kXzDevice);
     uint8_t *tab = (uint8_t *)c->d_gz_tab;
-    MKXZ_HIP(hipMemcpyAsync(tab, blocks, B * sizeof(mkz::XzBlock), hipMemcpyHostToDevice, c->stream));
-    if (order) MKXZ_HIP(hipMemcpyAsync(tab + o_order, order, B * 4, hipMemcpyHostToDevice, c->stream));
-    MKXZ_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(tab, blocks, B * sizeof(mkz::XzBlock), hipMemcpyHostToDevice, c->stream), mkz::kXzDevice);
+    if (order) MKZ_HIP(hipMemcpyAsync(tab + o_order, order, B * 4, hipMemcpyHostToDevice, c->stream), mkz::kXzDevice);
+    MKZ_HIP(hipStreamSynchronize(c->stream), mkz::kXzDevice);
     ms[0] += (float)(now_ms() - t0);
     int32_t *d_status = (int32_t *)(tab + o_status), *d_check = (int32_t *)(tab + o_check);
     const uint32_t *d_order = order ? (const uint32_t *)(tab + o_order) : nullptr;
-    MKXZ_HIP(hipEventRecord(c->ev[0], c->stream));
+    MKZ_HIP(hipEventRecord(c->ev[0], c->stream), mkz::kXzDevice);
     mkz::launch_xz_decode((const uint8_t *)c->d_gz_in, n_words, tab, d_order, (uint32_t)B, d_text, lclp, d_status, c->stream);
-    MKXZ_HIP(hipGetLastError());
-    MKXZ_HIP(hipEventRecord(c->ev[1], c->stream));
+    MKZ_HIP(hipGetLastError(), mkz::kXzDevice);
+    MKZ_HIP(hipEventRecord(c->ev[1], c->stream), mkz::kXzDevice);
     mkz::launch_xz_check((const uint8_t *)c->d_gz_in, tab, d_order, (uint32_t)B, d_text, d_status, d_check, c->stream);
-    MKXZ_HIP(hipGetLastError());
-    MKXZ_HIP(hipEventRecord(c->ev[2], c->stream));
+    MKZ_HIP(hipGetLastError(), mkz::kXzDevice);
+    MKZ_HIP(hipEventRecord(c->ev[2], c->stream), mkz::kXzDevice);
     std::vector<int32_t> status(2 * B);
-    MKXZ_HIP(hipMemcpyAsync(status.data(), d_status, B * 4, hipMemcpyDeviceToHost, c->stream));
-    MKXZ_HIP(hipMemcpyAsync(status.data() + B, d_check, B * 4, hipMemcpyDeviceToHost, c->stream));
-    MKXZ_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(status.data(), d_status, B * 4, hipMemcpyDeviceToHost, c->stream), mkz::kXzDevice);
+    MKZ_HIP(hipMemcpyAsync(status.data() + B, d_check, B * 4, hipMemcpyDeviceToHost, c->stream), mkz::kXzDevice);
+    MKZ_HIP(hipStreamSynchronize(c->stream), mkz::kXzDevice);
     ms[1] += elapsed(c->ev[0], c->ev[1]), ms[2] += elapsed(c->ev[1], c->ev[2]);
     for (size_t k = 0; k < B; ++k) {  // the first block that failed
         if (status[k] != 0) return status[k];
@@ -95,13 +78,12 @@ int xz_inflate(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t *text_bytes,
     const size_t B = P.blocks.size();
     if (!mkz::xz_spread_ok(P, c->xz_spread ? c->xz_spread : mkz::kXzSpreadDefault)) return mkz::kXzSpread;
     if (B) {
-        MKXZ_HIP(hipSetDevice(c->device));
+        MKZ_HIP(hipSetDevice(c->device), mkz::kXzDevice);
         size_t free_b = 0, total_b = 0;
-        MKXZ_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (P.text_total > free_b / 2) return mkz::kXzTooLarge;
-        const uint64_t need = xz_run_bytes(n, B, false) + P.text_total + 128, held = c->gz_in_cap + c->gz_tab_cap + c->gz_text_cap;
-        if (need > held && need - held > free_b / 2) return mkz::kXzTooLarge;
-        if (!xz_ensure(&c->d_gz_text, &c->gz_text_cap, P.text_total + 128)) return mkz::kXzTooLarge;
+        MKZ_HIP(hipMemGetInfo(&free_b, &total_b), mkz::kXzDevice);
+        if (P.text_total > free_b / 2) return mkz::kXzTooLarge;  // (the text alone, whatever is held: not mkz::room, which credits what is held)
+        if (!mkz::room(xz_run_bytes(n, B, false) + P.text_total + 128, c->gz_in_cap + c->gz_tab_cap + c->gz_text_cap, free_b)) return mkz::kXzTooLarge;
+        if (!mkz::ensure_quiet(&c->d_gz_text, &c->gz_text_cap, P.text_total + 128)) return mkz::kXzTooLarge;
         const int st = xz_run(c, xz, n, P.blocks.data(), B, nullptr, P.lclp_max, (uint8_t *)c->d_gz_text, c->xz_ms);
         if (st) return st;
     }
@@ -116,19 +98,14 @@ struct XzStreamDev {
     mk_codec *c;
     mk_xz_stream &D;
     int decode(const mkz::XzWork &K) {
-        const int buf = D.text_cur ^ 1;
         const size_t B = K.blocks.size();
         size_t free_b = 0, total_b = 0;
-        MKXZ_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t need = xz_run_bytes(K.bytes, B, true) + K.text + 128, held = c->gz_in_cap + c->gz_tab_cap + D.text_cap[buf];
-        if (need > held && need - held > free_b / 2) return mkz::kXzTooLarge;
-        if (!xz_ensure(&D.d_text[buf], &D.text_cap[buf], K.text + 128)) return mkz::kXzTooLarge;
-        return xz_run(c, D.s.xz + K.from, K.bytes, K.blocks.data(), B, K.order.data(), K.lclp, (uint8_t *)D.d_text[buf], D.s.stats.ms);
+        MKZ_HIP(hipMemGetInfo(&free_b, &total_b), mkz::kXzDevice);
+        if (!mkz::room(xz_run_bytes(K.bytes, B, true) + K.text + 128, c->gz_in_cap + c->gz_tab_cap + D.text.cap[D.text.other()], free_b)) return mkz::kXzTooLarge;
+        if (!D.text.ensure_other(K.text + 128)) return mkz::kXzTooLarge;
+        return xz_run(c, D.s.xz + K.from, K.bytes, K.blocks.data(), B, K.order.data(), K.lclp, D.text.other_text(), D.s.stats.ms);
     }
-    void commit(uint64_t) {
-        D.text_cur ^= 1;
-        c->d_gz_text = D.d_text[D.text_cur], c->gz_text_cap = D.text_cap[D.text_cur];
-    }
+    void commit(uint64_t) { D.text.flip(c); }
 };
 
 // Two text buffers of T beside the largest window's upload and tables in half of what is free: T = a sixth of the free memory (xz
@@ -136,29 +113,7 @@ struct XzStreamDev {
 // against the half itself at _begin).  An unmeasured choice (profiles/e2e_unxz_windows.txt)
 uint64_t xz_default_text_cap(uint64_t free_b) { return std::max<uint64_t>(free_b / 6, 1u << 20); }
 
-uint64_t xz_stream_held(const mk_codec *c) { return c->gz_in_cap + c->gz_tab_cap + c->xzs.text_cap[0] + c->xzs.text_cap[1]; }
-
 }  // namespace
-
-namespace mkz {
-
-void xz_stream_close(mk_codec *c) {
-    mk_xz_stream &D = c->xzs;
-    if (!D.active) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *&p : D.d_text) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    c->d_gz_text = nullptr, c->gz_text_cap = 0;  // (it pointed into one of the stream's two)
-    gz_release(c);
-    const mk_xz_stream_stats last = D.s.stats;  // (mk_xz_stream_info without an open stream: what the last one left)
-    D = mk_xz_stream();
-    D.s.stats = last;
-}
-
-}  // namespace mkz
 
 extern "C" {
 
@@ -167,7 +122,7 @@ int mk_xz_inflate_device(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t *t
     if (!c || !text_bytes || !taken || !n_blocks || (n && !xz)) return mk::fail(MK_E_INVALID_ARG, "mk_xz_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_blocks = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_xz_inflate_device: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end, mk_xz_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_xz_inflate_device");
     c->gz_text_bytes = 0, c->xz_blocks = c->xz_streams = 0, c->xz_status = 0, c->xz_largest = 0;
     for (float &x : c->xz_ms) x = 0;
     // (whatever keeps the file from being taken -- anything the walk, a block or a check refuses, the spread rule, no room, a device
@@ -200,8 +155,7 @@ int mk_xz_stream_begin(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t wind
     if (!c || !taken || (n && !xz)) return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_begin: NULL argument");
     *taken = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open())
-        return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_begin: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end, mk_xz_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_xz_stream_begin");
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
     // (whatever keeps the stream from opening is MK_OK with *taken = 0 and a named status in mk_xz_stream_info: the file is liblzma's)
     c->xzs = mk_xz_stream();
@@ -217,7 +171,7 @@ int mk_xz_stream_begin(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t wind
     if (mkz::xz_stream_open(S, xz, n, window_bytes, T, c->xz_spread ? c->xz_spread : mkz::kXzSpreadDefault)) return MK_OK;
     uint64_t text = 0, upload = 0, blocks = 0;
     mkz::xz_stream_needs(S, &text, &upload, &blocks);
-    if (2 * (text + 128) + xz_run_bytes(upload, blocks, true) > (free_b + held) / 2) {
+    if (2 * (text + 128) + xz_run_bytes(upload, blocks, true) > (free_b + held) / 2) {  // (what is held goes back first: it counts as free, not as had)
         S.stats.status = mkz::kXzTooLarge;
         return MK_OK;
     }
@@ -230,45 +184,20 @@ int mk_xz_stream_begin(mk_codec *c, const uint8_t *xz, uint64_t n, uint64_t wind
 }
 
 int mk_xz_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
-    MK_ABI_BEGIN
-    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_next: NULL argument");
-    *text_bytes = 0, *state = 2;
-    std::lock_guard<std::mutex> lock(c->mu);
-    mk_xz_stream &D = c->xzs;
-    if (!D.active) return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_next: no open stream (mk_xz_stream_begin)");
-    c->gz_text_bytes = 0;
-    if (hipSetDevice(c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        D.s.dead = true, D.s.stats.status = mkz::kXzDevice;
-        return MK_OK;
-    }
-    XzStreamDev dev{c, D};
-    const double t0 = now_ms();
-    mkz::xz_stream_next(D.s, dev, text_bytes, state);
-    D.s.stats.ms[3] += (float)(now_ms() - t0);
-    if (*state == 0) c->gz_text_bytes = *text_bytes;
-    D.s.stats.peak_device_bytes = std::max<uint64_t>(D.s.stats.peak_device_bytes, xz_stream_held(c));
-    return MK_OK;
-    MK_ABI_END
+    return mkz::chain_stream_next(
+        c, &mk_codec::xzs, text_bytes, state,
+        [&](mk_xz_stream &D) {
+            XzStreamDev dev{c, D};
+            const double t0 = now_ms();
+            mkz::xz_stream_next(D.s, dev, text_bytes, state);
+            D.s.stats.ms[3] += (float)(now_ms() - t0);
+        },
+        [](mk_xz_stream &D) { D.s.stats.status = mkz::kXzDevice; });
 }
 
-int mk_xz_stream_info(const mk_codec *c, mk_xz_stream_stats *out) {
-    MK_ABI_BEGIN
-    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_info: NULL argument");
-    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_xz_stream_next writes them under it: a call beside it waits for the window)
-    *out = c->xzs.s.stats;  // (no stream open: what the last one left -- a refusal at _begin included --, zeros if there was none)
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_xz_stream_info(const mk_codec *c, mk_xz_stream_stats *out) { return mkz::stream_info(c, &mk_codec::xzs, out); }
 
-int mk_xz_stream_end(mk_codec *c) {
-    MK_ABI_BEGIN
-    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_xz_stream_end: NULL handle");
-    std::lock_guard<std::mutex> lock(c->mu);
-    mkz::xz_stream_close(c);
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_xz_stream_end(mk_codec *c) { return mkz::stream_end(c, &mk_codec::xzs); }
 
 int mk_codec_set_xz_spread(mk_codec *c, uint32_t spread) {
     if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_codec_set_xz_spread: NULL handle");

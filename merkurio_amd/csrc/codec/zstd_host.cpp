@@ -13,8 +13,8 @@
 #include <vector>
 
 #include "../host_common.h"
-#include "codec_internal.h"
 #include "codec_kernels.h"
+#include "codec_stream.hpp"
 #include "xxh64.hpp"
 #include "zstd_plan.hpp"
 
@@ -23,28 +23,6 @@ using mkz::now_ms;
 
 namespace {
 
-// a device error on this path hands the file back (*taken stays 0), it is not the caller's error.  NOTE: the macro RETURNS false from
-// the function that uses it, behind a wait for the stream: a copy may still be on its way into a vector of that function
-#define MKZS_HIP(call)                              \
-    do {                                            \
-        if ((call) != hipSuccess) {                 \
-            (void)hipGetLastError();                \
-            (void)hipStreamSynchronize(c->stream);  \
-            (void)hipGetLastError();                \
-            return false;                           \
-        }                                           \
-    } while (0)
-
-bool zs_room(uint64_t need, uint64_t held) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    return need <= held || need - held <= free_b / 2;
-}
-bool zs_ensure(void **p, size_t *cap, size_t need) {
-    if (mk::ensure_device(p, cap, need) == MK_OK) return true;
-    (void)hipGetLastError();
-    return false;
-}
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 // the device tables of B blocks behind each other: blocks | reports | starts | status | two counters
@@ -70,25 +48,25 @@ bool zs_decode(mk_codec *c, const uint8_t *pre, uint64_t n_pre, const uint8_t *z
     const uint64_t n_in = n_pre + n, n_words = (n_in + mkz::kZsStreamPad + 3) / 4;
     const ZsSym sym(P);
     const ZsTab t(B);
-    if (!zs_room(n_words * 4 + sym.bytes() + t.bytes, c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap) || !zs_ensure(&c->d_gz_in, &c->gz_in_cap, n_words * 4) ||
-        !zs_ensure(&c->d_gz_sym, &c->gz_sym_cap, sym.bytes()) || !zs_ensure(&c->d_gz_tab, &c->gz_tab_cap, t.bytes))
+    if (!mkz::room(n_words * 4 + sym.bytes() + t.bytes, c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap) || !mkz::ensure_quiet(&c->d_gz_in, &c->gz_in_cap, n_words * 4) ||
+        !mkz::ensure_quiet(&c->d_gz_sym, &c->gz_sym_cap, sym.bytes()) || !mkz::ensure_quiet(&c->d_gz_tab, &c->gz_tab_cap, t.bytes))
         return false;
-    if (n_pre) MKZS_HIP(hipMemcpyAsync(c->d_gz_in, pre, n_pre, hipMemcpyHostToDevice, c->stream));
+    if (n_pre) MKZ_HIP(hipMemcpyAsync(c->d_gz_in, pre, n_pre, hipMemcpyHostToDevice, c->stream), false);
     if (mkz::upload(c, (uint8_t *)c->d_gz_in + n_pre, zs, n)) return false;
-    MKZS_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n_in, 0, n_words * 4 - n_in, c->stream));
+    MKZ_HIP(hipMemsetAsync((uint8_t *)c->d_gz_in + n_in, 0, n_words * 4 - n_in, c->stream), false);
     uint8_t *tab = (uint8_t *)c->d_gz_tab;
-    MKZS_HIP(hipMemcpyAsync(tab, P.blocks.data(), B * sizeof(mkz::ZsBlock), hipMemcpyHostToDevice, c->stream));
-    MKZS_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(tab, P.blocks.data(), B * sizeof(mkz::ZsBlock), hipMemcpyHostToDevice, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     ms[0] += (float)(now_ms() - t0);
     uint8_t *lit = (uint8_t *)c->d_gz_sym;
     uint32_t *ll = (uint32_t *)(lit + sym.lit_bytes), *ml = (uint32_t *)(lit + sym.lit_bytes + sym.seq_bytes), *of = (uint32_t *)(lit + sym.lit_bytes + 2 * sym.seq_bytes);
-    MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
+    MKZ_HIP(hipEventRecord(c->ev[0], c->stream), false);
     mkz::launch_zs_decode((const uint8_t *)c->d_gz_in, n_in, n_words, tab, (uint32_t)B, lit, ll, ml, of, tab + t.o_rep, c->stream);
-    MKZS_HIP(hipGetLastError());
-    MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
+    MKZ_HIP(hipGetLastError(), false);
+    MKZ_HIP(hipEventRecord(c->ev[1], c->stream), false);
     rep.resize(B);
-    MKZS_HIP(hipMemcpyAsync(rep.data(), tab + t.o_rep, B * sizeof(mkz::ZsReport), hipMemcpyDeviceToHost, c->stream));
-    MKZS_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(rep.data(), tab + t.o_rep, B * sizeof(mkz::ZsReport), hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     ms[1] += elapsed(c->ev[0], c->ev[1]);
     return true;
 }
@@ -101,35 +79,35 @@ bool zs_text(mk_codec *c, const mkz::ZsPlan &P, const std::vector<mkz::ZsStart> 
              uint32_t *rounds, float *ms) {
     const size_t B = P.blocks.size();
     *rounds = 0;
-    if (settled) MKZS_HIP(hipMemcpyAsync(d_text, d_hist, settled, hipMemcpyDeviceToDevice, c->stream));
+    if (settled) MKZ_HIP(hipMemcpyAsync(d_text, d_hist, settled, hipMemcpyDeviceToDevice, c->stream), false);
     if (!B) {
-        MKZS_HIP(hipStreamSynchronize(c->stream));
+        MKZ_HIP(hipStreamSynchronize(c->stream), false);
         return true;
     }
     const ZsSym sym(P);
     const ZsTab t(B);
     const uint64_t src_bytes = up16(total * 4 + 16);
-    if (!zs_room(2 * src_bytes, c->gz_ctx_cap) || !zs_ensure(&c->d_gz_ctx, &c->gz_ctx_cap, 2 * src_bytes)) return false;
+    if (!mkz::room(2 * src_bytes, c->gz_ctx_cap) || !mkz::ensure_quiet(&c->d_gz_ctx, &c->gz_ctx_cap, 2 * src_bytes)) return false;
     uint8_t *tab = (uint8_t *)c->d_gz_tab, *lit = (uint8_t *)c->d_gz_sym;
     uint32_t *ll = (uint32_t *)(lit + sym.lit_bytes), *ml = (uint32_t *)(lit + sym.lit_bytes + sym.seq_bytes), *of = (uint32_t *)(lit + sym.lit_bytes + 2 * sym.seq_bytes);
     uint32_t *src[2] = {(uint32_t *)c->d_gz_ctx, (uint32_t *)((uint8_t *)c->d_gz_ctx + src_bytes)};
     unsigned long long *d_open = (unsigned long long *)(tab + t.o_count);
-    MKZS_HIP(hipMemcpyAsync(tab + t.o_start, start.data(), B * sizeof(mkz::ZsStart), hipMemcpyHostToDevice, c->stream));
-    MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
-    MKZS_HIP(hipEventRecord(c->ev[0], c->stream));
+    MKZ_HIP(hipMemcpyAsync(tab + t.o_start, start.data(), B * sizeof(mkz::ZsStart), hipMemcpyHostToDevice, c->stream), false);
+    MKZ_HIP(hipMemsetAsync(d_open, 0, 8, c->stream), false);
+    MKZ_HIP(hipEventRecord(c->ev[0], c->stream), false);
     if (settled) {  // (kZsResolved is all ones)
-        MKZS_HIP(hipMemsetAsync(src[0], 0xff, settled * 4, c->stream));
-        MKZS_HIP(hipMemsetAsync(src[1], 0xff, settled * 4, c->stream));
+        MKZ_HIP(hipMemsetAsync(src[0], 0xff, settled * 4, c->stream), false);
+        MKZ_HIP(hipMemsetAsync(src[1], 0xff, settled * 4, c->stream), false);
     }
     mkz::launch_zs_execute((const uint8_t *)c->d_gz_in, tab, tab + t.o_start, tab + t.o_rep, (uint32_t)B, lit, ll, ml, of, d_text, src[0], settled,
                            (int32_t *)(tab + t.o_status), d_open, c->stream);
-    MKZS_HIP(hipGetLastError());
-    MKZS_HIP(hipEventRecord(c->ev[1], c->stream));
+    MKZ_HIP(hipGetLastError(), false);
+    MKZ_HIP(hipEventRecord(c->ev[1], c->stream), false);
     std::vector<int32_t> status(B);
     unsigned long long open = 0;
-    MKZS_HIP(hipMemcpyAsync(status.data(), tab + t.o_status, B * 4, hipMemcpyDeviceToHost, c->stream));
-    MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
-    MKZS_HIP(hipStreamSynchronize(c->stream));
+    MKZ_HIP(hipMemcpyAsync(status.data(), tab + t.o_status, B * 4, hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream), false);
+    MKZ_HIP(hipStreamSynchronize(c->stream), false);
     ms[3] += elapsed(c->ev[0], c->ev[1]);
     for (int32_t st : status)
         if (st != 0) return false;
@@ -139,11 +117,11 @@ bool zs_text(mk_codec *c, const mkz::ZsPlan &P, const std::vector<mkz::ZsStart> 
     int cur = 0;
     while (open) {
         if (*rounds == cap) return false;
-        MKZS_HIP(hipMemsetAsync(d_open, 0, 8, c->stream));
+        MKZ_HIP(hipMemsetAsync(d_open, 0, 8, c->stream), false);
         mkz::launch_zs_resolve(src[cur], src[cur ^ 1], d_text, settled, total, d_open, c->num_cus, c->stream);
-        MKZS_HIP(hipGetLastError());
-        MKZS_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream));
-        MKZS_HIP(hipStreamSynchronize(c->stream));
+        MKZ_HIP(hipGetLastError(), false);
+        MKZ_HIP(hipMemcpyAsync(&open, d_open, 8, hipMemcpyDeviceToHost, c->stream), false);
+        MKZ_HIP(hipStreamSynchronize(c->stream), false);
         cur ^= 1, ++*rounds;
     }
     ms[4] += (float)(now_ms() - t0);
@@ -170,7 +148,7 @@ bool zstd_inflate(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_byt
     uint32_t rounds = 0;
     if (B) {
         if (B >= (1u << 30)) return false;
-        MKZS_HIP(hipSetDevice(c->device));
+        MKZ_HIP(hipSetDevice(c->device), false);
         std::vector<mkz::ZsReport> rep;
         if (!zs_decode(c, nullptr, 0, zs, n, P, rep, c->zs_ms)) return false;
         for (const mkz::ZsReport &r : rep)
@@ -181,7 +159,7 @@ bool zstd_inflate(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t *text_byt
         if (!mkz::zs_scan(P, rep, start, &total)) return false;
         c->zs_ms[2] = (float)(now_ms() - t0);
         // ---- execution and rounds: the text, 8 bytes of sources per byte beside it
-        if (!zs_room(total + 128 + 2 * up16(total * 4 + 16), c->gz_text_cap + c->gz_ctx_cap) || !zs_ensure(&c->d_gz_text, &c->gz_text_cap, total + 128)) return false;
+        if (!mkz::room(total + 128 + 2 * up16(total * 4 + 16), c->gz_text_cap + c->gz_ctx_cap) || !mkz::ensure_quiet(&c->d_gz_text, &c->gz_text_cap, total + 128)) return false;
         if (!zs_text(c, P, start, (uint8_t *)c->d_gz_text, nullptr, 0, total, &rounds, c->zs_ms)) return false;
         // ---- content checksums: the low 32 bits of XXH64 of every frame's text that carries one
         for (const mkz::ZsFrame &F : P.frames) {
@@ -218,41 +196,18 @@ struct ZsStreamDev {
         return zs_decode(c, W.prelude, mkz::kZsPrelude, D.s.zs + W.from, W.to - W.from, W.P, rep, D.s.stats.ms);
     }
     bool execute(const mkz::ZsWindow &W, const std::vector<mkz::ZsStart> &start, uint64_t history, uint64_t total, uint32_t *rounds) {
-        const int buf = D.text_cur ^ 1;
         if (history > D.text_total) return false;
-        if (!zs_room(total + 128 + 2 * up16(total * 4 + 16), D.text_cap[buf] + c->gz_ctx_cap) || !zs_ensure(&D.d_text[buf], &D.text_cap[buf], total + 128)) return false;
-        const uint8_t *hist = history ? (const uint8_t *)D.d_text[D.text_cur] + (D.text_total - history) : nullptr;
-        return zs_text(c, W.P, start, (uint8_t *)D.d_text[buf], hist, history, total, rounds, D.s.stats.ms);
+        if (!mkz::room(total + 128 + 2 * up16(total * 4 + 16), D.text.cap[D.text.other()] + c->gz_ctx_cap) || !D.text.ensure_other(total + 128)) return false;
+        const uint8_t *hist = history ? (const uint8_t *)D.text.d[D.text.cur] + (D.text_total - history) : nullptr;
+        return zs_text(c, W.P, start, D.text.other_text(), hist, history, total, rounds, D.s.stats.ms);
     }
-    bool hash(uint64_t off, uint64_t len, mkz::Xxh64 &h) { return zs_hash(c, (const uint8_t *)D.d_text[D.text_cur ^ 1] + off, len, h, D.s.stats.ms); }
-    void commit(uint64_t history, uint64_t total) {
-        D.text_cur ^= 1, D.text_total = total;
-        c->d_gz_text = D.d_text[D.text_cur] ? (uint8_t *)D.d_text[D.text_cur] + history : nullptr;
-        c->gz_text_cap = D.d_text[D.text_cur] ? D.text_cap[D.text_cur] - history : 0;
-    }
+    bool hash(uint64_t off, uint64_t len, mkz::Xxh64 &h) { return zs_hash(c, D.text.other_text() + off, len, h, D.s.stats.ms); }
+    void commit(uint64_t history, uint64_t total) { D.text.flip(c, history), D.text_total = total; }
 };
-
-uint64_t stream_held(const mk_codec *c) { return c->gz_in_cap + c->gz_sym_cap + c->gz_tab_cap + c->gz_ctx_cap + c->zss.text_cap[0] + c->zss.text_cap[1]; }
 
 }  // namespace
 
 namespace mkz {
-
-void zstd_stream_close(mk_codec *c) {
-    mk_zstd_stream &D = c->zss;
-    if (!D.active) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *&p : D.d_text) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    c->d_gz_text = nullptr, c->gz_text_cap = 0;  // (it pointed into one of the stream's two)
-    gz_release(c);
-    const mk_zstd_stream_stats last = D.s.stats;  // (mk_zstd_stream_info without an open stream: what the last one left)
-    D = mk_zstd_stream();
-    D.s.stats = last;
-}
 
 void zstd_deflate_reset(mk_codec *c) {
     c->zd_frames = 0;
@@ -340,7 +295,7 @@ int mk_zstd_inflate_device(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t 
     if (!c || !text_bytes || !taken || !n_blocks || (n && !zs)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_inflate_device: NULL argument");
     *text_bytes = 0, *taken = 0, *n_blocks = 0;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_inflate_device: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_zstd_inflate_device");
     c->gz_text_bytes = 0, c->zs_blocks = c->zs_frames = c->zs_rounds = 0;
     for (float &x : c->zs_ms) x = 0;
     // (whatever keeps the file from being taken -- anything the walk, a block or a checksum refuses, no room, a device error -- is MK_OK
@@ -372,7 +327,7 @@ int mk_zstd_stream_begin(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t wi
     *taken = 0;
     if (window_bytes > (1ull << 40)) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_begin: a window of 1 TiB at most");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_begin: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_zstd_stream_begin");
     mkz::ZsStream s;
     if (!mkz::zs_stream_open(s, zs, n, window_bytes)) return MK_OK;  // (not a zstd file)
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
@@ -387,47 +342,20 @@ int mk_zstd_stream_begin(mk_codec *c, const uint8_t *zs, uint64_t n, uint64_t wi
 }
 
 int mk_zstd_stream_next(mk_codec *c, uint64_t *text_bytes, uint32_t *state) {
-    MK_ABI_BEGIN
-    if (!c || !text_bytes || !state) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_next: NULL argument");
-    *text_bytes = 0, *state = 2;
-    std::lock_guard<std::mutex> lock(c->mu);
-    mk_zstd_stream &D = c->zss;
-    if (!D.active) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_next: no open stream (mk_zstd_stream_begin)");
-    c->gz_text_bytes = 0;
-    if (hipSetDevice(c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        D.s.dead = true;
-        return MK_OK;
-    }
-    ZsStreamDev dev{c, D};
-    const double t0 = now_ms();
-    const float in_steps = D.s.stats.ms[0] + D.s.stats.ms[1] + D.s.stats.ms[3] + D.s.stats.ms[4] + D.s.stats.ms[5];
-    mkz::zs_stream_next(D.s, dev, text_bytes, state);
-    // (scans: what the window's call spent on the host outside the device steps -- the walk and the two scans)
-    D.s.stats.ms[2] += std::max(0.f, (float)(now_ms() - t0) - (D.s.stats.ms[0] + D.s.stats.ms[1] + D.s.stats.ms[3] + D.s.stats.ms[4] + D.s.stats.ms[5] - in_steps));
-    if (*state == 0) c->gz_text_bytes = *text_bytes;
-    D.s.stats.peak_device_bytes = std::max<uint64_t>(D.s.stats.peak_device_bytes, stream_held(c));
-    return MK_OK;
-    MK_ABI_END
+    return mkz::chain_stream_next(c, &mk_codec::zss, text_bytes, state, [&](mk_zstd_stream &D) {
+        ZsStreamDev dev{c, D};
+        const float *ms = D.s.stats.ms;
+        const double t0 = now_ms();
+        const float in_steps = ms[0] + ms[1] + ms[3] + ms[4] + ms[5];
+        mkz::zs_stream_next(D.s, dev, text_bytes, state);
+        // (scans: what the window's call spent on the host outside the device steps -- the walk and the two scans)
+        D.s.stats.ms[2] += std::max(0.f, (float)(now_ms() - t0) - (ms[0] + ms[1] + ms[3] + ms[4] + ms[5] - in_steps));
+    });
 }
 
-int mk_zstd_stream_info(const mk_codec *c, mk_zstd_stream_stats *out) {
-    MK_ABI_BEGIN
-    if (!c || !out) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_info: NULL argument");
-    std::lock_guard<std::mutex> lock(const_cast<mk_codec *>(c)->mu);  // (mk_zstd_stream_next writes them under it: a call beside it waits for the window)
-    *out = c->zss.s.stats;  // (no stream open: what the last one left, zeros if there was none)
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_zstd_stream_info(const mk_codec *c, mk_zstd_stream_stats *out) { return mkz::stream_info(c, &mk_codec::zss, out); }
 
-int mk_zstd_stream_end(mk_codec *c) {
-    MK_ABI_BEGIN
-    if (!c) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_stream_end: NULL handle");
-    std::lock_guard<std::mutex> lock(c->mu);
-    mkz::zstd_stream_close(c);
-    return MK_OK;
-    MK_ABI_END
-}
+int mk_zstd_stream_end(mk_codec *c) { return mkz::stream_end(c, &mk_codec::zss); }
 
 // ---- zstd frames written on the device (zstd_deflate.hip): the kept records of `extract` as a .zst file, one frame per cut
 
@@ -453,7 +381,7 @@ int mk_zstd_deflate_records(mk_codec *c, const uint8_t *text, uint64_t n, const 
     for (uint64_t r = 1; r < n_rec; ++r)
         if (rec_end[r] < rec_end[r - 1]) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: record end %llu lies in front of the one before it", (unsigned long long)r);
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->stream_open()) return mk::fail(MK_E_INVALID_ARG, "mk_zstd_deflate_records: the handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+    if (c->stream_open()) return mkz::refuse_open_stream("mk_zstd_deflate_records");
     MKC_HIP(hipSetDevice(c->device), "hipSetDevice");
     mkz::zstd_deflate_reset(c);
     if (!n) return MK_OK;

@@ -214,8 +214,7 @@ int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_
         if (codec->device != m->device) return fail(MK_E_INVALID_ARG, "%s: the codec and the matcher are on different devices", entry_name(kind));
         if (kind == Packed::kFrames) {  // (the frame writer's rule, as mk_zstd_deflate_records has it; what it reports starts again)
             std::lock_guard<std::mutex> lock(codec->mu);
-            if (codec->stream_open())
-                return fail(MK_E_INVALID_ARG, "mk_extract_window_frames: the codec handle has an open stream (mk_gzip_stream_end, mk_bzip2_stream_end, mk_zstd_stream_end)");
+            if (codec->stream_open()) return mkz::refuse_open_stream("mk_extract_window_frames");
             mkz::zstd_deflate_reset(codec);
         }
     }

@@ -11,6 +11,7 @@ reference's matcher surface, so tests read like the reference's own tests:
 Everything that searches text runs in the gfx950 kernels; there is no CPU fallback here: if
 the library or a GPU is missing, construction raises.
 """
+import collections
 import ctypes as C
 import time
 import importlib.util
@@ -1204,6 +1205,28 @@ def bgzf_record_cuts(rec_end):
     return cut[:n.value].copy()
 
 
+def _stats_dict(st):
+    """a mk_*_stream_stats as a dict, its times rounded"""
+    out = {k: getattr(st, k) for k, _ in st._fields_ if k not in ("ms", "reserved")}
+    out["ms"] = tuple(round(x, 2) for x in st.ms)
+    return out
+
+
+# what Codec._stream is told of a format: its four entries, its stats struct, the setter of its text cap (or None), and whether
+# mk_*_stream_info names a refusal at _begin (then stream_stats is set for a file that was not taken, too)
+_StreamCalls = collections.namedtuple("_StreamCalls", "begin next info end stats set_text_cap refusal_in_stats")
+
+
+def _stream_calls(fmt, stats, set_text_cap=None, refusal_in_stats=False):
+    return _StreamCalls(*("mk_%s_stream_%s" % (fmt, e) for e in ("begin", "next", "info", "end")), stats, set_text_cap, refusal_in_stats)
+
+
+_GZIP_STREAM = _stream_calls("gzip", GzipStreamStats)
+_BZIP2_STREAM = _stream_calls("bzip2", Bzip2StreamStats)
+_ZSTD_STREAM = _stream_calls("zstd", ZstdStreamStats, "mk_codec_set_zstd_text_cap")
+_XZ_STREAM = _stream_calls("xz", XzStreamStats, "mk_codec_set_xz_text_cap", True)
+
+
 class Codec:
     """mk_codec: BGZF members deflated / inflated by the gfx950 kernels (no CPU path: without a device creation raises)"""
 
@@ -1406,36 +1429,11 @@ class Codec:
         the default) -> a generator of the text windows.  self.stream_state = 1 when it ends at the file's end (every block and
         stream CRC agrees), 2 when the device handed the file back (what was yielded before is a prefix of libbz2's text; nothing
         was, for a file without "BZh1-9" in front); self.stream_stats = mk_bzip2_stream_info of the stream as it ended (a dict)"""
-        src = np.frombuffer(blob, dtype=np.uint8)
-        taken = C.c_uint32(0)
-        self.stream_state, self.stream_stats = 2, None
-        _check(self._L.mk_bzip2_stream_begin(self._h, src.ctypes.data if src.size else None, src.size, window, C.byref(taken)))
-        if not taken.value:
-            return
-        try:
-            n, state = C.c_uint64(0), C.c_uint32(0)
-            while True:
-                _check(self._L.mk_bzip2_stream_next(self._h, C.byref(n), C.byref(state)))
-                st = Bzip2StreamStats()
-                _check(self._L.mk_bzip2_stream_info(self._h, C.byref(st)))
-                self.stream_stats = {k: getattr(st, k) for k, _ in Bzip2StreamStats._fields_ if k not in ("ms", "reserved")}
-                self.stream_stats["ms"] = tuple(round(x, 2) for x in st.ms)
-                self.stream_state = state.value
-                if state.value != 0:
-                    return
-                out = np.empty(n.value, dtype=np.uint8)
-                _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
-                yield out.tobytes()
-        finally:
-            _check(self._L.mk_bzip2_stream_end(self._h))
+        return self._stream(_BZIP2_STREAM, blob, window)
 
     def unzstd_stream_info(self):
         """mk_zstd_stream_info as a dict: of the open stream, or what the last one left"""
-        st = ZstdStreamStats()
-        _check(self._L.mk_zstd_stream_info(self._h, C.byref(st)))
-        out = {k: getattr(st, k) for k, _ in ZstdStreamStats._fields_ if k != "ms"}
-        out["ms"] = tuple(round(x, 2) for x in st.ms)
-        return out
+        return self._stream_info(_ZSTD_STREAM)
 
     def unzstd_stream(self, blob, window_bytes=0, text_cap=0):
         """mk_zstd_stream_begin / _next / _end: a .zst file of any size decoded window by window (`window_bytes` compressed bytes
@@ -1444,38 +1442,11 @@ class Codec:
         device handed the file back (what was yielded before is a prefix of libzstd's text; nothing was, for a file that starts
         with no frame); self.stream_stats = unzstd_stream_info() of the stream as it ended, self.stream_windows = that dict behind
         every call of _next (a list)"""
-        src = np.frombuffer(blob, dtype=np.uint8)
-        taken = C.c_uint32(0)
-        self.stream_state, self.stream_stats, self.stream_windows = 2, None, []
-        _check(self._L.mk_codec_set_zstd_text_cap(self._h, text_cap))
-        try:
-            _check(self._L.mk_zstd_stream_begin(self._h, src.ctypes.data if src.size else None, src.size, window_bytes, C.byref(taken)))
-        finally:
-            _check(self._L.mk_codec_set_zstd_text_cap(self._h, 0))  # (the stream took it when it began)
-        if not taken.value:
-            return
-        try:
-            n, state = C.c_uint64(0), C.c_uint32(0)
-            while True:
-                _check(self._L.mk_zstd_stream_next(self._h, C.byref(n), C.byref(state)))
-                self.stream_stats = self.unzstd_stream_info()
-                self.stream_windows.append(self.stream_stats)
-                self.stream_state = state.value
-                if state.value != 0:
-                    return
-                out = np.empty(n.value, dtype=np.uint8)
-                _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
-                yield out.tobytes()
-        finally:
-            _check(self._L.mk_zstd_stream_end(self._h))
+        return self._stream(_ZSTD_STREAM, blob, window_bytes, text_cap)
 
     def unxz_stream_info(self):
         """mk_xz_stream_info as a dict: of the open stream, or what the last one left (a refusal at _begin included: its status)"""
-        st = XzStreamStats()
-        _check(self._L.mk_xz_stream_info(self._h, C.byref(st)))
-        out = {k: getattr(st, k) for k, _ in XzStreamStats._fields_ if k not in ("ms", "reserved")}
-        out["ms"] = tuple(round(x, 2) for x in st.ms)
-        return out
+        return self._stream_info(_XZ_STREAM)
 
     def unxz_stream(self, blob, window_bytes=0, text_cap=0):
         """mk_xz_stream_begin / _next / _end: an .xz file of any size decoded window by window (`window_bytes`: a bound on a window's
@@ -1484,31 +1455,7 @@ class Codec:
         back (what was yielded before is a prefix of liblzma's text in whole blocks; nothing was, for a file refused at _begin);
         self.stream_stats = unxz_stream_info() of the stream as it ended (its status names a refusal),
         self.stream_windows = that dict behind every call of _next (a list)"""
-        src = np.frombuffer(blob, dtype=np.uint8)
-        taken = C.c_uint32(0)
-        self.stream_state, self.stream_stats, self.stream_windows = 2, None, []
-        _check(self._L.mk_codec_set_xz_text_cap(self._h, text_cap))
-        try:
-            _check(self._L.mk_xz_stream_begin(self._h, src.ctypes.data if src.size else None, src.size, window_bytes, C.byref(taken)))
-        finally:
-            _check(self._L.mk_codec_set_xz_text_cap(self._h, 0))  # (the stream took it when it began)
-        self.stream_stats = self.unxz_stream_info()
-        if not taken.value:
-            return
-        try:
-            n, state = C.c_uint64(0), C.c_uint32(0)
-            while True:
-                _check(self._L.mk_xz_stream_next(self._h, C.byref(n), C.byref(state)))
-                self.stream_stats = self.unxz_stream_info()
-                self.stream_windows.append(self.stream_stats)
-                self.stream_state = state.value
-                if state.value != 0:
-                    return
-                out = np.empty(n.value, dtype=np.uint8)
-                _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
-                yield out.tobytes()
-        finally:
-            _check(self._L.mk_xz_stream_end(self._h))
+        return self._stream(_XZ_STREAM, blob, window_bytes, text_cap)
 
     def gunzip_members(self, gz):
         """mk_gzip_members_inflate_device + mk_gzip_text_read: a gzip file of one or more members, all of them inflated in one batch of
@@ -1532,20 +1479,36 @@ class Codec:
         the default) -> a generator of the windows' texts.  self.stream_state = 1 when it ends at the file's end (every member proved),
         2 when the device handed the file back (what was yielded before is zlib's prefix; nothing was, for a file that is not gzip);
         self.stream_stats = mk_gzip_stream_info of the stream as it ended (a dict)"""
+        return self._stream(_GZIP_STREAM, blob, window)
+
+    def _stream_info(self, calls):
+        st = calls.stats()
+        _check(getattr(self._L, calls.info)(self._h, C.byref(st)))
+        return _stats_dict(st)
+
+    def _stream(self, calls, blob, window, text_cap=None):
+        """The generator behind gunzip_stream, bunzip2_stream, unzstd_stream and unxz_stream: `calls` names the format's _begin / _next /
+        _info / _end, its stats struct and (or None) the setter of the text cap, which the stream takes when it begins"""
         src = np.frombuffer(blob, dtype=np.uint8)
         taken = C.c_uint32(0)
-        self.stream_state, self.stream_stats = 2, None
-        _check(self._L.mk_gzip_stream_begin(self._h, src.ctypes.data if src.size else None, src.size, window, C.byref(taken)))
+        self.stream_state, self.stream_stats, self.stream_windows = 2, None, []
+        if calls.set_text_cap:
+            _check(getattr(self._L, calls.set_text_cap)(self._h, text_cap))
+        try:
+            _check(getattr(self._L, calls.begin)(self._h, src.ctypes.data if src.size else None, src.size, window, C.byref(taken)))
+        finally:
+            if calls.set_text_cap:
+                _check(getattr(self._L, calls.set_text_cap)(self._h, 0))  # (the stream took it when it began)
+        if calls.refusal_in_stats:
+            self.stream_stats = self._stream_info(calls)
         if not taken.value:
             return
         try:
             n, state = C.c_uint64(0), C.c_uint32(0)
             while True:
-                _check(self._L.mk_gzip_stream_next(self._h, C.byref(n), C.byref(state)))
-                st = GzipStreamStats()
-                _check(self._L.mk_gzip_stream_info(self._h, C.byref(st)))
-                self.stream_stats = {k: getattr(st, k) for k, _ in GzipStreamStats._fields_ if k not in ("ms", "reserved")}
-                self.stream_stats["ms"] = tuple(round(x, 2) for x in st.ms)
+                _check(getattr(self._L, calls.next)(self._h, C.byref(n), C.byref(state)))
+                self.stream_stats = self._stream_info(calls)
+                self.stream_windows.append(self.stream_stats)
                 self.stream_state = state.value
                 if state.value != 0:
                     return
@@ -1553,7 +1516,7 @@ class Codec:
                 _check(self._L.mk_gzip_text_read(self._h, 0, out.ctypes.data if out.size else None, out.size))
                 yield out.tobytes()
         finally:
-            _check(self._L.mk_gzip_stream_end(self._h))
+            _check(getattr(self._L, calls.end)(self._h))
 
     def set_inflate_kernel(self, which=0):
         """0 = chosen per call, 1 = a lane per member, 2 = a wave per member (mk_codec_set_inflate_kernel)"""
