@@ -571,6 +571,47 @@ int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t 
                       uint32_t *pattern_hit_counts, uint32_t *status);
 
 /* -------------------------------------------------------------------------------------
+ * A text window that may START ANYWHERE (v7 addition) -- mk_extract_window for a window whose first byte may lie inside a record: a
+ * range of BGZF members that begins at a member boundary, a slice of a plain file.  The call finds a record start itself, hands back
+ * the text in front of it and processes the records from there; windows of one file can then run side by side, on any device, and
+ * the text between two of them -- the tail of window k - 1 ++ the front of window k -- goes through one small mk_extract_window call.
+ * Same arguments, outputs and body as mk_extract_window, plus `fronts` (one mk_window_front: n_sources must be 1 -- mate i of one
+ * file of a pair has no index in the other -- and n_head 0; anything else is MK_E_INVALID_ARG, raised before any device use).
+ *
+ * THE START RULE, on the lines of the window text (line 0 begins at byte 0, a '\n' ends a line; a line is COMPLETE when the text
+ * holds its '\n'):
+ *   FASTQ  the smallest line j >= 1 such that the record shape holds at j AND at j + 4, all eight lines complete.  The shape at j is
+ *          mk_extract_window's: line j begins with '@' and holds at least three bytes with its '\n'; line j + 2 begins with '+';
+ *          lines j + 1 and j + 3 have one length, a '\r' in front of the '\n' counted as part of the line end.
+ *   FASTA  the smallest line j >= 1 whose first byte is '>' (a line that begins inside the text; it need not be complete).
+ * Line 0 is never taken: whether byte 0 follows a line end is not known to the call.
+ * out: front[0, n_front) = the text in front of line j; the records are indexed from byte n_front on as by mk_extract_window, and
+ *      rec_start[] (rec_start[0] = n_front), n_used and n_tail stay offsets in the WHOLE window text.
+ * *status = 2: no start was found (fewer than nine complete lines, one record longer than the window, an empty window): nothing is
+ *      produced, n_front = n_window and `front` is not written.  *status = 1: as mk_extract_window, n_front is stated.
+ * front_cap too small: MK_E_CAPACITY with n_front = the need; in the order of "the first thing that does not fit" it stands behind
+ *      rec_cap and in front of tail.
+ *
+ * THE FOUND START IS A GUESS, and the caller proves it.  A FASTA start is always true: every line that begins with '>' begins a
+ * record.  A FASTQ quality line may begin with '@', and texts exist in which the shape holds twice at lines that begin no record.
+ * The proof is the seam call: mk_extract_window on tail(k - 1) ++ front(k) with ends_at_record = 1.  By induction tail(k - 1)
+ * begins at a true record start (window 0 begins the file; a window that begins at a true start counts whole records, so what it
+ * leaves behind begins at one).  In a well-formed file every record is four lines, so the lines from that true start to the found
+ * start are a multiple of four, every group of which has the shape, if and only if the found start is a record start: the seam call
+ * returns *status = 0 and n_used = n_window exactly then.  Anything else (status != 0, n_used != n_window, or status 2 from the open
+ * call) disproves the guess; the caller then runs window k the chained way, head = tail(k - 1), and drops the open call's results.
+ * A file that is not well formed fails the seam or the window behind it and ends up on the same chained path, which words the error.
+ * --------------------------------------------------------------------------------------- */
+typedef struct mk_window_front {
+    uint8_t *front;     /* in: where the text in front of the found start goes */
+    uint64_t front_cap;
+    uint64_t n_front;   /* out */
+} mk_window_front;
+int mk_extract_window_open(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *sources, int logging, int invert,
+                           uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters,
+                           uint32_t *pattern_hit_counts, uint32_t *status, mk_window_front *fronts);
+
+/* -------------------------------------------------------------------------------------
  * BGZF members that end at record ends (v7 addition) -- the output side of `extract -z`: the kept records are deflated on the
  * device, and every member is a FASTQ / FASTA fragment that parses on its own, so a reader that splits its work at member boundaries needs
  * no head / tail chain.  (mk_bgzf_deflate cuts its text every block_bytes: a record may straddle two members.  The reference writes

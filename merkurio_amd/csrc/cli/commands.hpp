@@ -76,6 +76,9 @@ struct ExtractArgs : CommonArgs {
     // --xz-stream (implies --device-xz): a larger .xz input is decoded window by window (mk_xz_stream_*), windows of whole blocks
     // bounded by --xz-text-cap bytes of text (0 = the library's default, by the free device memory).  Opt-in like its sibling: not timed
     bool xz_stream = false;
+    // --open-windows: the windows of ONE bgzip'ed input with plain-text output start at member boundaries and find their own first
+    // record (mk_extract_window_open); the text between two windows goes through a seam call that also proves the found start
+    bool open_windows = false;
     uint64_t xz_text_cap = 0;
 };
 

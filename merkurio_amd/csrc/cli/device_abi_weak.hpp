@@ -20,5 +20,9 @@ __attribute__((weak)) int mk_extract_window_frames(mk_matcher *m, mk_codec *code
                                                    mk_window_members *frames, int logging, int invert, uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep,
                                                    mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *counters, uint32_t *pattern_hit_counts,
                                                    uint32_t *status);
+// (an open window of `extract`: the window's first record start is found on the device)
+__attribute__((weak)) int mk_extract_window_open(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *sources, int logging,
+                                                 int invert, uint64_t rec_cap, uint64_t *n_rec, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows,
+                                                 mk_counters *counters, uint32_t *pattern_hit_counts, uint32_t *status, mk_window_front *fronts);
 __attribute__((weak)) int mk_zstd_deflate_info(const mk_codec *c, uint64_t *n_frames, uint32_t kinds[3], float ms[3]);
 }

@@ -105,6 +105,11 @@ struct Win {
     mk_counters cb;
     std::vector<uint32_t> cnt;
     bool by_host = false;
+    // --open-windows: `open` -- the window starts at a member, not at a record: the call finds its first record and `front` is the text
+    // in front of it; `probe` -- a seam, tail(k - 1) ++ front(k) as host text; `refused` -- an open window or a seam the device did
+    // not take as it is (the guess is disproved: the window is run again the chained way); `job` -- the writer waits for this one
+    bool open = false, probe = false, refused = false, job = false;
+    std::vector<char> front;
     float z_ms[4] = {0, 0, 0, 0};  // -z on the device: written form (select, scan, gather), cut, deflate, download (--zstd-output: cut is in deflate)
     void index_kept() {
         kept.clear();

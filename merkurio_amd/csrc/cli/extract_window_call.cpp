@@ -14,7 +14,9 @@ struct WindowExtract::Impl::Call {  // the arguments of one window's device call
     mk_window_members mem[2];
     bool use_members = false, any_bgzf = false;
     uint64_t cap_text = 0, rec_cap = 0;
+    mk_window_front front;  // (an open window)
     Call() {
+        memset(&front, 0, sizeof(front));
         memset(src, 0, sizeof(src));
         memset(mem, 0, sizeof(mem));
     }
@@ -161,6 +163,7 @@ bool WindowExtract::Impl::grow_named(Win &W, Call &c) {
     bool grown = false;
     if (W.n_rec > c.rec_cap) c.rec_cap = W.n_rec + W.n_rec / 16, grown = true, rec_cap_seen = std::max<uint64_t>(rec_cap_seen.load(), c.rec_cap);
     if (W.n_rows > W.rows.size()) W.rows.resize(W.n_rows), grown = true;
+    if (W.open && c.front.n_front > c.front.front_cap) W.front.resize(c.front.n_front + (1u << 16)), grown = true;
     for (int i = 0; i < n_in; ++i) {
         Side::Result &R = W.side[i].out;
         mk_window_source &Q = c.src[i];
@@ -237,7 +240,13 @@ void WindowExtract::Impl::device_window(Win &W, mk_matcher *m, mk_codec *codec) 
     for (bool use_members = z_members;; use_members = false) {
         Call c;
         c.use_members = use_members;
-        if (bind_outputs(W, c) >= 0xFFFFFFF0ull) return host_window(W, m);  // (a FASTA record of 4 GiB or more: the host path's own limits apply)
+        if (bind_outputs(W, c) >= 0xFFFFFFF0ull) {
+            if (W.open || W.probe) {  // (the host parser reads from a record start: the chained re-run's business)
+                W.refused = true;
+                return;
+            }
+            return host_window(W, m);
+        }  // (a FASTA record of 4 GiB or more: the host path's own limits apply)
         // (a guess the call corrects: for rec_cap MK_E_CAPACITY comes back before anything is scanned)
         c.rec_cap = std::max<uint64_t>(rec_cap_seen.load(), c.cap_text / (fastq ? 192 : 1024) + 16);
         W.rows.resize(std::max<size_t>(W.rows.size(), 4096));
@@ -256,16 +265,26 @@ void WindowExtract::Impl::device_window(Win &W, mk_matcher *m, mk_codec *codec) 
                 c.mem[i].text_below = a.z_members_from;
             }
             if (W.keep.size() < c.rec_cap) W.keep.resize(c.rec_cap);
+            if (W.open) {
+                if (W.front.empty()) W.front.resize(1u << 20);
+                c.front.front = (uint8_t *)W.front.data(), c.front.front_cap = W.front.size();
+            }
             memset(&W.cb, 0, sizeof(W.cb));
             std::fill(W.cnt.begin(), W.cnt.end(), 0);
             const uint32_t format = fastq ? MK_TEXT_FASTQ : MK_TEXT_FASTA;
             const auto packed = a.zstd_output ? mk_extract_window_frames : mk_extract_window_members;
-            const int rc = use_members ? packed(m, codec, format, (uint32_t)n_in, c.src, c.mem, lg->active, a.invert_match, c.rec_cap,
+            const int rc = W.open ? mk_extract_window_open(m, c.any_bgzf ? codec : nullptr, format, 1, c.src, lg->active, a.invert_match, c.rec_cap, &W.n_rec,
+                                                           W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status, &c.front)
+                           : use_members ? packed(m, codec, format, (uint32_t)n_in, c.src, c.mem, lg->active, a.invert_match, c.rec_cap,
                                                 &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status)
                                        : mk_extract_window(m, c.any_bgzf ? codec : nullptr, format, (uint32_t)n_in, c.src, lg->active, a.invert_match, c.rec_cap,
                                                            &W.n_rec, W.keep.data(), W.rows.data(), W.rows.size(), &W.n_rows, &W.cb, W.cnt.data(), &status);
             if (rc == MK_E_CAPACITY && attempt < 8 && grow_named(W, c)) continue;  // once more with what was too small grown
             if (rc == MK_E_CORRUPT) bail("Error while decompressing " + in[c.src[1].n_members && !c.src[0].n_members ? 1 : 0].path);
+            if ((rc == MK_E_UNSUPPORTED || rc == MK_E_NOMEM) && (W.open || W.probe)) {  // (the chained re-run takes what follows from it)
+                W.refused = true;
+                return;
+            }
             if (rc == MK_E_UNSUPPORTED || rc == MK_E_NOMEM) {
                 // too much for the device in one piece (a pair of windows above 2 GiB under BNDMq; no memory for the window): the
                 // host path takes this window in batches, and BGZF windows shrink from here on
@@ -282,7 +301,12 @@ void WindowExtract::Impl::device_window(Win &W, mk_matcher *m, mk_codec *codec) 
             for (int i = 0; i < n_in; ++i) W.side[i].out.text.clear(), W.side[i].out.ids.clear(), W.side[i].out.id_end.clear();
             continue;
         }
+        if (status != 0 && (W.open || W.probe)) {  // no start, or not what the device takes from there: the guess is disproved
+            W.refused = true;
+            return;
+        }
         if (status != 0) return host_window(W, m);
+        if (W.open) W.front.resize(c.front.n_front);
         return collect(W, c, codec);
     }
 }

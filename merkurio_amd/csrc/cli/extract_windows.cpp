@@ -28,6 +28,7 @@
 namespace cli {
 
 using xw::kFirstWindow;
+using Win = xw::Win;
 
 void WindowExtract::Impl::reader_loop() {
     const size_t N = devs.size();
@@ -43,8 +44,14 @@ void WindowExtract::Impl::reader_loop() {
             S.from = src[i].get(), S.on_device = src[i]->on_device();
             src[i]->next(k, S, target, m_ahead);
         };
+        if (open_mode && k > 0) {  // open windows finish out of order: no more than N + 2 of them ahead of the writer
+            std::unique_lock<std::mutex> lk(gate.mu);
+            gate.cv.wait(lk, [&] { return gate.failed || k < written + N + 2; });
+            if (gate.failed) return;
+            W->open = !open_off;
+        }
         for (int i = 0; i < n_in; ++i) ask(i, k == 0);
-        if (chained && k > 0) {  // the tails of window k - 1 are this window's heads
+        if (chained && k > 0 && !W->open) {  // the tails of window k - 1 are this window's heads
             std::unique_lock<std::mutex> lk(gate.mu);
             gate.cv.wait(lk, [&] { return gate.failed || tails.count(k - 1); });
             if (gate.failed) return;
@@ -107,7 +114,8 @@ void WindowExtract::Impl::device_loop(size_t d) {
         std::unique_ptr<Win> W;
         {
             std::unique_lock<std::mutex> lk(gate.mu);
-            gate.cv.wait(lk, [&] { return gate.failed || !queue[d].empty() || reader_done; });
+            // (--open-windows: the writer sends seams and re-runs until it has ended)
+            gate.cv.wait(lk, [&] { return gate.failed || !queue[d].empty() || (reader_done && (!open_mode || writer_done)); });
             if (gate.failed) return;
             if (queue[d].empty()) return;  // (reader_done)
             W = std::move(queue[d].front());
@@ -138,7 +146,12 @@ void WindowExtract::Impl::device_loop(size_t d) {
             std::vector<char>().swap(S.own);
             if (!chained) std::vector<char>().swap(S.head);
         }
-        if (chained) {
+        if (W->job) {  // a seam or a re-run: the writer waits for it
+            job_done = std::move(W);
+            gate.cv.notify_all();
+            continue;
+        }
+        if (chained && !open_mode) {  // (--open-windows: a tail counts once its window is proved -- the writer publishes it)
             std::vector<std::vector<char>> t(2);
             for (int i = 0; i < n_in; ++i) t[i] = W->side[i].out.tail;  // (a copy: the window itself goes to the writer)
             tails[W->k] = std::move(t);
@@ -148,6 +161,66 @@ void WindowExtract::Impl::device_loop(size_t d) {
         done[k] = std::move(W);
         gate.cv.notify_all();
     }
+}
+
+// ---- `extract --open-windows`: what the writer does when it reaches an OPEN window, one that started at a BGZF member
+// and found its own first record (mk_extract_window_open).  The text between the window in front and that record -- tail(k - 1) ++
+// front(k) -- goes through a seam call, which also proves the found start: begun at a true record start it takes its whole text
+// (status 0, n_used = n_window) if and only if the found start is a record start.  A disproved window is run again the
+// chained way, head = tail(k - 1); after 4 of them in a row the reader chains the rest of the file.  Seams and re-runs run on the
+// window's device thread (a matcher handle serves one call at a time): the writer queues them in front and waits.
+// W to the front of its device's queue; -> W once its device thread is through with it.  NO OVERLAP is gained here: the writer issues a
+// seam only when it reaches window k (not as soon as windows k - 1 and k are both done), one at a time, and the job lands behind
+// whatever call that device thread has in flight -- on one device a seam can cost the writer up to one whole window call of waiting
+std::unique_ptr<Win> WindowExtract::Impl::run_job(std::unique_ptr<Win> W) {
+    W->job = true;
+    std::unique_lock<std::mutex> lk(gate.mu);
+    queue[W->dev].push_front(std::move(W));
+    gate.cv.notify_all();
+    gate.cv.wait(lk, [&] { return gate.failed || job_done; });
+    if (!job_done) bail(gate.failure);
+    return std::move(job_done);
+}
+
+// -> the window whose results stand for window k: W itself behind a seam that passed (the seam has been emitted), else its chained re-run
+std::unique_ptr<Win> WindowExtract::Impl::settle_open_window(std::unique_ptr<Win> W, const std::vector<char> &prev_tail, int &disproved_in_a_row,
+                                                             const std::function<void(Win &)> &emit) {
+    ++n_open;
+    bool proved = false;
+    if (!W->refused) {
+        std::unique_ptr<Win> seam(new Win);
+        seam->k = W->k, seam->dev = W->dev, seam->probe = true;
+        xw::Side &S = seam->side[0];
+        S.head = prev_tail;
+        S.own = W->front;
+        S.body = S.own.data(), S.n_body = S.own.size();
+        S.ends = true;
+        ++n_seams;
+        seam = run_job(std::move(seam));
+        // (an error of the seam's own -- nothing but a failing device call -- disproves nothing: it is the job's error)
+        if (!seam->error.empty()) bail(seam->error);
+        proved = !seam->refused && seam->side[0].out.n_used == seam->side[0].out.n_window;
+        if (proved) emit(*seam);
+    }
+    if (proved) {
+        disproved_in_a_row = 0;
+        return W;
+    }
+    // disproved: the same members once more, with the tail in front as their head; the first results are dropped, their counters with them
+    ++n_reruns;
+    if (++disproved_in_a_row >= 4) {
+        std::lock_guard<std::mutex> lk(gate.mu);
+        open_off = true;
+    }
+    std::unique_ptr<Win> R(new Win);
+    R->k = W->k, R->dev = W->dev;
+    xw::Side &S = R->side[0], &O = W->side[0];
+    S.head = prev_tail;
+    S.grp = O.grp, S.ends = O.ends, S.from = O.from, S.on_device = O.on_device;
+    W.reset();
+    R = run_job(std::move(R));
+    if (!R->error.empty()) bail(R->error);
+    return R;
 }
 
 WindowExtract::~WindowExtract() {
@@ -339,6 +412,7 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
             J.codecs.push_back(c);
         }
     }
+    J.open_mode = a.open_windows && J.n_in == 1 && J.members_input(0) && !a.bgzf_output && !a.zstd_output && !a.host_ingest;
     if (any_bgzf) J.bound_device_windows();
     J.take_inputs_on_device();
     bool any_dev_text = false;
@@ -373,6 +447,8 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     th.emplace_back(guarded([&J] { J.reader_loop(); }));
     for (size_t d = 0; d < N; ++d) th.emplace_back(guarded([&J, d] { J.device_loop(d); }));
     std::string writer_error;
+    std::vector<char> prev_tail;  // --open-windows: the tail of the window in front, final
+    int disproved_in_a_row = 0;
     try {
         for (uint64_t k = 0;; ++k) {
             std::unique_ptr<xw::Win> W;
@@ -385,15 +461,32 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
                 J.done.erase(k);
             }
             if (!W->error.empty()) bail(W->error);
-            tm.mark(W->by_host ? "window: host parser + scan" : "window: H2D + index + scan + D2H");
-            add_counters(dev_c[W->dev], W->cb);
-            add_counts(dev_counts[W->dev], W->cnt);
-            J.write_window(*W, w1, w2, name1, name2, tm);
-            w1.window_done(), w2.window_done();
+            auto emit = [&](xw::Win &X) {
+                tm.mark(X.by_host ? "window: host parser + scan" : "window: H2D + index + scan + D2H");
+                add_counters(dev_c[X.dev], X.cb);
+                add_counts(dev_counts[X.dev], X.cnt);
+                J.write_window(X, w1, w2, name1, name2, tm);
+                w1.window_done(), w2.window_done();
+            };
+            if (W->open) W = J.settle_open_window(std::move(W), prev_tail, disproved_in_a_row, emit);  // (the seam's records go out first)
+            emit(*W);
+            if (J.open_mode) {  // this window's tail is final: the seam behind it, or a chained window, may use it
+                prev_tail = W->side[0].out.tail;
+                std::lock_guard<std::mutex> lk(G.mu);
+                J.tails.clear();
+                J.tails[k] = std::vector<std::vector<char>>{prev_tail, {}};
+                J.written = k + 1;
+                G.cv.notify_all();
+            }
         }
     } catch (const Error &e) {
         writer_error = e.what()[0] ? e.what() : "error";
         G.fail_all(writer_error);
+    }
+    {
+        std::lock_guard<std::mutex> lk(G.mu);
+        J.writer_done = true;
+        G.cv.notify_all();
     }
     for (auto &t : th) t.join();
     for (auto &t : pin_threads) t.join();
@@ -404,6 +497,9 @@ void WindowExtract::run(const ExtractArgs &a, const Patterns &pats, Loggers &lg,
     }
     if (!writer_error.empty()) bail(writer_error);
     if (G.failed) bail(G.failure);
+    if (G.timing && J.open_mode)
+        fprintf(stderr, "[timing] extract --open-windows: %llu open windows, %llu seams, %llu re-runs\n", (unsigned long long)J.n_open,
+                (unsigned long long)J.n_seams, (unsigned long long)J.n_reruns);
     if (G.timing && a.bgzf_output) {
         fprintf(stderr, "[timing] extract -z: %llu windows as members, %llu as text\n", (unsigned long long)J.z_member_windows,
                 (unsigned long long)J.z_text_windows);

@@ -2,6 +2,7 @@
 // (extract_windows.cpp), the window call (extract_window_call.cpp) and the writer (extract_write.cpp).
 #pragma once
 #include <atomic>
+#include <functional>
 #include <map>
 
 #include "extract_sources.hpp"
@@ -37,6 +38,12 @@ struct WindowExtract::Impl {
     bool reader_done = false;
     uint64_t n_windows = 0;  // (valid once reader_done)
     uint64_t last_head[2] = {0, 0};  // (the reader's)
+    // --open-windows (one BGZF input, plain-text output).  Under gate.mu: windows the writer is through with, whether
+    // it has ended, whether the rest of the file is chained (4 disproved windows in a row), the seam / re-run the writer waits for
+    bool open_mode = false, open_off = false, writer_done = false;
+    uint64_t written = 0;
+    std::unique_ptr<Win> job_done;
+    uint64_t n_open = 0, n_seams = 0, n_reruns = 0;  // (the writer's)
     std::atomic<uint64_t> rec_cap_seen{0};
     // -z / --zstd-output: the kept records leave the device as BGZF members (mk_extract_window_members) / zstd frames
     // (mk_extract_window_frames) -- not with --host-codec, and not with logs under -v, whose rows name records that are not kept
@@ -74,6 +81,10 @@ struct WindowExtract::Impl {
     // ---- extract_write.cpp
     void write_window(Win &W, Sink &w1, Sink &w2, const std::string &name1, const std::string &name2, PhaseTimer &tm);
     void write_members_window(Win &W, Sink **w, const std::string **names, PhaseTimer &tm);
+    // (--open-windows: the writer's seam and re-run steps)
+    std::unique_ptr<Win> run_job(std::unique_ptr<Win> W);
+    std::unique_ptr<Win> settle_open_window(std::unique_ptr<Win> W, const std::vector<char> &prev_tail, int &disproved_in_a_row,
+                                            const std::function<void(Win &)> &emit);
 };
 
 }  // namespace cli

@@ -23,7 +23,7 @@ const Spec kCommon[] = {{'s', "kmer-seq", 2},      {'f', "kmer-file", 1},    {'r
                         {'I', "case-insensitive", 0}, {'L', "lowercase", 0}, {'U', "uppercase", 0},          {'q', "q-size", 1},
                         {'a', "aho-corasick", 0},  {0, "device", 1},         {0, "batch-mb", 1},           {0, "gpus", 1},                 {0, "window-mb", 1},
                         {0, "host-ingest", 0},     {0, "host-codec", 0},     {0, "device-codec-always", 0}};
-const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}, {'z', "bgzf-output", 0}, {0, "z-members-from", 1}, {0, "gzip-window", 1}, {0, "bzip2-window", 1}, {0, "zstd-window", 1}, {0, "device-zstd", 0}, {0, "zstd-stream", 0}, {0, "zstd-output", 0}, {0, "device-xz", 0}, {0, "xz-window", 1}, {0, "xz-spread", 1}, {0, "xz-stream", 0}, {0, "xz-text-cap", 1}};
+const Spec kExtract[] = {{'i', "in-fastx", 1}, {'1', "in-fastx", 1}, {'2', "in-fastq-2", 1}, {'o', "out-fastx", 1}, {'z', "bgzf-output", 0}, {0, "z-members-from", 1}, {0, "gzip-window", 1}, {0, "bzip2-window", 1}, {0, "zstd-window", 1}, {0, "device-zstd", 0}, {0, "zstd-stream", 0}, {0, "zstd-output", 0}, {0, "device-xz", 0}, {0, "xz-window", 1}, {0, "xz-spread", 1}, {0, "xz-stream", 0}, {0, "xz-text-cap", 1}, {0, "open-windows", 0}};
 const Spec kTag[] = {{'i', "in-file", 1}, {'o', "out-file", 1}, {'t', "tag", 1}, {'p', "threads", 1}, {'m', "filter-matching", 0}};
 
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -56,6 +56,7 @@ void print_help(const char *sub) {
              "      --xz-spread <K>          with --device-xz: only when the largest block's text x K <= the whole text (0 = the default) [107]\n"
              "      --xz-stream              implies --device-xz: a larger .xz input is decoded on the GPU window by window, windows of whole blocks (not timed either)\n"
              "      --xz-text-cap <BYTES>    with --xz-stream: text bytes a window may hold (0 = by the free device memory, an unmeasured default) [0]\n"
+             "      --open-windows           ONE bgzip'ed FASTQ / FASTA input, plain-text output: every window starts at a BGZF member and finds its own first record, so windows need not wait for each other; seams are proved, a disproved window is run again (inert otherwise; not timed)\n"
              "      --zstd-stream            implies --device-zstd: a larger .zst input is decoded on the GPU window by window (not timed either)\n"
              "  -c, --canonical              search canonical forms only\n  -l, --out-log [<PATH>]       text log (stdout without a value)\n"
              "  -j, --json-log [<PATH>]      JSON log\n  -S, --suppress-output        write no records (requires -l/-j)\n"
@@ -264,6 +265,7 @@ int main(int argc, char **argv) {
             if (auto v = p.get("bzip2-window")) a.bzip2_window = std::max<uint64_t>(1, to_num((*v)[0], "--bzip2-window <BYTES>"));
             if (auto v = p.get("zstd-window")) a.zstd_window = std::max<uint64_t>(1, to_num((*v)[0], "--zstd-window <BYTES>"));
             a.zstd_stream = p.get("zstd-stream") != nullptr;
+            a.open_windows = p.get("open-windows") != nullptr;
             a.xz_stream = p.get("xz-stream") != nullptr;
             a.device_xz = a.xz_stream || p.get("device-xz") != nullptr;
             if (auto v = p.get("xz-text-cap")) a.xz_text_cap = to_num((*v)[0], "--xz-text-cap <BYTES>");  // (0 = the library's default)

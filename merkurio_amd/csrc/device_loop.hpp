@@ -306,7 +306,8 @@ enum SeqForm { kSeqPlain, kSeqBam, kSeqSam };
 // ---- the steps of a text window (window_ingest.cpp; each is described where it is defined)
 int window_assemble(mk_matcher *m, mk_codec *codec, mk_window_source &S, WindowSide &W, DeviceLoop &dl);
 int line_table(WindowSide &W, hipStream_t st, size_t extra_bytes, uint8_t *first_byte);
-int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide &W, uint8_t *d_seq_out, hipStream_t st, uint32_t *status);
+int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide &W, uint8_t *d_seq_out, hipStream_t st, uint32_t *status,
+                 uint64_t *open_from = nullptr);
 int scan_sequences(mk_matcher *m, const WindowSide &W, uint64_t n, SeqForm form, DeviceLoop &dl, uint32_t mode, uint8_t *flags, uint64_t *flagged,
                    uint64_t *n_seq);
 // pieces of the window's text, back to back in m->d_seq: scan_offsets into m->d_off says where each goes and what they take, then

@@ -183,8 +183,9 @@ int window_members(mk_matcher *m, mk_codec *codec, Packed kind, uint32_t format,
 }
 
 // the body of mk_extract_window (mem == nullptr) and of mk_extract_window_members / mk_extract_window_frames (one mk_window_members per
-// source; kind: which of the two)
-int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem, Packed kind, int logging,
+// source; kind: which of the two), and of mk_extract_window_open (front != nullptr: the one source's window may begin anywhere -- the index
+// step finds its first record start, the text in front of it goes back through *front)
+int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem, mk_window_front *front, Packed kind, int logging,
                         int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
                         uint32_t *counts, uint32_t *status) {
     if (!m || !src || !n_rec_out || !status || !c || (logging && !counts)) return fail(MK_E_INVALID_ARG, "null argument");
@@ -240,13 +241,19 @@ int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_
     for (uint32_t k = 0; k < n_sources; ++k) {
         if (W[k].n_window == 0) {  // nothing of this input in the window
             W[k].n_avail = 0;
+            if (front) {  // (no text, no start)
+                *status = 2;
+                return MK_OK;
+            }
         } else {
             uint8_t *fa_seq = nullptr;
             if (format == MK_TEXT_FASTA) {  // the index step compacts the sequences already: every input has a buffer of its own for them
                 if ((rc = ensure_device(&W[k].T->d_fa_seq, &W[k].T->d_fa_seq_cap, W[k].n_window + 64))) return rc;
                 fa_seq = (uint8_t *)W[k].T->d_fa_seq;
             }
-            if ((rc = window_index(m, format, src[k].ends_at_record != 0, W[k], fa_seq, st, status))) return rc;
+            uint64_t from = 0;
+            if ((rc = window_index(m, format, src[k].ends_at_record != 0, W[k], fa_seq, st, status, front ? &from : nullptr))) return rc;
+            if (front) front->n_front = *status == 2 ? W[k].n_window : from;
             if (*status) return MK_OK;
         }
         src[k].n_rec_seen = W[k].n_avail;
@@ -271,6 +278,12 @@ int extract_window_body(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_
         S.n_tail = W[k].n_window - W[k].n_used;
         if (S.rec_start)
             for (uint64_t r = 0; r <= n; ++r) S.rec_start[r] = rs[k][r];
+        if (front) {  // the text in front of the found start
+            if (front->n_front > front->front_cap)
+                return fail(MK_E_CAPACITY, "mk_extract_window_open: the text in front of the window's first record takes %llu bytes", (unsigned long long)front->n_front);
+            if (front->n_front && hipMemcpyAsync(front->front, W[k].T->d_text, front->n_front, hipMemcpyDeviceToHost, st) != hipSuccess)
+                return fail(MK_E_HIP, "download of the front failed");
+        }
         if (S.tail || S.tail_cap) {
             if (S.n_tail > S.tail_cap) return fail(MK_E_CAPACITY, "mk_extract_window: the text behind the window's records takes %llu bytes", (unsigned long long)S.n_tail);
             if (S.n_tail && hipMemcpyAsync(S.tail, (const uint8_t *)W[k].T->d_text + W[k].n_used, S.n_tail, hipMemcpyDeviceToHost, st) != hipSuccess)
@@ -351,21 +364,33 @@ extern "C" {
 int mk_extract_window(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, int logging, int invert,
                       uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
                       uint32_t *counts, uint32_t *status) {
-    return extract_window_body(m, codec, format, n_sources, src, nullptr, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+    return extract_window_body(m, codec, format, n_sources, src, nullptr, nullptr, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 int mk_extract_window_members(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem,
                               int logging, int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap,
                               uint64_t *n_rows, mk_counters *c, uint32_t *counts, uint32_t *status) {
     if (!mem) return fail(MK_E_INVALID_ARG, "null argument");
-    return extract_window_body(m, codec, format, n_sources, src, mem, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+    return extract_window_body(m, codec, format, n_sources, src, mem, nullptr, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 int mk_extract_window_frames(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, mk_window_members *mem,
                              int logging, int invert, uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap,
                              uint64_t *n_rows, mk_counters *c, uint32_t *counts, uint32_t *status) {
     if (!mem) return fail(MK_E_INVALID_ARG, "null argument");
-    return extract_window_body(m, codec, format, n_sources, src, mem, Packed::kFrames, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+    return extract_window_body(m, codec, format, n_sources, src, mem, nullptr, Packed::kFrames, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
+}
+
+int mk_extract_window_open(mk_matcher *m, mk_codec *codec, uint32_t format, uint32_t n_sources, mk_window_source *src, int logging, int invert,
+                           uint64_t rec_cap, uint64_t *n_rec_out, uint8_t *keep, mk_row *rows, uint64_t rows_cap, uint64_t *n_rows, mk_counters *c,
+                           uint32_t *counts, uint32_t *status, mk_window_front *fronts) {
+    // (what only this entry refuses comes first, in front of any use of the handle or the device)
+    if (!src || !fronts) return fail(MK_E_INVALID_ARG, "null argument");
+    if (n_sources != 1) return fail(MK_E_INVALID_ARG, "mk_extract_window_open: one source -- the two files of a pair cannot be opened independently");
+    if (src[0].n_head != 0) return fail(MK_E_INVALID_ARG, "mk_extract_window_open: an open window has no head");
+    if (fronts->front_cap && !fronts->front) return fail(MK_E_INVALID_ARG, "mk_extract_window_open: a size without its buffer (front)");
+    fronts->n_front = 0;
+    return extract_window_body(m, codec, format, n_sources, src, nullptr, fronts, Packed::kMembers, logging, invert, rec_cap, n_rec_out, keep, rows, rows_cap, n_rows, c, counts, status);
 }
 
 // (v4 / v5 entry points, kept: one FASTQ source whose window ends at a record end / one bgzip'ed FASTQ source with a head)

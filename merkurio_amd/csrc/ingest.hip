@@ -134,6 +134,24 @@ __global__ __launch_bounds__(kIngestThreads) void mk_ingest_lines_kernel(const u
     }
 }
 
+// THE RECORD SHAPE at table entries line_start[0 .. 4] -- the one test of the records kernel and of the open-start search below (the
+// seam proof of mk_extract_window_open rests on the two being the same test): '@' line of at least three bytes with its '\n', '+' line
+// two lines on, sequence and quality of one length, a '\r' in front of the '\n' counted as line end.  The last of the four lines may be
+// the text's last, without a '\n' (its end is then the virtual one at n: no byte to read there); -> *len = the sequence's length
+__device__ __forceinline__ bool fq_shape(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ line_start, uint32_t *len) {
+    const uint32_t l0 = line_start[0], l1 = line_start[1], l2 = line_start[2], l3 = line_start[3], l4 = line_start[4];
+    // line k is [l_k, l_{k+1} - 1) without its '\n'; a '\r' in front of the '\n' belongs to the line end
+    uint32_t e1 = l2 - 1, e3 = l4 - 1;
+    if (e1 > l1 && text[e1 - 1] == '\r') --e1;
+    if (e3 > l3 && e3 - 1 < n && text[e3 - 1] == '\r') --e3;
+    *len = e1 - l1;
+    uint32_t bad = text[l0] != '@';
+    bad |= l1 - l0 < 3;  // "@\n" (l1 - l0 == 2): no id at all is left to the host reader; "@\r\n" is taken, its id is empty
+    bad |= (l3 - l2 < 2) || text[l2] != '+';
+    bad |= (e3 - l3) != *len;
+    return !bad;
+}
+
 // st[0] status bits, st[1] smallest, st[2] largest sequence length
 __global__ __launch_bounds__(256) void mk_ingest_records_kernel(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ line_start,
                                                                uint64_t n_rec, uint32_t *__restrict__ rec_start, uint32_t *__restrict__ seq_start,
@@ -144,19 +162,9 @@ __global__ __launch_bounds__(256) void mk_ingest_records_kernel(const uint8_t *_
     if (i == n_rec) rec_start[n_rec] = min(line_start[4 * n_rec], (uint32_t)n);
     bool live = i < n_rec;
     if (live) {
-        const uint32_t l0 = line_start[4 * i], l1 = line_start[4 * i + 1], l2 = line_start[4 * i + 2], l3 = line_start[4 * i + 3],
-                       l4 = line_start[4 * i + 4];
-        // line k is [l_k, l_{k+1} - 1) without its '\n'; a '\r' in front of the '\n' belongs to the line end
-        uint32_t e1 = l2 - 1, e3 = l4 - 1;
-        if (e1 > l1 && text[e1 - 1] == '\r') --e1;
-        if (e3 > l3 && e3 - 1 < n && text[e3 - 1] == '\r') --e3;
-        len = e1 - l1;
-        bad |= text[l0] != '@';
-        bad |= l1 - l0 < 3;  // "@\n" (l1 - l0 == 2): no id at all is left to the host reader; "@\r\n" is taken, its id is empty
-        bad |= (l3 - l2 < 2) || text[l2] != '+';
-        bad |= (e3 - l3) != len;
-        rec_start[i] = l0;
-        seq_start[i] = l1;
+        bad = !fq_shape(text, n, line_start + 4 * i, &len);
+        rec_start[i] = line_start[4 * i];
+        seq_start[i] = line_start[4 * i + 1];
         seq_len[i] = len;
     }
     // per-wave reductions, one atomic each
@@ -171,6 +179,44 @@ __global__ __launch_bounds__(256) void mk_ingest_records_kernel(const uint8_t *_
     if ((threadIdx.x & 63) == 0) {
         if (mn < __atomic_load_n(&st[1], __ATOMIC_RELAXED)) atomicMin(&st[1], mn);
         if (mx > __atomic_load_n(&st[2], __ATOMIC_RELAXED)) atomicMax(&st[2], mx);
+    }
+}
+
+// ---- the first record start of a window that may begin anywhere (mk_extract_window_open) --------------------------------------
+// The window's byte 0 may lie inside a record, so lines cannot be counted from it: the start is FOUND in the line table.
+//   FASTQ  the smallest line j >= 1 at which the shape the records kernel tests holds twice in a row, at j and at j + 4, all eight
+//          lines complete (ended by a '\n' of the text: j + 8 <= total_nl).  One shape alone is also what a quality line that starts
+//          with '@' makes of its neighbours; a found start is a guess, which the caller proves (include/merkurio_hip.h).
+//   FASTA  the smallest line j >= 1 that starts with '>' (inside the text: the empty "line" behind a final '\n' is none).
+// Line 0 is never taken: whether byte 0 follows a line end is not known.  *found = j << 32 | line_start[j], ~0 if there is none:
+// a grid-stride loop over the candidates, the first set lane of a wave's ballot, one atomicMin per wave that found one; a wave whose
+// first candidate lies behind the minimum so far stops without a load.
+__global__ __launch_bounds__(256) void mk_ingest_open_start_kernel(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ line_start,
+                                                                   uint32_t total_nl, uint32_t fasta, unsigned long long *__restrict__ found) {
+    const uint32_t lane = threadIdx.x & 63u;
+    // candidates 1 .. last (the caller launches nothing when there is none)
+    const uint64_t last = fasta ? total_nl : (uint64_t)total_nl - 8;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = 1 + (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base <= last; base += stride) {
+        const uint32_t best = __builtin_amdgcn_readfirstlane((uint32_t)(__atomic_load_n(found, __ATOMIC_RELAXED) >> 32));
+        if (base > best) break;  // (wave-uniform, as every exit of this loop)
+        const uint64_t j = base + lane;
+        bool ok = false;
+        uint32_t at = 0;
+        if (j <= last) {
+            at = line_start[j];
+            if (fasta) {
+                ok = at < n && text[at] == '>';
+            } else if (text[at] == '@') {  // (three lines of four end here, with one byte read)
+                uint32_t len;
+                ok = fq_shape(text, n, line_start + j, &len) && fq_shape(text, n, line_start + j + 4, &len);
+            }
+        }
+        const unsigned long long b = __ballot(ok);
+        if (b) {  // the wave's later candidates, and those of its later rounds, are larger
+            if (lane == (uint32_t)__ffsll(b) - 1u) atomicMin(found, (unsigned long long)j << 32 | at);
+            break;
+        }
     }
 }
 
@@ -404,9 +450,10 @@ __device__ __forceinline__ uint32_t eq_mask(uint32_t v, uint32_t c4) {  // 0x80 
 
 // counts of one thread's 64 bytes: low 32 bits kept bytes, high 32 bits header lines that START in them.  EMIT: the bytes are also
 // written to stage[0 ...] (the block's LDS staging area, at this thread's place in it) and the headers' record entries stored
-// (goff = where the thread's first kept byte lies in the scan buffer).
+// (goff = where the thread's first kept byte lies in the scan buffer).  Only the bytes [first, nbytes) of the 64 count: those in
+// front of an open window's found start are nobody's.
 template <bool EMIT>
-__device__ __forceinline__ unsigned long long fa_walk(const uint32_t w[16], uint64_t pos, uint32_t nbytes, bool hdr, bool at_line_start,
+__device__ __forceinline__ unsigned long long fa_walk(const uint32_t w[16], uint64_t pos, uint32_t first, uint32_t nbytes, bool hdr, bool at_line_start,
                                                       uint8_t *__restrict__ stage, unsigned long long goff, uint32_t rec, uint32_t *__restrict__ rec_start,
                                                       unsigned long long *__restrict__ off) {
     uint32_t kept = 0, heads = 0;
@@ -417,7 +464,7 @@ __device__ __forceinline__ unsigned long long fa_walk(const uint32_t w[16], uint
         for (int b = 0; b < 4; ++b) {
             const uint32_t i = 4u * d + b;
             const uint32_t c = (w[d] >> (8 * b)) & 0xFFu;
-            if (i < nbytes) {
+            if (i - first < nbytes - first) {  // (first <= i < nbytes; first <= nbytes)
                 if (ls) {
                     hdr = c == '>';
                     if (hdr) {
@@ -479,7 +526,7 @@ template <bool EMIT>
 __global__ __launch_bounds__(kIngestThreads) void mk_ingest_fa_kernel(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ nl_block_off,
                                                                       const uint32_t *__restrict__ line_start, unsigned long long *__restrict__ block_sum,
                                                                       uint8_t *__restrict__ seq, uint32_t *__restrict__ rec_start,
-                                                                      unsigned long long *__restrict__ off) {
+                                                                      unsigned long long *__restrict__ off, uint64_t from) {
     __shared__ uint32_t wave_sum[4];
     __shared__ unsigned long long wave_sum64[4];
     __shared__ uint8_t stage[EMIT ? kIngestBlockBytes : 4];
@@ -503,7 +550,14 @@ __global__ __launch_bounds__(kIngestThreads) void mk_ingest_fa_kernel(const uint
         at_ls = ls == (uint32_t)pos;
         hdr = text[ls] == '>';
     }
-    const unsigned long long mine = fa_walk<false>(w, pos, nbytes, hdr, at_ls, nullptr, 0, 0, nullptr, nullptr);
+    // an open window (from > 0: the found start, a line start): the bytes in front of it are skipped where they lie -- the grid, the
+    // 16-byte loads and the newline counts stay those of the whole text, so the line table and every offset stay the window's
+    uint32_t first = 0;
+    if (from > pos) {
+        first = (uint32_t)min((uint64_t)nbytes, from - pos);
+        at_ls = true, hdr = false;
+    }
+    const unsigned long long mine = fa_walk<false>(w, pos, first, nbytes, hdr, at_ls, nullptr, 0, 0, nullptr, nullptr);
     unsigned long long total = 0;
     const unsigned long long before = block_excl_u64(mine, wave_sum64, &total);
     if (!EMIT) {
@@ -511,7 +565,7 @@ __global__ __launch_bounds__(kIngestThreads) void mk_ingest_fa_kernel(const uint
         return;
     }
     const unsigned long long block_base = block_sum[blockIdx.x], base = block_base + before;
-    if (nbytes) fa_walk<true>(w, pos, nbytes, hdr, at_ls, stage + (uint32_t)(before & 0xFFFFFFFFull), base & 0xFFFFFFFFull, (uint32_t)(base >> 32), rec_start, off);
+    if (nbytes) fa_walk<true>(w, pos, first, nbytes, hdr, at_ls, stage + (uint32_t)(before & 0xFFFFFFFFull), base & 0xFFFFFFFFull, (uint32_t)(base >> 32), rec_start, off);
     if (pos < n && pos + 64 >= n) {
         const unsigned long long end = base + mine;
         rec_start[end >> 32] = (uint32_t)n;
@@ -536,23 +590,33 @@ __global__ __launch_bounds__(kIngestThreads) void mk_ingest_fa_kernel(const uint
 // scanned per-block sums, d_block64[n_blocks] the totals (header lines << 32 | sequence bytes); the caller reads them, then
 // launch_ingest_fasta_emit fills seq / rec_start / off (records + 1 entries each)
 void launch_ingest_fasta_count(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                               unsigned long long *d_block64, hipStream_t st) {
+                               unsigned long long *d_block64, hipStream_t st, uint64_t from) {
     const uint32_t n_blocks = (uint32_t)((n + kIngestBlockBytes - 1) / kIngestBlockBytes);
     hipLaunchKernelGGL(mk_ingest_fa_kernel<false>, dim3(n_blocks), dim3(kIngestThreads), 0, st, d_text, n, d_nl_block_off, d_line_start, d_block64,
-                       (uint8_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr);
+                       (uint8_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr, from);
     // exclusive scan in place over n_blocks + 1 entries (the last one, cleared by the caller, receives the total)
     hipLaunchKernelGGL(mk_ingest_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, d_block64, n_blocks + 1);
 }
 void launch_ingest_fasta_emit(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                              unsigned long long *d_block64, uint8_t *d_seq, uint32_t *d_rec_start, unsigned long long *d_off, hipStream_t st) {
+                              unsigned long long *d_block64, uint8_t *d_seq, uint32_t *d_rec_start, unsigned long long *d_off, hipStream_t st, uint64_t from) {
     const uint32_t n_blocks = (uint32_t)((n + kIngestBlockBytes - 1) / kIngestBlockBytes);
     hipLaunchKernelGGL(mk_ingest_fa_kernel<true>, dim3(n_blocks), dim3(kIngestThreads), 0, st, d_text, n, d_nl_block_off, d_line_start, d_block64, d_seq,
-                       d_rec_start, d_off);
+                       d_rec_start, d_off, from);
 }
 // the line table alone (FASTA: no record kernel follows it)
 void launch_ingest_lines(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start, hipStream_t st) {
     const uint32_t n_blocks = (uint32_t)((n + kIngestBlockBytes - 1) / kIngestBlockBytes);
     hipLaunchKernelGGL(mk_ingest_lines_kernel, dim3(n_blocks), dim3(kIngestThreads), 0, st, d_text, n, d_block_off, d_total, d_line_start);
+}
+
+// the first record start of a window that may begin anywhere: *d_found = line << 32 | byte, ~0 when there is none (set here)
+void launch_ingest_open_start(const uint8_t *d_text, uint64_t n, const uint32_t *d_line_start, uint32_t total_nl, bool fasta, unsigned long long *d_found,
+                              hipStream_t st) {
+    (void)hipMemsetAsync(d_found, 0xFF, 8, st);
+    const uint64_t last = fasta ? total_nl : (total_nl >= 9 ? total_nl - 8 : 0);
+    if (!last) return;  // (FASTQ: fewer than nine complete lines hold no two shapes behind line 0)
+    const unsigned blocks = (unsigned)std::min<uint64_t>((last + 255) / 256, 256);
+    hipLaunchKernelGGL(mk_ingest_open_start_kernel, dim3(blocks), dim3(256), 0, st, d_text, n, d_line_start, total_nl, fasta ? 1u : 0u, d_found);
 }
 
 void launch_ingest_select(const uint8_t *d_flags, uint32_t invert, const uint32_t *d_rec_start, uint64_t n_rec, uint32_t n_text, uint32_t *d_sel_len,
@@ -587,6 +651,11 @@ void launch_ingest_records(const uint8_t *d_text, uint64_t n, const uint32_t *d_
                            uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start, uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st) {
     const uint32_t n_blocks = (uint32_t)((n + kIngestBlockBytes - 1) / kIngestBlockBytes);
     hipLaunchKernelGGL(mk_ingest_lines_kernel, dim3(n_blocks), dim3(kIngestThreads), 0, st, d_text, n, d_block_off, d_total, d_line_start);
+    launch_ingest_index(d_text, n, d_line_start, n_rec, d_rec_start, d_seq_start, d_seq_len, d_status, st);
+}
+// the record tables from a line table that exists, read from d_line_start[0] on (an open window: from its found line on)
+void launch_ingest_index(const uint8_t *d_text, uint64_t n, const uint32_t *d_line_start, uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start,
+                         uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st) {
     // (n_rec + 1 lanes: the last one writes the end of the records)
     hipLaunchKernelGGL(mk_ingest_records_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, st, d_text, n, d_line_start, n_rec, d_rec_start,
                        d_seq_start, d_seq_len, d_status);

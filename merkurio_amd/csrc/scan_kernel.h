@@ -152,6 +152,11 @@ void launch_ingest_count(const uint8_t *d_text, uint64_t n, uint32_t *d_block_cn
 void launch_ingest_records(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start,
                            uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start, uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st);
 void launch_ingest_lines(const uint8_t *d_text, uint64_t n, const uint32_t *d_block_off, const uint32_t *d_total, uint32_t *d_line_start, hipStream_t st);
+// an open window (mk_extract_window_open): its first record start from the line table, then the record tables from that line on
+void launch_ingest_open_start(const uint8_t *d_text, uint64_t n, const uint32_t *d_line_start, uint32_t total_nl, bool fasta, unsigned long long *d_found,
+                              hipStream_t st);
+void launch_ingest_index(const uint8_t *d_text, uint64_t n, const uint32_t *d_line_start, uint64_t n_rec, uint32_t *d_rec_start, uint32_t *d_seq_start,
+                         uint32_t *d_seq_len, uint32_t *d_status, hipStream_t st);
 void launch_ingest_offsets(const uint32_t *d_seq_len, uint64_t n_rec, unsigned long long *d_tile, unsigned long long *d_off, hipStream_t st);
 void launch_ingest_gather(const uint8_t *d_text, const uint32_t *d_seq_start, const uint32_t *d_seq_len, const unsigned long long *d_off,
                           uint32_t fixed_len, uint64_t n_rec, uint8_t *d_seq, hipStream_t st, uint32_t skip_from = 0xFFFFFFFFu);
@@ -167,9 +172,10 @@ void launch_ingest_written_gather(const uint8_t *d_text, bool fasta, const uint3
                                   uint64_t n_rec, uint32_t n_text, const uint32_t *d_sel_len, const unsigned long long *d_off, uint8_t *d_out,
                                   uint32_t big_from, hipStream_t st);
 void launch_ingest_fasta_count(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                               unsigned long long *d_block64, hipStream_t st);
+                               unsigned long long *d_block64, hipStream_t st, uint64_t from = 0);
 void launch_ingest_fasta_emit(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl_block_off, const uint32_t *d_line_start,
-                              unsigned long long *d_block64, uint8_t *d_seq, uint32_t *d_rec_start, unsigned long long *d_off, hipStream_t st);
+                              unsigned long long *d_block64, uint8_t *d_seq, uint32_t *d_rec_start, unsigned long long *d_off, hipStream_t st,
+                              uint64_t from = 0);
 uint32_t ingest_block_bytes();
 uint32_t ingest_scan_tile();
 void launch_bam_find(const uint8_t *d_text, uint64_t n, uint32_t piece, uint32_t n_pieces, uint32_t *d_start, hipStream_t st);

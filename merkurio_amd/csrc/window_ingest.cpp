@@ -127,19 +127,44 @@ int line_table(WindowSide &W, hipStream_t st, size_t extra_bytes, uint8_t *first
 // line table, whole records and their tables for the text in W.T (enqueued work waited for): W.n_avail, d_rec_start[n_avail + 1],
 // FASTQ: d_seq_start / d_seq_len / W.fixed; FASTA: the sequences already lie in d_seq_out with offsets d_fa_off[n_avail + 1].
 // *status = 1: this text is not what the device takes (the caller's reader decides what it is).
-int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide &W, uint8_t *d_seq_out, hipStream_t st, uint32_t *status) {
+// open_from != nullptr: the window may begin anywhere (mk_extract_window_open) -- its first record start is found in the line table
+// (mk_ingest_open_start_kernel) and the records are indexed from there; *open_from = that byte, every table stays in offsets of the
+// whole text.  *status = 2: no start was found.
+int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide &W, uint8_t *d_seq_out, hipStream_t st, uint32_t *status,
+                 uint64_t *open_from) {
     mk_matcher::TextSlot &T = *W.T;
     int rc;
     const uint64_t n_text = W.n_window;
     const uint8_t *d_text = (const uint8_t *)T.d_text;
     const uint32_t n_blocks = (uint32_t)((n_text + ingest_block_bytes() - 1) / ingest_block_bytes());
-    // (behind line_table's words: FASTA's u64 per block + 1)
+    // (behind line_table's words: FASTA's u64 per block + 1; an open window: one more, the word its start is found in)
     uint8_t first = 0;
-    if ((rc = line_table(W, st, 16 + ((size_t)n_blocks + 2) * 8, &first))) return rc;
+    if ((rc = line_table(W, st, 16 + ((size_t)n_blocks + 2 + (open_from ? 1 : 0)) * 8, &first))) return rc;
     W.d_block64 = (unsigned long long *)(((uintptr_t)(W.d_block + n_blocks + 8) + 15) & ~(uintptr_t)15);
     const uint32_t total_nl = W.total_nl;
+    // an open window: the line table first (its place in d_ing_b is the same in both layouts below), then the found start
+    uint64_t j0 = 0, from = 0;
+    if (open_from) {
+        // (room for the whole workspace now, sized as if the first line were the start: the table must not move afterwards)
+        const size_t most_rec = format == MK_TEXT_FASTA ? (size_t)total_nl + 2 : (size_t)total_nl / 4 + 1;
+        const size_t ws = format == MK_TEXT_FASTA ? ((size_t)total_nl + 4) * 4 + (most_rec + 2) * 4 + 16 + (most_rec + 2) * 8
+                                                  : ((size_t)total_nl + 4 + 3 * (most_rec + 2) + 8) * 4 + (most_rec / ingest_scan_tile() + 2) * 8 + 64;
+        if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, ws))) return rc;
+        unsigned long long *d_found = W.d_block64 + n_blocks + 2, found = ~0ull;
+        launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, (uint32_t *)T.d_ing_b, st);
+        launch_ingest_open_start(d_text, n_text, (const uint32_t *)T.d_ing_b, total_nl, format == MK_TEXT_FASTA, d_found, st);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&found, d_found, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return fail(MK_E_HIP, "search for the window's first record failed");
+        if (found == ~0ull) {
+            *status = 2;
+            return MK_OK;
+        }
+        j0 = found >> 32, from = found & 0xFFFFFFFFull;
+        *open_from = from;
+    }
     if (format == MK_TEXT_FASTA) {
-        if (first != '>') {  // blank lines or anything else in front of the first header: the host reader's business
+        if (!open_from && first != '>') {  // blank lines or anything else in front of the first header: the host reader's business
             *status = 1;
             return MK_OK;
         }
@@ -150,23 +175,23 @@ int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide
         W.d_line = (uint32_t *)T.d_ing_b;
         W.d_rec_start = W.d_line + total_nl + 4;
         W.d_fa_off = (unsigned long long *)(((uintptr_t)(W.d_rec_start + max_rec + 2) + 15) & ~(uintptr_t)15);
-        launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, W.d_line, st);
+        if (!open_from) launch_ingest_lines(d_text, n_text, W.d_block, W.d_total, W.d_line, st);  // (an open window's table exists, in this very place)
         if (hipMemsetAsync(W.d_block64 + n_blocks, 0, 8, st) != hipSuccess) return fail(MK_E_HIP, "hipMemsetAsync failed");
-        launch_ingest_fasta_count(d_text, n_text, W.d_block, W.d_line, W.d_block64, st);
+        launch_ingest_fasta_count(d_text, n_text, W.d_block, W.d_line, W.d_block64, st, from);
         unsigned long long totals = 0;
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&totals, W.d_block64 + n_blocks, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             return fail(MK_E_HIP, "FASTA indexing failed");
         const uint64_t heads = totals >> 32;
         W.seq_total = totals & 0xFFFFFFFFull;
-        launch_ingest_fasta_emit(d_text, n_text, W.d_block, W.d_line, W.d_block64, d_seq_out, W.d_rec_start, W.d_fa_off, st);
+        launch_ingest_fasta_emit(d_text, n_text, W.d_block, W.d_line, W.d_block64, d_seq_out, W.d_rec_start, W.d_fa_off, st, from);
         if (hipGetLastError() != hipSuccess) return fail(MK_E_HIP, "FASTA gather failed to launch");
         // a record is whole once the next header (or the end of the input) has been seen
         W.n_avail = ends_at_record ? heads : (heads ? heads - 1 : 0);
         W.fixed = 0;
         return MK_OK;
     }
-    uint64_t n_lines = total_nl;
+    uint64_t n_lines = total_nl - j0;  // (an open window: the lines from the found one on)
     if (ends_at_record) {
         n_lines += W.last_byte != '\n' ? 1 : 0;
         if (n_lines % 4 != 0) {  // not whole 4-line records: the caller's reader decides what this text is
@@ -180,14 +205,16 @@ int window_index(mk_matcher *m, uint32_t format, bool ends_at_record, WindowSide
     const size_t n_tiles = n_rec / ingest_scan_tile() + 2;
     const size_t ws = ((size_t)total_nl + 4 + 3 * (n_rec + 2) + 8) * 4 + n_tiles * 8 + 64;
     if ((rc = ensure_device(&T.d_ing_b, &T.d_ing_b_cap, ws))) return rc;
-    W.d_line = (uint32_t *)T.d_ing_b;
-    W.d_rec_start = W.d_line + total_nl + 4;
+    uint32_t *const d_line0 = (uint32_t *)T.d_ing_b;
+    W.d_line = d_line0 + j0;  // line 4 r + k of the table is line k of record r
+    W.d_rec_start = d_line0 + total_nl + 4;
     W.d_seq_start = W.d_rec_start + n_rec + 2;
     W.d_seq_len = W.d_seq_start + n_rec + 2;
     W.d_tile = (unsigned long long *)(((uintptr_t)(W.d_seq_len + n_rec + 2) + 15) & ~(uintptr_t)15);
     const uint32_t st_init[3] = {0u, 0xFFFFFFFFu, 0u};
     if (hipMemcpyAsync(W.d_st, st_init, sizeof(st_init), hipMemcpyHostToDevice, st) != hipSuccess) return fail(MK_E_HIP, "copy failed");
-    launch_ingest_records(d_text, n_text, W.d_block, W.d_total, W.d_line, n_rec, W.d_rec_start, W.d_seq_start, W.d_seq_len, W.d_st, st);
+    if (open_from) launch_ingest_index(d_text, n_text, W.d_line, n_rec, W.d_rec_start, W.d_seq_start, W.d_seq_len, W.d_st, st);  // (the table exists)
+    else launch_ingest_records(d_text, n_text, W.d_block, W.d_total, W.d_line, n_rec, W.d_rec_start, W.d_seq_start, W.d_seq_len, W.d_st, st);
     uint32_t st_host[3] = {0, 0, 0};
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(st_host, W.d_st, sizeof(st_host), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)

@@ -60,7 +60,7 @@ EXPORTS = [
     "mk_zstd_stream_begin", "mk_zstd_stream_next", "mk_zstd_stream_info", "mk_zstd_stream_end", "mk_codec_set_zstd_text_cap",
     "mk_xz_stream_begin", "mk_xz_stream_next", "mk_xz_stream_info", "mk_xz_stream_end", "mk_codec_set_xz_text_cap",
     "mk_gzip_stream_begin", "mk_gzip_stream_next", "mk_gzip_stream_info", "mk_gzip_stream_end", "mk_crc32_combine", "mk_extract_fastq_bgzf", "mk_extract_window",
-    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members", "mk_extract_window_frames",
+    "mk_bgzf_record_cuts", "mk_bgzf_deflate_records", "mk_codec_cut_times", "mk_extract_window_members", "mk_extract_window_frames", "mk_extract_window_open",
     "mk_tag_bam_window", "mk_matcher_set_bam_piece", "mk_tag_sam_window", "mk_tag_sam_bam_window", "mk_tag_bam_sam_window",
 ]
 
@@ -151,6 +151,11 @@ class WindowMembers(C.Structure):
     _fields_ = [("members", C.c_void_p), ("members_cap", C.c_uint64), ("ids", C.c_void_p), ("ids_cap", C.c_uint64), ("id_end", C.c_void_p),
                 ("text_below", C.c_uint64), ("n_member_bytes", C.c_uint64), ("n_members", C.c_uint64), ("n_written", C.c_uint64),
                 ("n_kept", C.c_uint64), ("n_id_bytes", C.c_uint64), ("as_text", C.c_uint32), ("written_ms", C.c_float)]
+
+
+class WindowFront(C.Structure):
+    """mk_window_front (include/merkurio_hip.h, v7): where the text in front of an open window's found start goes (mk_extract_window_open)"""
+    _fields_ = [("front", C.c_void_p), ("front_cap", C.c_uint64), ("n_front", C.c_uint64)]
 
 
 MK_TEXT_FASTQ, MK_TEXT_FASTA = 0, 1
@@ -373,6 +378,7 @@ def load(build_if_missing=True):
                                         C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Counters), C.c_void_p, C.POINTER(C.c_uint32)]
     L.mk_extract_window.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mk_extract_window_open.argtypes = L.mk_extract_window.argtypes + [C.c_void_p]  # (the same arguments, then the mk_window_front)
     L.mk_bgzf_record_cuts.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mk_extract_window_members.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64,
                                             C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Counters),
@@ -791,6 +797,17 @@ class Matcher:
              head (bytes, default b""), text (bytes) OR blob + members (bgzf_members entries), ends_at_record (bool)
         want: which texts come back per source, any of "tail", "kept", "all".
         -> dict(status, n_rec, keep, rows, counters, sources=[dict(n_window, n_used, n_rec_seen, rec_start, tail, kept, all)])"""
+        return self._extract_window_text(sources, fmt, logging, invert, codec, want, None)
+
+    def extract_window_open(self, sources, fmt=MK_TEXT_FASTQ, logging=True, invert=False, codec=None, want=("tail",), front_cap=None):
+        """mk_extract_window_open: extract_window on ONE source without a head whose text may begin anywhere -- the call finds the first
+        record start (the start rule of include/merkurio_hip.h) and processes the records from there.  front_cap: None = grow the
+        buffer to what the call names and ask again; a number = taken as it is (MK_E_CAPACITY is raised, the error's n_front = the need).
+        -> extract_window's dict plus n_front and front (bytes: the text in front of the found start; b"" when status is 2, where
+           n_front = n_window).  rec_start, n_used and the tail's place stay offsets in the whole window text."""
+        return self._extract_window_text(sources, fmt, logging, invert, codec, want, 64 if front_cap is None else ("fixed", int(front_cap)))
+
+    def _extract_window_text(self, sources, fmt, logging, invert, codec, want, front):
         L = load()
         n_src = len(sources)
         arr, hold, bound = self._window_sources(sources)
@@ -811,12 +828,26 @@ class Matcher:
         n_rec, status, n_rows = C.c_uint64(), C.c_uint32(), C.c_uint64()
         keep = np.zeros(cap, dtype=np.uint8)
         rows = np.zeros(4096, dtype=ROW_DTYPE)
+        F, front_buf, front_grows = WindowFront(), None, False
+        if front is not None:
+            front_grows = not isinstance(front, tuple)
+            front_buf = np.zeros(max(1, front if front_grows else front[1]), dtype=np.uint8)
+            F.front, F.front_cap = front_buf.ctypes.data, (front_buf.size if front_grows else front[1])
         for _ in range(8):
             c2, k2 = Counters(), np.zeros(len(self.patterns), dtype=np.uint32)
-            rc = L.mk_extract_window(self._h, codec._h if codec else None, fmt, n_src, arr, int(logging), int(invert), cap, C.byref(n_rec),
-                                     keep.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows), C.byref(c2), k2.ctypes.data, C.byref(status))
+            args = (self._h, codec._h if codec else None, fmt, n_src, arr, int(logging), int(invert), cap, C.byref(n_rec),
+                    keep.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows), C.byref(c2), k2.ctypes.data, C.byref(status))
+            rc = L.mk_extract_window(*args) if front is None else L.mk_extract_window_open(*args, C.addressof(F))
             if rc == MK_E_CAPACITY:  # the call states every need: grow what was too small and ask again
                 grown = False
+                if front is not None and F.n_front > F.front_cap:
+                    if not front_grows:
+                        err = MerkurioError(rc, L.mk_last_error().decode())
+                        err.n_front = F.n_front
+                        raise err
+                    front_buf = np.zeros(F.n_front, dtype=np.uint8)
+                    F.front, F.front_cap = front_buf.ctypes.data, front_buf.size
+                    grown = True
                 if n_rows.value > len(rows):
                     rows = np.zeros(n_rows.value, dtype=ROW_DTYPE)
                     grown = True
@@ -838,6 +869,9 @@ class Matcher:
         out = {"status": status.value, "n_rec": n, "keep": [bool(x) for x in keep[:n]],
                "rows": [(int(r["file"]), int(r["rec"]), int(r["pat"]), int(r["pos"])) for r in rows[:n_rows.value]] if logging else [],
                "counters": c2.as_dict(k2), "sources": []}
+        if front is not None:
+            out["n_front"] = F.n_front
+            out["front"] = front_buf[:F.n_front].tobytes() if status.value != 2 else b""
         for k in range(n_src):
             S, b = arr[k], bufs[k]
             out["sources"].append({"n_window": S.n_window, "n_used": S.n_used, "n_rec_seen": S.n_rec_seen,
